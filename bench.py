@@ -14,7 +14,10 @@ resident in HBM.
   --workload cfg3   configs[3] per-GPU shape instead (Phototourism: NeRF-W a+t, N_vocab 1500, black background,
                     per-ray near/far; --rays 1024 is the README batch)
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--mode train|render]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--mode train|render] [--dump-outputs DIR]
+
+  --dump-outputs DIR  after the K timed steps, what the last one returned (result dict, loss, gradients, updated
+                      parameters) as DIR/<name>.npy, so that two builds can be compared output for output
 
 N > 1: run plainly (`python bench.py --gpus N`), this process then starts N ranks itself -- one fresh process per
 GPU, rendezvous on 127.0.0.1, and exits non-zero if any rank fails -- or run under a launcher
@@ -41,7 +44,11 @@ N_SAMPLES, N_IMPORTANCE = 64, 64
 # algorithmic FLOPs (2 x weight-matrix MACs) per field evaluation, SURVEY.md section 8(d)
 FLOP_EVAL = {"base": 2 * 593408, "at": 2 * 684160}
 FOLDED_FLOP_EVAL = 2 * 256 * 256     # xyz_encoding_final: no tiles in the packed streams
-PEAK_F16_MFMA_TFLOPS = 2500.0     # dense fp16/bf16 MFMA, /opt/skills/guides/MI355X_MICROARCH.md
+PEAK_F16_MFMA_TFLOPS = 2500.0     # dense fp16/bf16 MFMA peak of the MI355X
+DUMP_BUDGET_BYTES = 64 << 20      # --dump-outputs: total size of the written arrays
+DUMP_SAMPLE_SEED = 2024           # --dump-outputs: the ray sample taken when the per-ray outputs exceed the budget
+
+
 def _latest_summary():
     import glob
     hits = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]*_summary.json")))
@@ -83,7 +90,18 @@ def parse_args(argv=None):
                     help="arithmetic of the MLP backward: f16 = single fp16 product (default), f16w = the gradient chain reads "
                          "hi+lo weight fragments (two products: no systematic training-curve offset), f16x3 = split operands, "
                          "3 products, hi+lo stashes (fp32-class, the reference's precision class)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: write what the timed path returned in its LAST step as DIR/<name>.npy "
+                         "(float32; rank 0's shard): the render_rays result, and in train mode the loss, the gradients and "
+                         f"the updated parameters.  At most {DUMP_BUDGET_BYTES >> 20} MB in all: beyond that, a fixed seeded "
+                         "sample of the rays.  Inputs are seeded, so two builds run with the same arguments can be compared "
+                         "array by array")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and args.dry:
+        ap.error("--dump-outputs: --dry runs no render path, there is nothing to write")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------
@@ -292,12 +310,14 @@ def run_rank(args):
                               grad_arena=arena)
             loss = sum(loss_fn(res, target).values())  # c_l + f_l (+ b_l + s_l), forward and backward one launch each
         else:       # NerfWLoss and its backward seeds in the render kernels' per-ray epilogue (losses.py:35-50)
-            loss = render_rays(models, emb, rays, ts, N_SAMPLES, False, 1.0, 1.0, N_IMPORTANCE, 32768, white_back, False,
-                               loss_target=target, grad_arena=arena)["_nerfw_loss"]
+            res = render_rays(models, emb, rays, ts, N_SAMPLES, False, 1.0, 1.0, N_IMPORTANCE, 32768, white_back, False,
+                              loss_target=target, grad_arena=arena)
+            loss = res["_nerfw_loss"]
         loss.backward()
         if dist is not None:
             arena.all_reduce(force=force)       # one in-place collective on the memory the backward wrote
         opt.step()
+        return res, loss
 
     graphed = None
     if args.mode == "train" and args.graph:
@@ -318,14 +338,20 @@ def run_rank(args):
         step()
     sync()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    last = step()                   # what the caller receives from the last timed step (--dump-outputs)
     sync()
     elapsed = time.perf_counter() - t0
     if dist is not None:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # written before anything below steps again (the sustained and companion steps move the parameters)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, last_step_outputs(args, last, models, emb, R), R)
+    last = None
 
     n_ranks = dist.get_world_size() if dist is not None else 1
     # sustained rate (>= 100 timed iterations, event-timed, median): outside the driver-specified steps, the
@@ -432,6 +458,8 @@ def run_rank(args):
                                            "fp16 MFMA, operands split hi+lo, 3 products, fp32 accumulate, hi+lo stashes (f16x3)"),
                    "mlp_evals_per_ray": N_SAMPLES + F, "hip_graph": bool(args.graph)},
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
 
     if args.no_extras:
         for _ in range(args.render_steps):
@@ -475,6 +503,57 @@ def event_timed(fn, n):
     torch.cuda.synchronize()
     d = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(n))
     return {"median_ms": d[n // 2], "p90_ms": d[min(n - 1, int(0.9 * n))], "mean_ms": sum(d) / n, "min_ms": d[0], "steps": n}
+
+
+def last_step_outputs(args, last, models, emb, n_rays):
+    """name -> (tensor, per_ray) of what one step of the timed path hands its caller: the render_rays result dict
+    (render mode, eager train step) or the graphed step's (loss, psnr), and in train mode the parameters Adam just
+    updated and the gradients they were updated with."""
+    out = {}
+    if args.mode == "render":
+        res = last
+    elif args.graph:
+        res = dict(zip(("loss", "psnr"), last))
+    else:
+        res, loss = last
+        res = dict(res, loss=loss)
+    for k, v in res.items():
+        out[k] = (v, n_rays > 0 and v.dim() >= 1 and v.shape[0] == n_rays)
+    if args.mode == "train":
+        named = [(f"{typ}.{n}", p) for typ, m in models.items() for n, p in m.named_parameters()]
+        named += [(f"embedding_{k}.{n}", p) for k in ("a", "t") if k in emb for n, p in emb[k].named_parameters()]
+        for n, p in named:
+            out["param." + n] = (p, False)
+            if p.grad is not None:
+                out["grad." + n] = (p.grad, False)
+    return out
+
+
+def dump_outputs(path, outputs, n_rays):
+    """Write `outputs` (last_step_outputs) as path/<name>.npy: float32 (float64 and integer tensors as float64).  If
+    they exceed DUMP_BUDGET_BYTES, every per-ray array keeps the same fixed, seeded sample of rays (in ray order)."""
+    import numpy as np
+    import torch
+    arrays = {}
+    for name, (t, per_ray) in outputs.items():
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 or not t.is_floating_point() else t.float()
+        arrays[name] = (t.cpu().numpy(), per_ray)
+    fixed = sum(a.nbytes for a, per_ray in arrays.values() if not per_ray)
+    per_ray_bytes = sum(a.nbytes // n_rays for a, per_ray in arrays.values() if per_ray)
+    keep = n_rays
+    if fixed + per_ray_bytes * n_rays > DUMP_BUDGET_BYTES:
+        keep = (DUMP_BUDGET_BYTES - fixed) // per_ray_bytes if per_ray_bytes else 0
+        if keep < 1:
+            raise SystemExit(f"--dump-outputs: {fixed} bytes of non-per-ray outputs alone exceed the "
+                             f"{DUMP_BUDGET_BYTES}-byte budget")
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_rays, keep, replace=False))
+        arrays = {k: (a[rows] if per_ray else a, per_ray) for k, (a, per_ray) in arrays.items()}
+    os.makedirs(path, exist_ok=True)
+    for name, (a, _) in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": os.path.abspath(path), "arrays": len(arrays), "bytes": sum(a.nbytes for a, _ in arrays.values()),
+            "rays": n_rays, "rays_written": keep, "ray_sample_seed": DUMP_SAMPLE_SEED if keep < n_rays else None}
 
 
 def roofline(args, rnd, models, emb, rays, ts, dev, fine_kind, white_back):

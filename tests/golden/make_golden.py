@@ -127,6 +127,26 @@ def g2_field():
                  x=x, y=y)
 
 
+def g19_make_c2w():
+    """The reference's SO(3) pose helper (utils/lie_group_helper.py make_c2w), one camera per call: the same draws
+    tests/test_poses_cpu.py used to make when the reference sat next to it (8 cameras at 0.7 x randn, then 5 at randn)."""
+    import importlib.util           # by file path: the reference's utils/__init__.py needs packages this helper does not
+    ref_root = os.path.dirname(os.path.dirname(os.path.abspath(sys.modules["models.nerf"].__file__)))
+    spec = importlib.util.spec_from_file_location("ref_lie", os.path.join(ref_root, "utils", "lie_group_helper.py"))
+    ref = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ref)
+    make_c2w = ref.make_c2w
+    torch.manual_seed(1)
+    rs, ts = [], []
+    for _ in range(8):
+        rs.append(torch.randn(3) * 0.7)
+        ts.append(torch.randn(3))
+    r5, t5 = torch.randn(5, 3), torch.randn(5, 3)
+    r, t = torch.cat([torch.stack(rs), r5]), torch.cat([torch.stack(ts), t5])
+    c2w = torch.stack([make_c2w(r[k], t[k]) for k in range(r.shape[0])])
+    save("g19_make_c2w", {"n_single": 8, "n_batched": 5}, r=r, t=t, c2w=c2w)
+
+
 def g3_sample_pdf():
     rng = np.random.default_rng(303)
     R, M, I = 48, 62, 64
@@ -394,6 +414,8 @@ def main():
         g3_sample_pdf()
     if sel("g3b_"):
         g3b_sample_pdf_from_coarse()
+    if sel("g19_"):
+        g19_make_c2w()
     for name, kw in RENDER_CASES:
         if sel(name):
             render_case(name, **kw)

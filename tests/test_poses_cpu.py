@@ -1,15 +1,10 @@
-"""Pose / ray helpers around render_rays for --refine_pose.  When /root/reference is present (build
-container) the SO(3) helper is pinned against the reference's own utils/lie_group_helper.py, loaded by
-file path (it needs only torch/numpy/scipy); everywhere it is checked against closed-form properties."""
-import importlib.util
-import os
-
-import pytest
+"""Pose / ray helpers around render_rays for --refine_pose.  The SO(3) helper is pinned against the reference's own
+utils/lie_group_helper.py through stored vectors (tests/golden/g19_make_c2w.npz, written by
+tests/golden/make_golden.py) and checked against closed-form properties."""
 import torch
 
+import golden_util as gu
 from nerf_fl_amd.poses import LearnPose, get_ray_directions, get_rays, make_c2w, so3_exp
-
-REF = "/root/reference/utils/lie_group_helper.py"
 
 
 def test_so3_exp_properties():
@@ -23,19 +18,14 @@ def test_so3_exp_properties():
     assert torch.allclose(so3_exp(torch.zeros(3)), torch.eye(3))
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference not present on this machine")
 def test_make_c2w_matches_reference():
-    spec = importlib.util.spec_from_file_location("ref_lie", REF)
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    torch.manual_seed(1)
-    for _ in range(8):
-        r, t = torch.randn(3) * 0.7, torch.randn(3)
-        assert torch.allclose(make_c2w(r, t), ref.make_c2w(r, t), atol=1e-6)
-    r, t = torch.randn(5, 3), torch.randn(5, 3)                                # batched == per camera
-    batched = make_c2w(r, t)
-    for k in range(5):
-        assert torch.allclose(batched[k], ref.make_c2w(r[k], t[k]), atol=1e-6)
+    cfg, a = gu.load("g19_make_c2w")
+    r, t, ref = a["r"], a["t"], a["c2w"]
+    for k in range(r.shape[0]):                                                # one camera per call, as the reference
+        assert torch.allclose(make_c2w(r[k], t[k]), ref[k], atol=1e-6)
+    nb = cfg["n_batched"]
+    assert torch.allclose(make_c2w(r[-nb:], t[-nb:]), ref[-nb:], atol=1e-6)     # batched == per camera
+    assert torch.allclose(make_c2w(r, t), ref, atol=1e-6)
 
 
 def test_rays_and_learnable_pose_gradients():
