@@ -403,6 +403,35 @@ typedef struct nfl_loss_args {
 int nfl_loss_forward(const nfl_loss_args* args, void* stream);
 int nfl_loss_backward(const nfl_loss_args* args, void* stream);
 
+/* ---- learnable camera poses (--refine_pose; reference models/poses.py, utils/lie_group_helper.py:63-84,
+ * datasets/ray_utils.py:29-55) --------------------------------------------------------------------------------
+ * Per camera c: c2w = make_c2w(r[c], t[c]) @ init_c2w[c] with Exp(r) = I + sin(n)/n K + (1-cos n)/n^2 K^2,
+ * n = |r| + 1e-15, K = skew(r).  Per ray i, with c = d_row_of_id[d_ts[i]]:
+ *   d_rays[i] = [c2w[:3, 3], normalize(c2w[:3, :3] . d_rays_cam[i, 0:3]), d_rays_cam[i, 3], d_rays_cam[i, 4]].
+ * nfl_pose_rays also writes d_rows[i] = c (int32), or -1 for an id outside [0, n_ids) or a row outside [0, n_cams):
+ * such a ray is written as NaN and NFL_STATUS_POSE_ID is OR-ed into *d_status (never an out-of-bounds read).
+ * nfl_pose_rays_backward reads d_rows (as the forward left it) and d_g_rays (n_rays, 8) and WRITES d_g_r / d_g_t
+ * (n_cams, 3; either may be NULL): every camera is written, 0 when no ray of the batch uses it.  No atomics: one
+ * wavefront per camera sums its rays in a fixed order, so two calls on the same inputs are bit-identical. */
+#define NFL_STATUS_POSE_ID 4     /* an image id (or its pose row) was outside the pose table: the ray came out as NaN */
+typedef struct nfl_pose_args {
+    const float*   d_r;           /* (n_cams, 3) axis-angle deltas                                   */
+    const float*   d_t;           /* (n_cams, 3) translation deltas                                  */
+    const float*   d_init_c2w;    /* (n_cams, 4, 4) or NULL (identity)                               */
+    const int64_t* d_row_of_id;   /* (n_ids): image id -> pose row                                   */
+    const int64_t* d_ts;          /* (n_rays) image ids                                              */
+    const float*   d_rays_cam;    /* (n_rays, cam_stride >= 5): camera-frame direction, near, far     */
+    int32_t n_cams, n_ids, n_rays, cam_stride;
+    float*         d_rays;        /* forward out: (n_rays, 8) o, d, near, far                         */
+    int32_t*       d_rows;        /* forward out / backward in: (n_rays) pose row per ray, -1 = bad  */
+    const float*   d_g_rays;      /* backward in: (n_rays, 8)                                        */
+    float*         d_g_r;         /* backward out: (n_cams, 3) or NULL                               */
+    float*         d_g_t;         /* backward out: (n_cams, 3) or NULL                               */
+    int32_t*       d_status;      /* optional status word (NFL_STATUS_POSE_ID)                       */
+} nfl_pose_args;
+int nfl_pose_rays(const nfl_pose_args* args, void* stream);
+int nfl_pose_rays_backward(const nfl_pose_args* args, void* stream);
+
 /* ---- hierarchical sampling (reference sample_pdf, rendering.py:7-46, plus the
  * concat + sort of rendering.py:267-272) -------------------------------------
  * d_z_coarse (R,S), d_weights_coarse (R,S); d_u (R,I) or NULL with d_u_row (I)

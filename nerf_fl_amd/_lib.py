@@ -19,6 +19,7 @@ NFL_PREC_F16 = 1
 NFL_PREC_F16W = 2      # backward only: one-product arithmetic, but the gradient chain reads hi + lo weight fragments
 NFL_STATUS_NONFINITE = 1
 NFL_STATUS_RANGE = 2
+NFL_STATUS_POSE_ID = 4   # nfl_pose_rays: an image id (or its pose row) outside the pose table
 NFL_NUM_LAYERS = 19
 
 # layer slot -> state_dict prefix (reference models/nerf.py:121-151)
@@ -126,6 +127,13 @@ class FieldGrads(C.Structure):
     _fields_ = [("weight", C.c_void_p * NFL_NUM_LAYERS), ("bias", C.c_void_p * NFL_NUM_LAYERS)]
 
 
+class PoseArgs(C.Structure):
+    _fields_ = [("d_r", C.c_void_p), ("d_t", C.c_void_p), ("d_init_c2w", C.c_void_p), ("d_row_of_id", C.c_void_p),
+                ("d_ts", C.c_void_p), ("d_rays_cam", C.c_void_p), ("n_cams", C.c_int32), ("n_ids", C.c_int32),
+                ("n_rays", C.c_int32), ("cam_stride", C.c_int32), ("d_rays", C.c_void_p), ("d_rows", C.c_void_p),
+                ("d_g_rays", C.c_void_p), ("d_g_r", C.c_void_p), ("d_g_t", C.c_void_p), ("d_status", C.c_void_p)]
+
+
 # every symbol include/nerf_fl_amd.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("nfl_plan_bytes", C.c_size_t, [C.POINTER(FieldDesc)]),
@@ -161,6 +169,8 @@ SYMBOLS = [
     ("nfl_adam_step_dev", C.c_int, [C.POINTER(AdamTensors), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     ("nfl_loss_forward", C.c_int, [C.POINTER(LossArgs), C.c_void_p]),
     ("nfl_loss_backward", C.c_int, [C.POINTER(LossArgs), C.c_void_p]),
+    ("nfl_pose_rays", C.c_int, [C.POINTER(PoseArgs), C.c_void_p]),
+    ("nfl_pose_rays_backward", C.c_int, [C.POINTER(PoseArgs), C.c_void_p]),
     ("nfl_abi_version", C.c_int, []),
     ("nfl_version", C.c_char_p, []),
     ("nfl_strerror", C.c_char_p, [C.c_int]),

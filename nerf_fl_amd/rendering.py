@@ -33,7 +33,8 @@ import torch
 
 from . import _lib
 
-__all__ = ["render_rays", "set_precision", "get_precision", "get_backward_precision", "check_status", "CameraRays"]
+__all__ = ["render_rays", "set_precision", "get_precision", "get_backward_precision", "check_status", "CameraRays",
+           "fill_barf_weights"]
 
 _PREC = {"f16x3": _lib.NFL_PREC_F16X3, "f16": _lib.NFL_PREC_F16}
 _BPREC = dict(_PREC, f16w=_lib.NFL_PREC_F16W)
@@ -170,8 +171,22 @@ def check_status(device=None):
                 what.append("a weight or an activation exceeded fp16's range (|x| > 65504) inside the fused MLP")
             if bits & _lib.NFL_STATUS_NONFINITE:
                 what.append("a composited per-ray output was not finite")
+            if bits & _lib.NFL_STATUS_POSE_ID:
+                what.append("an image id of a posed_rays batch has no pose (outside the id -> row table); its ray is NaN")
             raise FloatingPointError(f"nerf_fl_amd: render pass on {k}: " + "; ".join(what)
                                      + " (see INTEGRATION.md, 'Numerical range')")
+
+
+def fill_barf_weights(embeddings, epoch, buffers):
+    """Write the BARF per-frequency weights of `epoch` (BarfPosEmbedding.weights, quirks included) into the caller's
+    device buffers `(w_xyz, w_dir)` in place, for `render_rays(..., barf_weights=buffers)`.  A host -> device copy: call it
+    outside graph capture (RayTrainer does when its epoch changes), as Adam.sync_hyper()."""
+    for key, buf in zip(("xyz", "dir"), buffers):
+        emb = embeddings[key]
+        w = emb.weights(epoch) if hasattr(emb, "weights") else \
+            torch.tensor([float(emb.barf_weight(f, epoch)) for f in emb.freqs], dtype=torch.float32)
+        buf.copy_(w)
+    return buffers
 
 
 def _stream():
@@ -765,7 +780,16 @@ def render_rays(models, embeddings, rays, ts, N_samples=64, use_disp=False, pert
             cfg["loss"] = dict(target=_f32c(kwargs["loss_target"], "loss_target", (R, 3)),
                                losses=torch.zeros(4, dtype=torch.float32, device=dev),
                                coef=float(kwargs.get("loss_coef", 1.0)), lambda_u=float(kwargs.get("lambda_u", 0.01)))
-        if getattr(models["coarse"], "refine_pose", False):
+        if getattr(models["coarse"], "refine_pose", False) and kwargs.get("barf_weights") is not None:
+            # build-defined: the BARF weights as device buffers the caller owns and refills per epoch (fill_barf_weights),
+            # so that a captured step reads the current epoch's weights without a host -> device copy of its own
+            w_xyz, w_dir = kwargs["barf_weights"]
+            for name, w, n in (("barf_weights[0]", w_xyz, n_xyz), ("barf_weights[1]", w_dir, n_dir)):
+                if not (isinstance(w, torch.Tensor) and w.device == dev and w.dtype == torch.float32
+                        and tuple(w.shape) == (n,) and w.is_contiguous() and w.data_ptr() % 16 == 0):
+                    raise ValueError(f"`{name}` must be a 16-byte aligned, contiguous fp32 ({n},) tensor on {dev}")
+            cfg["pe_w_xyz"], cfg["pe_w_dir"] = w_xyz.detach(), w_dir.detach()
+        elif getattr(models["coarse"], "refine_pose", False):
             # BARF (reference rendering.py:105-108, 235-238): coarse-to-fine weights of both encodings
             epoch = kwargs.get("current_epoch")
             if epoch is None:

@@ -10,7 +10,9 @@ What it keeps from the reference:
 What it does differently, because the renderer is ~10^3 x faster than the data path around it:
   * rays / colours / image ids live on the GPU as flat tensors; a batch is a slice of a device-side
     permutation (no DataLoader workers, no per-item collation: train.py:144-149);
-  * rays are the upstream 8-column Blender contract (o, d, near, far) handed straight to render_rays;
+  * rays are the upstream 8-column Blender contract (o, d, near, far) handed straight to render_rays; with
+    refine_pose=True they are the fork's camera-frame layout, turned into world rays by the HIP pose kernels
+    (poses.posed_rays) inside the step;
   * multi-GPU: every rank shuffles its own shard; gradients are averaged with one flat all-reduce.
 """
 import math
@@ -20,8 +22,9 @@ import torch
 from torch import nn
 
 from . import parallel
-from .nerf import NeRF, PosEmbedding
-from .rendering import render_rays
+from .nerf import BarfPosEmbedding, NeRF, PosEmbedding
+from .poses import LearnPose, posed_rays, row_table
+from .rendering import fill_barf_weights, render_rays
 
 __all__ = ["NerfWLoss", "psnr", "Adam", "RayTrainer", "GraphedTrainStep"]
 
@@ -233,13 +236,21 @@ class GraphedTrainStep:
 
     def __init__(self, models, embeddings, params, opt, loss_fn, rays, ts, target, N_samples, N_importance,
                  use_disp=False, perturb=1.0, noise_std=1.0, white_back=True, all_reduce=False, warmup=2,
-                 loss_coef=1.0, lambda_u=0.01, arena=None, capture_all_reduce=None, force_all_reduce=False):
+                 loss_coef=1.0, lambda_u=0.01, arena=None, capture_all_reduce=None, force_all_reduce=False,
+                 pose=None, row_of_id=None, barf_weights=None, keep_graph=False):
         """loss_coef / lambda_u: NerfWLoss's constants for the fused loss (loss_fn=None); with a loss_fn they are its own.
         arena: the GradArena that holds the parameters' gradients (created here when None): the backward writes into it
         and the all-reduce runs on it in place.
         capture_all_reduce: record the collective INSIDE the one graph (RCCL supports stream capture); None = yes for
         the nccl backend, no otherwise (gloo cannot be captured: the step is then two graphs around an eager collective).
-        force_all_reduce: issue the collective at world size 1 too (exercises RCCL on a single GPU)."""
+        force_all_reduce: issue the collective at world size 1 too (exercises RCCL on a single GPU).
+        pose / row_of_id: learnable poses (poses.LearnPose, its parameters in `params`) and the image id -> pose row table:
+        `rays` is then the camera-frame layout (direction, near, far, ...) and `ts` the image ids, and the pose forward and
+        backward (poses.posed_rays) are captured with the rest of the step.
+        barf_weights: (w_xyz, w_dir) device buffers for fields built with refine_pose=True (rendering.fill_barf_weights
+        refills them between replays).
+        keep_graph: keep the captured graph after instantiation (torch.cuda.CUDAGraph(keep_graph=True)), so that it can be
+        inspected through raw_cuda_graph()."""
         if not getattr(opt, "capturable", False):
             raise ValueError("GraphedTrainStep needs nerf_fl_amd.train.Adam(capturable=True)")
         import torch.distributed as dist
@@ -252,16 +263,19 @@ class GraphedTrainStep:
         self.captured_collective = bool(capture_all_reduce) and self.all_reduce
         dev = self.rays.device
 
+        extra = {} if barf_weights is None else dict(barf_weights=barf_weights)
+
         def fwd_bwd():
             # (parameters the backward never reaches keep the zeros the arena was created with)
+            rays = self.rays if pose is None else posed_rays(pose, self.rays, self.ts, row_of_id, grad_arena=self.arena)
             if loss_fn is None:      # NerfWLoss fused into the render kernels' per-ray epilogue (render_rays: loss_target)
-                res = render_rays(models, embeddings, self.rays, self.ts, N_samples, use_disp, perturb, noise_std,
+                res = render_rays(models, embeddings, rays, self.ts, N_samples, use_disp, perturb, noise_std,
                                   N_importance, 32768, white_back, False, loss_target=self.target,
-                                  loss_coef=loss_coef, lambda_u=lambda_u, grad_arena=self.arena)
+                                  loss_coef=loss_coef, lambda_u=lambda_u, grad_arena=self.arena, **extra)
                 total = res["_nerfw_loss"]
             else:
-                res = render_rays(models, embeddings, self.rays, self.ts, N_samples, use_disp, perturb, noise_std,
-                                  N_importance, 32768, white_back, False, grad_arena=self.arena)
+                res = render_rays(models, embeddings, rays, self.ts, N_samples, use_disp, perturb, noise_std,
+                                  N_importance, 32768, white_back, False, grad_arena=self.arena, **extra)
                 total = sum(loss_fn(res, self.target).values())
             total.backward()
             key = "rgb_fine" if "rgb_fine" in res else "rgb_coarse"
@@ -284,7 +298,7 @@ class GraphedTrainStep:
         if missing:      # a captured opt.step() would skip them for ever
             raise RuntimeError(f"GraphedTrainStep: {len(missing)} trainable parameters have no gradient after the warm-up "
                                f"steps (first: index {missing[0]}); pass only parameters the step reaches")
-        self.graph = torch.cuda.CUDAGraph()
+        self.graph = torch.cuda.CUDAGraph(keep_graph=True) if keep_graph else torch.cuda.CUDAGraph()
         self.graph_opt = None
         # With a process group alive, its watchdog thread polls the events of earlier collectives (hipEventQuery) at any
         # time; under the default "global" capture mode such a call from ANOTHER thread invalidates the capture
@@ -300,6 +314,10 @@ class GraphedTrainStep:
             self.graph_opt = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph_opt, pool=self.graph.pool(), **mode):
                 opt.step()
+        if keep_graph:
+            self.graph.instantiate()
+            if self.graph_opt is not None:
+                self.graph_opt.instantiate()
 
     def load(self, rays, ts, target):
         self.rays.copy_(rays)
@@ -326,10 +344,29 @@ class RayTrainer:
     def __init__(self, device, N_emb_xyz=10, N_emb_dir=4, N_samples=64, N_importance=64, use_disp=False,
                  perturb=1.0, noise_std=1.0, white_back=True, encode_a=False, encode_t=False, N_vocab=100,
                  N_a=48, N_tau=16, beta_min=0.1, lr=5e-4, batch_size=1024, lr_scheduler=None, num_epochs=16,
-                 decay_step=(20,), decay_gamma=0.1, seed=0, use_graph=False):
+                 decay_step=(20,), decay_gamma=0.1, seed=0, use_graph=False, refine_pose=False, init_c2w=None,
+                 image_ids=None):
         """use_graph: run the steps of fit_epoch from one captured HIP graph (GraphedTrainStep).  At the README batch of
         1024 rays the ~35 launches of an eager step are the critical path (1.9 vs 1.67 ms per step); at 4096 rays it
-        makes no difference.  The first fit_epoch call spends two extra steps on its first batch (warm-up before the capture)."""
+        makes no difference.  The first fit_epoch call spends two extra steps on its first batch (warm-up before the capture).
+
+        refine_pose: the reference's --refine_pose (train.py:42-44, 84-98, 136): BARF embeddings BarfPosEmbedding(N-1, N, 4, 8),
+        fields built with refine_pose=True, and a LearnPose(C, True, True, init_c2w) under the checkpoint prefix
+        `learn_poses`, trained by the same Adam through the same GradArena.  `step` / `fit_epoch` then take the fork's
+        training layout: rays = camera-frame direction, near, far (further columns ignored), ts = image ids; the BARF
+        weights follow `current_epoch` (0 in the first fit_epoch call, as Lightning's).
+        init_c2w: (C, 3|4, 4) initial camera-to-world poses (None: identity, C = len(image_ids) or N_vocab).
+        image_ids: the image id of each pose row (the reference's `enumerate(poses_dict.keys())`); default 0 .. C-1."""
+        self.refine_pose = bool(refine_pose)
+        if not self.refine_pose and (init_c2w is not None or image_ids is not None):
+            raise ValueError("init_c2w / image_ids are the poses of refine_pose=True")
+        if self.refine_pose:
+            init_c2w = self._init_poses(init_c2w, image_ids, N_vocab)
+            n_cams = init_c2w.shape[0] if init_c2w is not None else (len(image_ids) if image_ids is not None else int(N_vocab))
+            ids = list(range(n_cams)) if image_ids is None else [int(i) for i in image_ids]
+            if len(ids) != n_cams:
+                raise ValueError(f"image_ids has {len(ids)} entries for {n_cams} poses")
+            row_of_id = row_table(ids)                 # validates: distinct, >= 0
         self.dev = torch.device(device)
         if self.dev.type != "cuda":
             raise RuntimeError("nerf_fl_amd.train.RayTrainer needs a ROCm device (this build has no CPU path)")
@@ -342,21 +379,35 @@ class RayTrainer:
         import torch.distributed as dist
         from .rendering import set_rounding_seed
         set_rounding_seed(seed * 1000003 + (dist.get_rank() if dist.is_initialized() else 0))
-        self.embeddings = {"xyz": PosEmbedding(N_emb_xyz - 1, N_emb_xyz), "dir": PosEmbedding(N_emb_dir - 1, N_emb_dir)}
+        if self.refine_pose:
+            self.embeddings = {"xyz": BarfPosEmbedding(N_emb_xyz - 1, N_emb_xyz, 4, 8),
+                               "dir": BarfPosEmbedding(N_emb_dir - 1, N_emb_dir, 4, 8)}
+        else:
+            self.embeddings = {"xyz": PosEmbedding(N_emb_xyz - 1, N_emb_xyz), "dir": PosEmbedding(N_emb_dir - 1, N_emb_dir)}
         self.modules = {}                                   # checkpoint prefix -> module (train.py:48-76)
         if encode_a:
             self.embeddings["a"] = self.modules["embedding_a"] = nn.Embedding(N_vocab, N_a).to(self.dev)
         if encode_t:
             self.embeddings["t"] = self.modules["embedding_t"] = nn.Embedding(N_vocab, N_tau).to(self.dev)
         cx, cd = 6 * N_emb_xyz + 3, 6 * N_emb_dir + 3
-        self.models = {"coarse": NeRF("coarse", in_channels_xyz=cx, in_channels_dir=cd).to(self.dev)}
+        rp = self.refine_pose
+        self.models = {"coarse": NeRF("coarse", in_channels_xyz=cx, in_channels_dir=cd, refine_pose=rp).to(self.dev)}
         self.modules["nerf_coarse"] = self.models["coarse"]
         if N_importance > 0:
             self.models["fine"] = NeRF("fine", in_channels_xyz=cx, in_channels_dir=cd, encode_appearance=encode_a,
                                        in_channels_a=N_a, encode_transient=encode_t, in_channels_t=N_tau,
-                                       beta_min=beta_min).to(self.dev)
+                                       beta_min=beta_min, refine_pose=rp).to(self.dev)
             self.modules["nerf_fine"] = self.models["fine"]
-        self.params = [p for m in self.modules.values() for p in m.parameters()]
+        self.pose = self.row_of_id = self.barf_w = None
+        self.current_epoch = 0                              # Lightning's current_epoch: fit_epoch counts it
+        self._barf_epoch = None
+        if rp:
+            self.pose = self.modules["learn_poses"] = LearnPose(n_cams, True, True, init_c2w).to(self.dev)
+            self.row_of_id = row_of_id.to(self.dev)
+            self.barf_w = (torch.zeros(N_emb_xyz, dtype=torch.float32, device=self.dev),
+                           torch.zeros(N_emb_dir, dtype=torch.float32, device=self.dev))
+        # trainable parameters only (learn_poses.init_c2w is a frozen Parameter, as in the reference)
+        self.params = [p for m in self.modules.values() for p in m.parameters() if p.requires_grad]
         # one-launch Adam.  (torch's own fused=True variant is not an option here: it updates the parameters without
         # moving their version counters, so render_rays never re-packed its weight streams and kept rendering with
         # the initial weights -- tests/test_train_gpu.py: validation PSNR 26.89 -> 26.93 instead of 35.9)
@@ -372,19 +423,61 @@ class RayTrainer:
         self.fused_loss = True          # False: the NerfWLoss module on the result dict (two extra launches), as the reference composes it
         self.gen = torch.Generator(device=self.dev).manual_seed(seed + 1)
 
+    @staticmethod
+    def _init_poses(init_c2w, image_ids, n_vocab):
+        """(C, 3|4, 4) -> (C, 4, 4) fp32 on the host (convert3x4_4x4, utils/lie_group_helper.py:28-47), validated."""
+        if init_c2w is None:
+            return None
+        c2w = torch.as_tensor(init_c2w).detach().to("cpu", torch.float32)
+        if c2w.dim() != 3 or c2w.shape[1] not in (3, 4) or c2w.shape[2] != 4 or c2w.shape[0] < 1:
+            raise ValueError(f"init_c2w must be (C, 3|4, 4), got {tuple(c2w.shape)}")
+        if c2w.shape[1] == 3:
+            c2w = torch.cat([c2w, torch.zeros_like(c2w[:, :1])], 1)
+            c2w[:, 3, 3] = 1.0
+        return c2w.contiguous()
+
+    def _sync_barf(self):
+        """Refill the BARF weight buffers when current_epoch changed (a host -> device copy: outside graph capture)."""
+        if self.refine_pose and self._barf_epoch != self.current_epoch:
+            fill_barf_weights(self.embeddings, self.current_epoch, self.barf_w)
+            self._barf_epoch = self.current_epoch
+
+    def _world_rays(self, rays, ts, grad_arena=None):
+        """Training-layout rays through the learned poses (refine_pose), or the world rays themselves."""
+        if not self.refine_pose:
+            return rays
+        return posed_rays(self.pose, rays, ts, self.row_of_id, grad_arena=grad_arena)
+
+    def c2w(self, rows):
+        """Refined (len(rows), 3, 4) camera-to-world poses of pose rows `rows` (make_c2w(r, t) @ init_c2w), e.g. for
+        eval.render_frame."""
+        if not self.refine_pose:
+            raise RuntimeError("RayTrainer.c2w: poses are learned only with refine_pose=True")
+        rows = torch.as_tensor(rows, dtype=torch.int64, device=self.dev).reshape(-1)
+        with torch.no_grad():
+            return self.pose(rows)[:, :3].clone()
+
+    def _extra(self):
+        self._sync_barf()
+        return {} if not self.refine_pose else dict(barf_weights=self.barf_w)
+
     # ---- one optimisation step on a ready batch ------------------------------------------------
     def step(self, rays, rgbs, ts):
+        """rays: (R, 8) world rays, or with refine_pose the training layout (camera-frame direction, near, far, ...)."""
         hp = self.hp
         self.arena.attach()          # parameters the backward never reaches keep the zeros the arena was created with
+        extra = self._extra()
+        rays = self._world_rays(rays, ts, self.arena)
         if self.fused_loss:
             # NerfWLoss computed in the render kernels' per-ray epilogue, its backward seeds with it
             res = render_rays(self.models, self.embeddings, rays, ts, hp["N_samples"], hp["use_disp"], hp["perturb"],
                               hp["noise_std"], hp["N_importance"], 32768, hp["white_back"], False, loss_target=rgbs,
-                              loss_coef=self.loss.coef, lambda_u=self.loss.lambda_u, grad_arena=self.arena)
+                              loss_coef=self.loss.coef, lambda_u=self.loss.lambda_u, grad_arena=self.arena, **extra)
             total = res["_nerfw_loss"]
         else:
             res = render_rays(self.models, self.embeddings, rays, ts, hp["N_samples"], hp["use_disp"], hp["perturb"],
-                              hp["noise_std"], hp["N_importance"], 32768, hp["white_back"], False, grad_arena=self.arena)
+                              hp["noise_std"], hp["N_importance"], 32768, hp["white_back"], False, grad_arena=self.arena,
+                              **extra)
             total = sum(self.loss(res, rgbs).values())
         total.backward()
         self.arena.all_reduce()
@@ -397,35 +490,48 @@ class RayTrainer:
         n, bs = rays.shape[0], self.hp["batch_size"]
         perm = torch.randperm(n, device=self.dev, generator=self.gen)
         log = []
+        self._sync_barf()
         for i in range(0, n - bs + 1, bs):
             idx = perm[i:i + bs]
             if self.use_graph and self.fused_loss:
                 if self._graphed is None:
-                    import torch.distributed as dist
-                    hp = self.hp
-                    self._graphed = GraphedTrainStep(
-                        self.models, self.embeddings, self.params, self.opt, None, rays[idx], ts[idx], rgbs[idx],
-                        hp["N_samples"], hp["N_importance"], hp["use_disp"], hp["perturb"], hp["noise_std"], hp["white_back"],
-                        all_reduce=dist.is_initialized() and dist.get_world_size() > 1,
-                        loss_coef=self.loss.coef, lambda_u=self.loss.lambda_u, arena=self.arena)
+                    self._graphed = self.graphed_step(rays[idx], ts[idx], rgbs[idx])
                 self._graphed.load(rays[idx], ts[idx], rgbs[idx])
                 log.append(tuple(x.clone() for x in self._graphed.replay()))      # the outputs live in the graph's pool
             else:
                 log.append(self.step(rays[idx], rgbs[idx], ts[idx]))
         if self.sched is not None:
             self.sched.step()
+        self.current_epoch += 1
         from .rendering import check_status
         check_status(self.dev)              # fp16 range audit of the epoch's render passes (raises FloatingPointError)
         return torch.stack([torch.stack(x) for x in log]).mean(0).tolist() if log else [math.nan, math.nan]
 
+    def graphed_step(self, rays, ts, rgbs, **kw):
+        """The GraphedTrainStep fit_epoch replays (use_graph=True), captured on this batch; `kw` go to GraphedTrainStep."""
+        import torch.distributed as dist
+        hp = self.hp
+        self._sync_barf()
+        return GraphedTrainStep(
+            self.models, self.embeddings, self.params, self.opt, None, rays, ts, rgbs,
+            hp["N_samples"], hp["N_importance"], hp["use_disp"], hp["perturb"], hp["noise_std"], hp["white_back"],
+            all_reduce=dist.is_initialized() and dist.get_world_size() > 1,
+            loss_coef=self.loss.coef, lambda_u=self.loss.lambda_u, arena=self.arena,
+            pose=self.pose, row_of_id=self.row_of_id, barf_weights=self.barf_w, **kw)
+
     @torch.no_grad()
     def validate(self, rays, rgbs, ts, chunk=32768):
-        """Mean PSNR of a deterministic render (perturb 0, noise 0; train.py:176-210)."""
+        """Mean PSNR of a deterministic render (perturb 0, noise 0; train.py:176-210).  rays: (R, 8) world rays; with
+        refine_pose, any other width is the training layout and is rendered through the learned poses."""
         hp = self.hp
+        extra = self._extra()
         outs = []
         for i in range(0, rays.shape[0], chunk):
-            res = render_rays(self.models, self.embeddings, rays[i:i + chunk], ts[i:i + chunk], hp["N_samples"],
-                              hp["use_disp"], 0, 0, hp["N_importance"], chunk, hp["white_back"], False)
+            r = rays[i:i + chunk]
+            if self.refine_pose and r.shape[1] != 8:
+                r = self._world_rays(r, ts[i:i + chunk])
+            res = render_rays(self.models, self.embeddings, r, ts[i:i + chunk], hp["N_samples"],
+                              hp["use_disp"], 0, 0, hp["N_importance"], chunk, hp["white_back"], False, **extra)
             outs.append(res["rgb_fine" if "rgb_fine" in res else "rgb_coarse"])
         return float(psnr(torch.cat(outs), rgbs))
 
