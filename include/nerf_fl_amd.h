@@ -380,6 +380,48 @@ int nfl_adam_step(const nfl_adam_tensors* tensors, int32_t n_tensors, float lr, 
 int nfl_adam_step_dev(const nfl_adam_tensors* tensors, int32_t n_tensors, const float* d_hyper, int32_t* d_step,
                       int32_t bump, void* stream);
 
+/* ---- the reference's other optimisers (utils/__init__.py:24-42: --optimizer sgd | adam | radam | ranger with
+ * --momentum and --weight_decay) over up to NFL_ADAM_MAX_TENSORS fp32 tensors in one launch.  t = the 1-based step,
+ * g the gradient, p the parameter; all per-element arithmetic is fp32, every per-launch scalar is computed in fp64
+ * from the fp32 hyper-parameters (in the kernel, for both forms: the eager and the captured launch round alike).
+ *   NFL_OPT_SGD     torch.optim.SGD(lr, momentum, dampening=0, weight_decay), no nesterov:
+ *                     d = g + wd p;  buf = momentum buf + d (buf starts at 0, so buf = d at t = 1);  p -= lr buf.
+ *                     Without a momentum buffer (state0 NULL): p -= lr d.
+ *   NFL_OPT_ADAM    torch.optim.Adam(lr, betas, eps, weight_decay), no amsgrad: g += wd p (coupled L2), then
+ *                     nfl_adam_step's arithmetic in its order (wd = 0: bit-identical to nfl_adam_step).
+ *   NFL_OPT_RADAM   torch_optimizer.RAdam (0.3): v = b2 v + (1-b2) g^2;  m = b1 m + (1-b1) g;
+ *                     N_max = 2/(1-b2) - 1;  N = N_max - 2t b2^t/(1-b2^t);  p -= (lr wd) p (decoupled, wd != 0);
+ *                     N >= threshold: p -= lr r/(1-b1^t) m/(sqrt(v) + eps),
+ *                                     r = sqrt((1-b2^t)(N-4)(N-2) N_max / ((N_max-4)(N_max-2) N));
+ *                     otherwise:      p -= lr/(1-b1^t) m.
+ *   NFL_OPT_RANGER  torch_optimizer.Ranger (0.3) = RAdam with the test N > threshold, then Lookahead: when t % k == 0,
+ *                     slow += alpha (p - slow); p = slow.  (The caller initialises slow to p before the first step.)
+ * hyper = float[NFL_OPT_HYPER] {lr, beta1 | momentum, beta2, eps, weight_decay, alpha, k, threshold}; a kind ignores
+ * what it does not use.  State: state0 = exp_avg | momentum_buffer, state1 = exp_avg_sq, state2 = slow_buffer.
+ * A tensor whose grad pointer is NULL is left untouched.  NFL_EINVAL: NULL tensors / hyper, n_tensors outside
+ * [0, NFL_ADAM_MAX_TENSORS], an unknown kind, step < 1, a NULL param or a NULL state the kind needs (SGD: state0 when
+ * momentum > 0), a negative momentum, Ranger with k < 1.  No memset or memcpy, no atomics: bit-reproducible. */
+#define NFL_OPT_SGD 0
+#define NFL_OPT_ADAM 1
+#define NFL_OPT_RADAM 2
+#define NFL_OPT_RANGER 3
+#define NFL_OPT_HYPER 8
+typedef struct nfl_optim_tensors {
+    float*       param[NFL_ADAM_MAX_TENSORS];
+    const float* grad[NFL_ADAM_MAX_TENSORS];
+    float*       state0[NFL_ADAM_MAX_TENSORS];   /* exp_avg | momentum_buffer */
+    float*       state1[NFL_ADAM_MAX_TENSORS];   /* exp_avg_sq (Adam, RAdam, Ranger) */
+    float*       state2[NFL_ADAM_MAX_TENSORS];   /* slow_buffer (Ranger) */
+    int32_t      numel[NFL_ADAM_MAX_TENSORS];
+} nfl_optim_tensors;
+int nfl_optim_step(const nfl_optim_tensors* tensors, int32_t n_tensors, int32_t kind, const float* hyper, int32_t step,
+                   void* stream);
+/* Graph-capturable form, as nfl_adam_step_dev: d_hyper = float[NFL_OPT_HYPER] in device memory, *d_step = updates
+ * already applied (the kernel uses *d_step + 1), bump != 0 increments *d_step after the update.  SGD: a NULL state0
+ * means no momentum (the device-side momentum is then not read). */
+int nfl_optim_step_dev(const nfl_optim_tensors* tensors, int32_t n_tensors, int32_t kind, const float* d_hyper,
+                       int32_t* d_step, int32_t bump, void* stream);
+
 /* ---- NerfWLoss (reference losses.py:35-50) on the renderer's outputs, forward and backward in one launch each.
  * Terms (d_losses[4], zeroed by nfl_loss_forward): c_l, f_l, b_l, s_l; f_l uses beta when d_beta != NULL
  * (then d_rgb_fine is required; b_l and, with d_transient_sigmas, s_l are produced too).

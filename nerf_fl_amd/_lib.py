@@ -115,6 +115,16 @@ class AdamTensors(C.Structure):
                 ("numel", C.c_int32 * NFL_ADAM_MAX_TENSORS)]
 
 
+NFL_OPT_SGD, NFL_OPT_ADAM, NFL_OPT_RADAM, NFL_OPT_RANGER = 0, 1, 2, 3
+NFL_OPT_HYPER = 8      # lr, beta1 | momentum, beta2, eps, weight_decay, alpha, k, threshold
+
+
+class OptimTensors(C.Structure):
+    _fields_ = [("param", C.c_void_p * NFL_ADAM_MAX_TENSORS), ("grad", C.c_void_p * NFL_ADAM_MAX_TENSORS),
+                ("state0", C.c_void_p * NFL_ADAM_MAX_TENSORS), ("state1", C.c_void_p * NFL_ADAM_MAX_TENSORS),
+                ("state2", C.c_void_p * NFL_ADAM_MAX_TENSORS), ("numel", C.c_int32 * NFL_ADAM_MAX_TENSORS)]
+
+
 class LossArgs(C.Structure):
     _fields_ = [("d_rgb_coarse", C.c_void_p), ("d_rgb_fine", C.c_void_p), ("d_beta", C.c_void_p),
                 ("d_transient_sigmas", C.c_void_p), ("d_target", C.c_void_p), ("n_rays", C.c_int32), ("n_samples", C.c_int32),
@@ -167,6 +177,10 @@ SYMBOLS = [
     ("nfl_adam_step", C.c_int, [C.POINTER(AdamTensors), C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32,
                                 C.c_void_p]),
     ("nfl_adam_step_dev", C.c_int, [C.POINTER(AdamTensors), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("nfl_optim_step", C.c_int, [C.POINTER(OptimTensors), C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int32,
+                                 C.c_void_p]),
+    ("nfl_optim_step_dev", C.c_int, [C.POINTER(OptimTensors), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                     C.c_void_p]),
     ("nfl_loss_forward", C.c_int, [C.POINTER(LossArgs), C.c_void_p]),
     ("nfl_loss_backward", C.c_int, [C.POINTER(LossArgs), C.c_void_p]),
     ("nfl_pose_rays", C.c_int, [C.POINTER(PoseArgs), C.c_void_p]),

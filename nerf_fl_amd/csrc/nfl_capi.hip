@@ -107,7 +107,9 @@ int nfl_field_forward(const void* h_plan, const void* d_plan, const void* d_pack
 
 int nfl_abi_version(void) { return NFL_ABI_VERSION; }
 
-const char* nfl_version(void) { return "nerf_fl_amd 0.1 (gfx950, HIP; abi 8)"; }
+#define NFL_STR_(x) #x
+#define NFL_STR(x) NFL_STR_(x)
+const char* nfl_version(void) { return "nerf_fl_amd 0.1 (gfx950, HIP; abi " NFL_STR(NFL_ABI_VERSION) ")"; }
 
 const char* nfl_strerror(int code) {
     switch (code) {

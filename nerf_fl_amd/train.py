@@ -5,8 +5,9 @@ What it keeps from the reference:
   * modules and their checkpoint key prefixes -- `nerf_coarse.*`, `nerf_fine.*`, `embedding_a.*`,
     `embedding_t.*` (train.py:51-76) -- so `utils.load_ckpt` (utils/__init__.py:67-88) and this
     harness can exchange weights;
-  * Adam(lr, eps=1e-8) (utils/__init__.py:30-32), optional cosine / step decay per epoch
-    (utils/__init__.py:44-61), NerfWLoss (losses.py:18-50), PSNR = -10 log10(mse) (metrics.py:12-13).
+  * the optimisers of --optimizer sgd | adam | radam | ranger with --momentum / --weight_decay (utils/__init__.py:24-42),
+    the per-epoch schedules steplr / cosine / poly with the linear warm-up (utils/__init__.py:44-61,
+    utils/warmup_scheduler.py), NerfWLoss (losses.py:18-50), PSNR = -10 log10(mse) (metrics.py:12-13).
 What it does differently, because the renderer is ~10^3 x faster than the data path around it:
   * rays / colours / image ids live on the GPU as flat tensors; a batch is a slice of a device-side
     permutation (no DataLoader workers, no per-item collation: train.py:144-149);
@@ -21,12 +22,13 @@ import os
 import torch
 from torch import nn
 
-from . import parallel
+from . import _lib, parallel
 from .nerf import BarfPosEmbedding, NeRF, PosEmbedding
 from .poses import LearnPose, posed_rays, row_table
 from .rendering import fill_barf_weights, render_rays
 
-__all__ = ["NerfWLoss", "psnr", "Adam", "RayTrainer", "GraphedTrainStep"]
+__all__ = ["NerfWLoss", "psnr", "Adam", "SGD", "RAdam", "Ranger", "GradualWarmupLR", "make_optimizer", "make_scheduler",
+           "RayTrainer", "GraphedTrainStep"]
 
 
 class NerfWLoss(nn.Module):
@@ -102,38 +104,77 @@ def psnr(pred, gt):
     return -10.0 * torch.log10(((pred - gt) ** 2).mean())
 
 
-class Adam(torch.optim.Optimizer):
-    """torch.optim.Adam(lr, betas, eps) -- no weight decay, no amsgrad, the reference's settings
-    (utils/__init__.py:30-32) -- with the whole step in ONE kernel launch (C ABI `nfl_adam_step`).  A regular
-    torch Optimizer otherwise: param_groups (LR schedulers work), state[p] = {step, exp_avg, exp_avg_sq} with
-    torch's names, so state_dict()s are interchangeable with torch.optim.Adam's."""
+class _OneLaunchOptimizer(torch.optim.Optimizer):
+    """Shared machinery of this package's optimisers: each (param group, device, step) is updated by ONE kernel launch per
+    NFL_ADAM_MAX_TENSORS tensors, the parameters' version counters are moved after it (render_rays re-packs its weight
+    streams on that), and with capturable=True the launch reads its hyper-parameters and the step count from device
+    memory, so that `step()` can be captured in a HIP graph (GraphedTrainStep).  A regular torch Optimizer otherwise:
+    param_groups (LR schedulers work) and per-parameter state under torch's names.
 
-    def __init__(self, params, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, capturable=False):
-        """capturable=True: learning rate, betas, eps and the step count are kept in device memory and read by the
-        kernel (C ABI `nfl_adam_step_dev`), so `step()` can be captured in a HIP graph and replayed while a scheduler
-        changes the rate (GraphedTrainStep); `sync_hyper()` uploads the current param_groups' values.
-        The device-side step count is ONE counter per (param group, device), seeded from the largest host-side step of
-        the group: all tensors of a group share their bias corrections (torch.optim.Adam counts per parameter; the two
-        agree whenever every parameter of a group receives a gradient at every step, which is how this package trains)."""
-        self._dev = {}            # (group index, device) -> dict(hyper=float[4] tensor, step=int32 tensor, host=tuple)
+    capturable=True: the device-side step count is ONE counter per (param group, device), seeded from the largest host-side
+    step of the group: all tensors of a group share their bias corrections (torch counts per parameter; the two agree
+    whenever every parameter of a group receives a gradient at every step, which is how this package trains).
+    `sync_hyper()` uploads the current param_groups' values; `note_replay()` counts a replayed captured step."""
+
+    _name = "optimizer"
+    _state_keys = ()          # per-parameter state tensors, created as zeros on the first step
+    _counts_steps = True      # state[p]["step"] (torch.optim.SGD keeps none)
+
+    def __init__(self, params, defaults, capturable):
+        self._dev = {}            # (group index, device) -> dict(hyper=float[8] tensor, step=int32 tensor, host=tuple)
         self._captured = set()    # id(p) of the parameters a captured step() updates
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
+        super().__init__(params, defaults)
         self.capturable = bool(capturable)
 
+    # ---- per-kind hooks ----------------------------------------------------------------------------------------
+    def _hyper(self, group):
+        """The NFL_OPT_HYPER floats of a group: lr, beta1 | momentum, beta2, eps, weight_decay, alpha, k, threshold."""
+        raise NotImplementedError
+
+    def _kind(self, group):
+        raise NotImplementedError
+
+    def _init_state(self, p, st, group):
+        if self._counts_steps:
+            st["step"] = 0
+        for k in self._state_keys:
+            st[k] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+
+    def _state_ptrs(self, st):
+        """(state0, state1, state2) of nfl_optim_tensors, None where the kind has none."""
+        ptrs = [st[k] if st.get(k) is not None else None for k in self._state_keys]
+        return tuple(ptrs + [None] * (3 - len(ptrs)))
+
+    # ---- device-side state ------------------------------------------------------------------------------------
     def _dev_state(self, gi, group, dev):
         k = (gi, str(dev))
         if k not in self._dev:
-            steps = [int(self.state[p]["step"]) for p in group["params"] if self.state.get(p)]
-            self._dev[k] = dict(hyper=torch.zeros(4, dtype=torch.float32, device=dev),
-                                step=torch.full((1,), max(steps) if steps else 0, dtype=torch.int32, device=dev), host=None)
+            self._dev[k] = dict(hyper=torch.zeros(_lib.NFL_OPT_HYPER, dtype=torch.float32, device=dev),
+                                step=torch.full((1,), self._group_step(group), dtype=torch.int32, device=dev), host=None)
         return self._dev[k]
 
+    def _group_step(self, group):
+        steps = [int(self.state[p]["step"]) for p in group["params"] if "step" in self.state.get(p, {})]
+        return max(steps) if steps else 0
+
     def load_state_dict(self, state_dict):
-        """torch's loader, then the device-side step counters of a capturable optimizer are dropped so that the next
-        step() re-seeds them from the loaded state (bias corrections follow the checkpoint, not the steps this object took
-        before)."""
+        """torch's loader, then the loaded values are copied INTO the state tensors this optimizer already had, and the
+        device-side step counters are reset in place from the loaded steps (hyper-parameters re-uploaded by the next
+        sync_hyper()): a step() captured before keeps reading and writing live memory, and continues from the checkpoint."""
+        old = {p: {k: v for k, v in st.items() if torch.is_tensor(v) and k in self._state_keys}
+               for p, st in self.state.items()}
         super().load_state_dict(state_dict)
-        self._dev = {}
+        for p, st in self.state.items():
+            if "step" in st:
+                st["step"] = int(st["step"])             # torch.optim.RAdam / SGD checkpoints hold tensors
+            for k, t in old.get(p, {}).items():
+                new = st.get(k)
+                if torch.is_tensor(new) and new.shape == t.shape:
+                    t.copy_(new)
+                    st[k] = t
+        for (gi, _dev), ds in self._dev.items():
+            ds["step"].fill_(self._group_step(self.param_groups[gi]))
+            ds["host"] = None
 
     def add_param_group(self, param_group):
         super().add_param_group(param_group)
@@ -141,11 +182,10 @@ class Adam(torch.optim.Optimizer):
             self._dev = {}
 
     def sync_hyper(self):
-        """Upload lr / betas / eps of every param group to the device copies the captured launches read (host -> device
+        """Upload the hyper-parameters of every param group to the device copies the captured launches read (host -> device
         copies: call it outside graph capture; GraphedTrainStep.replay() does)."""
         for (gi, _dev), st in self._dev.items():
-            g = self.param_groups[gi]
-            host = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]))
+            host = tuple(float(x) for x in self._hyper(self.param_groups[gi]))
             if st["host"] != host:
                 st["hyper"].copy_(torch.tensor(host, dtype=torch.float32))
                 st["host"] = host
@@ -153,74 +193,288 @@ class Adam(torch.optim.Optimizer):
     def note_replay(self):
         """A captured step() was replayed: advance the host-side step counts (state_dict compatibility) of the parameters
         the captured launch updates (those that had a gradient when it was captured)."""
+        if not self._counts_steps:
+            return
         for group in self.param_groups:
             for p in group["params"]:
                 if self.state.get(p) and (not self._captured or id(p) in self._captured):
                     self.state[p]["step"] = int(self.state[p]["step"]) + 1
 
+    # ---- the step ---------------------------------------------------------------------------------------------
+    def _launch(self, L, group, chunk, step, ds, last, stream):
+        import ctypes as C
+        t = _lib.OptimTensors()
+        for k, (p, g, st) in enumerate(chunk):
+            s0, s1, s2 = self._state_ptrs(st)
+            t.param[k], t.grad[k] = p.data_ptr(), g.data_ptr()
+            t.state0[k], t.state1[k], t.state2[k] = (x.data_ptr() if x is not None else None for x in (s0, s1, s2))
+            t.numel[k] = p.numel()
+        kind = self._kind(group)
+        if ds is not None:
+            _lib.check(L.nfl_optim_step_dev(C.byref(t), len(chunk), kind, C.c_void_p(ds["hyper"].data_ptr()),
+                                            C.c_void_p(ds["step"].data_ptr()), int(last), stream), "nfl_optim_step_dev")
+        else:
+            hyper = (C.c_float * _lib.NFL_OPT_HYPER)(*self._hyper(group))
+            _lib.check(L.nfl_optim_step(C.byref(t), len(chunk), kind, hyper, max(1, step), stream), "nfl_optim_step")
+
     @torch.no_grad()
     def step(self, closure=None):
         import ctypes as C
-
-        from . import _lib
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         L = _lib.lib()
+        who = f"nerf_fl_amd.train.{type(self).__name__}"
         capturing = self.capturable and torch.cuda.is_current_stream_capturing()
         for gi, group in enumerate(self.param_groups):
             if self.capturable:                  # device-side counters start from the steps ALREADY taken
                 for dev in {p.device for p in group["params"] if p.grad is not None}:
                     self._dev_state(gi, group, dev)
-            todo = {}                            # (device, step) -> list of (p, grad, m, v)
+            todo = {}                            # (device, step) -> list of (p, grad, state)
             for p in group["params"]:
                 if p.grad is None:
                     continue
                 if not p.is_cuda or p.dtype != torch.float32 or p.grad.is_sparse:
-                    raise RuntimeError("nerf_fl_amd.train.Adam: dense fp32 parameters on a ROCm device only")
-                st = self.state[p]
-                if not st:
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                if not capturing:                # a captured launch runs at replay time: note_replay() counts it
-                    st["step"] = int(st["step"]) + 1
-                else:
-                    self._captured.add(id(p))
+                    raise RuntimeError(f"{who}: dense fp32 parameters on a ROCm device only")
                 if not p.is_contiguous():
-                    raise RuntimeError("nerf_fl_amd.train.Adam: parameters must be contiguous")
+                    raise RuntimeError(f"{who}: parameters must be contiguous")
+                st = self.state[p]
+                if any(st.get(k) is None for k in self._state_keys) or (self._counts_steps and "step" not in st):
+                    if capturing:                # no allocation or copy inside a capture: the state exists before it
+                        raise RuntimeError(f"{who}: run one eager step() before capture")
+                    self._init_state(p, st, group)
+                if self._counts_steps:
+                    if not capturing:            # a captured launch runs at replay time: note_replay() counts it
+                        st["step"] = int(st["step"]) + 1
+                if capturing:
+                    self._captured.add(id(p))
                 # capturable: one device-side counter per (group, device), so all of a group's tensors step together
-                todo.setdefault((p.device, 0 if self.capturable else st["step"]), []).append(
-                    (p, p.grad.contiguous(), st["exp_avg"], st["exp_avg_sq"]))
-            b1, b2 = group["betas"]
+                key = 0 if self.capturable or not self._counts_steps else st["step"]
+                todo.setdefault((p.device, key), []).append((p, p.grad.contiguous(), st))
             for (dev, step), items in todo.items():
                 with torch.cuda.device(dev):
                     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+                    ds = None
                     if self.capturable:
                         ds = self._dev_state(gi, group, dev)
                         if not capturing:
                             self.sync_hyper()
                         elif ds["host"] is None:
-                            raise RuntimeError("nerf_fl_amd.train.Adam: run one eager step() (or sync_hyper()) before capture")
+                            raise RuntimeError(f"{who}: run one eager step() (or sync_hyper()) before capture")
                     for i0 in range(0, len(items), _lib.NFL_ADAM_MAX_TENSORS):
                         chunk = items[i0:i0 + _lib.NFL_ADAM_MAX_TENSORS]
-                        t = _lib.AdamTensors()
-                        for k, (p, g, m, v) in enumerate(chunk):
-                            t.param[k], t.grad[k], t.exp_avg[k], t.exp_avg_sq[k] = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
-                            t.numel[k] = p.numel()
-                        if self.capturable:
-                            last = i0 + _lib.NFL_ADAM_MAX_TENSORS >= len(items)
-                            _lib.check(L.nfl_adam_step_dev(C.byref(t), len(chunk), C.c_void_p(ds["hyper"].data_ptr()),
-                                                           C.c_void_p(ds["step"].data_ptr()), int(last), stream),
-                                       "nfl_adam_step_dev")
-                        else:
-                            _lib.check(L.nfl_adam_step(C.byref(t), len(chunk), float(group["lr"]), float(b1), float(b2),
-                                                       float(group["eps"]), step, stream), "nfl_adam_step")
+                        self._launch(L, group, chunk, step, ds, i0 + _lib.NFL_ADAM_MAX_TENSORS >= len(items), stream)
                         # the kernel wrote the parameters behind autograd's back: bump their version counters, which
                         # is what tells render_rays to re-pack the weight streams (and autograd to refuse stale graphs)
-                        torch.autograd.graph.increment_version([p for p, _, _, _ in chunk])
+                        torch.autograd.graph.increment_version([p for p, _, _ in chunk])
         return loss
+
+
+class Adam(_OneLaunchOptimizer):
+    """torch.optim.Adam(lr, betas, eps, weight_decay) -- coupled L2 weight decay, no amsgrad; the reference's settings are
+    lr, eps=1e-8 and --weight_decay (utils/__init__.py:30-32) -- with the whole step in ONE kernel launch.
+    state[p] = {step, exp_avg, exp_avg_sq} with torch's names, so state_dict()s are interchangeable with torch.optim.Adam's.
+    weight_decay == 0 runs C ABI `nfl_adam_step` (`_dev` when capturable), otherwise `nfl_optim_step(NFL_OPT_ADAM)`; a
+    captured step keeps the launch it was captured with."""
+
+    _name = "Adam"
+    _state_keys = ("exp_avg", "exp_avg_sq")
+
+    def __init__(self, params, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False):
+        """capturable=True: learning rate, betas, eps, weight decay and the step count are kept in device memory and read
+        by the kernel, so `step()` can be captured in a HIP graph and replayed while a scheduler changes the rate."""
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), capturable)
+
+    def _hyper(self, group):
+        b1, b2 = group["betas"]
+        return (group["lr"], b1, b2, group["eps"], group["weight_decay"], 0.0, 0.0, 0.0)
+
+    def _kind(self, group):
+        return _lib.NFL_OPT_ADAM
+
+    def _launch(self, L, group, chunk, step, ds, last, stream):
+        if group["weight_decay"] != 0:
+            return super()._launch(L, group, chunk, step, ds, last, stream)
+        import ctypes as C
+        t = _lib.AdamTensors()
+        for k, (p, g, st) in enumerate(chunk):
+            t.param[k], t.grad[k] = p.data_ptr(), g.data_ptr()
+            t.exp_avg[k], t.exp_avg_sq[k] = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
+            t.numel[k] = p.numel()
+        if ds is not None:       # the hyper vector's first four floats are nfl_adam_step_dev's {lr, beta1, beta2, eps}
+            _lib.check(L.nfl_adam_step_dev(C.byref(t), len(chunk), C.c_void_p(ds["hyper"].data_ptr()),
+                                           C.c_void_p(ds["step"].data_ptr()), int(last), stream), "nfl_adam_step_dev")
+        else:
+            b1, b2 = group["betas"]
+            _lib.check(L.nfl_adam_step(C.byref(t), len(chunk), float(group["lr"]), float(b1), float(b2),
+                                       float(group["eps"]), step, stream), "nfl_adam_step")
+
+
+class SGD(_OneLaunchOptimizer):
+    """torch.optim.SGD(lr, momentum, dampening=0, weight_decay), no nesterov (the reference's --optimizer sgd,
+    utils/__init__.py:27-29), one launch of `nfl_optim_step(NFL_OPT_SGD)`.  state[p] = {momentum_buffer} (none without
+    momentum), loadable by torch.optim.SGD.  The buffer starts at zero, which makes the first update buf = g exactly."""
+
+    _name = "SGD"
+    _counts_steps = False
+
+    def __init__(self, params, lr, momentum=0.0, weight_decay=0.0, capturable=False):
+        if momentum < 0.0:
+            raise ValueError(f"momentum must be >= 0, got {momentum}")
+        self._state_keys = ("momentum_buffer",) if momentum != 0.0 else ()
+        # dampening / nesterov: torch.optim.SGD's fixed settings here, in the groups so that its step() can continue them
+        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, dampening=0, nesterov=False),
+                         capturable)
+
+    def _hyper(self, group):
+        return (group["lr"], group["momentum"], 0.0, 0.0, group["weight_decay"], 0.0, 0.0, 0.0)
+
+    def _kind(self, group):
+        return _lib.NFL_OPT_SGD
+
+
+class RAdam(_OneLaunchOptimizer):
+    """torch_optimizer.RAdam (0.3; the reference's --optimizer radam, utils/__init__.py:33-35): rectified Adam with
+    decoupled weight decay, un-rectified while N_sma < 5.  Arithmetic in include/nerf_fl_amd.h (NFL_OPT_RADAM); the same
+    algorithm as torch.optim.RAdam(decoupled_weight_decay=True).  state[p] = {step, exp_avg, exp_avg_sq}; state_dict()
+    stores the steps as tensors, so it loads into torch.optim.RAdam.  Per-group step sizes (torch_optimizer caches them
+    across groups)."""
+
+    _name = "RAdam"
+    _state_keys = ("exp_avg", "exp_avg_sq")
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False):
+        # decoupled_weight_decay: what torch.optim.RAdam needs to continue this state with the same algorithm
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, decoupled_weight_decay=True),
+                         capturable)
+
+    def _hyper(self, group):
+        b1, b2 = group["betas"]
+        return (group["lr"], b1, b2, group["eps"], group["weight_decay"], 0.0, 0.0, 5.0)
+
+    def _kind(self, group):
+        return _lib.NFL_OPT_RADAM
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["state"] = {i: {k: (torch.tensor(float(v), dtype=torch.float32) if k == "step" else v) for k, v in st.items()}
+                       for i, st in sd["state"].items()}
+        return sd
+
+
+class Ranger(RAdam):
+    """torch_optimizer.Ranger (0.3; the reference's --optimizer ranger, utils/__init__.py:36-38): RAdam (rectified while
+    N_sma > N_sma_threshhold = 5) plus Lookahead -- every k-th step slow += alpha (p - slow), p = slow, with slow a copy
+    of p taken when the state is created.  No gradient centralisation (0.3's Ranger has none).
+    state[p] = {step, exp_avg, exp_avg_sq, slow_buffer}."""
+
+    _name = "Ranger"
+    _state_keys = ("exp_avg", "exp_avg_sq", "slow_buffer")
+
+    def __init__(self, params, lr=1e-3, alpha=0.5, k=6, betas=(0.95, 0.999), eps=1e-8, weight_decay=0.0,
+                 capturable=False):
+        if not 0.0 <= alpha <= 1.0 or int(k) < 1:
+            raise ValueError(f"Ranger needs 0 <= alpha <= 1 and k >= 1, got alpha={alpha}, k={k}")
+        _OneLaunchOptimizer.__init__(self, params, dict(lr=lr, alpha=alpha, k=int(k), N_sma_threshhold=5, betas=betas,
+                                                        eps=eps, weight_decay=weight_decay), capturable)
+
+    def _hyper(self, group):
+        b1, b2 = group["betas"]
+        return (group["lr"], b1, b2, group["eps"], group["weight_decay"], group["alpha"], group["k"],
+                group["N_sma_threshhold"])
+
+    def _kind(self, group):
+        return _lib.NFL_OPT_RANGER
+
+    def _init_state(self, p, st, group):
+        super()._init_state(p, st, group)
+        st["slow_buffer"] = p.detach().clone(memory_format=torch.contiguous_format)
+
+
+OPTIMIZERS = ("sgd", "adam", "radam", "ranger")
+LR_SCHEDULERS = (None, "steplr", "cosine", "poly")
+
+
+def make_optimizer(name, params, lr=5e-4, momentum=0.9, weight_decay=0.0, eps=1e-8, capturable=False):
+    """The reference's get_optimizer (utils/__init__.py:24-42) over this package's one-launch optimisers: `name` is
+    opt.py's --optimizer (sgd | adam | radam | ranger); sgd takes `momentum`, the others eps=1e-8 as the reference
+    passes it."""
+    if name == "sgd":
+        return SGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay, capturable=capturable)
+    if name == "adam":
+        return Adam(params, lr=lr, eps=eps, weight_decay=weight_decay, capturable=capturable)
+    if name == "radam":
+        return RAdam(params, lr=lr, eps=eps, weight_decay=weight_decay, capturable=capturable)
+    if name == "ranger":
+        return Ranger(params, lr=lr, eps=eps, weight_decay=weight_decay, capturable=capturable)
+    raise ValueError(f"optimizer not recognized: {name!r} (one of {', '.join(OPTIMIZERS)})")
+
+
+class GradualWarmupLR(torch.optim.lr_scheduler.LRScheduler):
+    """Linear learning-rate warm-up per epoch, then another scheduler (the behaviour of the reference's
+    GradualWarmupScheduler, utils/warmup_scheduler.py, as get_scheduler drives it):
+      epochs e = 0 .. T:  lr = base ((multiplier - 1) e / T + 1);
+      epoch T + 1:        `after` takes over with its base lrs scaled by `multiplier`: the rate is its own update rule
+                          evaluated once at its epoch 0 from the current rate base multiplier (that rate itself for
+                          MultiStepLR and poly; CosineAnnealingLR's recursive form gives slightly more, x1.0062 at
+                          T_max = 20 -- what the reference computes);
+      later epochs:       each step() steps `after` (so its own epoch count, e.g. MultiStepLR's milestones, starts at
+                          T + 1).  Without `after` the rate stays at base multiplier."""
+
+    def __init__(self, optimizer, multiplier, warmup_epochs, after=None):
+        if multiplier < 1.0:
+            raise ValueError(f"warmup multiplier must be >= 1, got {multiplier}")
+        if warmup_epochs < 1:
+            raise ValueError(f"warmup_epochs must be >= 1, got {warmup_epochs}")
+        self.multiplier, self.warmup_epochs, self.after = float(multiplier), int(warmup_epochs), after
+        self.handed_over = False
+        super().__init__(optimizer)
+
+    def get_lr(self):
+        e = self.last_epoch
+        if e <= self.warmup_epochs:
+            return [b * ((self.multiplier - 1.0) * e / self.warmup_epochs + 1.0) for b in self.base_lrs]
+        if self.after is None:
+            return [b * self.multiplier for b in self.base_lrs]
+        import warnings
+        self.after.base_lrs = [b * self.multiplier for b in self.base_lrs]
+        self.handed_over = True
+        with warnings.catch_warnings():          # torch warns about get_lr() outside the follower's own step()
+            warnings.simplefilter("ignore")
+            return list(self.after.get_lr())
+
+    def step(self, epoch=None):
+        if epoch is not None:
+            raise ValueError("GradualWarmupLR steps one epoch at a time")
+        if self.handed_over:
+            self.after.step()
+            self._last_lr = self.after.get_last_lr()
+        else:
+            super().step()
+
+
+def make_scheduler(opt, name, num_epochs=16, decay_step=(20,), decay_gamma=0.1, poly_exp=0.9, warmup_multiplier=1.0,
+                   warmup_epochs=0, optimizer="adam"):
+    """The reference's get_scheduler (utils/__init__.py:44-61), stepped once per epoch: `name` is opt.py's --lr_scheduler
+    (steplr | cosine | poly) or None (a constant rate); warmup_epochs > 0 wraps it in GradualWarmupLR, for the sgd and
+    adam optimisers only (radam and ranger ignore it, as in the reference).  poly is LambdaLR((1 - e / num_epochs) ^
+    poly_exp), the reference's evident intent (its get_scheduler never imports LambdaLR)."""
+    if name not in LR_SCHEDULERS:
+        raise ValueError(f"scheduler not recognized: {name!r} (one of steplr, cosine, poly or None)")
+    if optimizer not in OPTIMIZERS:
+        raise ValueError(f"optimizer not recognized: {optimizer!r} (one of {', '.join(OPTIMIZERS)})")
+    sched = None
+    if name == "steplr":
+        sched = torch.optim.lr_scheduler.MultiStepLR(opt, milestones=list(decay_step), gamma=decay_gamma)
+    elif name == "cosine":
+        sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=num_epochs, eta_min=1e-8)
+    elif name == "poly":
+        sched = torch.optim.lr_scheduler.LambdaLR(
+            opt, lambda e: max(0.0, 1.0 - e / num_epochs) ** poly_exp)
+    if warmup_epochs > 0 and optimizer in ("sgd", "adam"):
+        sched = GradualWarmupLR(opt, warmup_multiplier, warmup_epochs, after=sched)
+    return sched
 
 
 class GraphedTrainStep:
@@ -229,7 +483,7 @@ class GraphedTrainStep:
     and their Python disappear from the host's critical path; what matters at the README batch of 1024 rays, where the
     kernels take ~1.3 ms).  Random draws come from torch's graph-safe Philox generator, so every replay draws afresh.
 
-    `opt` must be `Adam(..., capturable=True)`; `loss_fn=None` uses the loss fused into the render kernels.  Batches are
+    `opt` must be one of this module's optimisers (Adam, SGD, RAdam, Ranger) built with capturable=True; `loss_fn=None` uses the loss fused into the render kernels.  Batches are
     loaded into the static buffers with `load()`.
     Construction runs `warmup` REAL steps eagerly (kernel attributes, optimizer state) before capturing.
     With `all_reduce=True` (ranks > 1) the step is two graphs with the flat gradient all-reduce between them."""
@@ -252,7 +506,8 @@ class GraphedTrainStep:
         keep_graph: keep the captured graph after instantiation (torch.cuda.CUDAGraph(keep_graph=True)), so that it can be
         inspected through raw_cuda_graph()."""
         if not getattr(opt, "capturable", False):
-            raise ValueError("GraphedTrainStep needs nerf_fl_amd.train.Adam(capturable=True)")
+            raise ValueError("GraphedTrainStep needs one of nerf_fl_amd.train's optimisers (Adam, SGD, RAdam, Ranger) "
+                             "built with capturable=True")
         import torch.distributed as dist
         self.params, self.opt, self.all_reduce = list(params), opt, bool(all_reduce)
         self.rays, self.ts, self.target = rays.detach().clone(), ts.detach().clone(), target.detach().clone()
@@ -345,7 +600,8 @@ class RayTrainer:
                  perturb=1.0, noise_std=1.0, white_back=True, encode_a=False, encode_t=False, N_vocab=100,
                  N_a=48, N_tau=16, beta_min=0.1, lr=5e-4, batch_size=1024, lr_scheduler=None, num_epochs=16,
                  decay_step=(20,), decay_gamma=0.1, seed=0, use_graph=False, refine_pose=False, init_c2w=None,
-                 image_ids=None):
+                 image_ids=None, optimizer="adam", momentum=0.9, weight_decay=0.0, poly_exp=0.9, warmup_multiplier=1.0,
+                 warmup_epochs=0):
         """use_graph: run the steps of fit_epoch from one captured HIP graph (GraphedTrainStep).  At the README batch of
         1024 rays the ~35 launches of an eager step are the critical path (1.9 vs 1.67 ms per step); at 4096 rays it
         makes no difference.  The first fit_epoch call spends two extra steps on its first batch (warm-up before the capture).
@@ -356,7 +612,12 @@ class RayTrainer:
         training layout: rays = camera-frame direction, near, far (further columns ignored), ts = image ids; the BARF
         weights follow `current_epoch` (0 in the first fit_epoch call, as Lightning's).
         init_c2w: (C, 3|4, 4) initial camera-to-world poses (None: identity, C = len(image_ids) or N_vocab).
-        image_ids: the image id of each pose row (the reference's `enumerate(poses_dict.keys())`); default 0 .. C-1."""
+        image_ids: the image id of each pose row (the reference's `enumerate(poses_dict.keys())`); default 0 .. C-1.
+
+        optimizer (sgd | adam | radam | ranger), momentum (sgd), weight_decay, lr_scheduler (None | steplr | cosine | poly),
+        num_epochs, decay_step, decay_gamma, poly_exp, warmup_multiplier, warmup_epochs: opt.py's flags of the same names
+        (make_optimizer / make_scheduler; the scheduler steps once per fit_epoch).  The defaults are this trainer's: Adam
+        without weight decay and a constant rate."""
         self.refine_pose = bool(refine_pose)
         if not self.refine_pose and (init_c2w is not None or image_ids is not None):
             raise ValueError("init_c2w / image_ids are the poses of refine_pose=True")
@@ -408,16 +669,14 @@ class RayTrainer:
                            torch.zeros(N_emb_dir, dtype=torch.float32, device=self.dev))
         # trainable parameters only (learn_poses.init_c2w is a frozen Parameter, as in the reference)
         self.params = [p for m in self.modules.values() for p in m.parameters() if p.requires_grad]
-        # one-launch Adam.  (torch's own fused=True variant is not an option here: it updates the parameters without
-        # moving their version counters, so render_rays never re-packed its weight streams and kept rendering with
+        # one-launch optimisers (Adam by default).  (torch's own fused=True Adam is not an option here: it updates the
+        # parameters without moving their version counters, so render_rays never re-packed its weight streams and kept rendering with
         # the initial weights -- tests/test_train_gpu.py: validation PSNR 26.89 -> 26.93 instead of 35.9)
-        self.opt = Adam(self.params, lr=lr, eps=1e-8, capturable=self.use_graph)
-        if lr_scheduler == "cosine":
-            self.sched = torch.optim.lr_scheduler.CosineAnnealingLR(self.opt, T_max=num_epochs, eta_min=1e-8)
-        elif lr_scheduler == "steplr":
-            self.sched = torch.optim.lr_scheduler.MultiStepLR(self.opt, milestones=list(decay_step), gamma=decay_gamma)
-        else:
-            self.sched = None
+        self.opt = make_optimizer(optimizer, self.params, lr=lr, momentum=momentum, weight_decay=weight_decay, eps=1e-8,
+                                  capturable=self.use_graph)
+        self.sched = make_scheduler(self.opt, lr_scheduler, num_epochs=num_epochs, decay_step=decay_step,
+                                    decay_gamma=decay_gamma, poly_exp=poly_exp, warmup_multiplier=warmup_multiplier,
+                                    warmup_epochs=warmup_epochs, optimizer=optimizer)
         self.arena = parallel.GradArena(self.params)      # flat gradient memory: written by the backward, all-reduced in place
         self.loss = NerfWLoss()
         self.fused_loss = True          # False: the NerfWLoss module on the result dict (two extra launches), as the reference composes it
