@@ -84,6 +84,38 @@ class GradArena:
             self.flat.div_(world)
 
 
+def broadcast_tensors_(tensors, src=0, group=None):
+    """Overwrite `tensors` on every rank, in place, with rank `src`'s values (a replica's weights, optimiser state, ...).
+
+    The tensors are packed into one flat buffer PER DTYPE (and device), so the call issues one `dist.broadcast` for each
+    dtype present -- e.g. two for fp32 parameters plus int32 step counters -- and unpacked with one `torch._foreach_copy_`.
+    Every destination keeps its storage (a HIP graph captured on it stays valid) and has its version counter moved:
+    render_rays re-packs a field's weight streams only when a parameter's version changes.  A no-op without a process
+    group, at world size 1, or for an empty list.  `src` is a global rank, as for `dist.broadcast`."""
+    tensors = list(tensors)
+    if not tensors or not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return
+    me = dist.get_rank()
+    buckets = {}
+    for t in tensors:
+        buckets.setdefault((t.dtype, t.device), []).append(t)
+    for (dtype, dev), ts in buckets.items():
+        if me == src:
+            flat = torch.cat([t.detach().reshape(-1) for t in ts])
+        else:
+            flat = torch.empty(sum(t.numel() for t in ts), dtype=dtype, device=dev)
+        dist.broadcast(flat, src=src, group=group)
+        if me == src:
+            continue
+        views = [v.view(t.shape) for v, t in zip(flat.split([t.numel() for t in ts]), ts)]
+        before = [t._version for t in ts]
+        with torch.no_grad():
+            torch._foreach_copy_(ts, views)
+        stale = [t for t, v in zip(ts, before) if t._version == v]
+        if stale:                # _foreach_copy_ moves them in the torch this was written for; make sure of it
+            torch.autograd.graph.increment_version(stale)
+
+
 def all_reduce_gradients(params, group=None, average=True, arena=None, force=False):
     """Average (or sum) the .grad of `params` across ranks with one flat all-reduce.  With a `GradArena` that holds
     them this is a single in-place collective; without one the gradients are gathered into a temporary flat buffer and

@@ -28,7 +28,7 @@ from .poses import LearnPose, posed_rays, row_table
 from .rendering import fill_barf_weights, render_rays
 
 __all__ = ["NerfWLoss", "psnr", "Adam", "SGD", "RAdam", "Ranger", "GradualWarmupLR", "make_optimizer", "make_scheduler",
-           "RayTrainer", "GraphedTrainStep"]
+           "RayTrainer", "GraphedTrainStep", "rank_seed", "reference_parameter_names"]
 
 
 class NerfWLoss(nn.Module):
@@ -453,6 +453,20 @@ class GradualWarmupLR(torch.optim.lr_scheduler.LRScheduler):
         else:
             super().step()
 
+    def state_dict(self):
+        """Plain values only (the follower as its own state dict, not the object and its optimizer), so that a checkpoint
+        holding it loads with torch.load(weights_only=True)."""
+        sd = {k: v for k, v in self.__dict__.items() if k not in ("optimizer", "after")}
+        sd["after"] = None if self.after is None else self.after.state_dict()
+        return sd
+
+    def load_state_dict(self, state_dict):
+        sd = dict(state_dict)
+        after = sd.pop("after", None)
+        self.__dict__.update(sd)
+        if self.after is not None and after is not None:
+            self.after.load_state_dict(after)
+
 
 def make_scheduler(opt, name, num_epochs=16, decay_step=(20,), decay_gamma=0.1, poly_exp=0.9, warmup_multiplier=1.0,
                    warmup_epochs=0, optimizer="adam"):
@@ -475,6 +489,33 @@ def make_scheduler(opt, name, num_epochs=16, decay_step=(20,), decay_gamma=0.1, 
     if warmup_epochs > 0 and optimizer in ("sgd", "adam"):
         sched = GradualWarmupLR(opt, warmup_multiplier, warmup_epochs, after=sched)
     return sched
+
+
+def rank_seed(seed, rank, epoch=0):
+    """The seed of rank `rank`'s random streams in a run of more than one rank: (seed * 1000003 + rank) * 1000003 + epoch,
+    modulo 2**63 -- distinct for every rank (and epoch) below 1000003.  Under a process group RayTrainer seeds the device's
+    default generator (stratified jitter, sigma noise, importance u) with it and its permutation generator with it + 1:
+    at construction with epoch 0, and again on ranks other than 0 after resume(), with the epoch resumed at.  A single
+    process keeps `seed` and `seed + 1`, as before."""
+    return ((int(seed) * 1000003 + int(rank)) * 1000003 + int(epoch)) % (1 << 63)
+
+
+def reference_parameter_names(modules):
+    """Checkpoint names of the parameters of the reference's optimiser, in its order: get_parameters(models_to_train)
+    (utils/__init__.py:11-22) over [embedding_a, embedding_t, {coarse, fine}, learn_poses] (train.py:46-76, 134-136).
+    Its `optimizer_states[0]` is indexed by position in this list.  `modules` maps checkpoint prefixes to modules whose
+    parameters carry the reference's names in the reference's order (RayTrainer.modules; nerf_fl_amd.NeRF does).
+    `learn_poses` is always there in the reference, with init_c2w and, frozen unless --refine_pose, r and t."""
+    names = []
+    for prefix in ("embedding_a", "embedding_t", "nerf_coarse", "nerf_fine"):
+        if prefix in modules:
+            names += [f"{prefix}.{n}" for n, _ in modules[prefix].named_parameters()]
+    return names + ["learn_poses.init_c2w", "learn_poses.r", "learn_poses.t"]
+
+
+def _rank_world():
+    import torch.distributed as dist
+    return (dist.get_rank(), dist.get_world_size()) if dist.is_initialized() else (0, 1)
 
 
 class GraphedTrainStep:
@@ -555,6 +596,8 @@ class GraphedTrainStep:
                                f"steps (first: index {missing[0]}); pass only parameters the step reaches")
         self.graph = torch.cuda.CUDAGraph(keep_graph=True) if keep_graph else torch.cuda.CUDAGraph()
         self.graph_opt = None
+        from . import rendering
+        self.rounding_seed = rendering._rounding_seed      # a by-value kernel argument: replays keep this one
         # With a process group alive, its watchdog thread polls the events of earlier collectives (hipEventQuery) at any
         # time; under the default "global" capture mode such a call from ANOTHER thread invalidates the capture
         # ("operation not permitted when stream is capturing").  thread_local confines the checks to this thread.
@@ -617,7 +660,13 @@ class RayTrainer:
         optimizer (sgd | adam | radam | ranger), momentum (sgd), weight_decay, lr_scheduler (None | steplr | cosine | poly),
         num_epochs, decay_step, decay_gamma, poly_exp, warmup_multiplier, warmup_epochs: opt.py's flags of the same names
         (make_optimizer / make_scheduler; the scheduler steps once per fit_epoch).  The defaults are this trainer's: Adam
-        without weight decay and a constant rate."""
+        without weight decay and a constant rate.
+
+        Under a process group of more than one rank the trainer is built as above, then every parameter and buffer of
+        `modules` (learn_poses.init_c2w included) is broadcast from rank 0, and the device's default generator and the
+        permutation generator are re-seeded with rank_seed(seed, rank) and rank_seed(seed, rank) + 1: every rank starts
+        from rank 0's weights and draws its own jitter, noise and importance samples.  Without one, or at world size 1,
+        nothing of this happens."""
         self.refine_pose = bool(refine_pose)
         if not self.refine_pose and (init_c2w is not None or image_ids is not None):
             raise ValueError("init_c2w / image_ids are the poses of refine_pose=True")
@@ -635,6 +684,10 @@ class RayTrainer:
         self._graphed = None
         self.hp = dict(N_samples=N_samples, N_importance=N_importance, use_disp=use_disp, perturb=perturb,
                        noise_std=noise_std, white_back=white_back, batch_size=batch_size)
+        self.seed, self.optimizer_name = int(seed), optimizer
+        self._sched_args = dict(name=lr_scheduler, num_epochs=num_epochs, decay_step=decay_step, decay_gamma=decay_gamma,
+                                poly_exp=poly_exp, warmup_multiplier=warmup_multiplier, warmup_epochs=warmup_epochs,
+                                optimizer=optimizer)
         torch.manual_seed(seed)
         # draws of the backward's stochastic rounding: a function of the trainer's seed, and another stream on every rank
         import torch.distributed as dist
@@ -661,6 +714,7 @@ class RayTrainer:
             self.modules["nerf_fine"] = self.models["fine"]
         self.pose = self.row_of_id = self.barf_w = None
         self.current_epoch = 0                              # Lightning's current_epoch: fit_epoch counts it
+        self.global_step = 0                                # Lightning's global_step: optimisation steps taken
         self._barf_epoch = None
         if rp:
             self.pose = self.modules["learn_poses"] = LearnPose(n_cams, True, True, init_c2w).to(self.dev)
@@ -681,6 +735,21 @@ class RayTrainer:
         self.loss = NerfWLoss()
         self.fused_loss = True          # False: the NerfWLoss module on the result dict (two extra launches), as the reference composes it
         self.gen = torch.Generator(device=self.dev).manual_seed(seed + 1)
+        rank, world = _rank_world()
+        if world > 1:
+            parallel.broadcast_tensors_(self._module_tensors(), src=0)
+            self._seed_streams(rank_seed(seed, rank))
+
+    def _seed_streams(self, s):
+        torch.manual_seed(s)
+        self.gen.manual_seed(s + 1)
+
+    def _module_tensors(self):
+        return [t for m in self.modules.values() for t in list(m.parameters()) + list(m.buffers())]
+
+    def param_names(self):
+        """Checkpoint names of `params` (the trainable parameters), in their order."""
+        return [f"{prefix}.{n}" for prefix, m in self.modules.items() for n, p in m.named_parameters() if p.requires_grad]
 
     @staticmethod
     def _init_poses(init_c2w, image_ids, n_vocab):
@@ -741,6 +810,7 @@ class RayTrainer:
         total.backward()
         self.arena.all_reduce()
         self.opt.step()
+        self.global_step += 1
         key = "rgb_fine" if "rgb_fine" in res else "rgb_coarse"
         return total.detach(), psnr(res[key].detach(), rgbs)
 
@@ -757,6 +827,7 @@ class RayTrainer:
                     self._graphed = self.graphed_step(rays[idx], ts[idx], rgbs[idx])
                 self._graphed.load(rays[idx], ts[idx], rgbs[idx])
                 log.append(tuple(x.clone() for x in self._graphed.replay()))      # the outputs live in the graph's pool
+                self.global_step += 1
             else:
                 log.append(self.step(rays[idx], rgbs[idx], ts[idx]))
         if self.sched is not None:
@@ -779,9 +850,25 @@ class RayTrainer:
             pose=self.pose, row_of_id=self.row_of_id, barf_weights=self.barf_w, **kw)
 
     @torch.no_grad()
-    def validate(self, rays, rgbs, ts, chunk=32768):
+    def validate(self, rays, rgbs, ts, chunk=32768, shard=False):
         """Mean PSNR of a deterministic render (perturb 0, noise 0; train.py:176-210).  rays: (R, 8) world rays; with
-        refine_pose, any other width is the training layout and is rendered through the learned poses."""
+        refine_pose, any other width is the training layout and is rendered through the learned poses.
+        shard=True under a process group: every rank renders its parallel.shard_bounds slice, the squared error and the
+        element count are summed over the ranks with one fp64 all-reduce, and every rank returns the same PSNR.  Every
+        rank must pass the same rays."""
+        rank, world = _rank_world()
+        if not (shard and world > 1):
+            return float(psnr(self._render_eval(rays, ts, chunk), rgbs))
+        import torch.distributed as dist
+        lo, hi = parallel.shard_bounds(rays.shape[0], rank, world)
+        pred = self._render_eval(rays[lo:hi], ts[lo:hi], chunk) if hi > lo else rgbs[:0]
+        acc = torch.stack([((pred.double() - rgbs[lo:hi].double()) ** 2).sum(),
+                           torch.tensor(float(pred.numel()), dtype=torch.float64, device=pred.device)])
+        dist.all_reduce(acc)
+        sse, n = acc.tolist()
+        return -10.0 * math.log10(sse / n)
+
+    def _render_eval(self, rays, ts, chunk):
         hp = self.hp
         extra = self._extra()
         outs = []
@@ -792,7 +879,7 @@ class RayTrainer:
             res = render_rays(self.models, self.embeddings, r, ts[i:i + chunk], hp["N_samples"],
                               hp["use_disp"], 0, 0, hp["N_importance"], chunk, hp["white_back"], False, **extra)
             outs.append(res["rgb_fine" if "rgb_fine" in res else "rgb_coarse"])
-        return float(psnr(torch.cat(outs), rgbs))
+        return torch.cat(outs)
 
     # ---- checkpoints with the reference's key prefixes -----------------------------------------
     def state_dict(self):
@@ -807,8 +894,216 @@ class RayTrainer:
             m.load_state_dict(sub, strict=True)
 
     def save(self, path, epoch=0):
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        torch.save({"epoch": epoch, "state_dict": self.state_dict()}, path)
+        """Write a full-state checkpoint.  `epoch` and `state_dict` are what load() and the reference's utils.load_ckpt
+        read.  Lightning 1.2's keys come with them: `global_step`, `optimizer_states` (one element: opt.state_dict(),
+        indexed in `params` order) and `lr_schedulers` (the scheduler's state dict, or empty).  `nerf_fl_amd` holds the
+        rest resume() needs: current_epoch, the saving rank's generator states and rounding seed, the optimiser and
+        schedule names and the world size.  Under a process group only rank 0 writes, and every rank returns once it
+        has written (an error on rank 0 is raised on every rank)."""
+        from . import rendering
+        rank, world = _rank_world()
+        err = None
+        if rank == 0:
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+                own = dict(current_epoch=self.current_epoch, global_step=self.global_step, world_size=world,
+                           optimizer=self.optimizer_name, lr_scheduler=self._sched_args["name"], seed=self.seed,
+                           rng=dict(cpu=torch.get_rng_state(), device=torch.cuda.get_rng_state(self.dev),
+                                    perm=self.gen.get_state(), rounding_seed=rendering._rounding_seed))
+                torch.save({"epoch": epoch, "state_dict": self.state_dict(), "global_step": self.global_step,
+                            "optimizer_states": [self.opt.state_dict()],
+                            "lr_schedulers": [] if self.sched is None else [self.sched.state_dict()],
+                            "nerf_fl_amd": own}, path)
+            except Exception as e:           # noqa: BLE001 -- re-raised below, after the other ranks have heard of it
+                err = e
+        self._agree(err)
 
     def load(self, path):
         self.load_state_dict(torch.load(path, map_location=self.dev, weights_only=True))
+
+    # ---- resuming a run -----------------------------------------------------------------------------------------
+    def resume(self, path, start_epoch=None, weights_only=True):
+        """Continue the run a checkpoint was written by: weights, optimiser state (copied into the existing state
+        tensors, device-side step counters reset in place), schedule position, current_epoch (the BARF weights follow
+        at the next step), global_step and, at world size 1, the generator states and the rounding seed.  Everything
+        is restored in place, so a GraphedTrainStep captured before keeps replaying on live memory.
+
+        Accepts save()'s checkpoints and the reference's Lightning checkpoints (train.py, `--ckpt_path`).  For the
+        latter the optimiser state is mapped by name (reference_parameter_names), the schedule is rebuilt by stepping a
+        fresh scheduler `start_epoch` times, and `start_epoch` defaults to the checkpoint's `epoch`, read as the next
+        epoch to run (unverified).  An explicit `start_epoch` overrides the epoch of either kind.
+        weights_only=False: for trusted checkpoints that hold other objects (Lightning's hyper_parameters).
+
+        Under a process group rank 0 reads the file and broadcast() hands everything to the other ranks, which never
+        open it; they re-seed their streams with rank_seed(seed, rank, current_epoch).  The captured rounding seed of a
+        graph is a kernel argument: a step captured before resume() keeps the seed it was captured with."""
+        rank, world = _rank_world()
+        if world == 1:
+            self._restore(path, start_epoch, weights_only)
+            return
+        err = None
+        if rank == 0:
+            try:
+                self._restore(path, start_epoch, weights_only)
+            except Exception as e:           # noqa: BLE001 -- raised on every rank by _broadcast
+                err = e
+        self._broadcast(0, err)
+        if rank != 0:
+            self._seed_streams(rank_seed(self.seed, rank, self.current_epoch))
+
+    def _restore(self, path, start_epoch, weights_only):
+        import warnings
+
+        from . import rendering
+        ck = torch.load(path, map_location="cpu", weights_only=weights_only)
+        own = ck.get("nerf_fl_amd")
+        if "optimizer_states" not in ck:
+            raise ValueError(f"{path}: no optimizer_states (a weights-only checkpoint: use load())")
+        if own is not None:
+            for key, mine in (("optimizer", self.optimizer_name), ("lr_scheduler", self._sched_args["name"])):
+                if own[key] != mine:
+                    raise ValueError(f"{path} was written with {key}={own[key]!r}, this trainer has {mine!r}")
+        self.load_state_dict(ck)
+        if own is not None:
+            self.opt.load_state_dict(ck["optimizer_states"][0])
+            epoch = own["current_epoch"] if start_epoch is None else int(start_epoch)
+            if self.sched is not None and start_epoch is None and ck["lr_schedulers"]:
+                self.sched.load_state_dict(ck["lr_schedulers"][0])
+            else:
+                self._replay_schedule(epoch)
+            self.global_step = int(own["global_step"])
+        else:
+            self.opt.load_state_dict(self._from_reference_optimizer(ck["optimizer_states"][0]))
+            epoch = int(ck["epoch"]) if start_epoch is None else int(start_epoch)
+            self._replay_schedule(epoch)
+            self.global_step = int(ck.get("global_step", 0))
+        self.current_epoch = epoch
+        rng = own["rng"] if own is not None else None
+        if rng is None:                          # e.g. a Lightning checkpoint: streams re-derived
+            self._seed_streams(rank_seed(self.seed, _rank_world()[0], epoch))
+        else:
+            torch.set_rng_state(rng["cpu"])
+            torch.cuda.set_rng_state(rng["device"], self.dev)
+            self.gen.set_state(rng["perm"])
+            rendering.set_rounding_seed(rng["rounding_seed"])
+            if (self._graphed is not None and self._graphed.rounding_seed != rendering._rounding_seed
+                    and rendering.get_backward_precision() != "f16x3"):
+                warnings.warn("RayTrainer.resume: the captured step keeps the rounding seed it was captured with "
+                              f"({self._graphed.rounding_seed}, checkpoint {rendering._rounding_seed})")
+
+    def _replay_schedule(self, epoch):
+        """Put the schedule at `epoch` by stepping a fresh one that many times (the schedules are deterministic in the
+        epoch count; a scheduler of another implementation, the reference's GradualWarmupScheduler, need not load)."""
+        import warnings
+        if self.sched is None:
+            return
+        for g in self.opt.param_groups:
+            g["lr"] = g.get("initial_lr", g["lr"])
+        self.sched = make_scheduler(self.opt, **self._sched_args)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")       # lr_scheduler.step() before optimizer.step()
+            for _ in range(int(epoch)):
+                self.sched.step()
+
+    def _from_reference_optimizer(self, osd):
+        """The reference's optimizer state dict (one group over get_parameters order, frozen tensors included) as one
+        over `params`, matched by name."""
+        names = reference_parameter_names(self.modules)
+        groups = osd["param_groups"]
+        if len(groups) != 1 or len(groups[0]["params"]) != len(names):
+            raise ValueError(f"the checkpoint's optimiser has {[len(g['params']) for g in groups]} parameters; this "
+                             f"trainer's configuration has {len(names)} in the reference's order")
+        ours = {n: i for i, n in enumerate(self.param_names())}
+        state = {}
+        for name, pid in zip(names, groups[0]["params"]):
+            st = osd["state"].get(pid)
+            if not st:
+                continue
+            if name not in ours:
+                raise ValueError(f"the checkpoint has optimiser state for {name}, which this trainer does not train")
+            p = self.params[ours[name]]
+            for k, v in st.items():
+                if torch.is_tensor(v) and v.dim() > 0 and v.shape != p.shape:
+                    raise ValueError(f"optimiser state {name}.{k}: shape {tuple(v.shape)}, parameter {tuple(p.shape)}")
+            state[ours[name]] = st
+        missing = [n for n, i in ours.items() if i not in state]
+        if state and missing:
+            raise ValueError(f"the checkpoint has no optimiser state for {missing[0]} (another configuration?)")
+        group = dict(groups[0], params=list(range(len(self.params))))
+        return {"state": state, "param_groups": [group]}
+
+    # ---- keeping the ranks identical ------------------------------------------------------------------------------
+    def broadcast(self, src=0):
+        """Make every rank's trainer rank `src`'s: parameters and buffers of `modules`, optimiser state (the per-parameter
+        tensors and steps, the param groups' hyper-parameters, the capturable optimisers' device-side step and
+        hyper-parameter tensors), scheduler state, current_epoch and global_step.  Tensors travel through
+        parallel.broadcast_tensors_ (one collective per dtype: fp32 and, with a capturable optimiser, int32), the rest
+        through one dist.broadcast_object_list.  Every copy is in place, so a step captured before keeps replaying on
+        live memory.  Use it after a load() that only one rank performed.  A no-op without a process group."""
+        self._broadcast(src, None)
+
+    def _agree(self, err, src=0):
+        """Rank `src`'s error, raised on every rank (doubles as the barrier of save())."""
+        rank, world = _rank_world()
+        if world > 1:
+            import torch.distributed as dist
+            box = [None if err is None else f"{type(err).__name__}: {err}"]
+            dist.broadcast_object_list(box, src=src)
+            if box[0] is not None and err is None:
+                raise RuntimeError(f"RayTrainer: rank {src} failed: {box[0]}")
+        if err is not None:
+            raise err
+
+    def _broadcast(self, src, err):
+        import torch.distributed as dist
+        rank, world = _rank_world()
+        if world == 1:
+            if err is not None:
+                raise err
+            return
+        opt, pdev = self.opt, self.params[0].device         # the optimiser's device-side state is keyed by p.device
+        meta = None
+        if rank == src and err is None:
+            state = []
+            for p in self.params:
+                st = opt.state.get(p) or {}
+                state.append(dict(scalars={k: v for k, v in st.items() if not torch.is_tensor(v)},
+                                  tensors=[(k, tuple(v.shape), str(v.dtype).split(".")[-1])
+                                           for k, v in sorted(st.items()) if torch.is_tensor(v)]) if st else None)
+            meta = dict(epoch=self.current_epoch, global_step=self.global_step, state=state,
+                        groups=[{k: v for k, v in g.items() if k != "params"} for g in opt.param_groups],
+                        sched=None if self.sched is None else self.sched.state_dict(),
+                        dev_groups=sorted(gi for gi, d in opt._dev if d == str(pdev)))
+        box = [dict(error=None if err is None else f"{type(err).__name__}: {err}", meta=meta)]
+        dist.broadcast_object_list(box, src=src)
+        if box[0]["error"] is not None:
+            if err is not None:
+                raise err
+            raise RuntimeError(f"RayTrainer: rank {src} failed: {box[0]['error']}")
+        meta = box[0]["meta"]
+        if rank != src:
+            self.current_epoch, self.global_step = meta["epoch"], meta["global_step"]
+            for g, h in zip(opt.param_groups, meta["groups"]):
+                g.update(h)
+            for p, m in zip(self.params, meta["state"]):
+                if m is None:
+                    opt.state.pop(p, None)
+                    continue
+                st = opt.state[p]
+                st.update(m["scalars"])
+                for k, shape, dtype in m["tensors"]:
+                    if not torch.is_tensor(st.get(k)) or tuple(st[k].shape) != shape:
+                        st[k] = torch.empty(shape, dtype=getattr(torch, dtype), device=pdev)
+            if self.sched is not None and meta["sched"] is not None:
+                self.sched.load_state_dict(meta["sched"])
+            for gi in meta["dev_groups"]:
+                opt._dev_state(gi, opt.param_groups[gi], pdev)
+        tensors = self._module_tensors()
+        for p, m in zip(self.params, meta["state"]):
+            if m is not None:
+                tensors += [opt.state[p][k] for k, _, _ in m["tensors"]]
+        for gi in meta["dev_groups"]:
+            ds = opt._dev[(gi, str(pdev))]
+            tensors += [ds["step"], ds["hyper"]]
+            ds["host"] = None                # the next sync_hyper() re-uploads from the (now common) param groups
+        parallel.broadcast_tensors_(tensors, src=src)
