@@ -8,7 +8,7 @@ ignored), and the same result keys in the same insertion order (SURVEY.md
 appendix B).  Everything between the arguments and the result dict runs in the
 HIP library behind include/nerf_fl_amd.h:
 
-    nfl_pack_field   (only when parameters changed)
+    nfl_pack_fields  (only when parameters changed)
     nfl_render_pass  coarse   -> weights/opacity/rgb/depth _coarse
     nfl_sample_pdf            -> sorted fine depths
     nfl_render_pass  fine     -> ..._fine, transient outputs
@@ -177,15 +177,19 @@ def check_status(device=None):
                                      + " (see INTEGRATION.md, 'Numerical range')")
 
 
+def _barf_weights(emb, epoch):
+    """The BARF per-frequency weights of embedding `emb` at `epoch` (BarfPosEmbedding.weights, quirks included): fp32, host."""
+    if hasattr(emb, "weights"):
+        return emb.weights(epoch)
+    return torch.tensor([float(emb.barf_weight(f, epoch)) for f in emb.freqs], dtype=torch.float32)
+
+
 def fill_barf_weights(embeddings, epoch, buffers):
-    """Write the BARF per-frequency weights of `epoch` (BarfPosEmbedding.weights, quirks included) into the caller's
-    device buffers `(w_xyz, w_dir)` in place, for `render_rays(..., barf_weights=buffers)`.  A host -> device copy: call it
-    outside graph capture (RayTrainer does when its epoch changes), as Adam.sync_hyper()."""
+    """Write the BARF per-frequency weights of `epoch` into the caller's device buffers `(w_xyz, w_dir)` in place, for
+    `render_rays(..., barf_weights=buffers)`.  A host -> device copy: call it outside graph capture (RayTrainer does when
+    its epoch changes), as Adam.sync_hyper()."""
     for key, buf in zip(("xyz", "dir"), buffers):
-        emb = embeddings[key]
-        w = emb.weights(epoch) if hasattr(emb, "weights") else \
-            torch.tensor([float(emb.barf_weight(f, epoch)) for f in emb.freqs], dtype=torch.float32)
-        buf.copy_(w)
+        buf.copy_(_barf_weights(embeddings[key], epoch))
     return buffers
 
 
@@ -264,7 +268,7 @@ class _PackedField:
 
     def bwd_plan(self, rays_grad=False, bprec=None):
         """Plan + buffer of the dgrad stream (transposed weights, fp16 -- hi + lo fragments for the three-product backward);
-        packed by ensure_bwd_packed / _pack_streams."""
+        packed by _pack_streams."""
         L = _lib.lib()
         bprec = _BPREC[_backward] if bprec is None else bprec
         rg = (int(bool(rays_grad)), bprec)
@@ -278,15 +282,9 @@ class _PackedField:
         return self.bplans[rg]
 
     def ensure_bwd_packed(self, rays_grad=False, bprec=None):
-        """dgrad stream for the current parameters (the forward stream must be current: self.key)."""
-        L = _lib.lib()
-        bp = self.bwd_plan(rays_grad, bprec)
-        if bp["key"] != self.key:
-            fp, _keep = self._pack_params()
-            _lib.check(L.nfl_pack_field(bp["h"], _ptr(bp["d"]), C.byref(fp), _ptr(bp["packed"]), bp["nbytes"],
-                                        C.c_void_p(0), _stream()), "nfl_pack_field(bwd)")
-            bp["key"] = self.key
-        return bp
+        """Forward and dgrad streams for the current parameters; returns the dgrad plan (bwd_plan)."""
+        _pack_streams([self], bwd=True, rays_grad=rays_grad, bprec=bprec)
+        return self.bwd_plan(rays_grad, bprec)
 
     def _field_params(self):
         params = self._named()
@@ -335,14 +333,7 @@ class _PackedField:
         return tuple((n, p.data_ptr(), p._version) for n, p in self._named().items())
 
     def ensure_packed(self):
-        key = self.current_key()
-        if key == self.key:
-            return
-        fp, _keep = self._pack_params()
-        _lib.check(_lib.lib().nfl_pack_field(self.h_plan, _ptr(self.d_plan), C.byref(fp), _ptr(self.packed),
-                                             self.packed_bytes, _ptr(_status_word(self.device)), _stream()),
-                   "nfl_pack_field")
-        self.key = key
+        _pack_streams([self])
 
 
 _fields = weakref.WeakKeyDictionary()
@@ -361,9 +352,10 @@ def _field(model, n_emb_xyz, n_emb_dir, device, pack=True):
     return f
 
 
-def _pack_streams(fields, bwd, rays_grad):
-    """Bring the forward (and, for a training call, the dgrad) weight streams of `fields` up to date with ONE
-    nfl_pack_fields launch: after an optimizer step all four streams of a coarse + fine pair are stale."""
+def _pack_streams(fields, bwd=False, rays_grad=False, bprec=None):
+    """Bring the forward (and, for a training call, the dgrad: bwd_plan(rays_grad, bprec)) weight streams of `fields` up
+    to date with ONE nfl_pack_fields launch: after an optimizer step all four streams of a coarse + fine pair are stale.
+    The only place that packs a stream and moves its key."""
     jobs, done, keep = [], [], []
     for f in fields:
         if f is None or any(f is g for g, _ in done):
@@ -371,7 +363,7 @@ def _pack_streams(fields, bwd, rays_grad):
         key = f.current_key()
         done.append((f, key))
         stale_fwd = key != f.key
-        bp = f.bwd_plan(rays_grad) if bwd else None
+        bp = f.bwd_plan(rays_grad, bprec) if bwd else None
         stale_bwd = bp is not None and bp["key"] != key
         if not (stale_fwd or stale_bwd):
             continue
@@ -652,7 +644,7 @@ def _backward_pass(field, rays, st, typ, keys, grads, cfg, want_latents, g_rays=
         da.d_g_rays, da.d_rays, da.d_z = _ptr(g_rays), _ptr(rays), _ptr(st["z"])
         da.dir_is_data = int(cfg["view_dir"] is not None)
         da.d_pe_w_xyz, da.d_pe_w_dir = _ptr(cfg["pe_w_xyz"]), _ptr(cfg["pe_w_dir"])
-    bp = field.ensure_bwd_packed(cfg["rays_grad"], cfg["bprec"])
+    bp = field.bwd_plan(cfg["rays_grad"], cfg["bprec"])      # packed by render_rays; the weights are the forward's
     _lib.check(L.nfl_mlp_dgrad(bp["h"], _ptr(bp["d"]), _ptr(bp["packed"]), C.byref(da), _stream()), "nfl_mlp_dgrad")
 
     plist = field.param_list()
@@ -705,10 +697,8 @@ class _RenderRaysFn(torch.autograd.Function):
             a_rows = None if a_emb is None else _f32c(a_emb, "a_embedded")
             t_rows = None if t_emb is None else _f32c(t_emb, "t_embedded")
         result, saved = _forward(cfg, rays, a_rows, t_rows, train=True)
-        cfg["f_c"].ensure_bwd_packed(cfg["rays_grad"], cfg["bprec"])
-        cfg["f_c"].wgrad_plan(False)
+        cfg["f_c"].wgrad_plan(False)          # (the dgrad streams were packed with the forward ones by render_rays)
         if cfg["f_f"] is not None:
-            cfg["f_f"].ensure_bwd_packed(cfg["rays_grad"], cfg["bprec"])
             cfg["f_f"].wgrad_plan(cfg["use_t"])
         if cfg["loss"] is not None:
             terms = cfg["loss"]["losses"]
@@ -794,10 +784,8 @@ def render_rays(models, embeddings, rays, ts, N_samples=64, use_disp=False, pert
             epoch = kwargs.get("current_epoch")
             if epoch is None:
                 raise KeyError("current_epoch")
-            cfg["pe_w_xyz"] = embeddings["xyz"].weights(epoch).to(dev) if hasattr(embeddings["xyz"], "weights") else \
-                torch.tensor([float(embeddings["xyz"].barf_weight(f, epoch)) for f in embeddings["xyz"].freqs], device=dev)
-            cfg["pe_w_dir"] = embeddings["dir"].weights(epoch).to(dev) if hasattr(embeddings["dir"], "weights") else \
-                torch.tensor([float(embeddings["dir"].barf_weight(f, epoch)) for f in embeddings["dir"].freqs], device=dev)
+            cfg["pe_w_xyz"] = _barf_weights(embeddings["xyz"], epoch).to(dev)
+            cfg["pe_w_dir"] = _barf_weights(embeddings["dir"], epoch).to(dev)
         if kwargs.get("view_dir") is not None:
             if kwargs["view_dir"].requires_grad and torch.is_grad_enabled():
                 raise NotImplementedError("gradient w.r.t. `view_dir` (no caller of the reference asks for it); detach it")
@@ -864,7 +852,8 @@ def render_rays(models, embeddings, rays, ts, N_samples=64, use_disp=False, pert
         needs_grad = torch.is_grad_enabled() and (
             rays_grad or any(p.requires_grad for p in params)
             or any(t is not None and t.requires_grad for t in (a_emb, t_emb)))
-        _pack_streams([cfg["f_c"], cfg["f_f"]], bwd=needs_grad and not test_time and _precision == "f16x3", rays_grad=rays_grad)
+        _pack_streams([cfg["f_c"], cfg["f_f"]], bwd=needs_grad and not test_time and _precision == "f16x3", rays_grad=rays_grad,
+                      bprec=cfg["bprec"])
         if cfg["loss"] is not None and not (torch.is_grad_enabled() and not test_time):
             raise RuntimeError("loss_target fuses the loss into the TRAINING passes: call it with gradients enabled")
         if needs_grad:

@@ -16,6 +16,7 @@ What it does differently, because the renderer is ~10^3 x faster than the data p
     (poses.posed_rays) inside the step;
   * multi-GPU: every rank shuffles its own shard; gradients are averaged with one flat all-reduce.
 """
+import ctypes as C
 import math
 import os
 
@@ -55,46 +56,38 @@ class NerfWLoss(nn.Module):
         return ret
 
 
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
 class _FusedNerfWLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rgb_c, rgb_f, beta, tsig, targets, coef, lambda_u):
-        import ctypes as C
-
-        from . import _lib
         ctx.set_materialize_grads(False)
         f32c = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()
-        rgb_c, rgb_f, beta, tsig, targets = f32c(rgb_c), f32c(rgb_f), f32c(beta), f32c(tsig), f32c(targets)
-        a = _lib.LossArgs()
-        ptr = lambda t: None if t is None else t.data_ptr()
-        a.d_rgb_coarse, a.d_rgb_fine, a.d_beta, a.d_transient_sigmas, a.d_target = ptr(rgb_c), ptr(rgb_f), ptr(beta), ptr(tsig), ptr(targets)
+        ctx.inputs = rgb_c, rgb_f, beta, tsig, targets = f32c(rgb_c), f32c(rgb_f), f32c(beta), f32c(tsig), f32c(targets)
+        ctx.args = a = _lib.LossArgs()          # the backward fills in only its gradient pointers
+        a.d_rgb_coarse, a.d_rgb_fine, a.d_beta, a.d_transient_sigmas, a.d_target = map(_ptr, ctx.inputs)
         a.n_rays, a.n_samples = rgb_c.shape[0], (tsig.shape[1] if tsig is not None else 0)
         a.coef, a.lambda_u = coef, lambda_u
         losses = torch.empty(4, dtype=torch.float32, device=targets.device)
         a.d_losses = losses.data_ptr()
         with torch.cuda.device(targets.device):
             _lib.check(_lib.lib().nfl_loss_forward(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "nfl_loss_forward")
-        ctx.saved = (rgb_c, rgb_f, beta, tsig, targets, coef, lambda_u)
         return losses[0], losses[1], losses[2], losses[3]
 
     @staticmethod
     def backward(ctx, *go):
-        import ctypes as C
-
-        from . import _lib
-        rgb_c, rgb_f, beta, tsig, targets, coef, lambda_u = ctx.saved
-        a = _lib.LossArgs()
-        ptr = lambda t: None if t is None else t.data_ptr()
-        a.d_rgb_coarse, a.d_rgb_fine, a.d_beta, a.d_transient_sigmas, a.d_target = ptr(rgb_c), ptr(rgb_f), ptr(beta), ptr(tsig), ptr(targets)
-        a.n_rays, a.n_samples = rgb_c.shape[0], (tsig.shape[1] if tsig is not None else 0)
-        a.coef, a.lambda_u = coef, lambda_u
+        rgb_c, rgb_f, beta, tsig, targets = ctx.inputs
+        a = ctx.args
         keep = [None if g is None else g.to(torch.float32).contiguous() for g in go]
         for k in range(4):
-            a.d_grad_loss[k] = ptr(keep[k])
+            a.d_grad_loss[k] = _ptr(keep[k])
         g_c = torch.empty_like(rgb_c)
         g_f = torch.empty_like(rgb_f) if rgb_f is not None else None
         g_b = torch.empty_like(beta) if beta is not None else None
         g_s = torch.empty_like(tsig) if tsig is not None else None
-        a.d_g_rgb_coarse, a.d_g_rgb_fine, a.d_g_beta, a.d_g_transient_sigmas = ptr(g_c), ptr(g_f), ptr(g_b), ptr(g_s)
+        a.d_g_rgb_coarse, a.d_g_rgb_fine, a.d_g_beta, a.d_g_transient_sigmas = _ptr(g_c), _ptr(g_f), _ptr(g_b), _ptr(g_s)
         with torch.cuda.device(targets.device):
             _lib.check(_lib.lib().nfl_loss_backward(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "nfl_loss_backward")
         return g_c, g_f, g_b, g_s, None, None, None
@@ -153,6 +146,20 @@ class _OneLaunchOptimizer(torch.optim.Optimizer):
                                 step=torch.full((1,), self._group_step(group), dtype=torch.int32, device=dev), host=None)
         return self._dev[k]
 
+    def device_state(self, dev, groups=None):
+        """(groups, tensors): the device-side step and hyper-parameter tensors on `dev` of param groups `groups` (default:
+        every group that has them), created where missing, as [step, hyper] per group in `groups` order, for a caller
+        that overwrites them in place (RayTrainer.broadcast).  The cached host values are cleared, so the next
+        sync_hyper() uploads again."""
+        if groups is None:
+            groups = sorted(gi for gi, d in self._dev if d == str(dev))
+        tensors = []
+        for gi in groups:
+            ds = self._dev_state(gi, self.param_groups[gi], dev)
+            ds["host"] = None
+            tensors += [ds["step"], ds["hyper"]]
+        return groups, tensors
+
     def _group_step(self, group):
         steps = [int(self.state[p]["step"]) for p in group["params"] if "step" in self.state.get(p, {})]
         return max(steps) if steps else 0
@@ -202,7 +209,6 @@ class _OneLaunchOptimizer(torch.optim.Optimizer):
 
     # ---- the step ---------------------------------------------------------------------------------------------
     def _launch(self, L, group, chunk, step, ds, last, stream):
-        import ctypes as C
         t = _lib.OptimTensors()
         for k, (p, g, st) in enumerate(chunk):
             s0, s1, s2 = self._state_ptrs(st)
@@ -219,7 +225,6 @@ class _OneLaunchOptimizer(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
-        import ctypes as C
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -296,7 +301,6 @@ class Adam(_OneLaunchOptimizer):
     def _launch(self, L, group, chunk, step, ds, last, stream):
         if group["weight_decay"] != 0:
             return super()._launch(L, group, chunk, step, ds, last, stream)
-        import ctypes as C
         t = _lib.AdamTensors()
         for k, (p, g, st) in enumerate(chunk):
             t.param[k], t.grad[k] = p.data_ptr(), g.data_ptr()
@@ -518,6 +522,24 @@ def _rank_world():
     return (dist.get_rank(), dist.get_world_size()) if dist.is_initialized() else (0, 1)
 
 
+def _loss_backward(models, embeddings, hp, rays, ts, target, arena, loss_fn=None, loss_coef=1.0, lambda_u=0.01,
+                   pose=None, row_of_id=None, barf_weights=None):
+    """The body of a training step up to the gradients, eager or captured: rays through the learned poses (with `pose`),
+    render_rays with the sampling hyper-parameters `hp` (N_samples, N_importance, use_disp, perturb, noise_std,
+    white_back), the loss and its backward into `arena`.  `loss_fn=None`: NerfWLoss(loss_coef, lambda_u) fused into the
+    render kernels' per-ray epilogue, whose backward seeds with it; otherwise sum(loss_fn(result, target).values()).
+    Returns (loss, psnr) as device scalars."""
+    if pose is not None:
+        rays = posed_rays(pose, rays, ts, row_of_id, grad_arena=arena)
+    res = render_rays(models, embeddings, rays, ts, hp["N_samples"], hp["use_disp"], hp["perturb"], hp["noise_std"],
+                      hp["N_importance"], 32768, hp["white_back"], False, grad_arena=arena, barf_weights=barf_weights,
+                      loss_target=target if loss_fn is None else None, loss_coef=loss_coef, lambda_u=lambda_u)
+    total = res["_nerfw_loss"] if loss_fn is None else sum(loss_fn(res, target).values())
+    total.backward()
+    key = "rgb_fine" if "rgb_fine" in res else "rgb_coarse"
+    return total.detach(), psnr(res[key].detach(), target)
+
+
 class GraphedTrainStep:
     """One fixed-shape optimisation step -- weight re-pack, render_rays forward, NerfWLoss, the HIP backward, Adam --
     captured ONCE into a HIP graph and replayed: a step becomes one graph launch (~35 kernel launches, ~25 allocations
@@ -558,24 +580,13 @@ class GraphedTrainStep:
             capture_all_reduce = self.all_reduce and dist.is_initialized() and dist.get_backend() == "nccl"
         self.captured_collective = bool(capture_all_reduce) and self.all_reduce
         dev = self.rays.device
-
-        extra = {} if barf_weights is None else dict(barf_weights=barf_weights)
+        hp = dict(N_samples=N_samples, N_importance=N_importance, use_disp=use_disp, perturb=perturb, noise_std=noise_std,
+                  white_back=white_back)
 
         def fwd_bwd():
             # (parameters the backward never reaches keep the zeros the arena was created with)
-            rays = self.rays if pose is None else posed_rays(pose, self.rays, self.ts, row_of_id, grad_arena=self.arena)
-            if loss_fn is None:      # NerfWLoss fused into the render kernels' per-ray epilogue (render_rays: loss_target)
-                res = render_rays(models, embeddings, rays, self.ts, N_samples, use_disp, perturb, noise_std,
-                                  N_importance, 32768, white_back, False, loss_target=self.target,
-                                  loss_coef=loss_coef, lambda_u=lambda_u, grad_arena=self.arena, **extra)
-                total = res["_nerfw_loss"]
-            else:
-                res = render_rays(models, embeddings, rays, self.ts, N_samples, use_disp, perturb, noise_std,
-                                  N_importance, 32768, white_back, False, grad_arena=self.arena, **extra)
-                total = sum(loss_fn(res, self.target).values())
-            total.backward()
-            key = "rgb_fine" if "rgb_fine" in res else "rgb_coarse"
-            return total.detach(), psnr(res[key].detach(), self.target)
+            return _loss_backward(models, embeddings, hp, self.rays, self.ts, self.target, self.arena, loss_fn, loss_coef,
+                                  lambda_u, pose, row_of_id, barf_weights)
 
         def reduce():
             self.arena.all_reduce(force=self.force)
@@ -683,7 +694,8 @@ class RayTrainer:
         self.use_graph = bool(use_graph)
         self._graphed = None
         self.hp = dict(N_samples=N_samples, N_importance=N_importance, use_disp=use_disp, perturb=perturb,
-                       noise_std=noise_std, white_back=white_back, batch_size=batch_size)
+                       noise_std=noise_std, white_back=white_back)      # GraphedTrainStep's sampling arguments
+        self.batch_size = int(batch_size)
         self.seed, self.optimizer_name = int(seed), optimizer
         self._sched_args = dict(name=lr_scheduler, num_epochs=num_epochs, decay_step=decay_step, decay_gamma=decay_gamma,
                                 poly_exp=poly_exp, warmup_multiplier=warmup_multiplier, warmup_epochs=warmup_epochs,
@@ -732,8 +744,7 @@ class RayTrainer:
                                     decay_gamma=decay_gamma, poly_exp=poly_exp, warmup_multiplier=warmup_multiplier,
                                     warmup_epochs=warmup_epochs, optimizer=optimizer)
         self.arena = parallel.GradArena(self.params)      # flat gradient memory: written by the backward, all-reduced in place
-        self.loss = NerfWLoss()
-        self.fused_loss = True          # False: the NerfWLoss module on the result dict (two extra launches), as the reference composes it
+        self.loss = NerfWLoss()         # its constants, fused into the render kernels (render_rays: loss_target)
         self.gen = torch.Generator(device=self.dev).manual_seed(seed + 1)
         rank, world = _rank_world()
         if world > 1:
@@ -770,12 +781,6 @@ class RayTrainer:
             fill_barf_weights(self.embeddings, self.current_epoch, self.barf_w)
             self._barf_epoch = self.current_epoch
 
-    def _world_rays(self, rays, ts, grad_arena=None):
-        """Training-layout rays through the learned poses (refine_pose), or the world rays themselves."""
-        if not self.refine_pose:
-            return rays
-        return posed_rays(self.pose, rays, ts, self.row_of_id, grad_arena=grad_arena)
-
     def c2w(self, rows):
         """Refined (len(rows), 3, 4) camera-to-world poses of pose rows `rows` (make_c2w(r, t) @ init_c2w), e.g. for
         eval.render_frame."""
@@ -785,44 +790,27 @@ class RayTrainer:
         with torch.no_grad():
             return self.pose(rows)[:, :3].clone()
 
-    def _extra(self):
-        self._sync_barf()
-        return {} if not self.refine_pose else dict(barf_weights=self.barf_w)
-
     # ---- one optimisation step on a ready batch ------------------------------------------------
     def step(self, rays, rgbs, ts):
         """rays: (R, 8) world rays, or with refine_pose the training layout (camera-frame direction, near, far, ...)."""
-        hp = self.hp
         self.arena.attach()          # parameters the backward never reaches keep the zeros the arena was created with
-        extra = self._extra()
-        rays = self._world_rays(rays, ts, self.arena)
-        if self.fused_loss:
-            # NerfWLoss computed in the render kernels' per-ray epilogue, its backward seeds with it
-            res = render_rays(self.models, self.embeddings, rays, ts, hp["N_samples"], hp["use_disp"], hp["perturb"],
-                              hp["noise_std"], hp["N_importance"], 32768, hp["white_back"], False, loss_target=rgbs,
-                              loss_coef=self.loss.coef, lambda_u=self.loss.lambda_u, grad_arena=self.arena, **extra)
-            total = res["_nerfw_loss"]
-        else:
-            res = render_rays(self.models, self.embeddings, rays, ts, hp["N_samples"], hp["use_disp"], hp["perturb"],
-                              hp["noise_std"], hp["N_importance"], 32768, hp["white_back"], False, grad_arena=self.arena,
-                              **extra)
-            total = sum(self.loss(res, rgbs).values())
-        total.backward()
+        self._sync_barf()
+        out = _loss_backward(self.models, self.embeddings, self.hp, rays, ts, rgbs, self.arena, loss_coef=self.loss.coef,
+                             lambda_u=self.loss.lambda_u, pose=self.pose, row_of_id=self.row_of_id, barf_weights=self.barf_w)
         self.arena.all_reduce()
         self.opt.step()
         self.global_step += 1
-        key = "rgb_fine" if "rgb_fine" in res else "rgb_coarse"
-        return total.detach(), psnr(res[key].detach(), rgbs)
+        return out
 
     # ---- one epoch over device-resident data (this rank's shard) -------------------------------
     def fit_epoch(self, rays, rgbs, ts):
-        n, bs = rays.shape[0], self.hp["batch_size"]
+        n, bs = rays.shape[0], self.batch_size
         perm = torch.randperm(n, device=self.dev, generator=self.gen)
         log = []
         self._sync_barf()
         for i in range(0, n - bs + 1, bs):
             idx = perm[i:i + bs]
-            if self.use_graph and self.fused_loss:
+            if self.use_graph:
                 if self._graphed is None:
                     self._graphed = self.graphed_step(rays[idx], ts[idx], rgbs[idx])
                 self._graphed.load(rays[idx], ts[idx], rgbs[idx])
@@ -840,11 +828,9 @@ class RayTrainer:
     def graphed_step(self, rays, ts, rgbs, **kw):
         """The GraphedTrainStep fit_epoch replays (use_graph=True), captured on this batch; `kw` go to GraphedTrainStep."""
         import torch.distributed as dist
-        hp = self.hp
         self._sync_barf()
         return GraphedTrainStep(
-            self.models, self.embeddings, self.params, self.opt, None, rays, ts, rgbs,
-            hp["N_samples"], hp["N_importance"], hp["use_disp"], hp["perturb"], hp["noise_std"], hp["white_back"],
+            self.models, self.embeddings, self.params, self.opt, None, rays, ts, rgbs, **self.hp,
             all_reduce=dist.is_initialized() and dist.get_world_size() > 1,
             loss_coef=self.loss.coef, lambda_u=self.loss.lambda_u, arena=self.arena,
             pose=self.pose, row_of_id=self.row_of_id, barf_weights=self.barf_w, **kw)
@@ -870,14 +856,14 @@ class RayTrainer:
 
     def _render_eval(self, rays, ts, chunk):
         hp = self.hp
-        extra = self._extra()
+        self._sync_barf()
         outs = []
         for i in range(0, rays.shape[0], chunk):
             r = rays[i:i + chunk]
-            if self.refine_pose and r.shape[1] != 8:
-                r = self._world_rays(r, ts[i:i + chunk])
-            res = render_rays(self.models, self.embeddings, r, ts[i:i + chunk], hp["N_samples"],
-                              hp["use_disp"], 0, 0, hp["N_importance"], chunk, hp["white_back"], False, **extra)
+            if self.refine_pose and r.shape[1] != 8:      # the training layout, through the learned poses
+                r = posed_rays(self.pose, r, ts[i:i + chunk], self.row_of_id)
+            res = render_rays(self.models, self.embeddings, r, ts[i:i + chunk], hp["N_samples"], hp["use_disp"], 0, 0,
+                              hp["N_importance"], chunk, hp["white_back"], False, barf_weights=self.barf_w)
             outs.append(res["rgb_fine" if "rgb_fine" in res else "rgb_coarse"])
         return torch.cat(outs)
 
@@ -1073,7 +1059,7 @@ class RayTrainer:
             meta = dict(epoch=self.current_epoch, global_step=self.global_step, state=state,
                         groups=[{k: v for k, v in g.items() if k != "params"} for g in opt.param_groups],
                         sched=None if self.sched is None else self.sched.state_dict(),
-                        dev_groups=sorted(gi for gi, d in opt._dev if d == str(pdev)))
+                        dev_groups=opt.device_state(pdev)[0])
         box = [dict(error=None if err is None else f"{type(err).__name__}: {err}", meta=meta)]
         dist.broadcast_object_list(box, src=src)
         if box[0]["error"] is not None:
@@ -1096,14 +1082,10 @@ class RayTrainer:
                         st[k] = torch.empty(shape, dtype=getattr(torch, dtype), device=pdev)
             if self.sched is not None and meta["sched"] is not None:
                 self.sched.load_state_dict(meta["sched"])
-            for gi in meta["dev_groups"]:
-                opt._dev_state(gi, opt.param_groups[gi], pdev)
         tensors = self._module_tensors()
         for p, m in zip(self.params, meta["state"]):
             if m is not None:
                 tensors += [opt.state[p][k] for k, _, _ in m["tensors"]]
-        for gi in meta["dev_groups"]:
-            ds = opt._dev[(gi, str(pdev))]
-            tensors += [ds["step"], ds["hyper"]]
-            ds["host"] = None                # the next sync_hyper() re-uploads from the (now common) param groups
+        # the next sync_hyper() re-uploads from the (now common) param groups
+        tensors += opt.device_state(pdev, meta["dev_groups"])[1]
         parallel.broadcast_tensors_(tensors, src=src)
