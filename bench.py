@@ -14,10 +14,14 @@ resident in HBM.
   --workload cfg3   configs[3] per-GPU shape instead (Phototourism: NeRF-W a+t, N_vocab 1500, black background,
                     per-ray near/far; --rays 1024 is the README batch)
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--mode train|render] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--mode train|render] [--dump-outputs DIR] [--full]
 
   --dump-outputs DIR  after the K timed steps, what the last one returned (result dict, loss, gradients, updated
                       parameters) as DIR/<name>.npy, so that two builds can be compared output for output
+  --full              after the timed steps, also measure and check what the headline does not need: the sustained
+                      rate, the same step with the other two backward arithmetics, the forward-only rate, the roofline
+                      launches, the CPU baseline and (N > 1) that the replicas' parameters stayed identical.  Without it
+                      a run sets up, warms up, times the K steps, writes --dump-outputs and prints its line.
 
 N > 1: run plainly (`python bench.py --gpus N`), this process then starts N ranks itself -- one fresh process per
 GPU, rendezvous on 127.0.0.1, and exits non-zero if any rank fails -- or run under a launcher
@@ -69,23 +73,28 @@ def parse_args(argv=None):
     ap.add_argument("--precision", default="f16x3", choices=["f16x3", "f16"])
     ap.add_argument("--graph", action="store_true", help="train mode: replay the step from one captured HIP graph")
     ap.add_argument("--unfused-loss", action="store_true", help="NerfWLoss as a module on the result dict (two more launches)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps: the companion measurements and checks (sustained rate, other backward "
+                         "arithmetics, forward-only rate, roofline, CPU baseline, replica consistency); off = only what the "
+                         "headline needs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the warm-up and the timed steps (no render-only companion, roofline launches or CPU baseline): "
-                         "the command the PMC passes of profiles/collect.sh count bytes over")
+                    help="with --full: no render-only companion, roofline launches or CPU baseline (the sustained rate and "
+                         "the replica check stay)")
     ap.add_argument("--render-steps", type=int, default=0,
-                    help="with --no-extras: this many forward-only steps after the timed ones (gives the PMC passes the "
-                         "inference instantiation of the render kernel to count bytes on)")
+                    help="without the companions (no --full, or --no-extras): this many forward-only steps after the timed "
+                         "ones (gives the PMC passes of profiles/collect.sh the inference instantiation of the render kernel "
+                         "to count bytes on)")
     ap.add_argument("--dry", action="store_true")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the process group and issue the gradient all-reduce at world size 1 too: exercises the "
                          "RCCL path (init, in-place all-reduce on the gradient arena, capture in the step's graph) on one GPU")
     ap.add_argument("--sustained-seconds", type=float, default=2.0,
-                    help="after the timed steps: keep stepping for this long with one HIP-event pair per step and report "
-                         "median / p90 (`sustained`); 0 = off")
+                    help="with --full, after the timed steps: keep stepping for this long with one HIP-event pair per step "
+                         "and report median / p90 (`sustained`); 0 = off")
     ap.add_argument("--only-default-backward", action="store_true",
-                    help="skip the companion measurements of the other backward arithmetics (the rocprofv3 --stats pass of "
-                         "profiles/collect.sh: keeps one population per kernel in the trace)")
+                    help="with --full: skip the companion measurements of the other backward arithmetics (the rocprofv3 "
+                         "--stats pass of profiles/collect.sh: keeps one population per kernel in the trace)")
     ap.add_argument("--backward", default="f16", choices=["f16", "f16w", "f16x3"],
                     help="arithmetic of the MLP backward: f16 = single fp16 product (default), f16w = the gradient chain reads "
                          "hi+lo weight fragments (two products: no systematic training-curve offset), f16x3 = split operands, "
@@ -354,11 +363,12 @@ def run_rank(args):
     last = None
 
     n_ranks = dist.get_world_size() if dist is not None else 1
+    extras = args.full and not args.no_extras
     # sustained rate (>= 100 timed iterations, event-timed, median): outside the driver-specified steps, the
     # same step for >= --sustained-seconds with one HIP event per step on the launch stream.  The step count is fixed
     # from the (rank-maximised) timing above, so that every rank issues the same number of collectives.
     sustained = None
-    if args.sustained_seconds > 0:
+    if args.full and args.sustained_seconds > 0:
         n_sus = max(100, int(args.sustained_seconds / max(elapsed / args.steps, 1e-6)) + 1)
         sustained = event_timed(step, n_sus)
         sync()
@@ -368,7 +378,7 @@ def run_rank(args):
     #   f16x3: operands split everywhere, three products, split stashes -- the train-step figure at the reference's
     #          precision class (`value_fp32_class`)
     other_modes = {}
-    if (args.mode == "train" and args.precision == "f16x3" and args.backward == "f16" and not args.no_extras
+    if (extras and args.mode == "train" and args.precision == "f16x3" and args.backward == "f16"
             and not args.only_default_backward):
         descr = {"f16w": "as the default (fp16 MFMA, 1 product, fp16 stashes, loss scale) but the gradient chain W^T delta reads "
                          "hi+lo weight fragments (2 products): weights to fp32 class in the chain",
@@ -402,7 +412,7 @@ def run_rank(args):
         nerf_fl_amd.set_precision(backward="f16")
     fp32_class = other_modes.get("f16x3")
     sync_diff = None
-    if dist is not None:
+    if args.full and dist is not None:
         # data parallelism keeps the replicas identical: same seeded weights, the same averaged gradients, the same Adam.
         # Largest difference between this rank's parameters and rank 0's, maximised over ranks: must be exactly 0.
         flat = torch.cat([p.detach().reshape(-1) for p in params])
@@ -456,16 +466,16 @@ def run_rank(args):
                                            if args.backward == "f16" else
                                            "as f16, the gradient chain reading hi+lo weight fragments (2 products)" if args.backward == "f16w" else
                                            "fp16 MFMA, operands split hi+lo, 3 products, fp32 accumulate, hi+lo stashes (f16x3)"),
-                   "mlp_evals_per_ray": N_SAMPLES + F, "hip_graph": bool(args.graph)},
+                   "mlp_evals_per_ray": N_SAMPLES + F, "hip_graph": bool(args.graph), "full": bool(args.full)},
     }
     if dumped is not None:
         out["dump_outputs"] = dumped
 
-    if args.no_extras:
+    if not extras:
         for _ in range(args.render_steps):
             render_step()
         sync()
-    if args.mode == "train" and not args.no_extras:
+    if extras and args.mode == "train":
         # forward-only throughput of the same batch, reported beside the train-step value
         for _ in range(3):
             render_step()
@@ -477,9 +487,9 @@ def run_rank(args):
         out["render_only_value"] = R * F * n_ranks * 20 / (time.perf_counter() - t0)
 
     if rank == 0:
-        if not args.no_extras:
+        if extras:
             out.update(roofline(args, rnd, models, emb, rays, ts, dev, fine_kind, white_back))
-        if n_ranks == 1 and not args.no_cpu_baseline and not args.no_extras:
+        if extras and n_ranks == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.mode)
         print(json.dumps(out))
     if dist is not None:

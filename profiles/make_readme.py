@@ -23,7 +23,7 @@ txt = f'''# profiles/ — MI355X, 1 GPU, ROCm 7.2, rocprofv3
 All numbers: configs[1] = 4096 rays x (64 + 64) samples, base NeRF coarse + fine,
 perturb 1, noise 1, white background, precision `f16x3` forward (the mode that meets the
 1e-4 parity bar) + loss-scaled `f16` backward. `bash profiles/collect.sh <tag>` runs the four rocprofv3 passes
-(`--kernel-trace --stats` over `python3 bench.py --no-cpu-baseline --only-default-backward --sustained-seconds 0 --steps 20 --warmup 5`, then
+(`--kernel-trace --stats` over `python3 bench.py --full --no-cpu-baseline --only-default-backward --sustained-seconds 0 --steps 20 --warmup 5`, then
 `--pmc FETCH_SIZE`, `--pmc WRITE_SIZE`, `--pmc <SQ block>`, each its own run, over
 `python3 bench.py --no-extras --steps 20 --warmup 5 --render-steps 3`: only train steps plus three forward-only
 steps for the inference instantiation) and reduces them on the box (`profiles/make_summary.py`: the raw output is more than
@@ -47,7 +47,7 @@ of the backward offsets the NeRF-W training curve: the fp16-rounded transposed w
 
 | file | what |
 |---|---|
-| `{tag}_bench_train.json` | `python bench.py` (default = train step, `f16` backward): **{bt["value"]:.3e} ray-samples/s**, {bt["ms_per_step"]:.2f} ms/step on this box (sustained over {bt["sustained"]["steps"]} event-timed steps: median {bt["sustained"]["median_ms"]:.2f}, p90 {bt["sustained"]["p90_ms"]:.2f} ms); `f16w` (gradient chain on hi + lo weights) {bt["exact_weight_chain"]["ms_per_step"]:.2f} ms = {bt["value_exact_weight_chain"]:.3e}; `f16x3` (fp32-class) {bt["fp32_class"]["ms_per_step"]:.2f} ms = {bt["value_fp32_class"]:.3e}; forward-only {bt["render_only_value"]:.2e}; CPU oracle train step {bt["cpu_baseline"]["value"]:.2e} (16 threads; forward alone {bt["cpu_baseline"]["forward_value"]:.2e}) |
+| `{tag}_bench_train.json` | `python bench.py --full` (default = train step, `f16` backward): **{bt["value"]:.3e} ray-samples/s**, {bt["ms_per_step"]:.2f} ms/step on this box (sustained over {bt["sustained"]["steps"]} event-timed steps: median {bt["sustained"]["median_ms"]:.2f}, p90 {bt["sustained"]["p90_ms"]:.2f} ms); `f16w` (gradient chain on hi + lo weights) {bt["exact_weight_chain"]["ms_per_step"]:.2f} ms = {bt["value_exact_weight_chain"]:.3e}; `f16x3` (fp32-class) {bt["fp32_class"]["ms_per_step"]:.2f} ms = {bt["value_fp32_class"]:.3e}; forward-only {bt["render_only_value"]:.2e}; CPU oracle train step {bt["cpu_baseline"]["value"]:.2e} (16 threads; forward alone {bt["cpu_baseline"]["forward_value"]:.2e}) |
 | `{tag}_bench_render.json` | `python bench.py --mode render`: **{br["value"]:.3e} ray-samples/s**, {br["ms_per_step"]:.2f} ms/step |
 | `{tag}_bench_cfg3_r1024.json`, `{tag}_bench_cfg3_r1024_graph.json`, `{tag}_bench_cfg3_r4096.json` | `--workload cfg3` (configs[3] per-GPU shape: NeRF-W a+t, N_vocab 1500, per-ray near/far): at the README batch of 1024 rays **{c1["ms_per_step"]:.2f} ms/step = {c1["value"]:.2e}** eager, {c1g["ms_per_step"]:.2f} ms replayed from one HIP graph (`--graph`); {c4["ms_per_step"]:.2f} ms = {c4["value"]:.2e} at 4096 rays |
 | `{tag}_bench_configs.json` | `tests/bench_configs.py`: configs[2] full NeRF-W train step {bc["cfg3_nerfw_train"]["ms_per_step"]:.2f} ms = {bc["cfg3_nerfw_train"]["ray_samples_per_s"]:.2e}; configs[4]-like eval (NeRF-W, 128+128, `test_time`, 131072 rays) {bc["cfg5_eval_direct"]["ms_per_131072_rays"]:.0f} ms = {bc["cfg5_eval_direct"]["rays_per_s"]:.2e} rays/s direct, {bc["cfg5_eval_hip_graph"]["ms_per_131072_rays"]:.0f} ms HIP-graph replayed; one 800 x 800 frame from (pose, intrinsics) {bc["cfg5_frame_800x800_camera_prologue"]["ms_per_frame"]:.0f} ms with the rays generated in the kernel prologue, {bc["cfg5_frame_800x800_ray_matrix"]["ms_per_frame"]:.0f} ms from a materialised ray matrix, {bc["cfg5_frame_800x800_camera_prologue_hip_graph"]["ms_per_frame"]:.0f} ms with the chunk replayed from ONE HIP graph whose prologue reads the camera from device memory ({bc["cfg5_frame_800x800_camera_prologue_hip_graph"]["captures"]} capture) |

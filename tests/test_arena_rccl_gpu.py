@@ -78,7 +78,7 @@ def _bench(extra_args, env_extra=None):
 def test_rccl_world1_eager_step():
     """backend nccl IS RCCL on ROCm: init_process_group(device_id=...), one in-place all-reduce of the 1.2 M-float
     gradient arena per step, Adam, re-pack -- on the one GPU of this box."""
-    out = _bench([])
+    out = _bench(["--full"])           # --full: the replica check
     assert out["backend"] == "nccl" and out["n_gpus"] == 1
     assert out["all_reduce"]["forced_at_world_1"] is True and out["all_reduce"]["numel"] >= 2 * 595844
     assert out["replica_param_max_diff"] == 0.0 and out["value"] > 0

@@ -49,7 +49,7 @@ def test_two_ranks_drive_the_real_render_path():
     (gloo for the collective, both on device 0: NFL_BENCH_BACKEND / NFL_BENCH_ONE_DEVICE), each renders and
     back-propagates its own ray shard, the flat gradient all-reduce averages, Adam steps -- and the two replicas'
     parameters stay bit-identical (the RCCL run itself needs the 8-GPU node)."""
-    p = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--no-extras"],
+    p = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-extras"],
              {"NFL_BENCH_BACKEND": "gloo", "NFL_BENCH_ONE_DEVICE": "1"}, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -67,7 +67,7 @@ def test_two_ranks_graphed_step_keeps_replicas_identical():
     nfl_composite_backward -- can take effect out of order with the kernel after it when a second process replays graphs on the
     same GPU: the maxima wiped, the loss scale wrong, non-finite gradients on one rank in up to half of the runs on some boxes.
     The library zeroes with a kernel since; tests/diag_two_rank_graph.py is the reproducer.)"""
-    p = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--no-extras", "--graph", "--sustained-seconds", "0"],
+    p = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-extras", "--graph", "--sustained-seconds", "0"],
              {"NFL_BENCH_BACKEND": "gloo", "NFL_BENCH_ONE_DEVICE": "1"}, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
