@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NFL_ABI_VERSION 9
+#define NFL_ABI_VERSION 10
 #define NFL_GMAX_SLOTS 1024
 
 enum {
@@ -473,6 +473,50 @@ typedef struct nfl_pose_args {
 } nfl_pose_args;
 int nfl_pose_rays(const nfl_pose_args* args, void* stream);
 int nfl_pose_rays_backward(const nfl_pose_args* args, void* stream);
+
+/* ---- NeRF-W appearance codes of unseen images (test-time optimisation; the paper's Phototourism protocol) ----------
+ * With the fields frozen and deterministic sampling, the appearance code a_i of image i enters the fine field only
+ * through the appearance columns W_a = dir_encoding.0.weight[:, 256 + cd : 256 + cd + n_a] (cd = 6 n_emb_dir + 3):
+ *   Z_s   = pre-activation of dir_encoding.0 at sample s with a zero appearance input          (constant: the cache)
+ *   u_i   = W_a a_i;   rgb_s = sigmoid(W_rgb relu(Z_s + u_i) + b_rgb);   rgb_r = sum_s w_s rgb_s (+ 1 - opacity_r)
+ * nfl_appearance_cache runs one fine render pass (same arguments and outputs as nfl_render_pass; d_a_emb must hold
+ * ZEROS, no transient head, three-product plan only) that also writes Z: d_zcache (n_rays, 128, n_pad) fp32, layout
+ * [ray][feature][sample], n_pad >= n_samples a multiple of 64; samples n_samples .. n_pad - 1 are not written.  The
+ * pass's d_weights (w_s) and d_opacity are the other inputs of the fit. */
+int nfl_appearance_cache(const void* h_plan, const void* d_plan, const void* d_packed, const nfl_pass_args* args,
+                         float* d_zcache, int32_t n_pad, void* stream);
+/* One fit iteration on the MSE  L = sum_r |rgb_r - target_r|^2 / (3 R), in two launches and no atomics
+ * (bit-reproducible), no memset or memcpy (graph-capturable):
+ *   fit:    one wavefront per work item (a range of rays of ONE image; the caller groups the rays by image and
+ *           lists the items): u_i from the current codes, the forward above on the streamed cache, the backward
+ *           dL/dpre_s = (W_rgb^T (w_s g_r . rgb_s . (1 - rgb_s))) . [Z_s + u_i > 0], g_r = 2 (rgb_r - target_r) / (3 R),
+ *           summed over the item's samples in registers; writes one 128-float gradient partial and one squared-error
+ *           partial per item to d_partials, and rgb_r to d_rgb when that is set;
+ *   reduce: per image, the partials of its items in order, then W_a^T: WRITES d_grad (every row; an image without
+ *           items gets exact zeros) and *d_loss = L.
+ * Weights are read in fp32 from the ORIGINAL parameters (not the folded copies).  NFL_EINVAL: a NULL pointer the
+ * call needs, n_pad not a multiple of 64 or < n_samples, n_pad > 256, n_a outside 1..128, sizes < 0. */
+typedef struct nfl_appfit_args {
+    const float*   d_zcache;       /* (n_rays, 128, n_pad) from nfl_appearance_cache, rays grouped by image            */
+    const float*   d_weights;      /* (n_rays, n_samples) w_s of the cache pass                                         */
+    const float*   d_opacity;      /* (n_rays) of the cache pass; read only with white_back                             */
+    const float*   d_target;       /* (n_rays, 3)                                                                       */
+    const int32_t* d_items;        /* (n_items, 3): image, first ray, end ray (exclusive)                               */
+    const int32_t* d_image_items;  /* (n_images + 1): items of image i are [d_image_items[i], d_image_items[i + 1])      */
+    const float*   d_codes;        /* (n_images, n_a)                                                                   */
+    const float*   d_w_dir;        /* dir_encoding.0.weight (128, ld_dir)                                               */
+    const float*   d_w_rgb;        /* static_rgb.0.weight (3, 128)                                                      */
+    const float*   d_b_rgb;        /* static_rgb.0.bias (3)                                                             */
+    int32_t n_rays, n_samples, n_pad, n_items;
+    int32_t n_images, n_a, ld_dir, col_a;   /* col_a = 256 + cd: first appearance column of dir_encoding.0            */
+    int32_t white_back, reserved;
+    float*  d_partials;            /* scratch, nfl_appfit_partials_floats(n_items) floats, overwritten                 */
+    float*  d_grad;                /* out (n_images, n_a)                                                               */
+    float*  d_loss;                /* out (1)                                                                           */
+    float*  d_rgb;                 /* out (n_rays, 3) rgb_r under the current codes, or NULL                            */
+} nfl_appfit_args;
+size_t nfl_appfit_partials_floats(int32_t n_items);
+int nfl_appearance_fit(const nfl_appfit_args* args, void* stream);
 
 /* ---- hierarchical sampling (reference sample_pdf, rendering.py:7-46, plus the
  * concat + sort of rendering.py:267-272) -------------------------------------

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = ((os.environ.get("NFL_LIB") if os.environ.get("NERF_FL_AMD_DEV") == "1" else None)
             or os.path.join(_HERE, "libnerf_fl_amd.so"))
 
-NFL_ABI_VERSION = 9
+NFL_ABI_VERSION = 10
 NFL_GMAX_SLOTS = 1024
 NFL_PREC_F16X3 = 0
 NFL_PREC_F16 = 1
@@ -144,6 +144,16 @@ class PoseArgs(C.Structure):
                 ("d_g_rays", C.c_void_p), ("d_g_r", C.c_void_p), ("d_g_t", C.c_void_p), ("d_status", C.c_void_p)]
 
 
+class AppFitArgs(C.Structure):
+    _fields_ = [("d_zcache", C.c_void_p), ("d_weights", C.c_void_p), ("d_opacity", C.c_void_p), ("d_target", C.c_void_p),
+                ("d_items", C.c_void_p), ("d_image_items", C.c_void_p), ("d_codes", C.c_void_p), ("d_w_dir", C.c_void_p),
+                ("d_w_rgb", C.c_void_p), ("d_b_rgb", C.c_void_p),
+                ("n_rays", C.c_int32), ("n_samples", C.c_int32), ("n_pad", C.c_int32), ("n_items", C.c_int32),
+                ("n_images", C.c_int32), ("n_a", C.c_int32), ("ld_dir", C.c_int32), ("col_a", C.c_int32),
+                ("white_back", C.c_int32), ("reserved", C.c_int32),
+                ("d_partials", C.c_void_p), ("d_grad", C.c_void_p), ("d_loss", C.c_void_p), ("d_rgb", C.c_void_p)]
+
+
 # every symbol include/nerf_fl_amd.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("nfl_plan_bytes", C.c_size_t, [C.POINTER(FieldDesc)]),
@@ -185,6 +195,10 @@ SYMBOLS = [
     ("nfl_loss_backward", C.c_int, [C.POINTER(LossArgs), C.c_void_p]),
     ("nfl_pose_rays", C.c_int, [C.POINTER(PoseArgs), C.c_void_p]),
     ("nfl_pose_rays_backward", C.c_int, [C.POINTER(PoseArgs), C.c_void_p]),
+    ("nfl_appearance_cache", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PassArgs), C.c_void_p, C.c_int32,
+                                       C.c_void_p]),
+    ("nfl_appfit_partials_floats", C.c_size_t, [C.c_int32]),
+    ("nfl_appearance_fit", C.c_int, [C.POINTER(AppFitArgs), C.c_void_p]),
     ("nfl_abi_version", C.c_int, []),
     ("nfl_version", C.c_char_p, []),
     ("nfl_strerror", C.c_char_p, [C.c_int]),

@@ -95,6 +95,8 @@ struct RenderArgs {
     int n_a, n_tau;             // widths of the appearance / transient codes (<= 48 / 16; narrower: the k-steps are zero-padded)
     int gen_rays;               // rays come from `cam` (nfl_pass_args::h_cam), not from a.d_rays
     nfl_camera cam;
+    float* zcache;              // NFL_MODE_ZCACHE: the appearance cache (nfl_appearance_cache), else null
+    int zpad;                   // its padded sample count
 };
 
 // ---------------------------------------------------------------------------------
@@ -475,7 +477,7 @@ struct NflNoEpi {
 // Epilogue of an accumulator tile -> the two k-steps (ks, ks+1) of the next layer's B operand
 // (and, in the training forward, the fp16 activation stash), cut into 8 pair-ops per column
 // block so it can be spread over the k-steps of the following tile.
-template <int NP, int NCB, bool RELU, bool STASH, int NOUT, int MSLOT, int LO = 0>
+template <int NP, int NCB, bool RELU, bool STASH, int NOUT, int MSLOT, int LO = 0, bool ZST = false>
 struct NflActEpi {
     const f16v (&acc)[NCB];
     h8 (&out)[NOUT][NCB][NP];
@@ -486,6 +488,8 @@ struct NflActEpi {
     const int mword;                 // mask word of this tile
     unsigned (&mq)[NCB][4];          // the words of the current group of four tiles: one dwordx4 store per group
     unsigned& ovf;                   // NflRing::ovf
+    float* const* zc;                // ZST: per segment, the lane's sample column of its ray's appearance cache
+    const int zpad;                  // ZST: sample stride of the cache
     h8 tmp[NCB];
     h8 tmpl[LO != 0 ? NCB : 1];      // residual halves for the split stash (LO: their byte offset behind the hi image)
     unsigned m32[NCB];
@@ -496,6 +500,11 @@ struct NflActEpi {
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) {
             float x0 = acc[cb][8 * s + j], x1 = acc[cb][8 * s + j + 1];
+            if constexpr (ZST) {        // NFL_MODE_ZCACHE: the fp32 pre-activation of features f, f + 1 (NFL_SEG_ACT)
+                const int f = 16 * (ks + s) + 8 * (j >> 2) + 4 * (int)((threadIdx.x & 63) >> 5) + (j & 3);
+                zc[cb][(size_t)f * zpad] = x0;
+                zc[cb][(size_t)(f + 1) * zpad] = x1;
+            }
             if (RELU) {
                 x0 = nfl_relu(x0);
                 x1 = nfl_relu(x1);
@@ -556,12 +565,14 @@ struct NflActEpi {
 
 // A dense layer of NRT row tiles reading inA[ksA0..+NKA) then inB[ksB0..+NKB), TPC tiles per
 // ring chunk.  The epilogue of tile i-1 rides in the MFMA shadows of tile i.
-template <int NP, int NCB, int NKA, int NKB, bool RELU, int NRT, int TPC, bool STASH, int LO = 0, int PRODS = 3, int NINA, int NINB, int NOUT, class Ring>
+// ZST (NFL_MODE_ZCACHE, a layer whose output starts at k-step 0): the epilogue also stores the fp32 pre-activations to
+// zc[cb][f * zpad] (the appearance cache, nfl_appearance_cache).
+template <int NP, int NCB, int NKA, int NKB, bool RELU, int NRT, int TPC, bool STASH, int LO = 0, int PRODS = 3, bool ZST = false, int NINA, int NINB, int NOUT, class Ring>
 NFL_DEV void nfl_dense(Ring& ring, const float* bias_lds, int& rt, int h,
                        const h8 (&inA)[NINA][NCB][NP], int ksA0,
                        const h8 (&inB)[NINB][NCB][NP], int ksB0,
                        h8 (&out)[NOUT][NCB][NP], int out_ks0, char* const (&stash)[NCB], int slot0,
-                       char* const (&mstash)[NCB], int mw0) {
+                       char* const (&mstash)[NCB], int mw0, float* const* zc = nullptr, int zpad = 0) {
     constexpr int NK = NKA + NKB;
     constexpr int NST = 2 * NCB * (LO != 0 ? 2 : 1);     // activation-stash stores of one tile's epilogue (the mask
                                                          // words go out once per four tiles: not counted, the wait is only stricter)
@@ -580,7 +591,7 @@ NFL_DEV void nfl_dense(Ring& ring, const float* bias_lds, int& rt, int h,
         constexpr int frag0 = (i % TPC) * NK;
         nfl_bias_init<NP, NCB>(acc[i & 1], bias_lds + (rt + i) * 32, h);
         if constexpr (i > 0) {
-            NflActEpi<NP, NCB, RELU, STASH, NOUT, (i - 1) & 3, LO> epi{acc[(i - 1) & 1], out, out_ks0 + 2 * (i - 1), stash, slot0 + 2 * (i - 1), mstash, mw0 + i - 1, mq, ring.ovf};
+            NflActEpi<NP, NCB, RELU, STASH, NOUT, (i - 1) & 3, LO, ZST> epi{acc[(i - 1) & 1], out, out_ks0 + 2 * (i - 1), stash, slot0 + 2 * (i - 1), mstash, mw0 + i - 1, mq, ring.ovf, zc, zpad};
             nfl_tile_p<PRODS, NP, NCB, NK, frag0, h8>(acc[i & 1], wl, frag0, getb, epi, ring);
         } else {
             NflNoEpi epi;
@@ -589,7 +600,7 @@ NFL_DEV void nfl_dense(Ring& ring, const float* bias_lds, int& rt, int h,
         // pieces the k-loop of this chunk did not get to
         if (i % TPC == TPC - 1 || i == NRT - 1) ring.template pieces<((i % TPC) + 1) * NK, Ring::MAXP>();
     });
-    NflActEpi<NP, NCB, RELU, STASH, NOUT, (NRT - 1) & 3, LO> last{acc[(NRT - 1) & 1], out, out_ks0 + 2 * (NRT - 1), stash, slot0 + 2 * (NRT - 1), mstash, mw0 + NRT - 1, mq, ring.ovf};
+    NflActEpi<NP, NCB, RELU, STASH, NOUT, (NRT - 1) & 3, LO, ZST> last{acc[(NRT - 1) & 1], out, out_ks0 + 2 * (NRT - 1), stash, slot0 + 2 * (NRT - 1), mstash, mw0 + NRT - 1, mq, ring.ovf, zc, zpad};
     last.all();
     rt += NRT;
 }
@@ -705,9 +716,12 @@ NFL_DEV NflKCam nfl_kcam(NflKArgs K) {
 #define NFL_MODE_STASH2 3     // as STASH, with split (hi + lo) activation records for the three-product backward
 #define NFL_MODE_EMBED 2      // NeRF.forward on already-encoded inputs (reference models/nerf.py:153-212): no
                               // depth generation / encoding / compositing, 32 points per segment
+#define NFL_MODE_ZCACHE 4     // render + the pre-activation of dir_encoding.0 to the appearance cache (nfl_appearance_cache)
+
 template <int NSPLIT, int NCB, int NFX, int MODE>
 __global__ __launch_bounds__(256, 1) void nfl_render_kernel(const RenderArgs A) {
     constexpr bool STASH = MODE == NFL_MODE_STASH || MODE == NFL_MODE_STASH2, EMBED = MODE == NFL_MODE_EMBED;
+    constexpr bool ZC = MODE == NFL_MODE_ZCACHE;
     using C = NflRenderCfg<NSPLIT, NCB, NFX>;
     constexpr int NP = C::NP, NKP = C::NKP, NSLOT = C::NSLOT;
     constexpr int SMULT = MODE == NFL_MODE_STASH2 ? 2 : 1;                              // records per segment: hi (+ lo)
@@ -770,6 +784,7 @@ __global__ __launch_bounds__(256, 1) void nfl_render_kernel(const RenderArgs A) 
         h8 X[16][NCB][NP], Y[16][NCB][NP];
         char* st[NCB];        // this lane's slice of the segment's activation record (training forward) or null
         char* mst[NCB];       // ... and of its relu-mask record
+        float* zc[NCB];       // NFL_MODE_ZCACHE: the sample column of the segment's ray in the appearance cache
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) {
             const int g = tile * NSLOT + wave * NCB + cb;        // segment index inside this workgroup
@@ -827,6 +842,8 @@ __global__ __launch_bounds__(256, 1) void nfl_render_kernel(const RenderArgs A) 
             s_ray[cb] = ray;
             s_idx[cb] = ii;
             s_ok[cb] = ok;
+            // padded samples (ii clamped to N - 1) re-store the last real sample's values: identical bytes, no branch
+            zc[cb] = ZC ? K->zcache + (size_t)ray * 128 * K->zpad + ii : nullptr;
             s_z[cb] = z;
             s_dl[cb] = ii + 1 < N ? zn - z : 1e2f;
             if (K->a.d_z_out && ok && h == 0) K->a.d_z_out[(size_t)ray * N + ii] = z;
@@ -942,9 +959,9 @@ __global__ __launch_bounds__(256, 1) void nfl_render_kernel(const RenderArgs A) 
                 }
                 NFL_STAMP(11);
                 if (K->has_a)
-                    nfl_dense<NP, NCB, 16, 5, true, 4, 1, STASH, LO, NFL_PRODS[NFL_P_IDX_DIR]>(ring, bias_lds, rt, h, Y, 0, D, 0, X, 0, st, nfl_act_dirh(NKP), mst, nfl_msk_dirh());
+                    nfl_dense<NP, NCB, 16, 5, true, 4, 1, STASH, LO, NFL_PRODS[NFL_P_IDX_DIR], ZC>(ring, bias_lds, rt, h, Y, 0, D, 0, X, 0, st, nfl_act_dirh(NKP), mst, nfl_msk_dirh(), zc, ZC ? K->zpad : 0);
                 else
-                    nfl_dense<NP, NCB, 16, 2, true, 4, 1, STASH, LO, NFL_PRODS[NFL_P_IDX_DIR]>(ring, bias_lds, rt, h, Y, 0, D, 0, X, 0, st, nfl_act_dirh(NKP), mst, nfl_msk_dirh());
+                    nfl_dense<NP, NCB, 16, 2, true, 4, 1, STASH, LO, NFL_PRODS[NFL_P_IDX_DIR], ZC>(ring, bias_lds, rt, h, Y, 0, D, 0, X, 0, st, nfl_act_dirh(NKP), mst, nfl_msk_dirh(), zc, ZC ? K->zpad : 0);
             }
             NFL_STAMP(12);
             {
@@ -1218,9 +1235,11 @@ __global__ __launch_bounds__(256, 1) void nfl_render_kernel(const RenderArgs A) 
 
 template <int NSPLIT, int NCB, int NFX, int MODE>
 static int nfl_launch_render_t(const NflPlan* hp, const void* d_plan, const void* d_packed,
-                             const nfl_pass_args* args, hipStream_t stream) {
+                             const nfl_pass_args* args, hipStream_t stream, float* zcache = nullptr, int zpad = 0) {
     using C = NflRenderCfg<NSPLIT, NCB, NFX>;
     RenderArgs A;
+    A.zcache = zcache;
+    A.zpad = zpad;
     A.plan = static_cast<const NflPlan*>(d_plan);
     A.packed = static_cast<const char*>(d_packed);
     A.a = *args;
@@ -1288,4 +1307,17 @@ static int nfl_launch_render(const NflPlan* hp, const void* d_plan, const void* 
         return nfl_launch_render_t<NSPLIT, NCB, NFX, (NSPLIT == 3 ? NFL_MODE_STASH : NFL_MODE_RENDER)>(hp, d_plan, d_packed, args, stream);
     }
     return nfl_launch_render_t<NSPLIT, NCB, NFX, NFL_MODE_RENDER>(hp, d_plan, d_packed, args, stream);
+}
+
+// the cache-building pass of nfl_appearance_cache (three-product arithmetic only: the cache is fp32-class)
+template <int NSPLIT, int NCB, int NFX>
+static int nfl_launch_zcache(const NflPlan* hp, const void* d_plan, const void* d_packed, const nfl_pass_args* args,
+                             float* zcache, int zpad, hipStream_t stream) {
+#ifdef NFL_DIAG_INFERENCE_ONLY
+    return NFL_EINVAL;
+#else
+    if (NSPLIT != 3) return NFL_EINVAL;
+    return nfl_launch_render_t<NSPLIT, NCB, NFX, (NSPLIT == 3 ? NFL_MODE_ZCACHE : NFL_MODE_RENDER)>(hp, d_plan, d_packed, args,
+                                                                                                 stream, zcache, zpad);
+#endif
 }

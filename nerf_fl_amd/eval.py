@@ -15,7 +15,8 @@ import torch
 from . import parallel
 from .rendering import CameraRays, render_rays
 
-__all__ = ["batched_inference", "GraphedChunk", "frame_rays", "to_uint8", "dolly_path", "render_frame", "render_video"]
+__all__ = ["batched_inference", "GraphedChunk", "frame_rays", "to_uint8", "dolly_path", "render_frame", "render_video",
+           "fit_and_evaluate_halves"]
 
 
 class GraphedChunk:
@@ -196,6 +197,42 @@ def frame_rays_of(cam_rays):
     c2w = torch.tensor(list(c.c2w), dtype=torch.float32).reshape(3, 4)
     K = torch.tensor([[c.fx, 0.0, c.cx], [0.0, c.fy, c.cy], [0.0, 0.0, 1.0]])
     return frame_rays(c2w, K, cam_rays.H, cam_rays.W, c.near, c.far, cam_rays.device, cam_rays.start, cam_rays.count)
+
+
+def fit_and_evaluate_halves(models, embeddings, c2w, K, H, W, near, far, rgb, N_samples=64, N_importance=64, n_iters=300,
+                            lr=0.05, init=None, use_disp=False, white_back=False, chunk=1024 * 128, use_graph=False,
+                            device="cuda:0", **kwargs):
+    """The NeRF-W evaluation protocol for one image (H x W, pose `c2w`, intrinsics `K`, colours `rgb` (H, W, 3) or
+    (H*W, 3)): fit its appearance code on the left half's rays (appearance.AppearanceFit, `n_iters` iterations of Adam
+    at `lr`, starting from `init` (N_a,) or the mean of the table), render the right half with
+    batched_inference(test_time, output_transient=False, a_embedded=code[None]) and return (code (N_a,), PSNR of the
+    right half).  `barf_weights` / `current_epoch` (refine_pose fields) go to both the fit and the right-half render;
+    `view_dir` is given for the whole image (H*W, 3) and split into the halves; any other kwarg (max_cache_bytes, ...)
+    goes to AppearanceFit."""
+    import math
+
+    from .appearance import AppearanceFit
+    dev = torch.device(device)
+    rays = frame_rays(c2w, K, H, W, near, far, dev)
+    rgb = torch.as_tensor(rgb).to(dev, torch.float32).reshape(H * W, 3)
+    left = torch.arange(H * W, device=dev) % W < W // 2
+    rays_l, rgb_l, rays_r, rgb_r = rays[left], rgb[left], rays[~left], rgb[~left]
+    start = None if init is None else torch.as_tensor(init, dtype=torch.float32).reshape(1, -1)
+    shared = {k: kwargs.pop(k) for k in ("barf_weights", "current_epoch") if kwargs.get(k) is not None}
+    fit_kw, render_kw = dict(kwargs, **shared), dict(shared)
+    if kwargs.get("view_dir") is not None:
+        view_dir = torch.as_tensor(kwargs["view_dir"]).to(dev, torch.float32).reshape(H * W, 3)
+        fit_kw["view_dir"], render_kw["view_dir"] = view_dir[left], view_dir[~left]
+    fit = AppearanceFit(models, embeddings, rays_l, rgb_l, torch.zeros(rays_l.shape[0], dtype=torch.int64, device=dev),
+                        N_samples, N_importance, use_disp=use_disp, white_back=white_back, init=start, lr=lr, chunk=chunk,
+                        **fit_kw)
+    code = fit.fit(n_iters, use_graph=use_graph)[0].clone()
+    del fit                                 # the cache is 512 B per padded sample: free it before the right half
+    with torch.no_grad():
+        res = batched_inference(models, embeddings, rays_r, None, N_samples, N_importance, use_disp, chunk, white_back,
+                                output_transient=False, a_embedded=code[None], **render_kw)
+    mse = ((res["rgb_fine"] - rgb_r) ** 2).mean().item()
+    return code, (-10.0 * math.log10(mse) if mse > 0 else float("inf"))
 
 
 def to_uint8(rgb):

@@ -340,8 +340,8 @@ _fields = weakref.WeakKeyDictionary()
 _lin_cache = {}
 
 
-def _field(model, n_emb_xyz, n_emb_dir, device, pack=True):
-    prec = _PREC[_precision]
+def _field(model, n_emb_xyz, n_emb_dir, device, pack=True, prec=None):
+    prec = _PREC[_precision] if prec is None else prec
     slot = _fields.setdefault(model, {})
     k = (prec, str(device), n_emb_xyz, n_emb_dir)
     if k not in slot:
@@ -452,7 +452,9 @@ def _n_freqs(emb):
 def _run_pass(field, rays, n_samples, *, z=None, lin=None, perturb_rand=None, perturb=0.0, use_disp=False,
               noise=None, noise_std=0.0, a_emb=None, t_emb=None, view_dir=None, sigma_only=False,
               white_back=False, test_extras=False, want_rgb=True, want_z=False, field_raw=False, stash=False,
-              pe_w_xyz=None, pe_w_dir=None, loss=None, loss_slot=0, bprec=_lib.NFL_PREC_F16):
+              pe_w_xyz=None, pe_w_dir=None, loss=None, loss_slot=0, bprec=_lib.NFL_PREC_F16, zcache=None):
+    """One nfl_render_pass; with `zcache` ((R, 128, n_pad) fp32) the pass is nfl_appearance_cache instead, which also writes
+    the pre-activation of dir_encoding.0 there (nerf_fl_amd.appearance)."""
     R = rays.shape[0]
     dev = rays.device
     new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
@@ -506,6 +508,10 @@ def _run_pass(field, rays, n_samples, *, z=None, lin=None, perturb_rand=None, pe
         a.d_seed_rgb, a.d_seed_beta = _ptr(out["seed_rgb"]), _ptr(out.get("seed_beta"))
         a.loss_coef, a.lambda_u, a.loss_slot = float(loss["coef"]), float(loss["lambda_u"]), int(loss_slot)
     a.d_status = _ptr(_status_word(dev))
+    if zcache is not None:
+        _lib.check(_lib.lib().nfl_appearance_cache(field.h_plan, _ptr(field.d_plan), _ptr(field.packed), C.byref(a), _ptr(zcache),
+                                                   zcache.shape[2], _stream()), "nfl_appearance_cache")
+        return out
     _lib.check(_lib.lib().nfl_render_pass(field.h_plan, _ptr(field.d_plan), _ptr(field.packed), C.byref(a), _stream()),
                "nfl_render_pass")
     return out
