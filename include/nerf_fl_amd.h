@@ -518,6 +518,51 @@ typedef struct nfl_appfit_args {
 size_t nfl_appfit_partials_floats(int32_t n_items);
 int nfl_appearance_fit(const nfl_appfit_args* args, void* stream);
 
+/* ---- training batches from uint8 images kept on the device (reference datasets/blender.py:73-101,
+ * datasets/phototourism.py:150-183: the all_rays / all_rgbs buffers, never materialised) ------------------------------
+ * d_pixels holds the images back to back, each row-major H x W x C uint8 with C = 3 or 4 (an RGBA image starts at a
+ * 4-byte-aligned byte offset); d_table holds one nfl_image_rec per image, pix0 ascending from 0 and
+ * pix0[i + 1] = pix0[i] + width[i] * height[i].  Work item p in [start, start + count) handles flat pixel
+ *   q = p                       (key == 0)
+ *   q = perm_{key, n_pixels}(p) (key != 0): a keyed bijection of [0, n_pixels) that is computed, not stored -- a balanced
+ *       Feistel network (6 rounds) over 2 h bits, h = max(1, ceil(bits(n_pixels - 1) / 2)), walked until the value is
+ *       below n_pixels (at most ~4 evaluations on average).  With x = (L << h) | R, round i maps
+ *       (L, R) -> (R, L ^ (mix(R * 0x9E3779B1 + k_i) & (2^h - 1))) in uint32 arithmetic,
+ *       mix(v) = v ^= v >> 16, v *= 0x85EBCA6B, v ^= v >> 13, v *= 0xC2B2AE35, v ^= v >> 16  (murmur3's finaliser), and
+ *       k_i = low 32 bits of splitmix64's i-th output from state `key`
+ *       (z = (state += 0x9E3779B97F4A7C15); z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *       z ^ z >> 31).  It depends on (key, n_pixels) only.
+ * The image of q is found by a binary search of pix0, (x, y) from the image's width, and row p - start is written:
+ *   d_rays  NFL_LAYOUT_WORLD  (count, 8): origin, unit direction, near, far -- the arithmetic (and the device function) of
+ *                             nfl_gen_rays, so the row is bit-identical to that call for the same pose and pixel;
+ *           NFL_LAYOUT_CAMERA (count, 5): [(x - cx) / fx, -(y - cy) / fy, -1] (not normalised), near, far -- the
+ *                             training layout nfl_pose_rays consumes;
+ *   d_ts    (count) int64: the image's id;
+ *   d_rgb   (count, 3): c / 255.0f by true division (torchvision's ToTensor); for C = 4 then rgb * a + (1 - a) with every
+ *           operation rounded on its own (blender.py:89).
+ * Any of the three outputs may be NULL and is then skipped.  One launch.  NFL_EINVAL: args, d_pixels or d_table NULL,
+ * n_images < 1, n_pixels outside [1, 2^40), start or count < 0, start + count > n_pixels, an unknown layout. */
+enum { NFL_LAYOUT_WORLD = 0, NFL_LAYOUT_CAMERA = 1 };
+typedef struct nfl_image_rec {
+    int64_t pix0;               /* pixels of all earlier images                           */
+    int64_t byte0;              /* byte offset of this image in d_pixels                  */
+    int32_t width, height, channels, id;
+    float   fx, fy, cx, cy, near, far;
+    float   c2w[12];            /* 3 x 4 row-major */
+} nfl_image_rec;
+typedef struct nfl_gather_args {
+    const uint8_t*       d_pixels;
+    const nfl_image_rec* d_table;     /* (n_images) */
+    int32_t  n_images, layout;
+    int64_t  n_pixels, start;
+    uint64_t key;
+    int32_t  count, reserved;
+    float*   d_rays;                  /* out (count, 8 | 5) or NULL */
+    int64_t* d_ts;                    /* out (count) or NULL        */
+    float*   d_rgb;                   /* out (count, 3) or NULL     */
+} nfl_gather_args;
+int nfl_gather_batch(const nfl_gather_args* args, void* stream);
+
 /* ---- hierarchical sampling (reference sample_pdf, rendering.py:7-46, plus the
  * concat + sort of rendering.py:267-272) -------------------------------------
  * d_z_coarse (R,S), d_weights_coarse (R,S); d_u (R,I) or NULL with d_u_row (I)

@@ -154,6 +154,23 @@ class AppFitArgs(C.Structure):
                 ("d_partials", C.c_void_p), ("d_grad", C.c_void_p), ("d_loss", C.c_void_p), ("d_rgb", C.c_void_p)]
 
 
+# nfl_gather_batch (data.ImageBank) was added without moving NFL_ABI_VERSION: no existing struct or signature changed, and
+# a library that lacks the symbol already fails in lib() below (every SYMBOLS entry is looked up)
+NFL_LAYOUT_WORLD, NFL_LAYOUT_CAMERA = 0, 1
+
+
+class ImageRec(C.Structure):
+    _fields_ = [("pix0", C.c_int64), ("byte0", C.c_int64), ("width", C.c_int32), ("height", C.c_int32),
+                ("channels", C.c_int32), ("id", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("near", C.c_float), ("far", C.c_float), ("c2w", C.c_float * 12)]
+
+
+class GatherArgs(C.Structure):
+    _fields_ = [("d_pixels", C.c_void_p), ("d_table", C.c_void_p), ("n_images", C.c_int32), ("layout", C.c_int32),
+                ("n_pixels", C.c_int64), ("start", C.c_int64), ("key", C.c_uint64), ("count", C.c_int32),
+                ("reserved", C.c_int32), ("d_rays", C.c_void_p), ("d_ts", C.c_void_p), ("d_rgb", C.c_void_p)]
+
+
 # every symbol include/nerf_fl_amd.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("nfl_plan_bytes", C.c_size_t, [C.POINTER(FieldDesc)]),
@@ -199,6 +216,7 @@ SYMBOLS = [
                                        C.c_void_p]),
     ("nfl_appfit_partials_floats", C.c_size_t, [C.c_int32]),
     ("nfl_appearance_fit", C.c_int, [C.POINTER(AppFitArgs), C.c_void_p]),
+    ("nfl_gather_batch", C.c_int, [C.POINTER(GatherArgs), C.c_void_p]),
     ("nfl_abi_version", C.c_int, []),
     ("nfl_version", C.c_char_p, []),
     ("nfl_strerror", C.c_char_p, [C.c_int]),

@@ -648,7 +648,8 @@ class GraphedTrainStep:
 
 
 class RayTrainer:
-    """Fit coarse+fine fields to (rays, rgbs, ts) tensors that are already on the device."""
+    """Fit coarse+fine fields to (rays, rgbs, ts) tensors that are already on the device, or to a data.ImageBank of
+    uint8 images kept there (fit_epoch(bank))."""
 
     def __init__(self, device, N_emb_xyz=10, N_emb_dir=4, N_samples=64, N_importance=64, use_disp=False,
                  perturb=1.0, noise_std=1.0, white_back=True, encode_a=False, encode_t=False, N_vocab=100,
@@ -803,7 +804,16 @@ class RayTrainer:
         return out
 
     # ---- one epoch over device-resident data (this rank's shard) -------------------------------
-    def fit_epoch(self, rays, rgbs, ts):
+    def fit_epoch(self, rays, rgbs=None, ts=None):
+        """One epoch over (rays, rgbs, ts) tensors (this rank's shard, in a random order drawn from the trainer's
+        permutation generator), or fit_epoch(bank) over a data.ImageBank: the order is the computed permutation keyed
+        by data.epoch_key(seed, current_epoch), the same on every rank (build the ranks with the same `seed`); step s of
+        rank r of P takes its positions [(s P + r) bs, (s P + r + 1) bs), n_pixels // (bs P) steps, the tail dropped."""
+        from .data import ImageBank
+        if isinstance(rays, ImageBank):
+            if rgbs is not None or ts is not None:
+                raise ValueError("fit_epoch(bank) takes the bank alone")
+            return self._fit_epoch_bank(rays)
         n, bs = rays.shape[0], self.batch_size
         perm = torch.randperm(n, device=self.dev, generator=self.gen)
         log = []
@@ -818,12 +828,39 @@ class RayTrainer:
                 self.global_step += 1
             else:
                 log.append(self.step(rays[idx], rgbs[idx], ts[idx]))
+        self._end_epoch()
+        return torch.stack([torch.stack(x) for x in log]).mean(0).tolist() if log else [math.nan, math.nan]
+
+    def _end_epoch(self):
         if self.sched is not None:
             self.sched.step()
         self.current_epoch += 1
         from .rendering import check_status
         check_status(self.dev)              # fp16 range audit of the epoch's render passes (raises FloatingPointError)
-        return torch.stack([torch.stack(x) for x in log]).mean(0).tolist() if log else [math.nan, math.nan]
+
+    def _fit_epoch_bank(self, bank):
+        from .data import batch_range, epoch_key
+        rank, world = _rank_world()
+        bs, key = self.batch_size, epoch_key(self.seed, self.current_epoch)
+        layout = "camera" if self.refine_pose else "world"
+        steps = bank.n_pixels // (bs * world)
+        total = torch.zeros(2, dtype=torch.float32, device=self.dev)     # a running sum: nothing grows with the epoch
+        self._sync_barf()
+        for s in range(steps):
+            start = batch_range(s, rank, world, bs)
+            if self.use_graph:
+                if self._graphed is None:
+                    rays, rgbs, ts = bank.gather(start, bs, key, layout)
+                    self._graphed = self.graphed_step(rays, ts, rgbs)
+                g = self._graphed
+                bank.gather(start, bs, key, layout, out=(g.rays, g.target, g.ts))   # one launch into the static buffers
+                total += torch.stack(g.replay())
+                self.global_step += 1
+            else:
+                rays, rgbs, ts = bank.gather(start, bs, key, layout)
+                total += torch.stack(self.step(rays, rgbs, ts))
+        self._end_epoch()
+        return (total / steps).tolist() if steps else [math.nan, math.nan]
 
     def graphed_step(self, rays, ts, rgbs, **kw):
         """The GraphedTrainStep fit_epoch replays (use_graph=True), captured on this batch; `kw` go to GraphedTrainStep."""
