@@ -563,6 +563,79 @@ typedef struct nfl_gather_args {
 } nfl_gather_args;
 int nfl_gather_batch(const nfl_gather_args* args, void* stream);
 
+/* ---- scoring a rendered image where it lies: PSNR, masked PSNR, SSIM (reference metrics.py; eval.py:196-207,
+ * train.py:176-210) and the depth image (utils/visualization.py:10-15) ------------------------------------------------
+ * nfl_image_metrics scores the region [x0, x1) x [y0, y1) of a width x height prediction d_pred (height * width, 3) fp32,
+ * pixel order, against its ground truth, given in exactly one of two forms:
+ *   bank form    d_pixels + d_table + image: the uint8 image `image` of an image bank (above), converted to fp32 by the
+ *                device function nfl_gather_batch uses (c / 255.0f; RGBA: rgb * a + (1 - a)); its record must hold the
+ *                same width and height (checked on the device: a mismatch reads no pixel and yields NaN results);
+ *   tensor form  d_target (height * width, 3) fp32 and an optional d_mask (height * width) uint8.
+ * Everything is defined on the cropped images, as if both had been sliced to the region (w x h) first.  clip != 0 clamps
+ * the prediction to [0, 1] before anything else (NaN stays NaN).  A pixel is `valid` when alpha > 0 (bank form, RGBA),
+ * mask != 0 (tensor form with a mask), always otherwise.  Row `slot` of d_results (n_slots, 8) fp64 receives
+ *   [0] sse         sum over the 3 h w elements of (pred - truth)^2, differences and squares in fp64
+ *   [1] count       3 h w
+ *   [2] sse_valid   [3] count_valid      the same over the valid pixels
+ *   [4] ssim_sum    sum of the SSIM map
+ *   [5] psnr = -10 log10(sse / count)    (+inf for an exact match)
+ *   [6] psnr_valid                       (NaN when no pixel is valid)
+ *   [7] ssim = ssim_sum / count
+ * SSIM map (kornia 0.4.1's ssim with window 3, as metrics.ssim uses it), per channel, all in fp32:
+ *   g = exp(-(k - 1)^2 / (2 * 1.5^2)), k = 0..2, normalised to sum 1;  F(x) = correlation with g (outer) g, border by
+ *   reflection without repeating the edge (index -1 -> 1, n -> n - 2);
+ *   mu1 = F(p), mu2 = F(t), s1 = F(p p) - mu1^2, s2 = F(t t) - mu2^2, s12 = F(p t) - mu1 mu2,
+ *   S = ((2 mu1 mu2 + C1)(2 s12 + C2)) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)), C1 = 0.01^2, C2 = 0.03^2,
+ *   map = 1 - clamp(1 - S, 0, 1).
+ * Optional outputs (NULL: skipped): d_pred_u8 (h, w, 3) uint8 = (uint8)(clamp(pred, 0, 1) * 255) (truncation;
+ * eval.py:201-203), d_ssim_map (h, w, 3) fp32.
+ * Two launches (tiles -> one partial per workgroup in d_scratch; one workgroup adds them in a fixed order), no atomics,
+ * no memset or copy: bit-reproducible and capturable in a HIP graph.  d_scratch: at least
+ * nfl_image_metrics_scratch_bytes(h, w) bytes, 8-byte aligned, overwritten.
+ * NFL_EINVAL (nothing launched): args / d_pred / d_results / d_scratch NULL, both or neither ground-truth forms, a mask
+ * without a target, width or height < 1, height * width >= 2^31, a region outside the image or reversed, a non-empty
+ * region narrower or shorter than 2 pixels, slot outside [0, n_slots), image outside [0, n_images), scratch_bytes too
+ * small.  An empty region (x0 == x1 or y0 == y1) returns NFL_OK without a launch and leaves the slot untouched. */
+typedef struct nfl_metrics_args {
+    const float*         d_pred;       /* (height * width, 3)                          */
+    const uint8_t*       d_pixels;     /* bank form, or NULL                            */
+    const nfl_image_rec* d_table;      /* (n_images), bank form, or NULL                */
+    int32_t  n_images, image;
+    const float*         d_target;     /* (height * width, 3), tensor form, or NULL     */
+    const uint8_t*       d_mask;       /* (height * width), tensor form, or NULL        */
+    int32_t  width, height;
+    int32_t  x0, x1, y0, y1;
+    int32_t  clip, slot;
+    double*  d_results;                /* (n_slots, 8) */
+    int32_t  n_slots, reserved;
+    void*    d_scratch;
+    size_t   scratch_bytes;
+    uint8_t* d_pred_u8;                /* out (h, w, 3) or NULL */
+    float*   d_ssim_map;               /* out (h, w, 3) or NULL */
+} nfl_metrics_args;
+enum { NFL_METRIC_SSE = 0, NFL_METRIC_COUNT, NFL_METRIC_SSE_VALID, NFL_METRIC_COUNT_VALID, NFL_METRIC_SSIM_SUM,
+       NFL_METRIC_PSNR, NFL_METRIC_PSNR_VALID, NFL_METRIC_SSIM, NFL_METRIC_COLUMNS };
+size_t nfl_image_metrics_scratch_bytes(int32_t h, int32_t w);     /* 0 for h or w < 1 */
+int nfl_image_metrics(const nfl_metrics_args* args, void* stream);
+
+/* nfl_depth_image: the region of a width x height depth map d_depth (height * width) fp32 as an image (h, w, 3) uint8:
+ * NaN -> 0, mi / ma = minimum / maximum over the region, x = (d - mi) / (ma - mi + 1e-8f) in fp32 by true division,
+ * level = (uint8)(255 * x); the output is the level three times (d_lut NULL) or d_lut[level] of a (256, 3) uint8 table.
+ * Two launches (partial minima / maxima into d_scratch, then the image), no atomics.  d_scratch: at least
+ * nfl_depth_image_scratch_bytes(h, w) bytes, 4-byte aligned.  NFL_EINVAL: args / d_depth / d_image / d_scratch NULL,
+ * sizes and region as above (any non-empty region is allowed), scratch_bytes too small.  Empty region: NFL_OK, no launch. */
+typedef struct nfl_depth_args {
+    const float*   d_depth;            /* (height * width) */
+    int32_t  width, height;
+    int32_t  x0, x1, y0, y1;
+    const uint8_t* d_lut;              /* (256, 3) or NULL */
+    uint8_t* d_image;                  /* out (h, w, 3)    */
+    void*    d_scratch;
+    size_t   scratch_bytes;
+} nfl_depth_args;
+size_t nfl_depth_image_scratch_bytes(int32_t h, int32_t w);
+int nfl_depth_image(const nfl_depth_args* args, void* stream);
+
 /* ---- hierarchical sampling (reference sample_pdf, rendering.py:7-46, plus the
  * concat + sort of rendering.py:267-272) -------------------------------------
  * d_z_coarse (R,S), d_weights_coarse (R,S); d_u (R,I) or NULL with d_u_row (I)

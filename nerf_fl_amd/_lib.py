@@ -171,6 +171,25 @@ class GatherArgs(C.Structure):
                 ("reserved", C.c_int32), ("d_rays", C.c_void_p), ("d_ts", C.c_void_p), ("d_rgb", C.c_void_p)]
 
 
+# nfl_image_metrics / nfl_depth_image (nerf_fl_amd.metrics) were added the same way: new symbols, no struct changed
+NFL_METRIC_COLUMNS = 8
+
+
+class MetricsArgs(C.Structure):
+    _fields_ = [("d_pred", C.c_void_p), ("d_pixels", C.c_void_p), ("d_table", C.c_void_p), ("n_images", C.c_int32),
+                ("image", C.c_int32), ("d_target", C.c_void_p), ("d_mask", C.c_void_p), ("width", C.c_int32),
+                ("height", C.c_int32), ("x0", C.c_int32), ("x1", C.c_int32), ("y0", C.c_int32), ("y1", C.c_int32),
+                ("clip", C.c_int32), ("slot", C.c_int32), ("d_results", C.c_void_p), ("n_slots", C.c_int32),
+                ("reserved", C.c_int32), ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_size_t),
+                ("d_pred_u8", C.c_void_p), ("d_ssim_map", C.c_void_p)]
+
+
+class DepthArgs(C.Structure):
+    _fields_ = [("d_depth", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("x0", C.c_int32),
+                ("x1", C.c_int32), ("y0", C.c_int32), ("y1", C.c_int32), ("d_lut", C.c_void_p), ("d_image", C.c_void_p),
+                ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
+
+
 # every symbol include/nerf_fl_amd.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("nfl_plan_bytes", C.c_size_t, [C.POINTER(FieldDesc)]),
@@ -217,6 +236,10 @@ SYMBOLS = [
     ("nfl_appfit_partials_floats", C.c_size_t, [C.c_int32]),
     ("nfl_appearance_fit", C.c_int, [C.POINTER(AppFitArgs), C.c_void_p]),
     ("nfl_gather_batch", C.c_int, [C.POINTER(GatherArgs), C.c_void_p]),
+    ("nfl_image_metrics_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32]),
+    ("nfl_image_metrics", C.c_int, [C.POINTER(MetricsArgs), C.c_void_p]),
+    ("nfl_depth_image_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32]),
+    ("nfl_depth_image", C.c_int, [C.POINTER(DepthArgs), C.c_void_p]),
     ("nfl_abi_version", C.c_int, []),
     ("nfl_version", C.c_char_p, []),
     ("nfl_strerror", C.c_char_p, [C.c_int]),

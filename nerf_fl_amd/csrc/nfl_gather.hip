@@ -11,6 +11,7 @@
 // A world row is two 16-byte stores; a camera row (20 B) and a colour row (12 B) are not 16-byte aligned and go out as
 // dwords, which the write-combining L2 merges (rows are consecutive per lane).
 #include "nfl_render_impl.h"
+#include "nfl_pixel.h"
 
 #define NFL_PERM_ROUNDS 6
 
@@ -78,16 +79,7 @@ __global__ __launch_bounds__(256) void nfl_gather_kernel(const nfl_gather_args a
     if (a.d_ts) a.d_ts[row] = im.id;
     if (a.d_rgb) {
         float c[3];
-        if (im.channels == 4) {
-            const uint32_t w = *reinterpret_cast<const uint32_t*>(a.d_pixels + im.byte0 + local * 4);
-            const float al = (float)(w >> 24) / 255.0f, rest = 1.f - al;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) c[k] = (float)((w >> (8 * k)) & 255u) / 255.0f * al + rest;
-        } else {
-            const uint8_t* s = a.d_pixels + im.byte0 + local * 3;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) c[k] = (float)s[k] / 255.0f;
-        }
+        nfl_pixel_rgb(a.d_pixels, im, local, c);      // nfl_pixel.h: shared with nfl_image_metrics
         float* o = a.d_rgb + (size_t)row * 3;
         o[0] = c[0];
         o[1] = c[1];

@@ -16,7 +16,7 @@ from . import parallel
 from .rendering import CameraRays, render_rays
 
 __all__ = ["batched_inference", "GraphedChunk", "frame_rays", "to_uint8", "dolly_path", "render_frame", "render_video",
-           "fit_and_evaluate_halves"]
+           "fit_and_evaluate_halves", "evaluate_bank"]
 
 
 class GraphedChunk:
@@ -233,6 +233,117 @@ def fit_and_evaluate_halves(models, embeddings, c2w, K, H, W, near, far, rgb, N_
                                 output_transient=False, a_embedded=code[None], **render_kw)
     mse = ((res["rgb_fine"] - rgb_r) ** 2).mean().item()
     return code, (-10.0 * math.log10(mse) if mse > 0 else float("inf"))
+
+
+def evaluate_bank(models, embeddings, bank, N_samples, N_importance, *, images=None, ts=None, halves=False, fit=None,
+                  clip=True, rank=0, world=1, use_graph=False, return_images=False, return_depth=False, poses=None,
+                  **kwargs):
+    """Score a held-out data.ImageBank on the device: PSNR, masked PSNR and SSIM per image (metrics.image_metrics in
+    bank form), with one device-to-host copy after the last image and device memory that does not grow with the split.
+
+    images: indices into the bank (default all); image k of them is scored into row k of one (n, 8) fp64 table
+    (metrics.METRIC_COLUMNS) when k lies in parallel.shard_bounds(n, rank, world) -- the other rows stay zero, so one
+    all_reduce(SUM) of `table` merges the ranks.  Each image is rendered from its record's camera (CameraRays: no rays
+    are gathered or stored) by batched_inference (test_time); `kwargs` (use_disp, chunk, white_back -- default: the
+    bank's --, barf_weights, ...) go there.
+    ts: None renders image i with its record's id; an int, or one per entry of `images`, overrides it (the reference
+    evaluates Blender val / test images with t = 0).  poses: (n, 3|4, 4) camera-to-world poses that replace the records'
+    (RayTrainer.validate_bank: the learned ones).
+    halves=True scores the right half only (region x0 = W // 2).  fit=dict(n_iters=..., lr=..., [init=..., other
+    AppearanceFit arguments]) first fits the image's appearance code on its left half (appearance.AppearanceFit on the
+    rays and colours ImageBank.gather gives for that image) and renders with a_embedded = that code, ts = None and
+    output_transient=False: fit_and_evaluate_halves for a bank.
+    clip: clamp the prediction to [0, 1] before scoring (eval.py:201 does, train.py:200 does not).
+
+    Returns a dict: `table` (device), `psnr`, `psnr_valid`, `ssim` (fp64 host tensors, one per image, zero outside the
+    shard) and `mean_psnr`, `mean_psnr_valid`, `mean_ssim` over this rank's shard; with fit, `codes` (n, N_a); with
+    return_images / return_depth, `frames` / `depths`: lists of uint8 (h, w, 3) device tensors of the shard's images
+    (the scored region; depths through metrics.depth_image)."""
+    from . import metrics
+    from .appearance import AppearanceFit
+    if bank.device is None:
+        raise RuntimeError("evaluate_bank: the bank is not on a device (this build has no CPU path)")
+    dev = bank.device
+    images = list(range(bank.n_images)) if images is None else [int(i) for i in images]
+    n = len(images)
+    if any(not 0 <= i < bank.n_images for i in images):
+        raise ValueError(f"images outside the bank's {bank.n_images}")
+    if ts is not None and not isinstance(ts, int):
+        ts = [int(t) for t in ts]
+        if len(ts) != n:
+            raise ValueError(f"ts has {len(ts)} entries for {n} images")
+    if poses is not None:
+        poses = torch.as_tensor(poses).detach().to("cpu", torch.float32)
+        if poses.shape[0] != n:
+            raise ValueError(f"poses has {poses.shape[0]} entries for {n} images")
+    if fit is not None and not halves:
+        raise ValueError("evaluate_bank: fit= fits on the left half, so it needs halves=True")
+    kwargs.setdefault("white_back", bank.white_back)
+    use_disp, chunk, white_back = kwargs.get("use_disp", False), kwargs.get("chunk", 1024 * 128), kwargs["white_back"]
+    lo, hi = parallel.shard_bounds(n, rank, world)
+    table = torch.zeros(n, len(metrics.METRIC_COLUMNS), dtype=torch.float64, device=dev)
+    codes, frames, depths = None, [], []
+    for k in range(lo, hi):
+        i = images[k]
+        rec = bank.host_table[i]
+        H, W = int(rec["height"]), int(rec["width"])
+        c2w = torch.from_numpy(rec["c2w"].reshape(3, 4).copy()) if poses is None else poses[k][:3, :4]
+        K = torch.tensor([[float(rec["fx"]), 0.0, float(rec["cx"])], [0.0, float(rec["fy"]), float(rec["cy"])],
+                          [0.0, 0.0, 1.0]])
+        near, far = float(rec["near"]), float(rec["far"])
+        region = (W // 2, W, 0, H) if halves else (0, W, 0, H)
+        render_kw = dict(kwargs)
+        t = None
+        if fit is not None:
+            if poses is None:
+                rays, rgbs, _ = bank.frame(i)
+            else:
+                rays, rgbs = frame_rays(c2w, K, H, W, near, far, dev), bank.frame(i)[1]
+            left = torch.arange(H * W, device=dev) % W < W // 2
+            fit_kw = dict(fit)
+            n_iters, init = fit_kw.pop("n_iters", 300), fit_kw.pop("init", None)
+            fit_kw.setdefault("lr", 0.05)
+            shared = {key: kwargs[key] for key in ("barf_weights", "current_epoch") if kwargs.get(key) is not None}
+            if kwargs.get("view_dir") is not None:
+                fit_kw["view_dir"] = kwargs["view_dir"][left]
+            rays_l = rays[left]
+            fitter = AppearanceFit(models, embeddings, rays_l, rgbs[left],
+                                   torch.zeros(rays_l.shape[0], dtype=torch.int64, device=dev), N_samples, N_importance,
+                                   use_disp=use_disp, white_back=white_back, chunk=chunk,
+                                   init=None if init is None else torch.as_tensor(init, dtype=torch.float32).reshape(1, -1),
+                                   **fit_kw, **shared)
+            code = fitter.fit(n_iters, use_graph=use_graph)[0].clone()
+            del fitter, rays, rgbs, rays_l                       # the cache is 512 B per padded sample: free it first
+            if codes is None:
+                codes = torch.zeros(n, code.shape[0], dtype=torch.float32, device=dev)
+            codes[k] = code
+            render_kw.update(output_transient=False, a_embedded=code[None])
+        else:
+            t_id = int(rec["id"]) if ts is None else (ts if isinstance(ts, int) else ts[k])
+            t = torch.full((H * W,), t_id, dtype=torch.long, device=dev)
+        cam = CameraRays(c2w, K, H, W, near, far, dev)
+        res = batched_inference(models, embeddings, cam, t, N_samples, N_importance,
+                                use_graph=use_graph and fit is None, **render_kw)
+        tag = "fine" if "rgb_fine" in res else "coarse"
+        out = metrics.image_metrics(res[f"rgb_{tag}"], H, W, bank=bank, image=i, region=region, clip=clip, table=table,
+                                    slot=k, want_uint8=return_images)
+        if return_images:
+            frames.append(out[1])
+        if return_depth:
+            depths.append(metrics.depth_image(res[f"depth_{tag}"].contiguous(), H, W, region=region))
+        del res, out
+    host = table.cpu()                                              # the one device-to-host copy
+    col = {name: host[:, j] for j, name in enumerate(metrics.METRIC_COLUMNS)}
+    result = dict(table=table, first=lo, count=hi - lo, psnr=col["psnr"], psnr_valid=col["psnr_valid"], ssim=col["ssim"])
+    for name in ("psnr", "psnr_valid", "ssim"):
+        result[f"mean_{name}"] = float(col[name][lo:hi].mean()) if hi > lo else float("nan")
+    if codes is not None:
+        result["codes"] = codes
+    if return_images:
+        result["frames"] = frames
+    if return_depth:
+        result["depths"] = depths
+    return result
 
 
 def to_uint8(rgb):

@@ -891,6 +891,34 @@ class RayTrainer:
         sse, n = acc.tolist()
         return -10.0 * math.log10(sse / n)
 
+    def validate_bank(self, bank, images=None, chunk=32768, shard=False):
+        """(mean PSNR, mean SSIM) over the images `images` (default all) of a data.ImageBank, rendered deterministically
+        and scored on the device by eval.evaluate_bank (full images, predictions not clipped, as train.py:196-207).
+        With refine_pose the images are rendered through the learned poses of their ids.
+        shard=True under a process group: every rank renders its parallel.shard_bounds block of the images, the tables are
+        summed with one all-reduce, and every rank returns the same means."""
+        from .eval import evaluate_bank
+        rank, world = _rank_world()
+        if not (shard and world > 1):
+            rank, world = 0, 1
+        idx = list(range(bank.n_images)) if images is None else [int(i) for i in images]
+        kw = dict(use_disp=self.hp["use_disp"], white_back=self.hp["white_back"], chunk=chunk)
+        poses = None
+        if self.refine_pose:
+            self._sync_barf()
+            ids = torch.as_tensor(bank.host_table["id"][idx].astype("int64"), device=self.dev)
+            poses = self.c2w(self.row_of_id[ids])
+            kw["barf_weights"] = self.barf_w
+        res = evaluate_bank(self.models, self.embeddings, bank, self.hp["N_samples"], self.hp["N_importance"], images=idx,
+                            clip=False, rank=rank, world=world, poses=poses, **kw)
+        if world == 1:
+            return res["mean_psnr"], res["mean_ssim"]
+        import torch.distributed as dist
+        table = res["table"]
+        dist.all_reduce(table)
+        host = table.cpu()
+        return float(host[:, 5].mean()), float(host[:, 7].mean())
+
     def _render_eval(self, rays, ts, chunk):
         hp = self.hp
         self._sync_barf()
