@@ -31,16 +31,13 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 
-#include <type_traits>
-
 #include "../../include/nerf_fl_amd.h"
+#include "nfl_dev.h"
 #include "nfl_diag.h"
 #include "nfl_plan.h"
 #include "nfl_prods.h"
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef __bf16 b8 __attribute__((ext_vector_type(8)));
-typedef float f16v __attribute__((ext_vector_type(16)));
 template <class V8> struct nfl_elem;
 template <> struct nfl_elem<h8> { using type = _Float16; };
 template <> struct nfl_elem<b8> { using type = __bf16; };
@@ -48,18 +45,9 @@ __device__ __forceinline__ f16v nfl_mfma(h8 a, h8 b, f16v c) { return __builtin_
 __device__ __forceinline__ f16v nfl_mfma(b8 a, b8 b, f16v c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 typedef float f4v __attribute__((ext_vector_type(4)));
 
-#define NFL_DEV __device__ __forceinline__
 // stash stores are streaming (nt): A/B on one box, training forward 1.69 ms with nt, 1.74 with plain stores (step 5.20 / 5.36 ms)
 #define NFL_STREAM_STORE(v, p) __builtin_nontemporal_store(v, p)
 
-// compile-time loop: f(integral_constant<int, I>) for I in [I0, I1)
-template <int I0, int I1, class F>
-NFL_DEV void nfl_static_for(F&& f) {
-    if constexpr (I0 < I1) {
-        f(std::integral_constant<int, I0>{});
-        nfl_static_for<I0 + 1, I1>(f);
-    }
-}
 #define NFL_NST 20            // floats in a segment / ray compositing record
 #define NFL_REC 32            // record stride (floats)
 
@@ -447,23 +435,6 @@ NFL_DEV void nfl_tile_p(f16v (&acc)[NCB], const char* wl, const int frag0, GetB&
 template <int NP, int NCB, int NK, int P0, class V8, class GetB, class Epi, class Ring>
 NFL_DEV void nfl_tile(f16v (&acc)[NCB], const char* wl, const int frag0, GetB&& getb, Epi&& epi, Ring& ring) {
     nfl_tile_p<3, NP, NCB, NK, P0, V8>(acc, wl, frag0, getb, epi, ring);
-}
-
-// max over the NFL_GMAX_SLOTS words the compositing backward left (bit patterns of non-negative floats order
-// like unsigned integers); wave-uniform result
-NFL_DEV unsigned nfl_gmax_bits(const float* d_gmax) {
-    unsigned v = 0u;
-    if (d_gmax)
-        for (int i = threadIdx.x & 63; i < NFL_GMAX_SLOTS; i += 64) {
-            const unsigned o = reinterpret_cast<const unsigned*>(d_gmax)[i];
-            v = o > v ? o : v;
-        }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned o = __shfl_xor(v, d);
-        v = o > v ? o : v;
-    }
-    return __builtin_amdgcn_readfirstlane(v);
 }
 
 struct NflNoEpi {

@@ -5,7 +5,7 @@
 // (what autograd's Linear backward does per point chunk in the reference, models/nerf.py
 // 153-212).  Both operands come from the stashes the forward / dgrad kernels wrote: per
 // 32-sample segment, per layer, MFMA-fragment-ordered fp16 with the SAMPLE on the lane (the
-// gradients carry the pass' power-of-two loss scale, divided out at the flush).
+// gradients carry the pass' power-of-two loss scale, divided out by the reduction).
 // The contraction index here is the sample, so both operands have to be presented with
 // the FEATURE on the lane and 8 consecutive samples in registers: the 1 KiB k-step images
 // are DMA'd verbatim into LDS and read back with ds_read_b64_tr_b16 (hardware 4x16
@@ -23,88 +23,24 @@
 //
 // Roofline: HBM.  A 256x256 layer reads 32 KiB per segment for 2 x 64 MFMAs, 128 FLOP/B,
 // far under the MFMA ridge, so the kernel is a stream (wg_body_rs below), with fp32 accumulators
-// for the whole (<=256 x <=352) tile of dW in registers and one fp32 atomic flush per workgroup.
+// for the whole (<=256 x <=352) tile of dW in registers.  Every workgroup stores its accumulators once, as they are, and
+// nfl_wgrad_reduce_kernel adds the parts up in a fixed order and divides the loss scale out: no atomics.
+//
+// The job list of a field, the launch schedule of a call and the table of instantiations are host code: nfl_wgrad_plan.h / .cpp.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
-#include <type_traits>
-
 #include "../../include/nerf_fl_amd.h"
+#include "nfl_dev.h"
 #include "nfl_diag.h"
-#include "nfl_plan.h"
+#include "nfl_wgrad_plan.h"
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef float f16v __attribute__((ext_vector_type(16)));
-
-// segments in flight per wave, by pieces per wave (PW 4 / 5 / 6 / 8 with <= 6 in tiles / 8 with 8): what the register file holds
-#ifndef WG_D4
-#define WG_D4 8
-#define WG_D5 8
-#define WG_D6 7
-#define WG_D8A 6
-#define WG_D8B 5
-#endif
-#define WG_MAX_OT 8      // out tiles (32 features) per job
-#define WG_MAX_IT 11     // in tiles per job
-#define WG_NOT 2         // out tiles per wave
-#define WG_SLOT (2048 * (WG_MAX_OT + WG_MAX_IT))
-
-struct WgTile {
-    int16_t slot;        // first k-step of the tile inside the segment record
-    int16_t kind;        // NFL_SEG_ACT / NFL_SEG_NAT
-    int16_t idx0;        // row0 / col0 of feature 0 of this tile in the weight
-    int16_t nvalid;      // features of this tile that exist (<= 32)
-};
-#define WG_SCRATCH (-1)   // WgJob::layer of the job that accumulates G | Gt into WgArgs::scratch (256 x 256, ld 256)
-struct WgJob {
-    int32_t layer;       // NFL_P_* of the weight this job accumulates into, or WG_SCRATCH
-    int32_t ld;          // row stride of that weight
-    int32_t n_ot, n_it;
-    int32_t n_wo, n_wi;  // waves across out tiles / in tiles (n_wo * n_wi == 4)
-    int32_t do_bias;
-    int32_t bias_layer_of_ot[WG_MAX_OT];   // each out tile may belong to another layer, weight and bias (-1: use `layer`)
-    WgTile ot[WG_MAX_OT];
-    WgTile it[WG_MAX_IT];
-};
-#define WG_MAX_JOBS 20
-struct WgPlan {          // host-built once per (field, transient on/off); the caller keeps a device copy
-    uint32_t magic;
-    int32_t n_jobs;
-    int32_t act_slots, grd_slots;
-    int32_t w_numel[NFL_NUM_LAYERS], b_numel[NFL_NUM_LAYERS];   // sizes of the gradient tensors (0: layer absent)
-    int32_t cost[WG_MAX_JOBS];     // 1 KiB pieces per wave per segment (4 / 5 / 6 / 8): the job's relative cost
-    WgJob job[WG_MAX_JOBS];
-};
-struct WgArgs {
-    const WgPlan* plan;  // device
-    const char* act;     // activation stash
-    const char* grd;     // gradient stash
-    int n_seg;
-    int act_rec, grd_rec;            // slots per segment record of the two stashes (twice the plan's with split stashes)
-    int act_lo, grd_lo;              // split stashes: byte offset of the residual record behind the hi record (0: none)
-    int slot_bytes;                  // bytes of one LDS slot of this launch (all hi (+ lo) pieces of the largest job)
-    int wg_start[WG_MAX_JOBS + 1];   // workgroups [wg_start[j], wg_start[j+1]) work on job j
-    nfl_field_grads g;
-    float* scratch;      // (256, 256): rows 0..127 G (delta_dirh (x) h8), rows 128..255 Gt (delta_g1 (x) h8)
-    // partial sums: workgroup `part` of job j stores its accumulators at partial + part_off[j] + part * part_len[j] (floats), as
-    // [(wave * WG_NOT + a) * part_nitw[j] + b][r / 4][lane][r % 4] followed by the bias sums [(wave * WG_NOT + a)][lane]; nfl_wgrad_reduce_kernel
-    // adds the parts up in a fixed order, divides by the loss scale and writes the gradient tensors
-    float* partial;
-    int part_off[WG_MAX_JOBS], part_len[WG_MAX_JOBS], part_nitw[WG_MAX_JOBS];
-    int red_start[WG_MAX_JOBS + 1];  // reduction blocks [red_start[j], red_start[j+1]) belong to job j: one per (wave, a, b)
-};
-#define WG_MAX_WGS 256    // workgroups the partial-sum area is sized for (one per CU)
+typedef float wg_f4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ int wg_orig(int kind, int i) {
     return kind == NFL_SEG_ACT ? 16 * (i >> 4) + 8 * ((i & 7) >> 2) + 4 * ((i >> 3) & 1) + (i & 3) : i;
 }
-
-#define WG_PSTRIDE 1056   // LDS stride of a 1 KiB k-step image: +32 B so the two k-steps of a tile fall on
-                          // different banks for the transposed reads (4-way -> 2-way conflicts)
-#define WG_TSTRIDE (2 * WG_PSTRIDE)
-#undef WG_SLOT
-#define WG_SLOT (WG_TSTRIDE * (WG_MAX_OT + WG_MAX_IT))
 
 // feature-on-lane MFMA operand of MFMA k-step m (samples 16m..16m+15) from a tile image (2 k-step pieces)
 __device__ __forceinline__ h8 wg_operand(const char* tile, int lane, int m) {
@@ -123,14 +59,6 @@ __device__ __forceinline__ h8 wg_operand(const char* tile, int lane, int m) {
     return r;
 }
 
-template <int I0, int I1, class F>
-__device__ __forceinline__ void wg_static_for(F&& f) {
-    if constexpr (I0 < I1) {
-        f(std::integral_constant<int, I0>{});
-        wg_static_for<I0 + 1, I1>(f);
-    }
-}
-
 template <int NITW>
 __device__ __forceinline__ void wg_flush(const WgArgs& A, const int j, const int part, f16v (&acc)[WG_NOT][NITW], float (&bsum)[WG_NOT],
                                          const int wave, const int lane) {
@@ -139,7 +67,6 @@ __device__ __forceinline__ void wg_flush(const WgArgs& A, const int j, const int
     // the gradient tensors at the end of the launch, 55 us during which the HBM idled, a zeroing and an unscaling launch around
     // it -- and a summation order that changed from run to run.)
     float* P = A.partial + (size_t)A.part_off[j] + (size_t)part * A.part_len[j];
-    typedef float wg_f4 __attribute__((ext_vector_type(4)));
 #pragma unroll
     for (int a = 0; a < WG_NOT; ++a) {
 #pragma unroll
@@ -168,7 +95,7 @@ __global__ __launch_bounds__(256) void nfl_wgrad_reduce_kernel(const WgArgs A, c
     const int nparts = A.wg_start[j + 1] - A.wg_start[j];
     const int live = A.n_seg < nparts ? A.n_seg : nparts;        // workgroups beyond the segment count returned before their flush
     float inv;
-    {
+    {   // nfl_gmax_bits (nfl_dev.h) written out: through the helper the compiler schedules this kernel differently
         unsigned v = 0u;
         for (int i = lane; i < NFL_GMAX_SLOTS; i += 64) {
             const unsigned o = reinterpret_cast<const unsigned*>(gmax)[i];
@@ -187,7 +114,6 @@ __global__ __launch_bounds__(256) void nfl_wgrad_reduce_kernel(const WgArgs A, c
     const int layer = J.bias_layer_of_ot[ot] >= 0 ? J.bias_layer_of_ot[ot] : J.layer;
     const float* base = A.partial + (size_t)A.part_off[j];
     const int n = lane & 31, hh = lane >> 5;
-    typedef float wg_f4 __attribute__((ext_vector_type(4)));
     float* W = layer == WG_SCRATCH ? A.scratch : A.g.weight[layer];
     if (wi + b * J.n_wi < J.n_it && W != nullptr) {
         const WgTile TI = J.it[wi + b * J.n_wi];
@@ -351,9 +277,9 @@ __device__ __forceinline__ void wg_body_rs(const WgArgs& A, const WgJob& J, cons
         return;
     }
 #endif
-    wg_static_for<0, D>([&](auto DD) __attribute__((always_inline)) { gload(seg0 + decltype(DD)::value, DD); });
+    nfl_static_for<0, D>([&](auto DD) __attribute__((always_inline)) { gload(seg0 + decltype(DD)::value, DD); });
     for (int base = seg0; base < seg1; base += D) {
-        wg_static_for<0, D>([&](auto DD) __attribute__((always_inline)) {
+        nfl_static_for<0, D>([&](auto DD) __attribute__((always_inline)) {
             constexpr int d = decltype(DD)::value;
             const int seg = base + d;
             if (seg < seg1) {                                     // uniform
@@ -426,20 +352,17 @@ __device__ __forceinline__ void wg_body_rs(const WgArgs& A, const WgJob& J, cons
         });
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the surplus loads still target live registers
-#ifdef NFL_DIAG_WGRAD_NOFLUSH
-    if (A.n_seg >= 0) {       // timing ablation (nfl_diag.h): keep the accumulators alive, skip the atomics -- results wrong by construction
-        float keep = 0.f;
-#pragma unroll
-        for (int a = 0; a < WG_NOT; ++a)
-#pragma unroll
-            for (int b = 0; b < NITW; ++b)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) keep += acc[a][b][r];
-        if (keep == 123.456f) A.scratch[0] = keep;
-        return;
-    }
-#endif
     wg_flush<NITW>(A, jidx, (int)blockIdx.x - A.wg_start[jidx], acc, bsum, wave, lane);
+}
+
+// wg_body_rs in the instantiation of row I of WG_INST (nfl_wgrad_plan.h)
+template <bool SPLIT, int I>
+__device__ __forceinline__ void wg_row(const WgArgs& A, const WgJob& J, const int seg0, const int seg1, const int seg_first,
+                                       const int seg_step, const int j, char* smem) {
+    constexpr WgInst T = WG_INST[SPLIT][I];
+    static_assert(T.cost == WG_INST[0][I].cost && T.nitw == WG_INST[0][I].nitw, "the split kernel's rows are the one-product kernel's");
+    static_assert(T.pw >= (SPLIT ? 2 : 1) * T.cost, "the four waves hold every piece of the class");
+    wg_body_rs<T.pw, T.nitw, T.d, SPLIT>(A, J, A.act_rec, A.grd_rec, seg0, seg1, seg_first, seg_step, j, smem);
 }
 
 template <bool SPLIT>
@@ -464,42 +387,23 @@ __global__ __launch_bounds__(256, 1) void nfl_wgrad_kernel(const WgArgs A) {
     const WgJob& J = P.job[j];
     const int pw = P.cost[j];
     const int nitw = (J.n_it + J.n_wi - 1) / J.n_wi;       // in tiles per wave
-    if constexpr (SPLIT) {      // twice the pieces per segment in flight per set: fewer sets (the registers are the same)
-        if (pw <= 4) {
-            if (nitw <= 1) wg_body_rs<8, 1, 4, true>(A, J, A.act_rec, A.grd_rec, seg0, seg1, seg_first, seg_step, j, smem);
-            else wg_body_rs<8, 2, 4, true>(A, J, A.act_rec, A.grd_rec, seg0, seg1, seg_first, seg_step, j, smem);
-        } else if (pw <= 5) {       // 10 pieces per wave would do; that instantiation gave wrong sums on the GPU (not understood), 12 is verified
-            wg_body_rs<12, 2, 3, true>(A, J, A.act_rec, A.grd_rec, seg0, seg1, seg_first, seg_step, j, smem);
-        } else if (pw <= 6) {
-            wg_body_rs<12, 4, 3, true>(A, J, A.act_rec, A.grd_rec, seg0, seg1, seg_first, seg_step, j, smem);
-        } else {
-            if (nitw <= 5) wg_body_rs<16, 5, 2, true>(A, J, A.act_rec, A.grd_rec, seg0, seg1, seg_first, seg_step, j, smem);
-            else if (nitw <= 6) wg_body_rs<16, 6, 2, true>(A, J, A.act_rec, A.grd_rec, seg0, seg1, seg_first, seg_step, j, smem);
-            else wg_body_rs<16, 8, 2, true>(A, J, A.act_rec, A.grd_rec, seg0, seg1, seg_first, seg_step, j, smem);
-        }
-        return;
-    }
+    // wg_inst_row(pw, nitw) as a ladder: every rung runs the row that the table gives for the largest (pw, nitw) it admits
+    // (the planner rejects a job without a row, so the last rung of a class does not compare nitw, nor the last class pw)
+#define WG_RUN(PW_, NITW_) wg_row<SPLIT, wg_inst_row(PW_, NITW_)>(A, J, seg0, seg1, seg_first, seg_step, j, smem)
     if (pw <= 4) {
-        if (nitw <= 1) wg_body_rs<4, 1, WG_D4>(A, J, A.act_rec, A.grd_rec, seg0, seg1, seg_first, seg_step, j, smem);
-        else wg_body_rs<4, 2, WG_D4>(A, J, A.act_rec, A.grd_rec, seg0, seg1, seg_first, seg_step, j, smem);
+        if (nitw <= 1) WG_RUN(4, 1);
+        else WG_RUN(4, 2);
     } else if (pw <= 5) {
-        wg_body_rs<5, 2, WG_D5>(A, J, A.act_rec, A.grd_rec, seg0, seg1, seg_first, seg_step, j, smem);
-    } else if (pw <= 6) {          // G of a pass without the transient head: 4 out x 8 in tiles
-        wg_body_rs<6, 4, WG_D6>(A, J, A.act_rec, A.grd_rec, seg0, seg1, seg_first, seg_step, j, smem);
+        WG_RUN(5, 2);
+    } else if (pw <= 6) {          // layers 1 / 5a of a field with 11..15 position frequencies: 8 out x 3 in tiles
+        WG_RUN(6, 4);
     } else {
-        if (nitw <= 5) wg_body_rs<8, 5, WG_D8A>(A, J, A.act_rec, A.grd_rec, seg0, seg1, seg_first, seg_step, j, smem);
-        else if (nitw <= 6) wg_body_rs<8, 6, WG_D8A>(A, J, A.act_rec, A.grd_rec, seg0, seg1, seg_first, seg_step, j, smem);
-        else wg_body_rs<8, 8, WG_D8B>(A, J, A.act_rec, A.grd_rec, seg0, seg1, seg_first, seg_step, j, smem);
+        if (nitw <= 5) WG_RUN(8, 5);
+        else if (nitw <= 6) WG_RUN(8, 6);
+        else WG_RUN(8, 8);
     }
+#undef WG_RUN
 }
-
-// Whole-tensor passes around the GEMM kernel: op 0 zeroes the gradient tensors, op 1 divides them by the loss
-// scale.  blockIdx.y = tensor (weights then biases), blockIdx.x strides over its elements.
-#define WG_NTENS (2 * NFL_NUM_LAYERS + 1)     // weights, biases, the composition scratch
-struct WgTensors {
-    float* ptr[WG_NTENS];
-    int n[WG_NTENS];
-};
 
 // ---------------------------------------------------------------------------------
 // The four small fp32 products of the composition (file header), one launch: task t computes
@@ -529,7 +433,6 @@ struct WgCompose {
 // partial tiles meet in LDS.  MFMA j of a wave takes, in lane half h, k = k_wave + 8 (j / 4) + 4 h + (j % 4): any pairing
 // of the two k of a step is as good as another as long as A and B agree.  (The first version staged 32 x 128 operand
 // blocks through LDS for scalar FMAs and was LDS-bound: 20-30 us; this one is one memory round trip and 16-32 MFMAs per wave.)
-typedef float wg_f4 __attribute__((ext_vector_type(4)));
 template <int NJ>       // MFMAs per wave = (K / 4) / 2
 __device__ __forceinline__ void wg_compose_pass(f16v& acc, const float* A, int sam, int sak, const float* B, int sbk, int sbn,
                                                 int m, int n, bool n_ok, int k_wave, int h, bool avec, bool bvec) {
@@ -587,164 +490,27 @@ __global__ __launch_bounds__(256) void nfl_wgrad_compose_kernel(const WgCompose 
         if (n_ok) T.Cp[(size_t)row * T.ldc + n] = (T.u ? __builtin_fmaf(T.u[row], T.v[n], c) : c) + (T.addm ? T.addm[row] : 0.f);
     }
 }
-__global__ __launch_bounds__(256) void nfl_wgrad_scale_kernel(const WgTensors T, const int op, const float* gmax) {
+
+// Zeroes the gradient tensors and the composition scratch before the stream: the reduction stores only the elements a job owns.
+// blockIdx.y = tensor, blockIdx.x strides over its elements.
+#define WG_NTENS (2 * NFL_NUM_LAYERS + 1)     // weights, biases, the composition scratch
+struct WgTensors {
+    float* ptr[WG_NTENS];
+    int n[WG_NTENS];
+};
+__global__ __launch_bounds__(256) void nfl_wgrad_zero_kernel(const WgTensors T) {
     float* p = T.ptr[blockIdx.y];
-    const int n = T.n[blockIdx.y];
-    if (p == nullptr || n == 0) return;
-    float f = 0.f;
-    if (op != 0) {
-        unsigned v = 0u;
-        for (int i = threadIdx.x & 63; i < NFL_GMAX_SLOTS; i += 64) {
-            const unsigned o = reinterpret_cast<const unsigned*>(gmax)[i];
-            v = o > v ? o : v;
-        }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const unsigned o = __shfl_xor(v, d);
-            v = o > v ? o : v;
-        }
-        f = 1.0f / nfl_loss_scale_from_bits(__builtin_amdgcn_readfirstlane(v));
-    }
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) p[i] = op == 0 ? 0.f : p[i] * f;
+    if (p == nullptr) return;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < T.n[blockIdx.y]; i += gridDim.x * 256) p[i] = 0.f;
 }
 
-// ---------------------------------------------------------------------------------
-static void add_tiles(WgTile* dst, int& n, int slot0, int kind, int idx0, int count) {
-    for (int t = 0; 32 * t < count; ++t) {
-        WgTile w;
-        w.slot = (int16_t)(slot0 + 2 * t);
-        w.kind = (int16_t)kind;
-        w.idx0 = (int16_t)(idx0 + 32 * t);
-        w.nvalid = (int16_t)(count - 32 * t < 32 ? count - 32 * t : 32);
-        dst[n++] = w;
-    }
-}
-static WgJob make_job(int layer, int ld, bool bias) {
-    WgJob j;
-    memset(&j, 0, sizeof(j));
-    j.layer = layer;
-    j.ld = ld;
-    j.do_bias = bias ? 1 : 0;
-    for (int i = 0; i < WG_MAX_OT; ++i) j.bias_layer_of_ot[i] = -1;
-    return j;
-}
-static void finish_job(WgJob& j) {
-    if (j.n_ot > 4) { j.n_wo = 4; j.n_wi = 1; }          // 2 out tiles per wave, all in tiles
-    else if (j.n_ot > 2) { j.n_wo = 2; j.n_wi = 2; }
-    else { j.n_wo = 1; j.n_wi = 4; }                     // heads: split the in tiles
-}
-
-extern "C" size_t nfl_wgrad_plan_bytes(void) { return sizeof(WgPlan); }
-
-extern "C" int nfl_wgrad_plan_build(const nfl_field_desc* d, int32_t use_transient, void* h_plan, size_t bytes) {
-    NflPlan p;
-    if (!d || !h_plan) return NFL_EINVAL;
-    if (bytes < sizeof(WgPlan)) return NFL_ESMALL;
-    if (nfl_plan_fill(d, NFL_PREC_F16X3, &p) != NFL_OK) return NFL_EINVAL;
-    const int nkp = p.nkp, cx = 6 * d->n_emb_xyz + 3, cd = 6 * d->n_emb_dir + 3, W = NFL_W, H = NFL_W / 2;
-    const bool ut = p.has_t && use_transient;
-    WgPlan& P = *static_cast<WgPlan*>(h_plan);
-    memset(&P, 0, sizeof(P));
-    P.magic = NFL_PLAN_MAGIC ^ 0x57u;
-    P.act_slots = nfl_act_slots(nkp);
-    P.grd_slots = NFL_GRD_SLOTS;
-    int nj = 0;
-    auto push = [&](WgJob j) {
-        finish_job(j);
-        const int pw = (2 * (j.n_ot + j.n_it) + 3) / 4;
-        const int nitw = (j.n_it + j.n_wi - 1) / j.n_wi;
-        P.cost[nj] = pw <= 4 ? 4 : (pw <= 5 ? 5 : ((pw <= 6 && nitw <= 4) ? 6 : 8));
-        P.job[nj++] = j;
-    };
-    for (int l = 1; l <= 8; ++l) {
-        WgJob j = make_job(NFL_P_XYZ1 + l - 1, p.ld[NFL_P_XYZ1 + l - 1], true);
-        add_tiles(j.ot, j.n_ot, NFL_GRD_D(l), NFL_SEG_ACT, 0, W);
-        if (l == 1 || l == 5) {
-            add_tiles(j.it, j.n_it, 0, NFL_SEG_NAT, 0, cx);
-            if (l == 5) {
-                push(j);
-                j = make_job(NFL_P_XYZ1 + 4, p.ld[NFL_P_XYZ1 + 4], false);
-                add_tiles(j.ot, j.n_ot, NFL_GRD_D(5), NFL_SEG_ACT, 0, W);
-                add_tiles(j.it, j.n_it, nfl_act_h(nkp, 4), NFL_SEG_ACT, cx, W);
-            }
-        } else {
-            add_tiles(j.it, j.n_it, nfl_act_h(nkp, l - 1), NFL_SEG_ACT, 0, W);
-        }
-        push(j);
-    }
-    if (ut) {   // sigma head (without the transient head it shares the h8 stream of the next job)
-        WgJob j = make_job(NFL_P_SIGMA, W, true);
-        add_tiles(j.ot, j.n_ot, NFL_GRD_HEADS + 0, NFL_SEG_NAT, 0, 1);
-        add_tiles(j.it, j.n_it, nfl_act_h(nkp, 8), NFL_SEG_ACT, 0, W);
-        push(j);
-    }
-    {   // G | Gt = (delta_dirh | delta_g1) (x) h8 into the scratch: everything that touches `feat` (xyz_encoding_final
-        // itself and the first 256 input columns of dir_encoding / transient_encoding.0) is composed from it.
-        // Without the transient head there is room for a fifth out tile: the sigma head reads the same h8 (ld 256 too)
-        WgJob j = make_job(WG_SCRATCH, W, !ut);
-        add_tiles(j.ot, j.n_ot, NFL_GRD_DIRH, NFL_SEG_ACT, 0, H);
-        if (ut) {
-            add_tiles(j.ot, j.n_ot, NFL_GRD_G(1), NFL_SEG_ACT, H, H);
-        } else {
-            j.bias_layer_of_ot[j.n_ot] = NFL_P_SIGMA;
-            add_tiles(j.ot, j.n_ot, NFL_GRD_HEADS + 0, NFL_SEG_NAT, 0, 1);
-        }
-        add_tiles(j.it, j.n_it, nfl_act_h(nkp, 8), NFL_SEG_ACT, 0, W);
-        push(j);
-    }
-    {   // dir_encoding: the side inputs [dir PE | appearance] (columns 256..) and the bias
-        WgJob j = make_job(NFL_P_DIR, p.ld[NFL_P_DIR], true);
-        add_tiles(j.ot, j.n_ot, NFL_GRD_DIRH, NFL_SEG_ACT, 0, H);
-        add_tiles(j.it, j.n_it, nfl_act_d(nkp), NFL_SEG_NAT, W, cd);
-        if (p.has_a) add_tiles(j.it, j.n_it, nfl_act_d(nkp) + 2, NFL_SEG_NAT, W + cd, p.n_a);
-        push(j);
-    }
-    {   // rgb head
-        WgJob j = make_job(NFL_P_RGB, H, true);
-        add_tiles(j.ot, j.n_ot, NFL_GRD_HEADS + 1, NFL_SEG_NAT, 0, 3);
-        add_tiles(j.it, j.n_it, nfl_act_dirh(nkp), NFL_SEG_ACT, 0, H);
-        push(j);
-    }
-    if (ut) {
-        {
-            WgJob j = make_job(NFL_P_T0, p.ld[NFL_P_T0], true);
-            add_tiles(j.ot, j.n_ot, NFL_GRD_G(1), NFL_SEG_ACT, 0, H);
-            add_tiles(j.it, j.n_it, nfl_act_tau(nkp), NFL_SEG_NAT, W, d->n_tau);      // the transient code (columns 256..) and the bias
-            push(j);
-        }
-        for (int m = 2; m <= 4; ++m) {
-            WgJob j = make_job(NFL_P_T0 + m - 1, H, true);
-            add_tiles(j.ot, j.n_ot, NFL_GRD_G(m), NFL_SEG_ACT, 0, H);
-            add_tiles(j.it, j.n_it, nfl_act_g(nkp, m - 1), NFL_SEG_ACT, 0, H);
-            push(j);
-        }
-        {   // the three transient heads share the g4 stream: one out "tile" each
-            WgJob j = make_job(NFL_P_TSIGMA, H, true);
-            add_tiles(j.ot, j.n_ot, NFL_GRD_HEADS + 2, NFL_SEG_NAT, 0, 1);
-            add_tiles(j.ot, j.n_ot, NFL_GRD_HEADS + 3, NFL_SEG_NAT, 0, 3);
-            add_tiles(j.ot, j.n_ot, NFL_GRD_HEADS + 4, NFL_SEG_NAT, 0, 1);
-            j.bias_layer_of_ot[0] = NFL_P_TSIGMA;
-            j.bias_layer_of_ot[1] = NFL_P_TRGB;
-            j.bias_layer_of_ot[2] = NFL_P_TBETA;
-            add_tiles(j.it, j.n_it, nfl_act_g(nkp, 4), NFL_SEG_ACT, 0, H);
-            push(j);
-        }
-    }
-    P.n_jobs = nj;
-    for (int L = 0; L < NFL_NUM_LAYERS; ++L) {
-        const bool tr = L >= NFL_P_T0;
-        const int rows = (L <= NFL_P_FINAL) ? W : (L == NFL_P_DIR || (L >= NFL_P_T0 && L < NFL_P_T0 + 4)) ? H
-                         : (L == NFL_P_RGB || L == NFL_P_TRGB) ? 3 : 1;
-        const bool present = tr ? p.has_t != 0 : true;      // transient layers of the model that this pass does not use get zero gradients
-        P.w_numel[L] = present ? rows * p.ld[L] : 0;
-        P.b_numel[L] = present ? rows : 0;
-    }
-    return NFL_OK;
-}
-
-extern "C" size_t nfl_wgrad_scratch_bytes(void) {
-    // G (256 x 256) + the partial sums of at most WG_MAX_WGS workgroups with the largest accumulator set (2 x 8 tiles per wave)
-    return ((size_t)NFL_W * NFL_W + (size_t)WG_MAX_WGS * (4 * WG_NOT * 8 * 1024 + 4 * WG_NOT * 64)) * sizeof(float);
+// appends a task to a composition launch; vec: its k-contiguous operands have 16-byte aligned rows
+static void wg_add(WgCompose& Cc, WgGemm g, int vec) {
+    g.avec = g.bvec = vec;
+    g.tiles_n = (g.N + 31) / 32;
+    g.tile0 = Cc.n_wg;
+    Cc.n_wg += g.tiles_n * ((g.M + 31) / 32);
+    Cc.t[Cc.n_tasks++] = g;
 }
 
 extern "C" int nfl_mlp_wgrad(const void* h_wplan, const void* d_wplan, const char* d_act_stash,
@@ -752,7 +518,7 @@ extern "C" int nfl_mlp_wgrad(const void* h_wplan, const void* d_wplan, const cha
                              int32_t bwd_prec, const nfl_field_params* params, float* d_scratch,
                              const nfl_field_grads* grads, void* stream) {
     const WgPlan* hp = static_cast<const WgPlan*>(h_wplan);
-    if (!hp || hp->magic != (NFL_PLAN_MAGIC ^ 0x57u) || !d_wplan || !d_act_stash || !d_grad_stash || !d_gmax || !grads
+    if (!hp || hp->magic != WG_PLAN_MAGIC || !d_wplan || !d_act_stash || !d_grad_stash || !d_gmax || !grads
         || !params || !d_scratch)
         return NFL_EINVAL;
     // the composition reads these master weights; the side-input job of a layer needs its bias gradient as well
@@ -764,70 +530,18 @@ extern "C" int nfl_mlp_wgrad(const void* h_wplan, const void* d_wplan, const cha
     if (n_rays < 0 || n_samples < 1) return NFL_EINVAL;
     if (bwd_prec != NFL_PREC_F16 && bwd_prec != NFL_PREC_F16W && bwd_prec != NFL_PREC_F16X3) return NFL_EINVAL;
     const int mult = bwd_prec == NFL_PREC_F16X3 ? 2 : 1;       // split stashes: [hi record | lo record] per segment
+    int dev = 0, ncu = 256, n_wg = 0, red_blocks = 0;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
     WgArgs A;
     memset(&A, 0, sizeof(A));
+    const int rc = nfl_wgrad_schedule(hp, n_rays * ((n_samples + 31) / 32), ncu, mult, &A, &n_wg, &red_blocks);
+    if (rc != NFL_OK) return rc;
     A.plan = static_cast<const WgPlan*>(d_wplan);
     A.act = d_act_stash;
     A.grd = d_grad_stash;
-    A.act_rec = hp->act_slots * mult;
-    A.grd_rec = hp->grd_slots * mult;
-    A.act_lo = mult == 2 ? hp->act_slots * 1024 : 0;
-    A.grd_lo = mult == 2 ? hp->grd_slots * 1024 : 0;
-    int max_tiles = 1;
-    for (int j = 0; j < hp->n_jobs; ++j)
-        if (hp->job[j].n_ot + hp->job[j].n_it > max_tiles) max_tiles = hp->job[j].n_ot + hp->job[j].n_it;
-    A.slot_bytes = WG_TSTRIDE * max_tiles * mult;
-    A.n_seg = n_rays * ((n_samples + 31) / 32);
     A.g = *grads;
     A.scratch = d_scratch;
-    // one workgroup per CU, dealt to the jobs in proportion to their streamed bytes
-    int dev = 0, ncu = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    const int nj = hp->n_jobs;
-    int total_cost = 0;
-    for (int j = 0; j < nj; ++j) total_cost += hp->cost[j];
-    const int budget = ncu < WG_MAX_WGS ? ncu : WG_MAX_WGS;     // one resident workgroup per CU: a second round only repeats the pipeline fill / drain
-                                // (measured 1.06 / 1.14 / 1.23 / 1.32 ms for 1 / 2 / 3 / 4 workgroups per CU)
-    // proportional shares rounded down, then the workgroups left over go one at a time to the job whose workgroups
-    // carry the most bytes each (every CU gets a workgroup and the slowest job sets the kernel's time)
-    int n_wg[WG_MAX_JOBS], used = 0;
-    for (int j = 0; j < nj; ++j) {
-        int n = (int)((long long)budget * hp->cost[j] / total_cost);
-        if (n < 1) n = 1;
-        if (n > A.n_seg) n = A.n_seg;
-        n_wg[j] = n;
-        used += n;
-    }
-    while (used < budget) {
-        int best = -1;
-        for (int j = 0; j < nj; ++j)
-            if (n_wg[j] < A.n_seg && (best < 0 || (long long)hp->cost[j] * n_wg[best] > (long long)hp->cost[best] * n_wg[j])) best = j;
-        if (best < 0) break;
-        n_wg[best]++;
-        used++;
-    }
-    int acc_wg = 0;
-    for (int j = 0; j < nj; ++j) {
-        A.wg_start[j] = acc_wg;
-        acc_wg += n_wg[j];
-    }
-    A.wg_start[nj] = acc_wg;
-    // partial sums: area of every job's parts behind the G scratch, and the reduction's blocks (one per accumulator tile)
-    A.partial = d_scratch + NFL_W * NFL_W;
-    int part_floats = 0, red_blocks = 0;
-    for (int j = 0; j < nj; ++j) {
-        const int pw = hp->cost[j], nitw = (hp->job[j].n_it + hp->job[j].n_wi - 1) / hp->job[j].n_wi;
-        // the instantiation nfl_wgrad_kernel picks for (pw, nitw): its NITW is the tile count a part stores
-        const int inst = pw <= 4 ? (nitw <= 1 ? 1 : 2) : (pw <= 5 ? 2 : (pw <= 6 ? 4 : (nitw <= 5 ? 5 : (nitw <= 6 ? 6 : 8))));
-        A.part_nitw[j] = inst;
-        A.part_len[j] = 4 * WG_NOT * inst * 1024 + 4 * WG_NOT * 64;
-        A.part_off[j] = part_floats;
-        part_floats += n_wg[j] * A.part_len[j];
-        A.red_start[j] = red_blocks;
-        red_blocks += 4 * WG_NOT * inst;
-    }
-    A.red_start[nj] = red_blocks;
-    if ((size_t)part_floats > (size_t)WG_MAX_WGS * (4 * WG_NOT * 8 * 1024 + 4 * WG_NOT * 64)) return NFL_EINVAL;
+    A.partial = d_scratch + NFL_W * NFL_W;       // the parts lie behind G
     static bool attr_set = false;
     if (!attr_set) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&nfl_wgrad_kernel<false>),
@@ -837,7 +551,6 @@ extern "C" int nfl_mlp_wgrad(const void* h_wplan, const void* d_wplan, const cha
             return NFL_ENODEV;
         attr_set = true;
     }
-    if (2 * A.slot_bytes > 4 * WG_SLOT) return NFL_EINVAL;
     WgTensors T;
     for (int L = 0; L < NFL_NUM_LAYERS; ++L) {
         T.ptr[L] = grads->weight[L];
@@ -848,28 +561,13 @@ extern "C" int nfl_mlp_wgrad(const void* h_wplan, const void* d_wplan, const cha
     T.ptr[2 * NFL_NUM_LAYERS] = d_scratch;
     T.n[2 * NFL_NUM_LAYERS] = NFL_W * NFL_W;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(nfl_wgrad_scale_kernel, dim3(16, WG_NTENS), dim3(256), 0, s, T, 0, d_gmax);
+    hipLaunchKernelGGL(nfl_wgrad_zero_kernel, dim3(16, WG_NTENS), dim3(256), 0, s, T);
     if (n_rays == 0) return hipGetLastError() == hipSuccess ? NFL_OK : NFL_ELAUNCH;
-#ifdef NFL_DIAG_WGRAD_PASSES
-#error "NFL_DIAG_WGRAD_PASSES accumulated several launches with the atomic flush; it went with it (last: commit c170289)"
-    // diagnostic (nfl_diag.h): the split stashes read by the ONE-product GEMM, hi images only (1) or d_hi + d_lo (2)
-    {
-        WgArgs B = A;
-        B.act_lo = B.grd_lo = 0;
-        B.slot_bytes = A.slot_bytes / mult;
-        hipLaunchKernelGGL(nfl_wgrad_kernel<false>, dim3(acc_wg), dim3(256), 2 * B.slot_bytes, s, B);
-        if (mult == 2 && NFL_DIAG_WGRAD_PASSES >= 2) {
-            B.grd = d_grad_stash + (size_t)hp->grd_slots * 1024;
-            hipLaunchKernelGGL(nfl_wgrad_kernel<false>, dim3(acc_wg), dim3(256), 2 * B.slot_bytes, s, B);
-        }
-    }
-#else
     // NFL_PREC_F16X3: dW = sum_s (d_hi + d_lo) (x) (h_hi + h_lo) without the lo x lo term, in ONE pass over the hi and lo
     // records (fp16 x fp16 products are exact in the fp32 accumulators, so what is left is the 2^-22 lo x lo term and the
     // summation order); the bias gradients are sum_s (d_hi + d_lo).
-    if (mult == 2) hipLaunchKernelGGL(nfl_wgrad_kernel<true>, dim3(acc_wg), dim3(256), 2 * A.slot_bytes, s, A);
-    else hipLaunchKernelGGL(nfl_wgrad_kernel<false>, dim3(acc_wg), dim3(256), 2 * A.slot_bytes, s, A);
-#endif
+    if (mult == 2) hipLaunchKernelGGL(nfl_wgrad_kernel<true>, dim3(n_wg), dim3(256), 2 * A.slot_bytes, s, A);
+    else hipLaunchKernelGGL(nfl_wgrad_kernel<false>, dim3(n_wg), dim3(256), 2 * A.slot_bytes, s, A);
     // parts -> gradient tensors and G, summed in a fixed order and divided by the loss scale (what the tensors' zeroing above
     // still covers: elements no job owns, i.e. the heads a call leaves out)
     hipLaunchKernelGGL(nfl_wgrad_reduce_kernel, dim3(red_blocks), dim3(256), 0, s, A, d_gmax);
@@ -884,41 +582,34 @@ extern "C" int nfl_mlp_wgrad(const void* h_wplan, const void* d_wplan, const cha
     const float* Gt = d_scratch + (size_t)H * W;
     WgCompose Cc;
     memset(&Cc, 0, sizeof(Cc));
-    auto add = [&](WgGemm g) {
-        g.avec = g.bvec = 1;                 // G and W_fin rows are 1 KiB: checked below
-        g.tiles_n = (g.N + 31) / 32;
-        g.tile0 = Cc.n_wg;
-        Cc.n_wg += g.tiles_n * ((g.M + 31) / 32);
-        Cc.t[Cc.n_tasks++] = g;
-    };
     WgGemm g;
     if (grads->weight[NFL_P_FINAL]) {       // dW_fin[i, j] = sum_r Wd[r, i] G[r, j] (+ sum_r Wt[r, i] Gt[r, j])
         memset(&g, 0, sizeof(g));
         g.A = Wd; g.sam = 1; g.sak = ld_dir; g.B = G; g.sbk = W; g.sbn = 1; g.K = H;
         if (ut) { g.A2 = Wt; g.sam2 = 1; g.sak2 = ld_t0; g.B2 = Gt; g.sbk2 = W; g.sbn2 = 1; g.K2 = H; }
         g.Cp = grads->weight[NFL_P_FINAL]; g.ldc = W; g.M = W; g.N = W;
-        add(g);
+        wg_add(Cc, g, 1);      // G and W_fin rows are 1 KiB (checked below): float4 loads
     }
     if (grads->bias[NFL_P_FINAL]) {         // db_fin[i] = sum_r Wd[r, i] db_dir[r] (+ sum_r Wt[r, i] db_t0[r]): a 256 x 1 product
         memset(&g, 0, sizeof(g));
         g.A = Wd; g.sam = 1; g.sak = ld_dir; g.B = grads->bias[NFL_P_DIR]; g.sbk = 1; g.sbn = 1; g.K = H;
         if (ut) { g.A2 = Wt; g.sam2 = 1; g.sak2 = ld_t0; g.B2 = grads->bias[NFL_P_T0]; g.sbk2 = 1; g.sbn2 = 1; g.K2 = H; }
         g.Cp = grads->bias[NFL_P_FINAL]; g.ldc = 1; g.M = W; g.N = 1;
-        add(g);
+        wg_add(Cc, g, 1);
     }
     if (grads->weight[NFL_P_DIR]) {         // dW_dir[r, i] = sum_j G[r, j] W_fin[i, j] + db_dir[r] b_fin[i], i < 256
         memset(&g, 0, sizeof(g));
         g.A = G; g.sam = W; g.sak = 1; g.B = Wf; g.sbk = 1; g.sbn = W; g.K = W;
         g.u = grads->bias[NFL_P_DIR]; g.v = params->bias[NFL_P_FINAL];
         g.Cp = grads->weight[NFL_P_DIR]; g.ldc = ld_dir; g.M = H; g.N = W;
-        add(g);
+        wg_add(Cc, g, 1);
     }
     if (ut && grads->weight[NFL_P_T0]) {
         memset(&g, 0, sizeof(g));
         g.A = Gt; g.sam = W; g.sak = 1; g.B = Wf; g.sbk = 1; g.sbn = W; g.K = W;
         g.u = grads->bias[NFL_P_T0]; g.v = params->bias[NFL_P_FINAL];
         g.Cp = grads->weight[NFL_P_T0]; g.ldc = ld_t0; g.M = H; g.N = W;
-        add(g);
+        wg_add(Cc, g, 1);
     }
     if (((uintptr_t)d_scratch | (uintptr_t)Wf) & 15) return NFL_EINVAL;      // float4 loads along k (G, W_fin rows)
     if (Cc.n_wg > 0) hipLaunchKernelGGL(nfl_wgrad_compose_kernel, dim3(Cc.n_wg), dim3(256), 0, s, Cc);
@@ -940,12 +631,6 @@ extern "C" int nfl_compose_forward(const nfl_field_params* params, int32_t has_t
     const int W = NFL_W, H = NFL_W / 2;
     WgCompose Cc;
     memset(&Cc, 0, sizeof(Cc));
-    auto add = [&](WgGemm g) {
-        g.tiles_n = (g.N + 31) / 32;
-        g.tile0 = Cc.n_wg;
-        Cc.n_wg += g.tiles_n * ((g.M + 31) / 32);
-        Cc.t[Cc.n_tasks++] = g;
-    };
     for (int which = 0; which < (has_t ? 2 : 1); ++which) {
         const int L = which ? NFL_P_T0 : NFL_P_DIR;
         const int ld = W + (which ? n_tau : n_side);
@@ -954,12 +639,12 @@ extern "C" int nfl_compose_forward(const nfl_field_params* params, int32_t has_t
         memset(&g, 0, sizeof(g));          // W'[r, i] = sum_j W[r, j] W_fin[j, i]   (rows of W are not 16-byte aligned: scalar loads)
         g.A = Ws; g.sam = ld; g.sak = 1; g.B = Wf; g.sbk = W; g.sbn = 1; g.K = W;
         g.Cp = which ? d_wt0_c : d_wdir_c; g.ldc = ld; g.M = H; g.N = W;
-        add(g);
+        wg_add(Cc, g, 0);
         memset(&g, 0, sizeof(g));          // b'[r] = b[r] + sum_j W[r, j] b_fin[j]
         g.A = Ws; g.sam = ld; g.sak = 1; g.B = bf; g.sbk = 1; g.sbn = 1; g.K = W;
         g.addm = params->bias[L];
         g.Cp = which ? d_bt0_c : d_bdir_c; g.ldc = 1; g.M = H; g.N = 1;
-        add(g);
+        wg_add(Cc, g, 0);
     }
     hipLaunchKernelGGL(nfl_wgrad_compose_kernel, dim3(Cc.n_wg), dim3(256), 0, static_cast<hipStream_t>(stream), Cc);
     return hipGetLastError() == hipSuccess ? NFL_OK : NFL_ELAUNCH;

@@ -1,6 +1,7 @@
 """The host-side plan builder under AddressSanitizer + UBSan (GPU sanitizers are not available on this pool; the host code is
 where fixed-size tables are filled by configuration-dependent loops): tests/plan_sweep.cpp builds forward and backward plans
-for every encoder / latent width combination, accepted or rejected."""
+for every encoder / latent width combination, accepted or rejected, and for every accepted one the weight-gradient job list
+(csrc/nfl_wgrad_plan.cpp) and its launch schedule over segment counts, CU counts and both stash multipliers."""
 import os
 import shutil
 import subprocess
@@ -15,7 +16,8 @@ def test_plan_builder_is_clean_under_asan_ubsan(tmp_path):
     exe = str(tmp_path / "plan_sweep")
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
            "-fno-omit-frame-pointer", os.path.join(ROOT, "tests", "plan_sweep.cpp"),
-           os.path.join(ROOT, "nerf_fl_amd", "csrc", "nfl_plan.cpp"), "-o", exe]
+           os.path.join(ROOT, "nerf_fl_amd", "csrc", "nfl_plan.cpp"),
+           os.path.join(ROOT, "nerf_fl_amd", "csrc", "nfl_wgrad_plan.cpp"), "-o", exe]
     b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
     if b.returncode != 0 and "sanitize" in b.stderr and "cannot find" in b.stderr:
         pytest.skip("sanitizer runtime not installed")
@@ -25,3 +27,9 @@ def test_plan_builder_is_clean_under_asan_ubsan(tmp_path):
     assert "plans ok" in r.stdout and "ERROR" not in r.stderr
     n_ok = int(r.stdout.split("plans ok")[1].split()[0])
     assert n_ok > 10000
+    # every accepted field (11520 of the swept descriptors x transient on / off) got a wgrad plan, each scheduled 72 times
+    print(r.stdout)
+    assert "wgrad invariant broken" not in r.stdout
+    n_wplans, n_sched = (int(r.stdout.split(k)[1].split()[0]) for k in ("wgrad plans", "schedules"))
+    assert n_wplans > 10000 and n_sched == 72 * n_wplans
+    assert "wgrad rows reached" in r.stdout
