@@ -636,6 +636,29 @@ typedef struct nfl_depth_args {
 size_t nfl_depth_image_scratch_bytes(int32_t h, int32_t w);
 int nfl_depth_image(const nfl_depth_args* args, void* stream);
 
+/* ---- depth bounds of a sparse point cloud, per image (reference datasets/phototourism.py:122-131: every point into every
+ * camera, points behind it dropped, np.percentile of the depths) ---------------------------------------------------------
+ * d_xyz (n_points, 3) fp64 world points; d_row (n_images, 4) fp64, the THIRD row of each image's world-to-camera matrix.
+ * The depth of point p in image i is ((x r0 + y r1) + z r2) + r3 in fp64, every operation rounded on its own.  With m the
+ * number of points of depth > 0 (NaN depths are not counted) and d_(0) <= .. <= d_(m-1) their sorted depths, the quantile
+ * q is numpy's default (`linear`) one: v = q (m - 1), k = floor(v), t = v - k, a = d_(k), b = d_(min(k + 1, m - 1)),
+ * result = a + (b - a) t for t < 0.5 and b - (b - a)(1 - t) otherwise, all in fp64.  Outputs:
+ *   d_bounds (2, n_images) fp64: row 0 the q_lo quantile, row 1 the q_hi quantile;   d_count (n_images) int32: m.
+ * An image with m == 0 gets count 0 and NaN twice; m == 1 gets that depth twice.
+ * One launch, one workgroup per image: an exact most-significant-digit radix select over the bit pattern of the positive
+ * depths (8 passes of 8 bits, histograms in LDS by integer atomics), the depths recomputed from d_xyz in every pass.  No
+ * global scratch, no memset, no allocation, no host synchronisation; every output element is written by a plain store.
+ * NFL_EINVAL: a NULL pointer, n_images < 1, n_points outside [1, 2^30], a quantile outside [0, 1] (or NaN). */
+typedef struct nfl_bounds_args {
+    const double* d_xyz;              /* (n_points, 3) */
+    const double* d_row;              /* (n_images, 4) */
+    int32_t  n_points, n_images;
+    double   q_lo, q_hi;
+    double*  d_bounds;                /* out (2, n_images) */
+    int32_t* d_count;                 /* out (n_images)    */
+} nfl_bounds_args;
+int nfl_depth_bounds(const nfl_bounds_args* args, void* stream);
+
 /* ---- hierarchical sampling (reference sample_pdf, rendering.py:7-46, plus the
  * concat + sort of rendering.py:267-272) -------------------------------------
  * d_z_coarse (R,S), d_weights_coarse (R,S); d_u (R,I) or NULL with d_u_row (I)

@@ -190,6 +190,13 @@ class DepthArgs(C.Structure):
                 ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
 
 
+# nfl_depth_bounds (data.depth_bounds) likewise: a new symbol and a new struct, nothing existing moved, so NFL_ABI_VERSION
+# stays where the header has it
+class BoundsArgs(C.Structure):
+    _fields_ = [("d_xyz", C.c_void_p), ("d_row", C.c_void_p), ("n_points", C.c_int32), ("n_images", C.c_int32),
+                ("q_lo", C.c_double), ("q_hi", C.c_double), ("d_bounds", C.c_void_p), ("d_count", C.c_void_p)]
+
+
 # every symbol include/nerf_fl_amd.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("nfl_plan_bytes", C.c_size_t, [C.POINTER(FieldDesc)]),
@@ -240,6 +247,7 @@ SYMBOLS = [
     ("nfl_image_metrics", C.c_int, [C.POINTER(MetricsArgs), C.c_void_p]),
     ("nfl_depth_image_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32]),
     ("nfl_depth_image", C.c_int, [C.POINTER(DepthArgs), C.c_void_p]),
+    ("nfl_depth_bounds", C.c_int, [C.POINTER(BoundsArgs), C.c_void_p]),
     ("nfl_abi_version", C.c_int, []),
     ("nfl_version", C.c_char_p, []),
     ("nfl_strerror", C.c_char_p, [C.c_int]),

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .colmap import read_phototourism
 
 # one record per image: numpy mirror of nfl_image_rec (include/nerf_fl_amd.h)
 RECORD = np.dtype([("pix0", "<i8"), ("byte0", "<i8"), ("width", "<i4"), ("height", "<i4"), ("channels", "<i4"),
@@ -67,6 +68,54 @@ def _add_perturbation(img, perturbation, seed):
             random_color = tuple(np.random.choice(range(256), 3))
             draw.rectangle(((left + 20 * i, top), (left + 20 * (i + 1), top + 200)), fill=random_color)
     return img
+
+
+def depth_bounds(xyz, w2c, q=(0.001, 0.999), device=None):
+    """(near, far, count) per image: the q[0] and q[1] quantiles (numpy's default `linear` definition, in fp64) of the
+    depths of the points `xyz` (P, 3) that lie in front of each camera `w2c` (N, 3|4, 4) world-to-camera, and how many
+    do -- the reference's loop of phototourism.py:127-131 as one launch of nfl_depth_bounds (csrc/nfl_bounds.hip), which
+    builds no (N, P) intermediate.  near, far: (N,) fp64 device tensors (two rows of one (2, N) tensor: `near._base`
+    copies to the host in one go); count: (N,) int32.  An image with nothing in front of it has count 0 and NaN bounds.
+    Stream-ordered; nothing is synchronised.  Inputs may be numpy arrays or tensors; they are converted to fp64 on
+    `device` (default: the device of `xyz` if it is a device tensor)."""
+    if device is None and torch.is_tensor(xyz) and xyz.is_cuda:
+        device = xyz.device
+    dev = torch.device(device) if device is not None else None
+    if dev is None or dev.type != "cuda":
+        raise RuntimeError("nerf_fl_amd.data.depth_bounds needs a ROCm device (this build has no CPU path)")
+    xyz = torch.as_tensor(xyz).to(device=dev, dtype=torch.float64).contiguous()
+    w2c = torch.as_tensor(w2c).to(device=dev, dtype=torch.float64)
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1:
+        raise ValueError(f"xyz must be (P, 3) with P >= 1, got {tuple(xyz.shape)}")
+    if w2c.dim() != 3 or w2c.shape[0] < 1 or w2c.shape[1] not in (3, 4) or w2c.shape[2] != 4:
+        raise ValueError(f"w2c must be (N, 3|4, 4) with N >= 1, got {tuple(w2c.shape)}")
+    q_lo, q_hi = float(q[0]), float(q[1])
+    if not (0.0 <= q_lo <= 1.0 and 0.0 <= q_hi <= 1.0):
+        raise ValueError(f"quantiles must lie in [0, 1], got {q}")
+    n = w2c.shape[0]
+    row = w2c[:, 2, :].contiguous()                      # the depth needs the third row alone
+    bounds = torch.empty(2, n, dtype=torch.float64, device=dev)
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    a = _lib.BoundsArgs(C.c_void_p(xyz.data_ptr()), C.c_void_p(row.data_ptr()), xyz.shape[0], n, q_lo, q_hi,
+                        C.c_void_p(bounds.data_ptr()), C.c_void_p(count.data_ptr()))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().nfl_depth_bounds(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                   "nfl_depth_bounds")
+    return bounds[0], bounds[1], count
+
+
+def scene_bounds(scene, device):
+    """Unscaled (near, far), two (N,) fp64 host arrays, of every image of a colmap.PhototourismScene: depth_bounds at
+    the reference's percentiles 0.1 and 99.9 (phototourism.py:130-131) and ONE copy of 2 N doubles to the host.  An
+    image with no point in front of it raises ValueError naming it."""
+    near, _, _ = depth_bounds(scene.xyz_world, scene.w2c, q=(0.1 / 100, 99.9 / 100), device=device)
+    both = near._base.cpu().numpy()
+    bad = np.flatnonzero(np.isnan(both).any(0))
+    if len(bad):
+        i = int(bad[0])
+        raise ValueError(f"image {scene.filenames[i]!r} (id {int(scene.img_ids[i])}) has no sparse point in front of it: "
+                         "no depth bounds")
+    return both[0], both[1]
 
 
 class ImageBank:
@@ -174,6 +223,51 @@ class ImageBank:
             img = img.resize(tuple(img_wh), Image.LANCZOS)
             images.append(np.array(img))
         return cls(images, np.stack(poses), K, 2.0, 6.0, ids=np.arange(len(images)), device=device)
+
+    @classmethod
+    def from_phototourism(cls, root_dir, split="train", img_downscale=1, device=None):
+        """The `split` ("train" or "test") images of a Phototourism scene as the reference's PhototourismDataset
+        prepares them (datasets/phototourism.py:44-183): colmap.read_phototourism; near / far of EVERY image of the
+        TSV, train and test together, from the sparse points on the device (scene_bounds); scale_factor =
+        float32(largest far) / 5, which divides the pose translations, near, far and xyz_world (:133-140); the split's
+        images from dense/images/ as RGB, LANCZOS-resized to (w // s, h // s) of the image's OWN size for
+        img_downscale s > 1 (:162-168); ids = the COLMAP image ids.  "test" is the held-out list eval.evaluate_bank(
+        halves=True) and AppearanceFit are for.  The reference's forced downscale of its `val` split is an
+        out-of-memory workaround and is not reproduced.
+
+        Beyond an ImageBank's fields the bank carries scale_factor (np.float32), xyz_world (scaled, host, fp64),
+        img_ids (this split's ids in order) and max_id (over both splits: N_vocab must exceed it).  Needs a device (the
+        bounds run there) and Pillow."""
+        from PIL import Image
+        if split not in ("train", "test"):
+            raise ValueError(f'split must be "train" or "test", got {split!r}')
+        if device is None:
+            raise RuntimeError("ImageBank.from_phototourism needs a ROCm device (this build has no CPU path)")
+        scene = read_phototourism(root_dir, img_downscale)
+        near, far = scene_bounds(scene, device)
+        scale_factor = np.float32(far.max()) / np.float32(5)              # so that the max far is scaled to 5
+        poses = scene.poses.copy()
+        poses[..., 3] /= scale_factor
+        near, far = near / scale_factor, far / scale_factor
+        want = scene.img_ids_train if split == "train" else scene.img_ids_test
+        rows = [i for i, sp in enumerate(scene.splits) if sp == split]
+        assert [int(scene.img_ids[i]) for i in rows] == want
+        if not rows:
+            raise ValueError(f"{root_dir}: the TSV lists no {split} image")
+        s = scene.img_downscale
+        images = []
+        for i in rows:
+            img = Image.open(os.path.join(root_dir, "dense", "images", scene.filenames[i])).convert("RGB")
+            if s > 1:
+                img_w, img_h = img.size
+                img = img.resize((img_w // s, img_h // s), Image.LANCZOS)
+            images.append(np.array(img))
+        bank = cls(images, poses[rows], scene.K[rows], near[rows], far[rows], ids=scene.img_ids[rows], device=device)
+        bank.scale_factor = scale_factor
+        bank.xyz_world = scene.xyz_world / scale_factor
+        bank.img_ids = list(want)
+        bank.max_id = int(scene.img_ids.max())
+        return bank
 
     # ---- batches ------------------------------------------------------------------------------------------------
     def gather(self, start, count, key=0, layout="world", out=None):
