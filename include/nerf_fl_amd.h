@@ -659,6 +659,53 @@ typedef struct nfl_bounds_args {
 } nfl_bounds_args;
 int nfl_depth_bounds(const nfl_bounds_args* args, void* stream);
 
+/* ---- surface: the iso-surface of a regular lattice as an indexed triangle mesh (marching tetrahedra; the reference has
+ * no counterpart: it renders images only) -----------------------------------------------------------------------------------
+ * d_lattice (nz, ny, nx) fp32, x fastest; lattice point (x, y, z) lies at lo[k] + index[k] * spacing[k] (k = x, y, z),
+ * computed in fp32 with every operation rounded on its own.  A point is INSIDE when value >= iso; NaN is outside, +-inf
+ * compare as usual.
+ * Split: a corner of a cell is c = dx | dy << 1 | dz << 2; every cell is cut into the six Kuhn tetrahedra (0, a, a | b, 7),
+ * (a, b, c) over the permutations of the axis bits (1, 2, 4) in lexicographic order, which all share the body diagonal 0-7.
+ * Every tetrahedron edge joins corners lo and hi with lo a subset of hi; it belongs to the lattice point at corner lo and
+ * has the type m = hi ^ lo in 1..7 (1, 2, 4: axis edges; 3, 5, 6: face diagonals; 7: body diagonal).  An edge whose ends
+ * differ in the inside test carries ONE vertex, shared by all triangles around it (the mesh is welded):
+ *   t = (iso - v_a) / (v_b - v_a) clamped by fminf(fmaxf(t, 0), 1) (a NaN becomes 0), a the owner;  p = p_a + t (p_b - p_a);
+ *   normal = n / |n| with n = -(g_a + t (g_b - g_a)), |n| = sqrt((n_x n_x + n_y n_y) + n_z n_z), and 0 unless |n| > 0;
+ *   g = gradient of the lattice: (v[i+1] - v[i-1]) / (2 s) per axis, (v[i+1] - v[i]) / s and (v[i] - v[i-1]) / s at the border.
+ * Triangles wind so that their normal points from inside to outside; degenerate ones (values equal to iso) are kept.
+ * Order: vertices by (owner point in lattice order, m), triangles by (cell in lattice order, tetrahedron, place in the
+ * case table of csrc/nfl_surface.hip).  No atomics: the output is bit-reproducible.
+ *   nfl_surface_bytes(nx, ny, nz)  scratch size: 4 B per point + 16 B per slab of 256 points of an x-row; 0 for sizes
+ *                                  the calls below refuse.
+ *   nfl_surface_count   two launches: the crossing edges of every point and the triangles of every cell are counted into
+ *                       the scratch and prefix-summed there (exclusive, int64, by a scan kernel of the library); the totals
+ *                       go to d_totals[0] = V, d_totals[1] = T.  Reads d_lattice .. d_totals.
+ *   nfl_surface_emit    one launch: writes d_vertices (V, 3) fp32, d_normals (V, 3) fp32, d_triangles (T, 3) int32 (indices
+ *                       into d_vertices).  It needs the scratch nfl_surface_count left for the SAME lattice, sizes and iso,
+ *                       and n_vertices / n_triangles = the totals, which the caller has read back to size the outputs
+ *                       (the one host synchronisation of an extraction); no element past them is written.
+ * No memset, no copy, no allocation.  d_scratch: 8-byte aligned.
+ * NFL_EINVAL: args / d_lattice / d_scratch NULL or misaligned, a size below 2, ny or nz above 65535, more than 2^30 points;
+ * count: d_totals NULL; emit: n_vertices > INT32_MAX or 3 n_triangles > INT32_MAX (indices are int32), a negative total, an
+ * output NULL that its total needs.  NFL_ESMALL: scratch_bytes below nfl_surface_bytes.  Totals of 0: NFL_OK, no launch. */
+typedef struct nfl_surface_args {
+    const float* d_lattice;           /* (nz, ny, nx) */
+    int32_t  nx, ny, nz;
+    float    iso;
+    float    lo[3];                   /* position of lattice point (0, 0, 0): x, y, z */
+    float    spacing[3];              /* x, y, z */
+    void*    d_scratch;
+    size_t   scratch_bytes;
+    int64_t* d_totals;                /* out (2): V, T (count)                  */
+    int64_t  n_vertices, n_triangles; /* emit: the totals, read back by the caller */
+    float*   d_vertices;              /* out (V, 3) */
+    float*   d_normals;               /* out (V, 3) */
+    int32_t* d_triangles;             /* out (T, 3) */
+} nfl_surface_args;
+size_t nfl_surface_bytes(int32_t nx, int32_t ny, int32_t nz);
+int nfl_surface_count(const nfl_surface_args* args, void* stream);
+int nfl_surface_emit(const nfl_surface_args* args, void* stream);
+
 /* ---- hierarchical sampling (reference sample_pdf, rendering.py:7-46, plus the
  * concat + sort of rendering.py:267-272) -------------------------------------
  * d_z_coarse (R,S), d_weights_coarse (R,S); d_u (R,I) or NULL with d_u_row (I)

@@ -197,6 +197,14 @@ class BoundsArgs(C.Structure):
                 ("q_lo", C.c_double), ("q_hi", C.c_double), ("d_bounds", C.c_void_p), ("d_count", C.c_void_p)]
 
 
+# nfl_surface_* (nerf_fl_amd.geometry) likewise: three new symbols and a new struct
+class SurfaceArgs(C.Structure):
+    _fields_ = [("d_lattice", C.c_void_p), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("iso", C.c_float),
+                ("lo", C.c_float * 3), ("spacing", C.c_float * 3), ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_size_t),
+                ("d_totals", C.c_void_p), ("n_vertices", C.c_int64), ("n_triangles", C.c_int64),
+                ("d_vertices", C.c_void_p), ("d_normals", C.c_void_p), ("d_triangles", C.c_void_p)]
+
+
 # every symbol include/nerf_fl_amd.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("nfl_plan_bytes", C.c_size_t, [C.POINTER(FieldDesc)]),
@@ -248,6 +256,9 @@ SYMBOLS = [
     ("nfl_depth_image_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32]),
     ("nfl_depth_image", C.c_int, [C.POINTER(DepthArgs), C.c_void_p]),
     ("nfl_depth_bounds", C.c_int, [C.POINTER(BoundsArgs), C.c_void_p]),
+    ("nfl_surface_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    ("nfl_surface_count", C.c_int, [C.POINTER(SurfaceArgs), C.c_void_p]),
+    ("nfl_surface_emit", C.c_int, [C.POINTER(SurfaceArgs), C.c_void_p]),
     ("nfl_abi_version", C.c_int, []),
     ("nfl_version", C.c_char_p, []),
     ("nfl_strerror", C.c_char_p, [C.c_int]),
