@@ -14,7 +14,7 @@
 #include <string.h>
 
 #include "../../include/nerf_fl_amd.h"
-#include "nfl_plan.h"
+#include "nfl_dev.h"
 
 extern "C" int nfl_launch_zcache_x3(const NflPlan*, const void*, const void*, const nfl_pass_args*, float*, int, void*);
 
@@ -22,13 +22,6 @@ extern "C" int nfl_launch_zcache_x3(const NflPlan*, const void*, const void*, co
 #define NFL_AF_MAXCH 4        // n_pad <= 256 samples: 4 chunks of 64
 
 typedef float nfl_af4 __attribute__((ext_vector_type(4)));
-
-// sum over the 64 lanes; a butterfly, so every lane ends with the same bits
-__device__ __forceinline__ float nfl_af_wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
 
 // One wavefront per work item (a ray range of one image).  Per ray: all chunks of 64 samples forward (the relu masks,
 // the sample colours and w_s stay in registers), the composited colour and its MSE gradient, then the backward of the
@@ -105,9 +98,9 @@ __global__ __launch_bounds__(256) void nfl_appfit_kernel(const nfl_appfit_args A
             c1 = fmaf(ws[ch], rgb[ch][1], c1);
             c2 = fmaf(ws[ch], rgb[ch][2], c2);
         }
-        c0 = nfl_af_wave_sum(c0);
-        c1 = nfl_af_wave_sum(c1);
-        c2 = nfl_af_wave_sum(c2);
+        c0 = nfl_wave_sum(c0);
+        c1 = nfl_wave_sum(c1);
+        c2 = nfl_wave_sum(c2);
         if (A.white_back) {
             const float wb = 1.f - A.d_opacity[r];
             c0 += wb;
@@ -145,7 +138,7 @@ __global__ __launch_bounds__(256) void nfl_appfit_kernel(const nfl_appfit_args A
     float lo = 0.f, hi = 0.f;
 #pragma unroll
     for (int f = 0; f < NFL_AF_F; ++f) {
-        const float t = nfl_af_wave_sum(acc[f]);
+        const float t = nfl_wave_sum(acc[f]);
         if (f < 64) lo = lane == f ? t : lo;
         else hi = lane == f - 64 ? t : hi;
     }

@@ -160,7 +160,7 @@ __global__ __launch_bounds__(256) void nfl_compbwd_kernel(nfl_compbwd_args a) {
         }
     }
     if (a.d_gmax) {
-#pragma unroll
+#pragma unroll      // written out, not a helper as in nfl_dev.h: through one the compiler allocates this kernel's registers differently
         for (int d = 32; d >= 1; d >>= 1) gmax = fmaxf(gmax, __shfl_xor(gmax, d));
         // one atomic per wave, spread over NFL_GMAX_SLOTS words: every wave of the grid gets here at about the same
         // time, so a "look before you leap" load does not filter anything and same-address atomics serialise in L2

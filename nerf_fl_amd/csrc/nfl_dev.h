@@ -1,24 +1,42 @@
-// nfl_dev.h -- the device-side helpers that the fused MLP kernels (nfl_render_impl.h) and the weight-gradient kernels
-// (nfl_wgrad.hip) share.  Defines no device globals, so any translation unit may include it.
+// nfl_dev.h -- the small device-side helpers that kernels of different translation units share: wave reductions, the
+// kernarg re-read, the gradient-maximum word.  Defines no device globals, so any translation unit may include it.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <type_traits>
-
+#include "nfl_macros.h"
 #include "nfl_plan.h"
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));     // one lane's MFMA operand of v_mfma_f32_32x32x16_f16
-typedef float f16v __attribute__((ext_vector_type(16)));     // one lane's 32 x 32 accumulator
-
-#define NFL_DEV __device__ __forceinline__
-
-// compile-time loop: f(integral_constant<int, I>) for I in [I0, I1)
-template <int I0, int I1, class F>
-NFL_DEV void nfl_static_for(F&& f) {
-    if constexpr (I0 < I1) {
-        f(std::integral_constant<int, I0>{});
-        nfl_static_for<I0 + 1, I1>(f);
+// reductions over the 64 lanes of a wave by xor butterfly: every lane ends with the result, and the order of the
+// additions is the same on every lane
+NFL_DEV float nfl_wave_sum(float v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+NFL_DEV unsigned nfl_wave_max(unsigned v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned o = __shfl_xor(v, d);
+        v = o > v ? o : v;
     }
+    return v;
+}
+// sum over 32 lanes (both halves of the wave run it independently)
+NFL_DEV float nfl_sum32(float v) {
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) v += __shfl_xor(v, m, 32);
+    return v;
+}
+
+// A kernel's argument block (T = the type of its one by-value argument), re-read from the kernarg segment.  Values loaded
+// through the returned pointer cannot be hoisted above the call (the empty asm makes the pointer opaque), so arguments that
+// are only needed in the cold parts of a tile (ray set-up, compositing, outputs, loss) are s_load'ed there instead of being
+// kept in SGPRs -- or rather in SGPR spill lanes of VGPRs -- across the whole MLP, where every register is spoken for.
+template <class T>
+using NflKernarg = const __attribute__((address_space(4))) T*;
+template <class T>
+NFL_DEV NflKernarg<T> nfl_kernarg() {
+    NflKernarg<T> p = (NflKernarg<T>)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
 }
 
 // max over the NFL_GMAX_SLOTS words the compositing backward left (bit patterns of non-negative floats order
@@ -30,10 +48,5 @@ NFL_DEV unsigned nfl_gmax_bits(const float* d_gmax) {
             const unsigned o = reinterpret_cast<const unsigned*>(d_gmax)[i];
             v = o > v ? o : v;
         }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned o = __shfl_xor(v, d);
-        v = o > v ? o : v;
-    }
-    return __builtin_amdgcn_readfirstlane(v);
+    return __builtin_amdgcn_readfirstlane(nfl_wave_max(v));
 }

@@ -4,7 +4,7 @@
 // 153-212: for every sample, walk the network from the heads back to layer 2,
 //   delta_{l-1} = (W_l^T delta_l) (.) [h_{l-1} > 0]
 // with the same register-resident transposed formulation as the forward kernel
-// (nfl_render_impl.h): delta^T[feature, sample] tiles are MFMA accumulators, converted
+// (nfl_render_impl.h; the engine both share is nfl_mlp.h): delta^T[feature, sample] tiles are MFMA accumulators, converted
 // to fp16 they are the B operand of the next product; W^T streams through the LDS ring
 // as pre-packed fp16 fragments.  Mixed precision with a LOSS SCALE: every gradient in
 // this kernel is multiplied by the power of two S = nfl_loss_scale_from_bits(*d_gmax)
@@ -18,7 +18,10 @@
 // order) to the gradient stash for the weight-gradient GEMMs (nfl_wgrad.hip).  The
 // appearance / transient latent gradients are the extra rows of W_dir^T / W_t0^T,
 // reduced over the samples of the ray with wave shuffles and accumulated with fp32 atomics.
-#include "nfl_render_impl.h"
+#include "nfl_mlp.h"
+#ifdef NFL_STAMPS
+#include "nfl_stamps.h"      // make diag DIAGTU=nfl_dgrad: this unit carries the stamp buffer instead of nfl_render_x3
+#endif
 
 // Three arithmetics, one kernel template (M = DgMode<NP, NWP>: parts of a gradient operand, fragments of a weight k-step):
 //   <1, 1>  NFL_PREC_F16 (default): W_hi d_hi, one product.  Two 32-sample segments (column blocks) per wave and two row
@@ -57,13 +60,8 @@ struct DgradArgs {
     int n_a, n_tau;           // widths of the latent codes (<= 48 / 16)
 };
 
-struct DgradArgs;
-typedef const __attribute__((address_space(4))) DgradArgs* NflDgKArgs;
-NFL_DEV NflDgKArgs nfl_dg_kargs() {
-    NflDgKArgs p = (NflDgKArgs)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(p));
-    return p;
-}
+typedef NflKernarg<DgradArgs> NflDgKArgs;
+NFL_DEV NflDgKArgs nfl_dg_kargs() { return nfl_kernarg<DgradArgs>(); }
 
 template <int NFX, class M>
 struct NflDgradCfg {
@@ -524,7 +522,7 @@ __global__ __launch_bounds__(256, 1) void nfl_dgrad_kernel(const DgradArgs A) {
     // differ from step to step) and the caller's seed (independent repetitions of a fit)
     DgRng rng{(blockIdx.x * 256u + threadIdx.x) * 0x9E3779B9u + nfl_gmax_bits(a.d_gmax) * 0x85EBCA6Bu + a.rounding_seed * 0xC2B2AE35u};
     for (int tile = 0; tile < ntiles; ++tile) {
-        NflDgKArgs K = nfl_dg_kargs();      // arguments are re-read from the kernarg segment where they are used (nfl_render_impl.h: nfl_kargs)
+        NflDgKArgs K = nfl_dg_kargs();      // arguments are re-read from the kernarg segment where they are used (nfl_dev.h: nfl_kernarg)
         bool seg_ok[NCB];
         int ray[NCB];
         char* gst[NCB];

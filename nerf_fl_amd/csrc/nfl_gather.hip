@@ -10,7 +10,7 @@
 // moves 52 B per ray out and at most one cache line per ray in: it is bound by launch and load latency, not by bandwidth.
 // A world row is two 16-byte stores; a camera row (20 B) and a colour row (12 B) are not 16-byte aligned and go out as
 // dwords, which the write-combining L2 merges (rows are consecutive per lane).
-#include "nfl_render_impl.h"
+#include "nfl_math.h"
 #include "nfl_pixel.h"
 
 #define NFL_PERM_ROUNDS 6

@@ -7,10 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/nerf_fl_amd.h"
-
-#ifndef NFL_DEV
-#define NFL_DEV __device__ __forceinline__
-#endif
+#include "nfl_macros.h"
 
 // colour of pixel `local` (row-major) of image `im`; returns its alpha code value (255 for an RGB image)
 NFL_DEV uint32_t nfl_pixel_rgb(const uint8_t* d_pixels, const nfl_image_rec& im, long long local, float c[3]) {

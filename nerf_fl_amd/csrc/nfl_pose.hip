@@ -16,6 +16,7 @@
 #include <math.h>
 
 #include "../../include/nerf_fl_amd.h"
+#include "nfl_dev.h"
 
 namespace {
 
@@ -136,9 +137,7 @@ __global__ __launch_bounds__(256) void nfl_pose_rays_bwd_kernel(const nfl_pose_a
         }
     }
 #pragma unroll
-    for (int k = 0; k < 12; ++k)
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) G[k] += __shfl_xor(G[k], m, 64);
+    for (int k = 0; k < 12; ++k) G[k] = nfl_wave_sum(G[k]);
     if (lane) return;
 
     // through c2w[:3] = [R | t] @ init_c2w:  dL/dR_ik = sum_j G_ij init[k, j];  dL/dt_i = sum_j G_ij init[3, j]

@@ -11,59 +11,19 @@
 //   * workgroup = 4 waves, one per SIMD, up to 512 VGPR/AGPR each.  A workgroup owns a
 //     contiguous range of rays and walks their samples in "segments" of 32 samples
 //     (= one MFMA column block); a wave carries NCB segments at a time.
-//   * the MLP is evaluated transposed, H^T[out,sample] = W[out,in] . H^T[in,sample]
-//     with v_mfma_f32_32x32x16_f16.  Activations live in registers for the whole
-//     network: the 32x32 fp32 accumulator tile of one layer, converted to fp16, IS the
-//     B operand of the next layer (column = sample stays on the lane; the k-slot
-//     permutation this implies is folded into the packed weights, nfl_plan.h).
-//   * W streams global(L2) -> LDS through a 3-slot ring with global_load_lds (16 B per
-//     lane, lane-linear = exactly the fragment image), one raw s_barrier per chunk and
-//     a counted vmcnt so two chunks stay in flight across barriers; all four waves read
-//     every fragment with conflict-free ds_read_b128.
-//   * NSPLIT == 3: operands are split hi+lo in fp16 and three products are accumulated
-//     (w_lo*x_hi + w_hi*x_lo + w_hi*x_hi): ~2^-21 relative error per product instead of
-//     2^-11, at 3x the MFMA issue.  NSPLIT == 1 is the fast mode.
+//   * the MLP itself -- transposed MFMA tiles, activations in registers, the weight ring, the
+//     three-product arithmetic -- is the engine of nfl_mlp.h, shared with the dgrad kernel.
 //   * compositing: per segment, an exclusive product scan of (1-alpha) over 32 lanes
 //     gives the local transmittance; partial sums are linear in the incoming
 //     transmittance, so segments (and tiles) of one ray are folded through a tiny LDS
 //     record.  Nothing per-sample except the API's own (R,N) outputs is written.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <string.h>
 
-#include "../../include/nerf_fl_amd.h"
-#include "nfl_dev.h"
-#include "nfl_diag.h"
-#include "nfl_plan.h"
-#include "nfl_prods.h"
-
-typedef __bf16 b8 __attribute__((ext_vector_type(8)));
-template <class V8> struct nfl_elem;
-template <> struct nfl_elem<h8> { using type = _Float16; };
-template <> struct nfl_elem<b8> { using type = __bf16; };
-__device__ __forceinline__ f16v nfl_mfma(h8 a, h8 b, f16v c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f16v nfl_mfma(b8 a, b8 b, f16v c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-typedef float f4v __attribute__((ext_vector_type(4)));
-
-// stash stores are streaming (nt): A/B on one box, training forward 1.69 ms with nt, 1.74 with plain stores (step 5.20 / 5.36 ms)
-#define NFL_STREAM_STORE(v, p) __builtin_nontemporal_store(v, p)
+#include "nfl_mlp.h"
 
 #define NFL_NST 20            // floats in a segment / ray compositing record
 #define NFL_REC 32            // record stride (floats)
-
-// ray of pixel p of a frame (reference datasets/ray_utils.py:5-55); the ONE implementation behind nfl_gen_rays and the
-// render kernel's camera prologue, so that both produce the same bits
-template <class Cam>
-NFL_DEV void nfl_cam_ray(const Cam& c, long long p, f4v& r0, f4v& r1) {
-    const float i = (float)(p % c.width), j = (float)(p / c.width);
-    const float dx = (i - c.cx) / c.fx, dy = -(j - c.cy) / c.fy, dz = -1.f;
-    float d[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) d[r] = dx * c.c2w[4 * r] + dy * c.c2w[4 * r + 1] + dz * c.c2w[4 * r + 2];
-    const float n = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    r0 = f4v{c.c2w[3], c.c2w[7], c.c2w[11], d[0] / n};
-    r1 = f4v{d[1] / n, d[2] / n, c.near, c.far};
-}
 
 struct RenderArgs {
     const NflPlan* plan;      // device copy of the plan
@@ -86,510 +46,6 @@ struct RenderArgs {
     float* zcache;              // NFL_MODE_ZCACHE: the appearance cache (nfl_appearance_cache), else null
     int zpad;                   // its padded sample count
 };
-
-// ---------------------------------------------------------------------------------
-// small math
-// ---------------------------------------------------------------------------------
-NFL_DEV float nfl_softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }   // torch default beta=1, threshold=20
-NFL_DEV float nfl_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-
-// sin(2*pi*r) for r in about [-1, 2]; abs error < 2e-7 (minimax odd polynomial on [-1/4,1/4])
-NFL_DEV float nfl_sin_rev(float r) {
-    r = r - rintf(r);                                   // [-1/2, 1/2]
-    float a = fabsf(r);
-    a = a > 0.25f ? 0.5f - a : a;                       // sin(pi - t) = sin(t)
-    a = copysignf(a, r);
-    const float a2 = a * a;
-    float p = 3.953670604e+01f;
-    p = __builtin_fmaf(p, a2, -7.654978229e+01f);
-    p = __builtin_fmaf(p, a2, 8.160100407e+01f);
-    p = __builtin_fmaf(p, a2, -4.134165503e+01f);
-    p = __builtin_fmaf(p, a2, 6.283185160e+00f);
-    return a * p;
-}
-
-// x / (2*pi) as an unevaluated sum th + tl (exact to ~2^-45 relative)
-NFL_DEV void nfl_turns(float x, float& th, float& tl) {
-    const float C_HI = 0.15915493667125702f;            // fl32(1/(2 pi))
-    const float C_LO = 6.4206382432985265e-09f;         // 1/(2 pi) - C_HI
-    th = x * C_HI;
-    const float e = __builtin_fmaf(x, C_HI, -th);
-    tl = __builtin_fmaf(x, C_LO, e);
-}
-
-// feature f of [x | sin(2^0 x) | cos(2^0 x) | sin(2^1 x) ...] (3 columns per block);
-// f, N compile-time after unrolling, coordinates as turns (th, tl) + raw value
-// `pw` = per-frequency weights (LDS, broadcast reads): all ones, or the BARF coarse-to-fine weights
-// of reference models/nerf.py:47-75 (computed on the host exactly as the reference does)
-template <int N>
-NFL_DEV float nfl_pe_feature(int f, const float (&raw)[3], const float (&th)[3], const float (&tl)[3], const float* pw) {
-    if (f < 3) return raw[f];
-    if (f >= 6 * N + 3) return 0.f;
-    const int g = f - 3, k = g / 6, rem = g % 6, t = rem / 3, c = rem % 3;
-    const float sc = (float)(1 << k);
-    float r = __builtin_amdgcn_fractf(th[c] * sc) + tl[c] * sc;      // 2^k scaling is exact
-    if (t) r += 0.25f;                                                // cos(y) = sin(y + pi/2)
-    return pw[k] * nfl_sin_rev(r);
-}
-
-// relu on the bit pattern: one v_max_i32, and unlike v_max_f32 / v_med3_f32 it needs no canonicalising
-// v_max_f32 x,x in front (negative floats are negative integers; -0 and negative NaNs become +0)
-NFL_DEV float nfl_relu(float x) {
-    int b = __builtin_bit_cast(int, x);
-    b = b > 0 ? b : 0;
-    return __builtin_bit_cast(float, b);
-}
-template <class E>
-NFL_DEV unsigned nfl_pack2(float a, float b) {      // v_cvt_pk_f16_f32 / v_cvt_pk_bf16_f32 (round to nearest even)
-    typedef E e2v __attribute__((ext_vector_type(2)));
-    e2v r;
-    r[0] = (E)a;
-    r[1] = (E)b;
-    return __builtin_bit_cast(unsigned, r);
-}
-// (x0, x1) -> packed 16-bit hi pair (returned) and the fp32 residuals x - float(hi): one pack + (fp16) two
-// v_fma_mix_f32 reading the 16-bit halves directly (exact: a single rounding of x - hi, as the subtraction
-// it replaces; no v_cvt_f32_f16 / v_pk_add_f32 + s_nop)
-template <class E>
-NFL_DEV unsigned nfl_split_pair(float x0, float x1, float& l0, float& l1) {
-    const unsigned hi = nfl_pack2<E>(x0, x1);
-    if constexpr (__is_same(E, _Float16)) {
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(hi), "v"(x0));
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(hi), "v"(x1));
-    } else {
-        // bf16 -> f32 is a shift / a mask (gfx950 has no v_fma_mix_f32_bf16); the empty asm keeps the two
-        // subtractions scalar (v_pk_add_f32 beside MFMAs costs more than two v_sub_f32)
-        l0 = x0 - __builtin_bit_cast(float, hi << 16);
-        asm volatile("" : "+v"(l0));
-        l1 = x1 - __builtin_bit_cast(float, hi & 0xffff0000u);
-    }
-    return hi;
-}
-
-template <int NP, class V8>
-NFL_DEV void nfl_split8(const float (&v)[8], V8 (&dst)[NP]) {
-    using E = typename nfl_elem<V8>::type;
-#pragma unroll
-    for (int j = 0; j < 8; j += 2) {
-        if constexpr (NP == 2) {
-            float l0, l1;
-            reinterpret_cast<unsigned(&)[4]>(dst[0])[j / 2] = nfl_split_pair<E>(v[j], v[j + 1], l0, l1);
-            reinterpret_cast<unsigned(&)[4]>(dst[NP - 1])[j / 2] = nfl_pack2<E>(l0, l1);
-        } else {
-            reinterpret_cast<unsigned(&)[4]>(dst[0])[j / 2] = nfl_pack2<E>(v[j], v[j + 1]);
-        }
-    }
-}
-
-// 8 values -> fp16 -> this lane's 16 B of a stash k-step (dst already includes lane*16); LO != 0: the fp16 residuals
-// x - fp16(x) go LO bytes behind (split stashes of the three-product backward, nfl_plan.h)
-template <int LO = 0>
-NFL_DEV void nfl_stash8(const float (&v)[8], char* dst) {
-    h8 t, tl;
-#pragma unroll
-    for (int j = 0; j < 8; j += 2) {
-        if constexpr (LO != 0) {
-            float l0, l1;
-            reinterpret_cast<unsigned(&)[4]>(t)[j / 2] = nfl_split_pair<_Float16>(v[j], v[j + 1], l0, l1);
-            reinterpret_cast<unsigned(&)[4]>(tl)[j / 2] = nfl_pack2<_Float16>(l0, l1);
-        } else {
-            reinterpret_cast<unsigned(&)[4]>(t)[j / 2] = nfl_pack2<_Float16>(v[j], v[j + 1]);
-        }
-    }
-    NFL_STREAM_STORE(t, reinterpret_cast<h8*>(dst));
-    if constexpr (LO != 0) NFL_STREAM_STORE(tl, reinterpret_cast<h8*>(dst + LO));
-}
-
-// natural-order B operand of one k-step of a positional encoding: lane half h holds
-// features 16*ks + 8*h + j.  Both candidates are evaluated per-lane via selects so the
-// instruction stream is uniform.
-template <int N, int NP, int LO = 0>
-NFL_DEV void nfl_pe_kstep(int ks, int h, const float (&raw)[3], const float (&th)[3], const float (&tl)[3],
-                          const float* pw, h8 (&dst)[NP], char* stash = nullptr) {
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int f0 = 16 * ks + j, f1 = f0 + 8;
-        // select the feature descriptor by lane half, then evaluate once
-        if (f0 < 3 || f0 >= 6 * N + 3 || f1 >= 6 * N + 3) {
-            const float v0 = nfl_pe_feature<N>(f0, raw, th, tl, pw);
-            const float v1 = nfl_pe_feature<N>(f1, raw, th, tl, pw);
-            v[j] = h ? v1 : v0;
-        } else {
-            const int g0 = f0 - 3, g1 = f1 - 3;
-            const int k0 = g0 / 6, k1 = g1 / 6, t0 = (g0 % 6) / 3, t1 = (g1 % 6) / 3, c0 = g0 % 3, c1 = g1 % 3;
-            const float sc = h ? (float)(1 << k1) : (float)(1 << k0);
-            const float thc = h ? th[c1] : th[c0];
-            const float tlc = h ? tl[c1] : tl[c0];
-            const float ph = h ? 0.25f * t1 : 0.25f * t0;
-            const float r = __builtin_amdgcn_fractf(thc * sc) + tlc * sc + ph;
-            v[j] = (h ? pw[k1] : pw[k0]) * nfl_sin_rev(r);
-        }
-    }
-    nfl_split8<NP>(v, dst);
-    if (stash) {        // the operand images ARE the stash (hi; with LO the residuals too)
-        NFL_STREAM_STORE(dst[0], reinterpret_cast<h8*>(stash));
-        if constexpr (LO != 0 && NP == 2) NFL_STREAM_STORE(dst[NP - 1], reinterpret_cast<h8*>(stash + LO));
-    }
-}
-
-// ---------------------------------------------------------------------------------
-// weight ring: global -> LDS by LDS-DMA, 3 slots, prefetch distance 2
-// ---------------------------------------------------------------------------------
-template <int SLOT_BYTES, int MAXP_>
-struct NflRing {
-    static constexpr int MAXP = MAXP_;     // DMA pieces (1 KiB per wave-instruction) every wave issues per chunk
-    const char* gsrc;
-    const int* chunk_off;
-    char* lds;          // ring base (LDS)
-    int n_chunks;
-    int c_issue;        // next chunk (index within the per-tile stream) to issue
-    int s_issue;        // slot it goes to
-    int s_read;         // slot of the next chunk to consume
-    int wave, lane;
-    // chunk currently being issued (pieces are spread over the MFMA loop of the chunk being consumed)
-    const char* i_src;
-    char* i_dst;
-    int i_nbytes;
-
-#ifdef NFL_STAMPS
-    unsigned long long t_wait = 0, t_bar = 0;   // cycles in consume(): DMA wait / workgroup barrier
-#endif
-    int n_off0, n_off1;   // table entries of chunk c_issue, fetched one step ahead (no LDS latency after the barrier)
-    // Not ring state, but it travels with the ring through every layer: per-lane running maximum (packed u16 pair) of
-    // the |fp16 bit patterns| the activation epilogues have formed.  >= 0x7c00 at the end of the kernel means an
-    // activation left fp16's range (the conversion gave inf); reported through nfl_pass_args::d_status.
-    unsigned ovf = 0;
-
-    NFL_DEV void begin_issue() {
-        i_nbytes = n_off1 - n_off0;
-        i_src = gsrc + n_off0;               // wave-uniform; the lane offset is added per piece (keeps no 64-bit VGPR live)
-        i_dst = lds + s_issue * SLOT_BYTES;
-        c_issue = c_issue + 1 == n_chunks ? 0 : c_issue + 1;
-        s_issue = s_issue == 2 ? 0 : s_issue + 1;
-        n_off0 = __builtin_amdgcn_readfirstlane(chunk_off[c_issue]);
-        n_off1 = __builtin_amdgcn_readfirstlane(chunk_off[c_issue + 1]);
-    }
-    template <int P>
-    NFL_DEV void piece() {
-        if constexpr (P < MAXP) {
-            // uniform byte offset (SALU min), one VALU add for the lane: SGPR base + 32-bit VGPR offset
-            unsigned byte = (unsigned)(wave + 4 * P) * 1024u;
-            const unsigned last = (unsigned)i_nbytes - 1024u;
-            byte = byte < last ? byte : last;                      // surplus pieces re-copy the last KiB
-            const unsigned vo = byte + (threadIdx.x & 63) * 16u;
-            __builtin_amdgcn_global_load_lds(
-                (const __attribute__((address_space(1))) void*)(i_src + vo),
-                (__attribute__((address_space(3))) void*)(i_dst + byte), 16, 0, 0);
-        }
-    }
-    template <int P0, int P1>
-    NFL_DEV void pieces() {                 // pieces [P0, P1)
-        nfl_static_for<P0, P1>([&](auto P) __attribute__((always_inline)) { piece<decltype(P)::value>(); });
-    }
-    NFL_DEV void prime() {
-        n_off0 = __builtin_amdgcn_readfirstlane(chunk_off[c_issue]);
-        n_off1 = __builtin_amdgcn_readfirstlane(chunk_off[c_issue + 1]);
-        begin_issue();
-        pieces<0, MAXP>();
-        begin_issue();
-        pieces<0, MAXP>();
-    }
-    // Wait for the oldest chunk in flight, make it visible to all waves and return this lane's
-    // read base; the caller then issues the MAXP pieces of the next chunk (piece<P>()) while it
-    // computes, into the slot everybody has just finished reading.
-    // EXTRA: VMEM ops (stash stores) known to have been issued after the pieces of the chunk waited for,
-    // besides the MAXP pieces of the next one -- without it the wait would also sit on those stores.
-    template <int EXTRA = 0>
-    NFL_DEV const char* consume() {
-#if defined(NFL_STAMPS) && NFL_STAMPS >= 2
-        const unsigned long long c0 = __builtin_amdgcn_s_memtime();
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(MAXP + EXTRA) : "memory");
-        const unsigned long long c1 = __builtin_amdgcn_s_memtime();
-        __builtin_amdgcn_s_barrier();
-        t_wait += c1 - c0;
-        t_bar += __builtin_amdgcn_s_memtime() - c1;
-#else
-        // all but the MAXP (+EXTRA) youngest VMEM ops (= the younger chunk's pieces) are done
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(MAXP + EXTRA) : "memory");
-        __builtin_amdgcn_s_barrier();
-#endif
-        asm volatile("" ::: "memory");
-        begin_issue();
-        const char* base = lds + s_read * SLOT_BYTES + (threadIdx.x & 63) * 16;
-        s_read = s_read == 2 ? 0 : s_read + 1;
-        return base;
-    }
-};
-
-// ---------------------------------------------------------------------------------
-// MFMA building blocks
-// ---------------------------------------------------------------------------------
-template <int NP, int NCB>
-NFL_DEV void nfl_bias_init(f16v (&acc)[NCB], const float* bias_rt, int h) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const f4v b = *reinterpret_cast<const f4v*>(bias_rt + 8 * q + 4 * h);
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) {
-            acc[cb][4 * q + 0] = b[0];
-            acc[cb][4 * q + 1] = b[1];
-            acc[cb][4 * q + 2] = b[2];
-            acc[cb][4 * q + 3] = b[3];
-        }
-    }
-}
-
-// One row tile, software-pipelined in source order.  Every MFMA is followed by a few
-// "fillers" that fit in the issue slots it leaves free (an MFMA holds the issue port for 8 of
-// its 32 cycles): the LDS reads of k-step k+2, one LDS-DMA piece of the chunk being prefetched,
-// and a slice of the PREVIOUS tile's VALU epilogue.  sched_barrier(0) after each micro-slice
-// pins that order (hipcc otherwise emits the DMA pieces and the epilogue back to back after
-// the barrier, with the matrix pipe idle).
-//   getb(K, cb, part) -> B operand of k-step K;  epi.template step<K, NK>() runs the epilogue
-//   work assigned to k-step K;  pieces P0+k are issued at k-step k.
-// The weight fragments are read with hand-issued ds_read_b128 and hand-counted s_waitcnt lgkmcnt(N): left to
-// hipcc, every third k-step got an `s_waitcnt lgkmcnt(0)` that also waits for the reads issued one instruction
-// earlier for k+2, so the full LDS latency was exposed once per three k-steps (1.4x the MFMA time with three
-// products per k-step, 2x with one).  LDS operations return in order, so "all but the N youngest" is exact: N =
-// the reads of k-step k+1.  Any LDS operation the compiler adds in between only makes the wait stricter.
-typedef unsigned nfl_u4 __attribute__((ext_vector_type(4)));
-template <int OFF>
-NFL_DEV nfl_u4 nfl_lds_read128(unsigned addr) {
-    static_assert(OFF >= 0 && OFF < 65536, "ds_read offset field is 16 bits");
-    nfl_u4 r;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-    return r;
-}
-// wait until at most N LDS operations are outstanding; the operands ride through so that their users stay below
-template <int N, int NREAD, int NWP>
-NFL_DEV void nfl_lds_wait(nfl_u4 (&w)[NWP]) {
-    if constexpr (NREAD == 2) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(w[0]), "+v"(w[1]) : "n"(N));
-    else asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(w[0]) : "n"(N));
-}
-
-// DEPTH = how many k-steps ahead the fragments are read (DEPTH + 1 register sets).  Two k-steps are 6 MFMAs with
-// three products per k-step but only 2 with one: the single-product kernels read 4 ahead, or every k-step waits
-// out most of the LDS latency (in-kernel stamps: 3.3 k cycles per 32-MFMA row tile with DEPTH 2).
-#ifndef NFL_DEPTH_X3
-#define NFL_DEPTH_X3 2
-#endif
-// PRODS (three-product mode only): which of the two correction products a layer issues besides w_hi x_hi --
-// bit 0: w_lo x_hi (the weights' fp16 residuals; without it the layer's weights are fp16-rounded and their lo fragments
-// are not even read from LDS), bit 1: w_hi x_lo (the activations' residuals).  3 = the full f16x3 product.  The per-layer
-// plan is NFL_PRODS (nfl_prods.h), chosen by measurement against the parity bar (tests/report_parity.py).
-// bit 2 (NP == 1 only): the stream carries hi + lo WEIGHT fragments although the B operands are single fp16 images -- the
-// default dgrad (nfl_dgrad.hip): W_hi d_hi + W_lo d_hi, the weights to fp32 class, the gradients fp16.
-template <int PRODS, int NP, int NCB, int NK, int P0, class V8, class GetB, class Epi, class Ring,
-          int DEPTH = ((NP == 1 && (PRODS & 4) == 0) ? 4 : NFL_DEPTH_X3)>
-NFL_DEV void nfl_tile_p(f16v (&acc)[NCB], const char* wl, const int frag0, GetB&& getb, Epi&& epi, Ring& ring) {
-    constexpr int NWP = (NP == 2 || (PRODS & 4) != 0) ? 2 : 1;          // weight fragments per k-step: hi (+ lo)
-    constexpr int KSB = 1024 * NWP;
-    constexpr int NW = DEPTH + 1;
-    constexpr bool W_LO = NWP == 2 && (PRODS & 1) != 0, X_LO = NP == 2 && (PRODS & 2) != 0;
-    constexpr int NREAD = W_LO ? 2 : 1;     // LDS reads per k-step
-    (void)frag0;                          // == P0 (kept in the signature for the callers' readability)
-    nfl_u4 w[NW][NWP];
-    const unsigned wa = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)wl;
-    auto load = [&](auto K) __attribute__((always_inline)) {
-        constexpr int k = decltype(K)::value;
-        w[k % NW][0] = nfl_lds_read128<(P0 + k) * KSB>(wa);
-        if constexpr (W_LO) w[k % NW][NWP - 1] = nfl_lds_read128<(P0 + k) * KSB + 1024>(wa);
-    };
-    nfl_static_for<0, (DEPTH < NK ? DEPTH : NK)>([&](auto K) __attribute__((always_inline)) { load(K); });
-    epi.early();                         // VALU work that hides the latency of the first LDS reads
-    __builtin_amdgcn_sched_barrier(0);
-    nfl_static_for<0, NK>([&](auto K) __attribute__((always_inline)) {
-        constexpr int k = decltype(K)::value;
-        // k-step k has landed; the reads of k+1 .. k+DEPTH-1 (already issued) may still be in flight
-        constexpr int younger = (NK - 1 - k) < (DEPTH - 1) ? (NK - 1 - k) : (DEPTH - 1);
-        nfl_lds_wait<younger * NREAD, NREAD>(w[k % NW]);
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) {
-            // fillers of the k-step (the LDS reads of k + DEPTH, one DMA piece) ride behind its first two MFMAs
-            if constexpr (W_LO) {
-                acc[cb] = nfl_mfma(__builtin_bit_cast(V8, w[k % NW][NWP - 1]), getb(K, cb, 0), acc[cb]);
-                if (cb == 0) {
-                    if constexpr (k + DEPTH < NK) load(std::integral_constant<int, k + DEPTH>{});
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if constexpr (X_LO) {
-                acc[cb] = nfl_mfma(__builtin_bit_cast(V8, w[k % NW][0]), getb(K, cb, NP - 1), acc[cb]);
-                if (cb == 0) {
-                    if constexpr (!W_LO && k + DEPTH < NK) load(std::integral_constant<int, k + DEPTH>{});
-                    ring.template piece<P0 + k>();
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            acc[cb] = nfl_mfma(__builtin_bit_cast(V8, w[k % NW][0]), getb(K, cb, 0), acc[cb]);
-            if (cb == 0) {
-                if constexpr (!W_LO && !X_LO && k + DEPTH < NK) load(std::integral_constant<int, k + DEPTH>{});
-                if constexpr (!X_LO) ring.template piece<P0 + k>();
-            }
-            if (cb == NCB - 1) epi.template step<k, NK>();
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    });
-}
-template <int NP, int NCB, int NK, int P0, class V8, class GetB, class Epi, class Ring>
-NFL_DEV void nfl_tile(f16v (&acc)[NCB], const char* wl, const int frag0, GetB&& getb, Epi&& epi, Ring& ring) {
-    nfl_tile_p<3, NP, NCB, NK, P0, V8>(acc, wl, frag0, getb, epi, ring);
-}
-
-struct NflNoEpi {
-    template <int K, int NK> NFL_DEV void step() {}
-    NFL_DEV void early() {}
-};
-#ifndef NFL_EPI_EARLY
-#define NFL_EPI_EARLY 2      // pair-ops done before the first MFMA of the following tile
-#endif
-
-// Epilogue of an accumulator tile -> the two k-steps (ks, ks+1) of the next layer's B operand
-// (and, in the training forward, the fp16 activation stash), cut into 8 pair-ops per column
-// block so it can be spread over the k-steps of the following tile.
-template <int NP, int NCB, bool RELU, bool STASH, int NOUT, int MSLOT, int LO = 0, bool ZST = false>
-struct NflActEpi {
-    const f16v (&acc)[NCB];
-    h8 (&out)[NOUT][NCB][NP];
-    const int ks;
-    char* const (&stash)[NCB];
-    const int slot;
-    char* const (&mstash)[NCB];      // relu-mask records of the lane's segments (training forward)
-    const int mword;                 // mask word of this tile
-    unsigned (&mq)[NCB][4];          // the words of the current group of four tiles: one dwordx4 store per group
-    unsigned& ovf;                   // NflRing::ovf
-    float* const* zc;                // ZST: per segment, the lane's sample column of its ray's appearance cache
-    const int zpad;                  // ZST: sample stride of the cache
-    h8 tmp[NCB];
-    h8 tmpl[LO != 0 ? NCB : 1];      // residual halves for the split stash (LO: their byte offset behind the hi image)
-    unsigned m32[NCB];
-
-    template <int OP>
-    NFL_DEV void pair() {                      // OP 0..7: elements 2*OP, 2*OP+1 of the 16 accumulators
-        constexpr int s = OP / 4, j = 2 * (OP % 4);
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) {
-            float x0 = acc[cb][8 * s + j], x1 = acc[cb][8 * s + j + 1];
-            if constexpr (ZST) {        // NFL_MODE_ZCACHE: the fp32 pre-activation of features f, f + 1 (NFL_SEG_ACT)
-                const int f = 16 * (ks + s) + 8 * (j >> 2) + 4 * (int)((threadIdx.x & 63) >> 5) + (j & 3);
-                zc[cb][(size_t)f * zpad] = x0;
-                zc[cb][(size_t)(f + 1) * zpad] = x1;
-            }
-            if (RELU) {
-                x0 = nfl_relu(x0);
-                x1 = nfl_relu(x1);
-            }
-            unsigned hi;
-            if constexpr (NP == 2) {
-                float l0, l1;
-                hi = nfl_split_pair<_Float16>(x0, x1, l0, l1);
-                const unsigned lo = nfl_pack2<_Float16>(l0, l1);
-                reinterpret_cast<unsigned(&)[4]>(out[ks + s][cb][NP - 1])[j / 2] = lo;
-                if constexpr (STASH && LO != 0) {
-                    reinterpret_cast<unsigned(&)[4]>(tmpl[cb])[j / 2] = lo;
-                    if (OP % 4 == 3) NFL_STREAM_STORE(tmpl[cb], reinterpret_cast<h8*>(stash[cb] + LO + (slot + s) * 1024));
-                }
-            } else {
-                hi = nfl_pack2<_Float16>(x0, x1);
-            }
-            reinterpret_cast<unsigned(&)[4]>(out[ks + s][cb][0])[j / 2] = hi;
-            {   // range tracking: after relu the halves are non-negative, so their bit patterns order like the values
-                const unsigned mag = RELU ? hi : (hi & 0x7fff7fffu);
-                asm("v_pk_max_u16 %0, %0, %1" : "+v"(ovf) : "v"(mag));
-            }
-            if (STASH) {        // the fp16 hi operand IS the stashed activation
-                reinterpret_cast<unsigned(&)[4]>(tmp[cb])[j / 2] = hi;
-                if (OP % 4 == 3) NFL_STREAM_STORE(tmp[cb], reinterpret_cast<h8*>(stash[cb] + (slot + s) * 1024));
-                if (RELU) {     // relu mask of the pair for the dgrad kernel: bit 2*OP / 16 + 2*OP (nfl_plan.h)
-                    unsigned on;
-                    asm("v_pk_min_u16 %0, %1, %2" : "=v"(on) : "v"(hi), "s"(0x00010001u));
-                    m32[cb] = OP == 0 ? on : ((on << (2 * OP)) | m32[cb]);
-                    if (OP == 7) {
-                        // mask words are grouped by four tiles (mw0 is a multiple of 4 for every layer): lane l keeps
-                        // words 4g..4g+3 in 16 contiguous bytes, record layout [group][lane][4]
-                        mq[cb][MSLOT] = m32[cb];              // MSLOT = mword & 3, known at compile time
-                        if (MSLOT == 3) {
-                            typedef unsigned nfl_mq4 __attribute__((ext_vector_type(4)));
-                            const nfl_mq4 v = {mq[cb][0], mq[cb][1], mq[cb][2], mq[cb][3]};
-                            NFL_STREAM_STORE(v, reinterpret_cast<nfl_mq4*>(mstash[cb] + (mword >> 2) * 1024));
-                        }
-                    }
-                }
-            }
-        }
-    }
-    template <int K, int NK>
-    NFL_DEV void step() {                      // the remaining pair-ops, spread evenly over the k-steps
-        constexpr int R = 8 - NFL_EPI_EARLY;
-        nfl_static_for<NFL_EPI_EARLY + (R * K) / NK, NFL_EPI_EARLY + (R * (K + 1)) / NK>([&](auto O) __attribute__((always_inline)) {
-            pair<decltype(O)::value>();
-        });
-    }
-    NFL_DEV void early() {
-        nfl_static_for<0, NFL_EPI_EARLY>([&](auto O) __attribute__((always_inline)) { pair<decltype(O)::value>(); });
-    }
-    NFL_DEV void all() {
-        nfl_static_for<0, 8>([&](auto O) __attribute__((always_inline)) { pair<decltype(O)::value>(); });
-    }
-};
-
-// A dense layer of NRT row tiles reading inA[ksA0..+NKA) then inB[ksB0..+NKB), TPC tiles per
-// ring chunk.  The epilogue of tile i-1 rides in the MFMA shadows of tile i.
-// ZST (NFL_MODE_ZCACHE, a layer whose output starts at k-step 0): the epilogue also stores the fp32 pre-activations to
-// zc[cb][f * zpad] (the appearance cache, nfl_appearance_cache).
-template <int NP, int NCB, int NKA, int NKB, bool RELU, int NRT, int TPC, bool STASH, int LO = 0, int PRODS = 3, bool ZST = false, int NINA, int NINB, int NOUT, class Ring>
-NFL_DEV void nfl_dense(Ring& ring, const float* bias_lds, int& rt, int h,
-                       const h8 (&inA)[NINA][NCB][NP], int ksA0,
-                       const h8 (&inB)[NINB][NCB][NP], int ksB0,
-                       h8 (&out)[NOUT][NCB][NP], int out_ks0, char* const (&stash)[NCB], int slot0,
-                       char* const (&mstash)[NCB], int mw0, float* const* zc = nullptr, int zpad = 0) {
-    constexpr int NK = NKA + NKB;
-    constexpr int NST = 2 * NCB * (LO != 0 ? 2 : 1);     // activation-stash stores of one tile's epilogue (the mask
-                                                         // words go out once per four tiles: not counted, the wait is only stricter)
-    unsigned mq[NCB][4];
-    f16v acc[2][NCB];
-    const char* wl = nullptr;
-    auto getb = [&](auto K, int cb, int part) __attribute__((always_inline)) -> const h8& {
-        constexpr int k = decltype(K)::value;
-        if constexpr (k < NKA) return inA[ksA0 + k][cb][part];
-        else return inB[ksB0 + k - NKA][cb][part];
-    };
-    nfl_static_for<0, NRT>([&](auto I) __attribute__((always_inline)) {
-        constexpr int i = decltype(I)::value;
-        // tile i-1 carried the stash stores of tile i-2's epilogue, issued after this chunk's pieces
-        if (i % TPC == 0) wl = ring.template consume<(STASH && TPC == 1 && i >= 2) ? NST : 0>();
-        constexpr int frag0 = (i % TPC) * NK;
-        nfl_bias_init<NP, NCB>(acc[i & 1], bias_lds + (rt + i) * 32, h);
-        if constexpr (i > 0) {
-            NflActEpi<NP, NCB, RELU, STASH, NOUT, (i - 1) & 3, LO, ZST> epi{acc[(i - 1) & 1], out, out_ks0 + 2 * (i - 1), stash, slot0 + 2 * (i - 1), mstash, mw0 + i - 1, mq, ring.ovf, zc, zpad};
-            nfl_tile_p<PRODS, NP, NCB, NK, frag0, h8>(acc[i & 1], wl, frag0, getb, epi, ring);
-        } else {
-            NflNoEpi epi;
-            nfl_tile_p<PRODS, NP, NCB, NK, frag0, h8>(acc[i & 1], wl, frag0, getb, epi, ring);
-        }
-        // pieces the k-loop of this chunk did not get to
-        if (i % TPC == TPC - 1 || i == NRT - 1) ring.template pieces<((i % TPC) + 1) * NK, Ring::MAXP>();
-    });
-    NflActEpi<NP, NCB, RELU, STASH, NOUT, (NRT - 1) & 3, LO, ZST> last{acc[(NRT - 1) & 1], out, out_ks0 + 2 * (NRT - 1), stash, slot0 + 2 * (NRT - 1), mstash, mw0 + NRT - 1, mq, ring.ovf, zc, zpad};
-    last.all();
-    rt += NRT;
-}
-
-// a single head tile (own chunk); the caller interprets the accumulator rows
-template <int NP, int NCB, int NK, int PRODS = 3, int NIN, class Ring>
-NFL_DEV void nfl_head(Ring& ring, const float* bias_lds, int& rt, int h,
-                      const h8 (&in)[NIN][NCB][NP], int ks0, f16v (&acc)[NCB]) {
-    const char* wl = ring.consume();
-    nfl_bias_init<NP, NCB>(acc, bias_lds + rt * 32, h);
-    auto getb = [&](auto K, int cb, int part) __attribute__((always_inline)) -> const h8& {
-        return in[ks0 + decltype(K)::value][cb][part];
-    };
-    NflNoEpi epi;
-    nfl_tile_p<PRODS, NP, NCB, NK, 0, h8>(acc, wl, 0, getb, epi, ring);
-    ring.template pieces<NK, Ring::MAXP>();
-    rt += 1;
-}
 
 // ---------------------------------------------------------------------------------
 // depths (reference models/rendering.py:243-259); every operation separately rounded
@@ -617,13 +73,6 @@ NFL_DEV float nfl_z_at(const PA& a, int ray, float near, float far, int i) {
     return z;
 }
 
-// 32-lane helpers (both halves of the wave run them independently)
-NFL_DEV float nfl_sum32(float v) {
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) v += __shfl_xor(v, m, 32);
-    return v;
-}
-
 // ---------------------------------------------------------------------------------
 // the kernel
 // ---------------------------------------------------------------------------------
@@ -643,15 +92,10 @@ struct NflRenderCfg {
     static constexpr int LDS_BYTES = LDS_RING + LDS_BIAS + LDS_REC + LDS_CHK;
 };
 
-// Diagnostic build only (make diag, -DNFL_STAMPS): per-phase s_memtime totals of every wave, written to a
-// buffer nothing else reads.  No stamp code exists in the product build.
+// Diagnostic build only (make diag, -DNFL_STAMPS): per-phase s_memtime totals of every wave, written to the buffer of
+// nfl_stamps.h.  No stamp code exists in the product build.
 #ifdef NFL_STAMPS
-#define NFL_NSTAMP 20
-__device__ unsigned long long nfl_stamp_buf[1024 * 4 * NFL_NSTAMP];
-// diagnostic build: copy the per-wave phase cycle totals of the last launch to the host
-extern "C" int nfl_debug_stamps(unsigned long long* host, int n_entries) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(nfl_stamp_buf), sizeof(unsigned long long) * n_entries) == hipSuccess ? 0 : -1;
-}
+#include "nfl_stamps.h"
 #define NFL_STAMP(i)                                                      \
     do {                                                                  \
         const unsigned long long t_now = __builtin_amdgcn_s_memtime();    \
@@ -663,17 +107,9 @@ extern "C" int nfl_debug_stamps(unsigned long long* host, int n_entries) {
 #endif
 
 #define NFL_LOSS_ON(a) ((a).d_loss_target != nullptr)
-// The kernel's argument block, re-read from the kernarg segment.  Values loaded through the returned pointer cannot be
-// hoisted above the call (the empty asm makes the pointer opaque), so arguments that are only needed in the cold parts
-// of a tile (ray set-up, compositing, outputs, loss) are s_load'ed there instead of being kept in SGPRs -- or rather in
-// SGPR spill lanes of VGPRs -- across the whole MLP, where every register is spoken for.
-struct RenderArgs;
-typedef const __attribute__((address_space(4))) RenderArgs* NflKArgs;
-NFL_DEV NflKArgs nfl_kargs() {
-    NflKArgs p = (NflKArgs)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(p));
-    return p;
-}
+// the kernel's argument block, re-read from the kernarg segment where it is used (nfl_dev.h: nfl_kernarg)
+typedef NflKernarg<RenderArgs> NflKArgs;
+NFL_DEV NflKArgs nfl_kargs() { return nfl_kernarg<RenderArgs>(); }
 
 // the camera of a ray-generating pass: in the kernarg segment (copied from nfl_pass_args::h_cam at launch) or, when the
 // caller keeps it in device memory (d_cam: graph replays), behind that pointer -- read with scalar loads either way

@@ -95,7 +95,7 @@ __global__ __launch_bounds__(256) void nfl_wgrad_reduce_kernel(const WgArgs A, c
     const int nparts = A.wg_start[j + 1] - A.wg_start[j];
     const int live = A.n_seg < nparts ? A.n_seg : nparts;        // workgroups beyond the segment count returned before their flush
     float inv;
-    {   // nfl_gmax_bits (nfl_dev.h) written out: through the helper the compiler schedules this kernel differently
+    {   // nfl_gmax_bits and its nfl_wave_max (nfl_dev.h) written out: through the helpers the compiler schedules this kernel differently
         unsigned v = 0u;
         for (int i = lane; i < NFL_GMAX_SLOTS; i += 64) {
             const unsigned o = reinterpret_cast<const unsigned*>(gmax)[i];

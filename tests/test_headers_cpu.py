@@ -1,0 +1,44 @@
+"""The layering of the device headers (file map): nfl_math.h is a leaf, nfl_mlp.h the MLP engine on top of it,
+nfl_render_impl.h the forward kernel on top of that.  Every header compiles from a one-line includer, and no translation
+unit reaches above the layer it needs."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "nerf_fl_amd", "csrc")
+HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+def includes(name):
+    with open(os.path.join(CSRC, name)) as f:
+        return set(re.findall(r'^\s*#\s*include\s*"([^"]+)"', f.read(), re.M))
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@pytest.mark.parametrize("header", ["nfl_math.h", "nfl_dev.h", "nfl_pixel.h", "nfl_mlp.h", "nfl_render_impl.h"])
+def test_header_compiles_on_its_own(header, tmp_path):
+    src = tmp_path / "includer.hip"
+    src.write_text('#include "%s"\n' % header)
+    r = subprocess.run([HIPCC, "-fsyntax-only", "--offload-arch=gfx950", "-std=c++17", "-x", "hip", "-I", CSRC, str(src)],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+
+
+def test_math_header_is_a_leaf():
+    assert not includes("nfl_math.h") & {"nfl_plan.h", "nfl_prods.h", "nfl_diag.h", "nfl_mlp.h", "nfl_render_impl.h"}
+    assert not includes("nfl_macros.h")          # what nfl_math.h does include pulls in nothing of the project either
+
+
+@pytest.mark.parametrize("unit", ["nfl_posenc.hip", "nfl_genrays.hip", "nfl_gather.hip"])
+def test_small_kernels_take_the_math_only(unit):
+    assert "nfl_math.h" in includes(unit)
+    assert not includes(unit) & {"nfl_mlp.h", "nfl_render_impl.h"}
+
+
+def test_dgrad_takes_the_engine_without_the_render_kernel():
+    assert "nfl_mlp.h" in includes("nfl_dgrad.hip")
+    assert "nfl_render_impl.h" not in includes("nfl_dgrad.hip")
