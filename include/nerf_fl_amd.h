@@ -706,6 +706,94 @@ size_t nfl_surface_bytes(int32_t nx, int32_t ny, int32_t nz);
 int nfl_surface_count(const nfl_surface_args* args, void* stream);
 int nfl_surface_emit(const nfl_surface_args* args, void* stream);
 
+/* ---- mesh: cleaning an indexed triangle mesh (connected components, a per-component table, compaction; the reference has
+ * no counterpart) ------------------------------------------------------------------------------------------------------------
+ * A mesh is d_triangles (T, 3) int32 over V vertices.  Definitions:
+ *   - two vertices are CONNECTED when some triangle names both; components are the classes of that relation.  Sharing one
+ *     vertex is enough to connect two triangles (a bow-tie is one component); a vertex named by no triangle is a component
+ *     of its own; repeated indices inside a triangle are allowed;
+ *   - the ROOT of a vertex is the smallest vertex index of its component; components are numbered 0 .. C-1 in ascending
+ *     order of root;
+ *   - a triangle with any index outside [0, V) is IGNORED by every pass: it connects nothing, belongs to no component, is
+ *     never kept, never causes an out-of-range access, and nfl_mesh_label counts it;
+ *   - V <= INT32_MAX and 3 T <= INT32_MAX; index arithmetic is 64-bit.
+ * Atomics are integer compare-and-swap, add, min and max only, whose results do not depend on the order of arrival: every
+ * output is bit-reproducible.  No memset, no copy, no allocation: kernels initialise what they accumulate into, and the
+ * caller provides the scratch (8-byte aligned; the *_bytes queries return 0 for sizes the calls refuse).  The prefix sums
+ * are taken by a scan of the library: tiles of 2048 elements, the tile sums scanned by the same kernel one level up (three
+ * levels cover 2^31 elements) and added back, int32 in, int64 out, a fixed order.
+ *
+ *   nfl_mesh_label   d_component (V) int32 = the dense id of every vertex; d_totals[0] = C, d_totals[1] = the number of
+ *                    ignored triangles.  A lock-free union-find (the larger root is pointed at the smaller by an agent-scope
+ *                    compare-and-swap; parent[] is read by agent-scope atomic loads while hooks run), a flatten launch, the
+ *                    scan of the root flags, a rank launch.  Scratch nfl_mesh_label_bytes(V, T): 16 B per vertex + tile sums.
+ *                    V == 0: NFL_OK, nothing launched, nothing written (C is 0 and every triangle is ignored).
+ *   nfl_mesh_stats   the table of the C components from d_component (as nfl_mesh_label wrote it; an id outside [0, C) is
+ *                    skipped): d_n_vertices (C) int32; d_n_triangles (C) int32, a triangle counting for the component of its
+ *                    FIRST index; d_bounds (C, 2, 3) fp32, per axis the min (row 0) and max (row 1) of the component's
+ *                    d_positions (V, 3), taken through the order-preserving integer map of fp32 (-0 < +0), non-finite
+ *                    coordinates skipped, +inf / -inf where a component has none.  No float sums, so no areas.  Equal ids
+ *                    of a wave are combined before one atomic per distinct id.  No scratch: d_bounds holds the integer keys
+ *                    until the last launch decodes them in place.  C == 0: NFL_OK, no launch.
+ *   nfl_mesh_compact_count / _emit   compaction under d_keep (C) uint8 (non-zero = keep the component).  A vertex is kept
+ *                    when its component is; a triangle when it is not ignored and its three vertices are kept.  count writes
+ *                    d_totals[0] = V', d_totals[1] = T' (the caller reads them back to size the outputs: the one host
+ *                    synchronisation).  emit, with the SAME arguments and scratch plus n_kept_vertices = V',
+ *                    n_kept_triangles = T', writes the kept rows of d_vertices, d_normals, d_colors (each (V, 3) fp32; a
+ *                    NULL input is skipped) to d_out_* in their original order, and the kept triangles in their original
+ *                    order with indices remapped to the kept vertices, and nothing past the totals it is given.
+ *                    emit reads neither d_component nor d_keep but refuses what count refuses, those two included.  What
+ *                    it reads from the scratch it checks against V, V' and T': with a scratch that is not the one count
+ *                    left it skips triangles, and still reads and writes nothing out of range.
+ *                    Scratch nfl_mesh_compact_bytes(V, T): a flag (4 B) and an offset (8 B) per vertex and per triangle,
+ *                    then one region of tile sums (8 B per 2048 elements and level) sized for the longer of the two
+ *                    scans, which run one after the other and share it.
+ * NFL_EINVAL: args NULL, a negative size, V > INT32_MAX or 3 T > INT32_MAX, n_components outside [0, V], a NULL pointer the
+ * sizes need, a misaligned scratch, d_totals NULL (label, count), kept totals negative or above V / T, an output NULL that
+ * an input and its total need (emit).  NFL_ESMALL: scratch_bytes below the query.  Totals of 0: NFL_OK, no launch. */
+typedef struct nfl_mesh_label_args {
+    const int32_t* d_triangles;       /* (T, 3) */
+    int64_t  n_vertices, n_triangles;
+    void*    d_scratch;
+    size_t   scratch_bytes;
+    int32_t* d_component;             /* out (V) */
+    int64_t* d_totals;                /* out (2): C, ignored triangles */
+} nfl_mesh_label_args;
+size_t nfl_mesh_label_bytes(int64_t n_vertices, int64_t n_triangles);
+int nfl_mesh_label(const nfl_mesh_label_args* args, void* stream);
+
+typedef struct nfl_mesh_stats_args {
+    const int32_t* d_component;       /* (V) */
+    const float*   d_positions;       /* (V, 3) */
+    const int32_t* d_triangles;       /* (T, 3) */
+    int64_t  n_vertices, n_triangles, n_components;
+    int32_t* d_n_vertices;            /* out (C) */
+    int32_t* d_n_triangles;           /* out (C) */
+    float*   d_bounds;                /* out (C, 2, 3) */
+} nfl_mesh_stats_args;
+int nfl_mesh_stats(const nfl_mesh_stats_args* args, void* stream);
+
+typedef struct nfl_mesh_compact_args {
+    const int32_t* d_component;       /* (V) */
+    const uint8_t* d_keep;            /* (C) */
+    const int32_t* d_triangles;       /* (T, 3) */
+    int64_t  n_vertices, n_triangles, n_components;
+    void*    d_scratch;
+    size_t   scratch_bytes;
+    int64_t* d_totals;                /* out (2): V', T' (count)                 */
+    int64_t  n_kept_vertices, n_kept_triangles;   /* emit: the totals, read back by the caller */
+    const float* d_vertices;          /* (V, 3) or NULL */
+    const float* d_normals;           /* (V, 3) or NULL */
+    const float* d_colors;            /* (V, 3) or NULL */
+    float*   d_out_vertices;          /* out (V', 3) */
+    float*   d_out_normals;           /* out (V', 3) */
+    float*   d_out_colors;            /* out (V', 3) */
+    int32_t* d_out_triangles;         /* out (T', 3) */
+} nfl_mesh_compact_args;
+size_t nfl_mesh_compact_bytes(int64_t n_vertices, int64_t n_triangles);
+int nfl_mesh_compact_count(const nfl_mesh_compact_args* args, void* stream);
+int nfl_mesh_compact_emit(const nfl_mesh_compact_args* args, void* stream);
+
 /* ---- hierarchical sampling (reference sample_pdf, rendering.py:7-46, plus the
  * concat + sort of rendering.py:267-272) -------------------------------------
  * d_z_coarse (R,S), d_weights_coarse (R,S); d_u (R,I) or NULL with d_u_row (I)

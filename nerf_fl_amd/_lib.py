@@ -205,6 +205,29 @@ class SurfaceArgs(C.Structure):
                 ("d_vertices", C.c_void_p), ("d_normals", C.c_void_p), ("d_triangles", C.c_void_p)]
 
 
+# nfl_mesh_* (nerf_fl_amd.geometry: components, table, compaction) likewise: six new symbols and three new structs
+class MeshLabelArgs(C.Structure):
+    _fields_ = [("d_triangles", C.c_void_p), ("n_vertices", C.c_int64), ("n_triangles", C.c_int64),
+                ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_size_t), ("d_component", C.c_void_p),
+                ("d_totals", C.c_void_p)]
+
+
+class MeshStatsArgs(C.Structure):
+    _fields_ = [("d_component", C.c_void_p), ("d_positions", C.c_void_p), ("d_triangles", C.c_void_p),
+                ("n_vertices", C.c_int64), ("n_triangles", C.c_int64), ("n_components", C.c_int64),
+                ("d_n_vertices", C.c_void_p), ("d_n_triangles", C.c_void_p), ("d_bounds", C.c_void_p)]
+
+
+class MeshCompactArgs(C.Structure):
+    _fields_ = [("d_component", C.c_void_p), ("d_keep", C.c_void_p), ("d_triangles", C.c_void_p),
+                ("n_vertices", C.c_int64), ("n_triangles", C.c_int64), ("n_components", C.c_int64),
+                ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_size_t), ("d_totals", C.c_void_p),
+                ("n_kept_vertices", C.c_int64), ("n_kept_triangles", C.c_int64),
+                ("d_vertices", C.c_void_p), ("d_normals", C.c_void_p), ("d_colors", C.c_void_p),
+                ("d_out_vertices", C.c_void_p), ("d_out_normals", C.c_void_p), ("d_out_colors", C.c_void_p),
+                ("d_out_triangles", C.c_void_p)]
+
+
 # every symbol include/nerf_fl_amd.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("nfl_plan_bytes", C.c_size_t, [C.POINTER(FieldDesc)]),
@@ -259,6 +282,12 @@ SYMBOLS = [
     ("nfl_surface_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     ("nfl_surface_count", C.c_int, [C.POINTER(SurfaceArgs), C.c_void_p]),
     ("nfl_surface_emit", C.c_int, [C.POINTER(SurfaceArgs), C.c_void_p]),
+    ("nfl_mesh_label_bytes", C.c_size_t, [C.c_int64, C.c_int64]),
+    ("nfl_mesh_label", C.c_int, [C.POINTER(MeshLabelArgs), C.c_void_p]),
+    ("nfl_mesh_stats", C.c_int, [C.POINTER(MeshStatsArgs), C.c_void_p]),
+    ("nfl_mesh_compact_bytes", C.c_size_t, [C.c_int64, C.c_int64]),
+    ("nfl_mesh_compact_count", C.c_int, [C.POINTER(MeshCompactArgs), C.c_void_p]),
+    ("nfl_mesh_compact_emit", C.c_int, [C.POINTER(MeshCompactArgs), C.c_void_p]),
     ("nfl_abi_version", C.c_int, []),
     ("nfl_version", C.c_char_p, []),
     ("nfl_strerror", C.c_char_p, [C.c_int]),

@@ -4,7 +4,10 @@
     extract_surface   marching tetrahedra on the device (csrc/nfl_surface.hip): welded vertices, normals, triangles
     surface_colors    static rgb at the vertices, seen along -normal
     write_ply         binary little-endian PLY (numpy only)
-    extract_mesh      the four in a row
+    mesh_components   connected components of a mesh and their table, on the device (csrc/nfl_mesh.hip)
+    filter_mesh       the mesh of the components a keep flag names: vertices, normals, colours, re-indexed triangles
+    clean_mesh        keep by size, rank or bounding box (the floaters of an in-the-wild field go here)
+    extract_mesh      all of it in a row
 
 Conventions: `lo`, `hi` and `res` are 3 numbers in (x, y, z) order; a lattice is a (nz, ny, nx) fp32 tensor, x fastest,
 whose point (x, y, z) lies at lo + (x, y, z) * spacing with spacing = (hi - lo) / (res - 1): `lattice_points` returns
@@ -20,7 +23,8 @@ import torch
 
 from . import _lib, rendering
 
-__all__ = ["density_lattice", "extract_surface", "surface_colors", "write_ply", "extract_mesh", "lattice_points"]
+__all__ = ["density_lattice", "extract_surface", "surface_colors", "write_ply", "extract_mesh", "lattice_points",
+           "mesh_components", "filter_mesh", "clean_mesh"]
 
 # Longest piece of an x-row handed to the render pass as one ray.  nfl_render_pass accepts any n_samples >= 1; the cut is
 # a scheduling choice, not a limit of the ABI: the kernel gives whole rays to workgroups (contiguous ray ranges, one
@@ -247,13 +251,171 @@ def write_ply(path, mesh, colors=None):
         f.write(frec.tobytes())
 
 
-def extract_mesh(models, embeddings, lo, hi, res, iso, chunk=1 << 20, a_embedded=None, path=None):
+def _mesh_tensors(mesh):
+    """(vertices, normals, colors or None, triangles) of a mesh dict, checked: device, dtype, shape, contiguity."""
+    try:
+        ver, nrm, tri = mesh["vertices"], mesh["normals"], mesh["triangles"]
+    except (TypeError, KeyError):
+        raise ValueError("mesh: a dict with vertices (V, 3), normals (V, 3) and triangles (T, 3)") from None
+    col = mesh.get("colors")
+    for t in (ver, nrm, tri) + (() if col is None else (col,)):
+        if not torch.is_tensor(t) or t.device.type != "cuda":
+            raise RuntimeError("nerf_fl_amd.geometry needs tensors on a ROCm device (this build has no CPU path)")
+    for t, what in ((ver, "vertices"), (nrm, "normals"), (col, "colors")):
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous()):
+            raise ValueError(f"mesh: {what}: expected a contiguous fp32 (V, 3) tensor")
+    if tri.dtype != torch.int32 or tri.dim() != 2 or tri.shape[1] != 3 or not tri.is_contiguous():
+        raise ValueError("mesh: triangles: expected a contiguous int32 (T, 3) tensor")
+    if nrm.shape != ver.shape or (col is not None and col.shape != ver.shape):
+        raise ValueError("mesh: vertices, normals and colors differ in shape")
+    if any(t.device != ver.device for t in (nrm, tri) + (() if col is None else (col,))):
+        raise ValueError("mesh: tensors on different devices")
+    if ver.shape[0] > 2 ** 31 - 1 or 3 * tri.shape[0] > 2 ** 31 - 1:
+        raise ValueError(f"mesh: {ver.shape[0]} vertices and {tri.shape[0]} triangles: more than int32 indices address")
+    return ver, nrm, col, tri
+
+
+def _scratch(nbytes, dev):
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+
+
+def mesh_components(mesh):
+    """The connected components of `mesh` (the dict extract_surface returns) as a dict: component (V,) int32, the id of
+    every vertex; n_components C; and the table vertices (C,) int32, triangles (C,) int32 (a triangle counts for the
+    component of its first index), bounds (C, 2, 3) fp32 (per-axis min and max of the vertex positions).  Two vertices
+    are connected when a triangle names both; a vertex no triangle names is a component of its own; ids run in ascending
+    order of a component's smallest vertex index.  Everything is integer work or min / max: two calls give the same bits.
+
+    ONE host synchronisation: C and the number of out-of-range triangles are read from the device to size the table.
+    ValueError when a triangle has an index outside [0, V)."""
+    ver, _, _, tri = _mesh_tensors(mesh)
+    dev, V, T = ver.device, ver.shape[0], tri.shape[0]
+    lib = _lib.lib()
+    component = torch.empty(V, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = rendering._stream()
+        if V:
+            scratch = _scratch(lib.nfl_mesh_label_bytes(V, T), dev)
+            totals = torch.empty(2, dtype=torch.int64, device=dev)
+            a = _lib.MeshLabelArgs()
+            a.d_triangles, a.n_vertices, a.n_triangles = _ptr(tri), V, T
+            a.d_scratch, a.scratch_bytes = _ptr(scratch), scratch.numel() * 8
+            a.d_component, a.d_totals = _ptr(component), _ptr(totals)
+            _lib.check(lib.nfl_mesh_label(C.byref(a), stream), "nfl_mesh_label")
+            n_comp, ignored = (int(v) for v in totals.tolist())            # the host synchronisation
+        else:
+            n_comp, ignored = 0, T
+        if ignored:
+            raise ValueError(f"mesh: {ignored} of {T} triangles have an index outside [0, {V})")
+        out = {"component": component, "n_components": n_comp,
+               "vertices": torch.empty(n_comp, dtype=torch.int32, device=dev),
+               "triangles": torch.empty(n_comp, dtype=torch.int32, device=dev),
+               "bounds": torch.empty(n_comp, 2, 3, dtype=torch.float32, device=dev)}
+        s = _lib.MeshStatsArgs()
+        s.d_component, s.d_positions, s.d_triangles = _ptr(component), _ptr(ver), _ptr(tri)
+        s.n_vertices, s.n_triangles, s.n_components = V, T, n_comp
+        s.d_n_vertices, s.d_n_triangles, s.d_bounds = _ptr(out["vertices"]), _ptr(out["triangles"]), _ptr(out["bounds"])
+        _lib.check(lib.nfl_mesh_stats(C.byref(s), stream), "nfl_mesh_stats")
+    return out
+
+
+def filter_mesh(mesh, keep, components=None):
+    """The part of `mesh` whose components `keep` ((C,) bool, on the device) names: a new dict with vertices, normals,
+    triangles (and colors when `mesh` has them); kept rows stay in their order and the triangles index the kept vertices.
+    `components` is what mesh_components(mesh) returned; without it that call is made here (its synchronisation too).
+
+    ONE host synchronisation: the two kept totals are read from the device to size the outputs."""
+    ver, nrm, col, tri = _mesh_tensors(mesh)
+    if components is None:
+        components = mesh_components(mesh)
+    component, n_comp = components["component"], int(components["n_components"])
+    dev, V, T = ver.device, ver.shape[0], tri.shape[0]
+    if not torch.is_tensor(keep) or keep.device.type != "cuda":
+        raise RuntimeError("nerf_fl_amd.geometry needs tensors on a ROCm device (this build has no CPU path)")
+    if keep.dtype != torch.bool or keep.shape != (n_comp,) or not keep.is_contiguous() or keep.device != dev:
+        raise ValueError(f"keep: expected a contiguous bool ({n_comp},) tensor on the mesh's device")
+    if component.dtype != torch.int32 or component.shape != (V,) or not component.is_contiguous() or component.device != dev:
+        raise ValueError(f"components: component: expected a contiguous int32 ({V},) tensor on the mesh's device")
+    lib = _lib.lib()
+    keep8 = keep.view(torch.uint8)
+    scratch = _scratch(lib.nfl_mesh_compact_bytes(V, T), dev)
+    totals = torch.empty(2, dtype=torch.int64, device=dev)
+    a = _lib.MeshCompactArgs()
+    a.d_component, a.d_keep, a.d_triangles = _ptr(component), _ptr(keep8), _ptr(tri)
+    a.n_vertices, a.n_triangles, a.n_components = V, T, n_comp
+    a.d_scratch, a.scratch_bytes, a.d_totals = _ptr(scratch), scratch.numel() * 8, _ptr(totals)
+    with torch.cuda.device(dev):
+        stream = rendering._stream()
+        if V + T:
+            _lib.check(lib.nfl_mesh_compact_count(C.byref(a), stream), "nfl_mesh_compact_count")
+            Vk, Tk = (int(v) for v in totals.tolist())                     # the host synchronisation
+        else:
+            Vk, Tk = 0, 0
+        out = {"vertices": torch.empty(Vk, 3, dtype=torch.float32, device=dev),
+               "normals": torch.empty(Vk, 3, dtype=torch.float32, device=dev),
+               "triangles": torch.empty(Tk, 3, dtype=torch.int32, device=dev)}
+        if col is not None:
+            out["colors"] = torch.empty(Vk, 3, dtype=torch.float32, device=dev)
+        a.n_kept_vertices, a.n_kept_triangles = Vk, Tk
+        a.d_vertices, a.d_normals, a.d_colors = _ptr(ver), _ptr(nrm), _ptr(col)
+        a.d_out_vertices, a.d_out_normals = _ptr(out["vertices"]), _ptr(out["normals"])
+        a.d_out_colors, a.d_out_triangles = _ptr(out.get("colors")), _ptr(out["triangles"])
+        if V + T:
+            _lib.check(lib.nfl_mesh_compact_emit(C.byref(a), stream), "nfl_mesh_compact_emit")
+    return out
+
+
+def clean_mesh(mesh, largest=None, min_triangles=None, box=None):
+    """`mesh` without the components that fail a criterion; each criterion is judged on its own, over all components, and
+    a component is kept when it passes every one that is given:
+        min_triangles   its triangle count is at least this;
+        box             (lo, hi), 3 numbers each: the bounds of its vertices lie inside, ends included; a component
+                        with no finite coordinate on some axis has no bounds there (+inf / -inf) and fails;
+        largest         it is among the `largest` components by triangle count; ties go to the lower id.
+    The flags are built on the device from the table of mesh_components and handed to filter_mesh: two host
+    synchronisations in all.  With no criterion the input is returned unchanged."""
+    if largest is None and min_triangles is None and box is None:
+        return mesh
+    if largest is not None and int(largest) < 0:
+        raise ValueError("largest must not be negative")
+    comps = mesh_components(mesh)
+    n_tri, dev = comps["triangles"], comps["component"].device
+    keep = torch.ones(comps["n_components"], dtype=torch.bool, device=dev)
+    if min_triangles is not None:
+        keep &= n_tri >= int(min_triangles)
+    if box is not None:
+        try:
+            lo, hi = ([float(v) for v in b] for b in box)
+        except (TypeError, ValueError):
+            raise ValueError("box: (lo, hi), 3 numbers each, in (x, y, z) order") from None
+        if len(lo) != 3 or len(hi) != 3:
+            raise ValueError("box: (lo, hi), 3 numbers each, in (x, y, z) order")
+        lo, hi = (torch.tensor(b, dtype=torch.float32, device=dev) for b in (lo, hi))
+        bmin, bmax = comps["bounds"][:, 0], comps["bounds"][:, 1]
+        keep &= ((bmin <= bmax) & (bmin >= lo) & (bmax <= hi)).all(dim=1)
+    if largest is not None:
+        order = torch.sort(n_tri.to(torch.int64), descending=True, stable=True).indices
+        among = torch.zeros_like(keep)
+        among[order[:int(largest)]] = True
+        keep &= among
+    return filter_mesh(mesh, keep, comps)
+
+
+def extract_mesh(models, embeddings, lo, hi, res, iso, chunk=1 << 20, a_embedded=None, path=None, largest=None,
+                 min_triangles=None):
     """density_lattice -> extract_surface -> surface_colors (-> write_ply when `path` is given) for the fine model of
-    `models` (the coarse one when there is no fine one).  Returns the mesh dict with `colors` (V, 3) added."""
+    `models` (the coarse one when there is no fine one).  Returns the mesh dict with `colors` (V, 3) added.
+
+    With `largest` or `min_triangles` (as in clean_mesh) the small components are dropped BEFORE the colour pass, so the
+    field is never evaluated at a discarded vertex."""
     model = models["fine"] if "fine" in models else models["coarse"]
     lattice = density_lattice(model, embeddings, lo, hi, res, chunk=chunk)
     mesh = extract_surface(lattice, iso, lo, hi)
-    mesh["colors"] = surface_colors(model, embeddings, mesh["vertices"], mesh["normals"], a_embedded=a_embedded)
+    mesh = clean_mesh(mesh, largest=largest, min_triangles=min_triangles)
+    if mesh["vertices"].shape[0] == 0 and not (largest is None and min_triangles is None):
+        mesh["colors"] = torch.empty_like(mesh["vertices"])               # the filter kept nothing: nothing to colour
+    else:
+        mesh["colors"] = surface_colors(model, embeddings, mesh["vertices"], mesh["normals"], a_embedded=a_embedded)
     if path is not None:
         write_ply(path, mesh, mesh["colors"])
     return mesh
