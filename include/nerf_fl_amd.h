@@ -794,6 +794,73 @@ size_t nfl_mesh_compact_bytes(int64_t n_vertices, int64_t n_triangles);
 int nfl_mesh_compact_count(const nfl_mesh_compact_args* args, void* stream);
 int nfl_mesh_compact_emit(const nfl_mesh_compact_args* args, void* stream);
 
+/* ---- occupancy: empty-space skipping at render time (a bit grid from a lattice, rays clipped to it; the reference has no
+ * counterpart: it samples all of [near, far] on every ray) -------------------------------------------------------------------
+ * The GRID.  A lattice (nz, ny, nx) as in "surface" has cx = nx - 1, cy = ny - 1, cz = nz - 1 cells; cell (i, j, k) spans the
+ * lattice points i .. i + 1, j .. j + 1, k .. k + 1, and lattice plane b of axis k lies at fl(lo[k] + fl(b * spacing[k])).
+ * A point is INSIDE when value >= threshold (NaN is outside, +-inf compare as usual).  A cell is occupied at dilation 0 when
+ * any of its 8 corners is inside, and at dilation d (0 .. 8) when a cell within Chebyshev distance d is occupied at dilation
+ * 0; cells outside the grid do not exist.  Storage: one bit per cell, bit i & 31 of the uint32 word
+ * (k * cy + j) * wx + (i >> 5), wx = ceil(cx / 32); the bits past cx in the last word of a row are zero.
+ *   nfl_occ_bytes(nx, ny, nz)               size of the bit grid: 4 cz cy wx; 0 for sizes the calls below refuse.
+ *   nfl_occ_build_bytes(nx, ny, nz, dilate) scratch of the build: two word arrays of one bit per lattice point (rows padded
+ *                                           to words, each array to 16 B); 0 for what nfl_occ_build refuses.
+ *   nfl_occ_build    four launches: the point flags are balloted into words, then the box-OR over the window
+ *                    [i - d, i + d + 1] of points, cut to the lattice (the 8 corners and the dilation in one), is taken
+ *                    separably in bit space: along x by shifts with carries from the neighbouring words, along y and z by
+ *                    ORing whole words.  No memset, no copy, no allocation, no atomics: the same input gives the same bits.
+ *                    NFL_EINVAL (nothing launched): args / d_lattice / d_scratch / d_bits NULL, d_lattice or d_bits not
+ *                    4-byte aligned, d_scratch not 8-byte aligned, a size below 2, ny or nz above 65535, more than 2^30
+ *                    points, dilate outside 0 .. 8.  NFL_ESMALL: scratch_bytes below nfl_occ_build_bytes.
+ *   nfl_occ_clip_rays   one launch, one thread per ray.  d_rays (R, 8) fp32 rows [o, d, near, far], 16-byte aligned; the
+ *                    outputs are d_near_far (R, 2) fp32 (8-byte aligned) and d_hit (R) uint8; nothing past R is written.
+ *                    Every operation below is fp32 and rounded on its own.  Per ray:
+ *                      a NaN among its 8 numbers: a miss.
+ *                      slab test against the box lo .. plane c of every axis (c = cx, cy, cz): t0 = near, t1 = far; per axis
+ *                        with d != 0: inv = 1 / d, ta = (lo - o) * inv, tb = (plane_c - o) * inv, t0 = fmaxf(t0, fminf(ta,
+ *                        tb)), t1 = fminf(t1, fmaxf(ta, tb)); an axis with d == 0 misses unless lo <= o <= plane_c.  The ray
+ *                        misses unless t0 < t1.  Space outside the box is empty.
+ *                      entry cell: floorf(((o + t0 * d) - lo) / spacing) per axis, clamped to [0, c - 1] by fmaxf / fminf
+ *                        before the conversion to an integer.
+ *                      walk (Amanatides-Woo): the next plane of an axis is b = cell + (d > 0 ? 1 : 0), its parameter
+ *                        ((lo + b * spacing) - o) * inv, recomputed from the integer b at every step (never accumulated),
+ *                        +inf where d == 0.  t_out is the smallest of the three, ties to the lowest axis.  An occupied cell
+ *                        sets t_first = the parameter it was entered at (t0 for the entry cell, else the t_out of the step
+ *                        before) if none was met before, and t_last = fminf(t_out, t1).  The walk ends unless t_out < t1, or
+ *                        when the step along that axis leaves the grid: at most cx + cy + cz + 1 cells.
+ *                      hit = 1, near' = t_first, far' = t_last when an occupied cell was met and t_last > t_first; otherwise
+ *                        hit = 0 and near, far are passed through unchanged.  |d| need not be 1: t is the ray's own depth
+ *                        parameter, the one the render kernel samples.
+ *                    R == 0: NFL_OK, no launch.  NFL_EINVAL (nothing launched): args NULL, sizes as above, a spacing that is
+ *                    not positive and finite, a lo that is not finite, R < 0 or above INT32_MAX, a NULL or misaligned
+ *                    pointer. */
+typedef struct nfl_occ_build_args {
+    const float* d_lattice;           /* (nz, ny, nx) */
+    int32_t  nx, ny, nz;
+    float    threshold;
+    int32_t  dilate;                  /* 0 .. 8 */
+    int32_t  reserved;
+    void*    d_scratch;
+    size_t   scratch_bytes;
+    uint32_t* d_bits;                 /* out (cz, cy, wx) */
+} nfl_occ_build_args;
+size_t nfl_occ_bytes(int32_t nx, int32_t ny, int32_t nz);
+size_t nfl_occ_build_bytes(int32_t nx, int32_t ny, int32_t nz, int32_t dilate);
+int nfl_occ_build(const nfl_occ_build_args* args, void* stream);
+
+typedef struct nfl_occ_clip_args {
+    const float* d_rays;              /* (R, 8) */
+    int64_t  n_rays;
+    const uint32_t* d_bits;           /* (cz, cy, wx) */
+    int32_t  nx, ny, nz;              /* of the LATTICE the grid was built from */
+    float    lo[3];                   /* position of lattice point (0, 0, 0): x, y, z */
+    float    spacing[3];              /* x, y, z */
+    int32_t  reserved;
+    float*   d_near_far;              /* out (R, 2) */
+    uint8_t* d_hit;                   /* out (R)    */
+} nfl_occ_clip_args;
+int nfl_occ_clip_rays(const nfl_occ_clip_args* args, void* stream);
+
 /* ---- hierarchical sampling (reference sample_pdf, rendering.py:7-46, plus the
  * concat + sort of rendering.py:267-272) -------------------------------------
  * d_z_coarse (R,S), d_weights_coarse (R,S); d_u (R,I) or NULL with d_u_row (I)

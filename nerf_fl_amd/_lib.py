@@ -228,6 +228,19 @@ class MeshCompactArgs(C.Structure):
                 ("d_out_triangles", C.c_void_p)]
 
 
+# nfl_occ_* (nerf_fl_amd.geometry: occupancy grid, ray clipping) likewise: four new symbols and two new structs
+class OccBuildArgs(C.Structure):
+    _fields_ = [("d_lattice", C.c_void_p), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
+                ("threshold", C.c_float), ("dilate", C.c_int32), ("reserved", C.c_int32), ("d_scratch", C.c_void_p),
+                ("scratch_bytes", C.c_size_t), ("d_bits", C.c_void_p)]
+
+
+class OccClipArgs(C.Structure):
+    _fields_ = [("d_rays", C.c_void_p), ("n_rays", C.c_int64), ("d_bits", C.c_void_p), ("nx", C.c_int32),
+                ("ny", C.c_int32), ("nz", C.c_int32), ("lo", C.c_float * 3), ("spacing", C.c_float * 3),
+                ("reserved", C.c_int32), ("d_near_far", C.c_void_p), ("d_hit", C.c_void_p)]
+
+
 # every symbol include/nerf_fl_amd.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("nfl_plan_bytes", C.c_size_t, [C.POINTER(FieldDesc)]),
@@ -288,6 +301,10 @@ SYMBOLS = [
     ("nfl_mesh_compact_bytes", C.c_size_t, [C.c_int64, C.c_int64]),
     ("nfl_mesh_compact_count", C.c_int, [C.POINTER(MeshCompactArgs), C.c_void_p]),
     ("nfl_mesh_compact_emit", C.c_int, [C.POINTER(MeshCompactArgs), C.c_void_p]),
+    ("nfl_occ_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    ("nfl_occ_build_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    ("nfl_occ_build", C.c_int, [C.POINTER(OccBuildArgs), C.c_void_p]),
+    ("nfl_occ_clip_rays", C.c_int, [C.POINTER(OccClipArgs), C.c_void_p]),
     ("nfl_abi_version", C.c_int, []),
     ("nfl_version", C.c_char_p, []),
     ("nfl_strerror", C.c_char_p, [C.c_int]),

@@ -16,7 +16,7 @@ from . import parallel
 from .rendering import CameraRays, render_rays
 
 __all__ = ["batched_inference", "GraphedChunk", "frame_rays", "to_uint8", "dolly_path", "render_frame", "render_video",
-           "fit_and_evaluate_halves", "evaluate_bank"]
+           "fit_and_evaluate_halves", "evaluate_bank", "clipped_inference"]
 
 
 class GraphedChunk:
@@ -165,6 +165,53 @@ def batched_inference(models, embeddings, rays, ts, N_samples, N_importance, use
         for k, v in out.items():
             results.setdefault(k, []).append(v)
     return {k: torch.cat(v, 0) for k, v in results.items()}
+
+
+@torch.no_grad()
+def clipped_inference(models, embeddings, rays, ts, grid, N_samples, N_importance, use_disp=False, chunk=1024 * 128,
+                      white_back=False, **kwargs):
+    """batched_inference with empty space skipped: `rays` ((B, 8) matrix) are clipped to the geometry.OccupancyGrid
+    `grid` (geometry.clip_rays), the rays that meet an occupied cell are rendered between their tightened bounds with
+    the same N_samples + N_importance, and the rows of the others are filled with what the compositing gives when every
+    weight is zero: 1 (white_back) or 0 for every key containing `rgb`, the fine model's beta_min for `beta`, 0 for the
+    rest.  `ts` and the per-ray kwargs (GraphedChunk.PER_RAY) with B rows follow their rays; a (1, C) one stays
+    broadcast; the other kwargs go to batched_inference (use_graph among them).  Keys beginning with `_` are internal to
+    the backward and are not returned.  When no ray hits, no render launch is made.
+
+    ONE host synchronisation per call: the hit rays are compacted, in their original order, with torch.nonzero.
+    Space outside the grid's box renders as empty."""
+    from . import geometry
+    B = rays.shape[0]
+    clipped, hit = geometry.clip_rays(grid, rays)
+    idx = torch.nonzero(hit).squeeze(1)                             # the host synchronisation
+    n = idx.shape[0]
+    kw = dict(kwargs)
+    for k in GraphedChunk.PER_RAY:
+        v = kwargs.get(k)
+        if v is not None and v.shape[0] == B:
+            kw[k] = v[idx]
+    ts_hit = ts[idx] if ts is not None else None
+    if n:
+        res = batched_inference(models, embeddings, clipped[idx], ts_hit, N_samples, N_importance, use_disp, chunk,
+                                white_back, **kw)
+    else:           # render_rays returns empty tensors of the right shapes for no rays, before any launch
+        for k in GraphedChunk.PER_RAY:
+            if kw.get(k) is not None:
+                kw[k] = kw[k].expand(0, -1) if kw[k].shape[0] == 1 else kw[k][:0]
+        for k in ("use_graph", "_graph_cache"):
+            kw.pop(k, None)
+        res = render_rays(models, embeddings, clipped[:0], ts_hit, N_samples, use_disp, 0, 0, N_importance, chunk,
+                          white_back, True, **kw)
+    beta_min = float(getattr(models.get("fine", models["coarse"]), "beta_min", 0.0))
+    out = {}
+    for k, v in res.items():
+        if k.startswith("_"):
+            continue
+        fill = (1.0 if white_back else 0.0) if "rgb" in k else beta_min if k == "beta" else 0.0
+        full = torch.full((B,) + tuple(v.shape[1:]), fill, dtype=v.dtype, device=v.device)
+        full[idx] = v
+        out[k] = full
+    return out
 
 
 def frame_rays(c2w, K, H, W, near, far, device, start=0, count=None):
@@ -373,10 +420,20 @@ def fov60_intrinsics(W, H):
 
 @torch.no_grad()
 def render_frame(models, embeddings, c2w, K, H, W, near, far, N_samples, N_importance, ts=None, use_disp=False,
-                 chunk=1024 * 128, white_back=False, device="cuda:0", use_graph=False, _graph_cache=None, **kwargs):
+                 chunk=1024 * 128, white_back=False, device="cuda:0", use_graph=False, _graph_cache=None, occupancy=None,
+                 **kwargs):
     """One H x W frame from (pose, intrinsics): the rays are generated in the render kernel's prologue (CameraRays), the
     image is converted on the device.  Returns (uint8 (H, W, 3), dict of the float outputs).  `ts`: image id for the
-    latent tables -- an int, a (H*W,) tensor, or None when `a_embedded` is given / the model has no latent inputs."""
+    latent tables -- an int, a (H*W,) tensor, or None when `a_embedded` is given / the model has no latent inputs.
+    `occupancy`: a geometry.OccupancyGrid; the frame's rays are then a matrix (frame_rays: the bounds are per ray) and go
+    through clipped_inference, which skips the pixels that see no occupied cell (one host synchronisation per frame)."""
+    if occupancy is not None:
+        rays = frame_rays(c2w, K, H, W, near, far, device)
+        if isinstance(ts, int):
+            ts = torch.full((H * W,), ts, dtype=torch.long, device=rays.device)
+        res = clipped_inference(models, embeddings, rays, ts, occupancy, N_samples, N_importance, use_disp, chunk,
+                                white_back, use_graph=use_graph, _graph_cache=_graph_cache, **kwargs)
+        return to_uint8(res["rgb_fine" if "rgb_fine" in res else "rgb_coarse"]).view(H, W, 3), res
     cam = CameraRays(c2w, K, H, W, near, far, device)
     if isinstance(ts, int):
         ts = torch.full((H * W,), ts, dtype=torch.long, device=cam.device)
