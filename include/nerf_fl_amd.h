@@ -794,6 +794,94 @@ size_t nfl_mesh_compact_bytes(int64_t n_vertices, int64_t n_triangles);
 int nfl_mesh_compact_count(const nfl_mesh_compact_args* args, void* stream);
 int nfl_mesh_compact_emit(const nfl_mesh_compact_args* args, void* stream);
 
+/* ---- mesh simplification: uniform vertex clustering of an indexed triangle mesh (the reference has no counterpart) ---------
+ * Inputs: d_vertices (V, 3) fp32, d_normals (V, 3) fp32, d_colors (V, 3) fp32 or NULL, d_triangles (T, 3) int32; a scalar
+ * cell > 0, an origin (3 doubles) and a placement (NFL_SIMPLIFY_MEAN or NFL_SIMPLIFY_QUADRIC).  Definitions:
+ *   CLUSTER of a vertex.  Per axis i = floor(((double)p - origin) / cell), in fp64.  A vertex is VALID when its three
+ *     coordinates are finite and every i lies in [-2^20, 2^20); other vertices belong to no cluster.  The key of a valid
+ *     vertex is (i + 2^20) | (j + 2^20) << 21 | (k + 2^20) << 42: there is no bounding box, the grid is unbounded and
+ *     hashed.  The centre of the cell is origin + (i + 0.5) * cell, in fp64.
+ *   NEW VERTEX IDS.  Clusters are numbered 0 .. V'-1 in ascending order of the smallest input vertex index they contain
+ *     (the rule by which nfl_mesh_label numbers components).  d_cluster (V) int32 maps an input vertex to its new id, -1
+ *     for a vertex that is not valid.
+ *   TRIANGLES.  An input triangle with an index outside [0, V) is counted (d_totals[2]) and dropped.  A triangle that names
+ *     a vertex which is not valid is dropped; so is one of whose three new ids two are equal.  Among the rest, two
+ *     triangles are DUPLICATES when their new-id triples are equal up to rotation; the winding is kept, so a reversed
+ *     triple is a different triangle.  Of each set of duplicates the lowest input index survives.  Survivors are emitted in
+ *     ascending input index with the new ids in the survivor's own corner order; T' is their count.
+ *   ATTRIBUTES of a new vertex.  A cluster with exactly one member keeps that member's position, normal and colour bit for
+ *     bit.  Otherwise every sum is taken in int64 fixed point, so that the order of summation cannot matter: a member
+ *     contributes llrint(x * 2^30) per component, with x = ((double)p - centre) / cell for positions and x = the component
+ *     itself for normals and colours (a non-finite normal or colour component contributes 0; finite ones are taken to be
+ *     below 2^31 in magnitude).  With n members:
+ *       colour     fl32(sum / (n * 2^30));
+ *       normal     the three sums as doubles s, fl32(s / |s|) with |s| = sqrt((s_x s_x + s_y s_y) + s_z s_z), zero when |s| = 0;
+ *       position, NFL_SIMPLIFY_MEAN      u~ = sum / (n * 2^30), fl32(centre + cell * u~), every operation fp64 and rounded
+ *                                        on its own;
+ *       position, NFL_SIMPLIFY_QUADRIC   the regularised quadric-error minimum, in the cell's own coordinates.  The
+ *         CONTRIBUTING triangles are the input triangles with three indices in range, three valid corners and a finite,
+ *         non-zero area a = |c| / 2, c = (p1 - p0) x (p2 - p0) in fp64 from the fp32 positions; n = c / |c|.  For EACH of
+ *         its three corners such a triangle adds to that corner's cluster A += w n n^T (6 numbers) and b += w d n, with
+ *         w = a / cell^2, d = -n . u0, u0 = (p0 - the centre of that cluster) / cell, p0 the triangle's FIRST corner.
+ *         These nine sums are fp64 (atomic adds on doubles: their order is not fixed).  With mu = NFL_SIMPLIFY_LAMBDA *
+ *         trace(A), solve (A + mu I) u = mu u~ - b in fp64 and clamp u per axis to [-0.5, 0.5]; u~ takes the place of u
+ *         when trace(A) == 0 or when the solve gives a non-finite number.  The position is fl32(centre + cell * u).
+ *         The regularisation bounds the condition number of the system by about 1 / NFL_SIMPLIFY_LAMBDA, so the order of
+ *         the fp64 sums moves the result by far less than an fp32 ulp; the clamp keeps a new vertex inside its own cell.
+ *   A cluster none of whose triangles survive stays as a vertex that no triangle names.
+ *   nfl_mesh_simplify_bytes(V, T)   scratch size, carved by the calls themselves: two open-addressed tables (vertex keys:
+ *                    the power of two >= 2 V slots of 8 + 4 B; triangles: the power of two >= 2 T slots of 4 + 4 B), per
+ *                    vertex a slot, a flag and a rank (4 + 4 + 8 B), per triangle the rotation-canonical new-id triple, a
+ *                    slot, a flag and an offset (12 + 4 + 4 + 8 B), the tile sums of the longer scan, and per vertex the
+ *                    accumulators of emit (a count, nine int64, nine doubles: 4 + 72 + 72 B).  0 for sizes the calls refuse.
+ *   nfl_mesh_simplify_count   writes d_cluster and d_totals = {V', T', out-of-range triangles, vertices that are not valid}.
+ *                    The tables are initialised by a kernel (empty marker: a key of all ones, which no vertex has; -1 for a
+ *                    triangle slot).  Vertex keys are inserted by linear probing with a 64-bit compare-and-swap; a per-slot
+ *                    atomic minimum of the vertex index names the leader of each cluster; the leader flags are scanned (the
+ *                    scan of "mesh") and d_cluster[v] = rank of v's leader.  The triangles are mapped and their canonical
+ *                    triples written by one launch; the NEXT launch inserts them into the second table, whose slots are
+ *                    claimed write-once by a triangle index and compared through the claimant's canonical triple; a
+ *                    per-slot atomic minimum of the triangle index names the survivor; the survivor flags are scanned.
+ *                    No thread waits for another: every probe sequence ends at the first empty slot, and both tables are
+ *                    at most half full.  Integer atomics only: every output is bit-reproducible.
+ *   nfl_mesh_simplify_emit    with the SAME arguments, d_cluster and scratch plus n_out_vertices = V', n_out_triangles = T':
+ *                    zeroes the accumulators of V' clusters, adds up (int64 atomic adds; for NFL_SIMPLIFY_QUADRIC a pass
+ *                    over the triangles with fp64 atomic adds), then the leader of each cluster writes its row of
+ *                    d_out_vertices, d_out_normals and (with d_colors) d_out_colors, solving the 3 x 3 system itself; the
+ *                    surviving triangles go to d_out_triangles.  Nothing past V' / T' is written, and what is read from
+ *                    the scratch and d_cluster is checked against V' and T' first.
+ * No memset, no copy, no allocation, no synchronisation.  d_scratch: 8-byte aligned.
+ * NFL_EINVAL: args NULL, a negative size, V > INT32_MAX or 3 T > INT32_MAX, cell not finite and positive, an origin that is
+ * not finite, an unknown placement, a NULL pointer the sizes need (d_vertices, d_triangles, d_cluster, d_scratch; count:
+ * d_totals; emit: d_normals and an output its total needs), a misaligned scratch, totals negative or above V / T (emit).
+ * NFL_ESMALL: scratch_bytes below the query.  V == 0: NFL_OK, nothing launched, nothing written. */
+#define NFL_SIMPLIFY_LAMBDA 1e-3
+#define NFL_SIMPLIFY_MEAN 0
+#define NFL_SIMPLIFY_QUADRIC 1
+typedef struct nfl_mesh_simplify_args {
+    const float* d_vertices;          /* (V, 3) */
+    const float* d_normals;           /* (V, 3) */
+    const float* d_colors;            /* (V, 3) or NULL */
+    const int32_t* d_triangles;       /* (T, 3) */
+    int64_t  n_vertices, n_triangles;
+    double   cell;
+    double   origin[3];               /* x, y, z */
+    int32_t  placement;               /* NFL_SIMPLIFY_MEAN / NFL_SIMPLIFY_QUADRIC */
+    int32_t  reserved;
+    void*    d_scratch;
+    size_t   scratch_bytes;
+    int64_t* d_totals;                /* out (4): V', T', out-of-range triangles, invalid vertices (count) */
+    int32_t* d_cluster;               /* out (V): count writes it, emit reads it */
+    int64_t  n_out_vertices, n_out_triangles;     /* emit: V' and T', read back by the caller */
+    float*   d_out_vertices;          /* out (V', 3) */
+    float*   d_out_normals;           /* out (V', 3) */
+    float*   d_out_colors;            /* out (V', 3), with d_colors */
+    int32_t* d_out_triangles;         /* out (T', 3) */
+} nfl_mesh_simplify_args;
+size_t nfl_mesh_simplify_bytes(int64_t n_vertices, int64_t n_triangles);
+int nfl_mesh_simplify_count(const nfl_mesh_simplify_args* args, void* stream);
+int nfl_mesh_simplify_emit(const nfl_mesh_simplify_args* args, void* stream);
+
 /* ---- occupancy: empty-space skipping at render time (a bit grid from a lattice, rays clipped to it; the reference has no
  * counterpart: it samples all of [near, far] on every ray) -------------------------------------------------------------------
  * The GRID.  A lattice (nz, ny, nx) as in "surface" has cx = nx - 1, cy = ny - 1, cz = nz - 1 cells; cell (i, j, k) spans the

@@ -228,6 +228,20 @@ class MeshCompactArgs(C.Structure):
                 ("d_out_triangles", C.c_void_p)]
 
 
+# nfl_mesh_simplify_* (nerf_fl_amd.geometry: vertex clustering) likewise: three new symbols and a new struct
+SIMPLIFY_LAMBDA = 1e-3
+SIMPLIFY_PLACEMENTS = {"mean": 0, "quadric": 1}
+
+
+class MeshSimplifyArgs(C.Structure):
+    _fields_ = [("d_vertices", C.c_void_p), ("d_normals", C.c_void_p), ("d_colors", C.c_void_p), ("d_triangles", C.c_void_p),
+                ("n_vertices", C.c_int64), ("n_triangles", C.c_int64), ("cell", C.c_double), ("origin", C.c_double * 3),
+                ("placement", C.c_int32), ("reserved", C.c_int32), ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_size_t),
+                ("d_totals", C.c_void_p), ("d_cluster", C.c_void_p), ("n_out_vertices", C.c_int64),
+                ("n_out_triangles", C.c_int64), ("d_out_vertices", C.c_void_p), ("d_out_normals", C.c_void_p),
+                ("d_out_colors", C.c_void_p), ("d_out_triangles", C.c_void_p)]
+
+
 # nfl_occ_* (nerf_fl_amd.geometry: occupancy grid, ray clipping) likewise: four new symbols and two new structs
 class OccBuildArgs(C.Structure):
     _fields_ = [("d_lattice", C.c_void_p), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
@@ -301,6 +315,9 @@ SYMBOLS = [
     ("nfl_mesh_compact_bytes", C.c_size_t, [C.c_int64, C.c_int64]),
     ("nfl_mesh_compact_count", C.c_int, [C.POINTER(MeshCompactArgs), C.c_void_p]),
     ("nfl_mesh_compact_emit", C.c_int, [C.POINTER(MeshCompactArgs), C.c_void_p]),
+    ("nfl_mesh_simplify_bytes", C.c_size_t, [C.c_int64, C.c_int64]),
+    ("nfl_mesh_simplify_count", C.c_int, [C.POINTER(MeshSimplifyArgs), C.c_void_p]),
+    ("nfl_mesh_simplify_emit", C.c_int, [C.POINTER(MeshSimplifyArgs), C.c_void_p]),
     ("nfl_occ_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     ("nfl_occ_build_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     ("nfl_occ_build", C.c_int, [C.POINTER(OccBuildArgs), C.c_void_p]),

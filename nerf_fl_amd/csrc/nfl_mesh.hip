@@ -25,30 +25,15 @@
 #include <stdint.h>
 
 #include "../../include/nerf_fl_amd.h"
+#include "nfl_mesh_scan.h"
 
-#define NM_THREADS 256
-#define NM_SCAN_THREADS 512
-#define NM_SCAN_ITEMS 4
-#define NM_SCAN_TILE (NM_SCAN_THREADS * NM_SCAN_ITEMS)      // 2048: 2^31 elements -> 2^20 -> 2^9 -> 1 tile sums
-#define NM_SCAN_LEVELS 3
 #define NM_KEY_POS_INF 0xFF800000u                          // nm_key(+inf)
 #define NM_KEY_NEG_INF 0x007FFFFFu                          // nm_key(-inf)
-
-typedef int64_t i64;
-
-#define NM_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define NM_STORE(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-
-static inline size_t nm_pad(size_t bytes) { return (bytes + 15) / 16 * 16; }
-static inline i64 nm_cdiv(i64 a, i64 b) { return (a + b - 1) / b; }
-static inline unsigned nm_grid(i64 n) { return (unsigned)nm_cdiv(n, NM_THREADS); }
-static inline bool nm_sizes_ok(i64 V, i64 T) { return V >= 0 && T >= 0 && V <= INT32_MAX && T <= INT32_MAX / 3; }
-static inline bool nm_launched() { return hipGetLastError() == hipSuccess; }
 
 // ---------------------------------------------------------------------------------------------------------------- scan
 
 // tile sums of all levels above the elements themselves, 8 B each
-static size_t nm_scan_bytes(i64 n) {
+size_t nm_scan_bytes(i64 n) {
     size_t entries = 0;
     for (i64 m = nm_cdiv(n, NM_SCAN_TILE); m > 1; m = nm_cdiv(m, NM_SCAN_TILE)) entries += (size_t)m;
     return nm_pad(entries * 8);
@@ -102,7 +87,7 @@ __global__ __launch_bounds__(64) void nfl_mesh_zero_total_kernel(i64* total) {
 }
 
 // out (n) int64 = exclusive prefix sums of in (n) int32, *total = their sum; `sums`: nm_scan_bytes(n) of scratch
-static void nm_scan(const int32_t* in, i64* out, i64 n, i64* sums, i64* total, hipStream_t s) {
+void nm_scan(const int32_t* in, i64* out, i64 n, i64* sums, i64* total, hipStream_t s) {
     if (n == 0) {
         hipLaunchKernelGGL(nfl_mesh_zero_total_kernel, dim3(1), dim3(64), 0, s, total);
         return;
@@ -158,10 +143,6 @@ __device__ __forceinline__ void nm_unite(int32_t* parent, int32_t a, int32_t b) 
                                                  __HIP_MEMORY_SCOPE_AGENT))
             return;
     }
-}
-
-__device__ __forceinline__ bool nm_in_range(int32_t a, int32_t b, int32_t c, i64 V) {
-    return a >= 0 && b >= 0 && c >= 0 && a < V && b < V && c < V;
 }
 
 __global__ __launch_bounds__(NM_THREADS) void nfl_mesh_hook_kernel(const int32_t* tri, i64 V, i64 T, int32_t* parent,
@@ -347,8 +328,6 @@ struct NmCompact {
     i64* off_t;             // (T)
     i64* sums;              // tile sums of the larger of the two scans (they run one after the other)
 };
-
-static inline size_t nm_max(size_t a, size_t b) { return a > b ? a : b; }
 
 extern "C" size_t nfl_mesh_compact_bytes(int64_t V, int64_t T) {
     if (!nm_sizes_ok(V, T)) return 0;

@@ -7,6 +7,7 @@
     mesh_components   connected components of a mesh and their table, on the device (csrc/nfl_mesh.hip)
     filter_mesh       the mesh of the components a keep flag names: vertices, normals, colours, re-indexed triangles
     clean_mesh        keep by size, rank or bounding box (the floaters of an in-the-wild field go here)
+    simplify_mesh     the same surface with fewer triangles: uniform vertex clustering on the device (csrc/nfl_simplify.hip)
     extract_mesh      all of it in a row
     occupancy_grid    one bit per cell of a lattice: occupied where a corner reaches a threshold, dilated (csrc/nfl_occupancy.hip)
     clip_rays         rays walked through such a grid: a tightened [near, far] per ray and a flag for rays that hit nothing
@@ -26,7 +27,7 @@ import torch
 from . import _lib, rendering
 
 __all__ = ["density_lattice", "extract_surface", "surface_colors", "write_ply", "extract_mesh", "lattice_points",
-           "mesh_components", "filter_mesh", "clean_mesh", "OccupancyGrid", "occupancy_grid", "clip_rays"]
+           "mesh_components", "filter_mesh", "clean_mesh", "simplify_mesh", "OccupancyGrid", "occupancy_grid", "clip_rays"]
 
 # Longest piece of an x-row handed to the render pass as one ray.  nfl_render_pass accepts any n_samples >= 1; the cut is
 # a scheduling choice, not a limit of the ABI: the kernel gives whole rays to workgroups (contiguous ray ranges, one
@@ -403,18 +404,99 @@ def clean_mesh(mesh, largest=None, min_triangles=None, box=None):
     return filter_mesh(mesh, keep, comps)
 
 
+def _simplify_arguments(cell, origin, placement):
+    """(cell, origin, placement code) of simplify_mesh, checked."""
+    try:
+        cell = float(cell)
+    except (TypeError, ValueError):
+        raise ValueError("cell: a finite positive number") from None
+    if not (np.isfinite(cell) and cell > 0.0):
+        raise ValueError(f"cell: a finite positive number, got {cell}")
+    if placement not in _lib.SIMPLIFY_PLACEMENTS:
+        raise ValueError(f"placement: one of {sorted(_lib.SIMPLIFY_PLACEMENTS)}, got {placement!r}")
+    try:
+        origin = [float(v) for v in origin]
+    except (TypeError, ValueError):
+        raise ValueError("origin: 3 finite numbers, in (x, y, z) order") from None
+    if len(origin) != 3 or not all(np.isfinite(origin)):
+        raise ValueError("origin: 3 finite numbers, in (x, y, z) order")
+    return cell, origin, _lib.SIMPLIFY_PLACEMENTS[placement]
+
+
+def simplify_mesh(mesh, cell, origin=(0.0, 0.0, 0.0), placement="mean", return_map=False):
+    """`mesh` simplified by uniform vertex clustering: the vertices that share a cube of side `cell` of the unbounded grid
+    through `origin` become ONE vertex, triangles that lose a corner that way or repeat another one are dropped, and
+    everything is re-indexed.  Returns a new dict with vertices, normals, triangles (and colors when `mesh` has them);
+    with `return_map` also cluster (V,) int32, the new id of every input vertex (-1: a non-finite vertex, or one more
+    than 2^20 cells from the origin).  The definition is written out in include/nerf_fl_amd.h, "mesh simplification":
+
+        ids        clusters in ascending order of their smallest input vertex; surviving triangles in their input order,
+                   the lowest index of each set of duplicates (equal up to rotation; a reversed triangle is another one);
+        placement  "mean": the mean of the members, in int64 fixed point relative to the cell centre: bit-reproducible;
+                   "quadric": the minimum of the members' triangle-plane quadric, regularised towards the mean and
+                   clamped to the cell, which keeps corners and edges sharp where the mean rounds them off;
+        normal     the normalised sum, colour the mean of the members'; a cluster of one keeps its member bit for bit.
+
+    A cluster none of whose triangles survive stays as a vertex that no triangle names: clean_mesh(min_triangles=1)
+    removes those.  ValueError when a triangle has an index outside [0, V).
+
+    ONE host synchronisation: the four totals are read from the device to size the outputs and to raise."""
+    cell, origin, code = _simplify_arguments(cell, origin, placement)
+    ver, nrm, col, tri = _mesh_tensors(mesh)
+    dev, V, T = ver.device, ver.shape[0], tri.shape[0]
+    lib = _lib.lib()
+    cluster = torch.empty(V, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        a = _lib.MeshSimplifyArgs()
+        if V:
+            stream = rendering._stream()
+            nbytes = lib.nfl_mesh_simplify_bytes(V, T)
+            scratch = _scratch(nbytes, dev)
+            totals = torch.empty(4, dtype=torch.int64, device=dev)
+            a.d_vertices, a.d_normals, a.d_colors, a.d_triangles = _ptr(ver), _ptr(nrm), _ptr(col), _ptr(tri)
+            a.n_vertices, a.n_triangles, a.cell, a.placement = V, T, cell, code
+            for k in range(3):
+                a.origin[k] = origin[k]
+            a.d_scratch, a.scratch_bytes = _ptr(scratch), scratch.numel() * 8
+            a.d_totals, a.d_cluster = _ptr(totals), _ptr(cluster)
+            _lib.check(lib.nfl_mesh_simplify_count(C.byref(a), stream), "nfl_mesh_simplify_count")
+            Vo, To, outside, _ = (int(v) for v in totals.tolist())         # the host synchronisation
+        else:
+            Vo, To, outside = 0, 0, T
+        if outside:
+            raise ValueError(f"mesh: {outside} of {T} triangles have an index outside [0, {V})")
+        out = {"vertices": torch.empty(Vo, 3, dtype=torch.float32, device=dev),
+               "normals": torch.empty(Vo, 3, dtype=torch.float32, device=dev),
+               "triangles": torch.empty(To, 3, dtype=torch.int32, device=dev)}
+        if col is not None:
+            out["colors"] = torch.empty(Vo, 3, dtype=torch.float32, device=dev)
+        if V:
+            a.n_out_vertices, a.n_out_triangles = Vo, To
+            a.d_out_vertices, a.d_out_normals = _ptr(out["vertices"]), _ptr(out["normals"])
+            a.d_out_colors, a.d_out_triangles = _ptr(out.get("colors")), _ptr(out["triangles"])
+            _lib.check(lib.nfl_mesh_simplify_emit(C.byref(a), stream), "nfl_mesh_simplify_emit")
+    return (out, cluster) if return_map else out
+
+
 def extract_mesh(models, embeddings, lo, hi, res, iso, chunk=1 << 20, a_embedded=None, path=None, largest=None,
-                 min_triangles=None):
+                 min_triangles=None, simplify=None, placement="mean"):
     """density_lattice -> extract_surface -> surface_colors (-> write_ply when `path` is given) for the fine model of
     `models` (the coarse one when there is no fine one).  Returns the mesh dict with `colors` (V, 3) added.
 
     With `largest` or `min_triangles` (as in clean_mesh) the small components are dropped BEFORE the colour pass, so the
-    field is never evaluated at a discarded vertex."""
+    field is never evaluated at a discarded vertex.
+
+    With `simplify` = a cell size the cleaned mesh goes through simplify_mesh (origin = `lo`, `placement` as there), also
+    before the colour pass: the field is evaluated at the simplified vertices only, seen along their new normals."""
+    if simplify is not None:
+        _simplify_arguments(simplify, lo, placement)                      # refused before anything is evaluated
     model = models["fine"] if "fine" in models else models["coarse"]
     lattice = density_lattice(model, embeddings, lo, hi, res, chunk=chunk)
     mesh = extract_surface(lattice, iso, lo, hi)
     mesh = clean_mesh(mesh, largest=largest, min_triangles=min_triangles)
-    if mesh["vertices"].shape[0] == 0 and not (largest is None and min_triangles is None):
+    if simplify is not None:
+        mesh = simplify_mesh(mesh, simplify, origin=lo, placement=placement)
+    if mesh["vertices"].shape[0] == 0 and not (largest is None and min_triangles is None and simplify is None):
         mesh["colors"] = torch.empty_like(mesh["vertices"])               # the filter kept nothing: nothing to colour
     else:
         mesh["colors"] = surface_colors(model, embeddings, mesh["vertices"], mesh["normals"], a_embedded=a_embedded)
