@@ -1,0 +1,86 @@
+// nfl_geom.h -- what the geometry translation units (nfl_surface, nfl_mesh, nfl_occupancy, nfl_simplify, nfl_mesh_scan)
+// share on the device side: launch sizes, the workgroup prefix sum, the library's tiled scan and the small pieces of the
+// mesh kernels.  The scratch layouts and the size checks are host arithmetic and live in nfl_geom_layout.h.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "nfl_geom_layout.h"
+
+#define NM_THREADS 256
+
+#define NM_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define NM_STORE(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+
+static inline unsigned nm_grid(i64 n) { return (unsigned)ng_cdiv(n, NM_THREADS); }
+static inline bool ng_launched() { return hipGetLastError() == hipSuccess; }
+
+__device__ __forceinline__ bool nm_in_range(int32_t a, int32_t b, int32_t c, i64 V) {
+    return a >= 0 && b >= 0 && c >= 0 && a < V && b < V && c < V;
+}
+
+// adds the wave's number of `bad` lanes to *counter: one atomic per wave that has any.  Every lane must call it.
+__device__ __forceinline__ void ng_count_bad(bool bad, i64* counter) {
+    const unsigned long long m = __ballot(bad);
+    if (m && (threadIdx.x & 63) == __ffsll(m) - 1) atomicAdd(reinterpret_cast<unsigned long long*>(counter), (unsigned long long)__popcll(m));
+}
+
+// vertex rows of a mesh (positions, normals, colours) and where their survivors go; a null input row is absent
+struct NgRows {
+    const float* in[3];
+    float* out[3];
+};
+
+template <typename T>
+__device__ __forceinline__ T ng_shfl_up(T v, int off) { return __shfl_up(v, off); }
+
+// Exclusive prefix sum of v over the THREADS threads of the workgroup (wave shuffle-up, the wave sums through LDS, the
+// sums of the waves before added); total = the sum over the workgroup.  T: an integer, or a struct with +, - and an
+// ng_shfl_up of its own.  `wave_sum` is THREADS / 64 entries of LDS; every thread calls.  A kernel that calls again with
+// the same wave_sum puts a barrier between the calls (the waves of this call are still reading it).
+template <typename T, int THREADS>
+__device__ __forceinline__ T ng_block_scan(T v, T* wave_sum, T& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    T incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const T up = ng_shfl_up(incl, off);
+        if (lane >= off) incl = incl + up;
+    }
+    if (lane == 63) wave_sum[wave] = incl;
+    __syncthreads();
+    T before = T(), all = T();
+#pragma unroll
+    for (int w = 0; w < THREADS / 64; ++w) {
+        const T s = wave_sum[w];
+        if (w < wave) before = before + s;
+        all = all + s;
+    }
+    total = all;
+    return before + incl - v;
+}
+
+// nfl_mesh_scan.hip.  out (n) int64 = exclusive prefix sums of in (n) int32, *total = their sum, by tiles of NM_SCAN_TILE
+// elements over up to NM_SCAN_LEVELS levels; `sums`: nm_scan_bytes(n) of scratch
+void nm_scan(const int32_t* in, i64* out, i64 n, i64* sums, i64* total, hipStream_t s);
+// ids[v] = rank[ids[v]] where ids[v] >= 0: from the smallest member of a group (a root, a leader) to the group's number
+void nm_rank(int32_t* ids, i64 n, const i64* rank, hipStream_t s);
+
+// Writes the flagged triangles, re-indexed through `map` (int64 offsets of kept vertices, or int32 cluster ids).  What is
+// read from the scratch, `map` and `tri` is checked like any other index, so a scratch that is not the count call's makes
+// a triangle be skipped, never read or written out of range.
+template <typename Tmap>
+__global__ __launch_bounds__(NM_THREADS) void nfl_mesh_emit_triangles_kernel(const int32_t* flag, const i64* off, const int32_t* tri,
+                                                                             const Tmap* map, i64 V, i64 T, i64 n_out_v, i64 n_out_t,
+                                                                             int32_t* out) {
+    const i64 t = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
+    if (t >= T || !flag[t]) return;                         // a flagged triangle has its three indices in range and kept
+    const i64 o = off[t];
+    if (o < 0 || o >= n_out_t) return;
+    const int32_t a = tri[3 * t], b = tri[3 * t + 1], c = tri[3 * t + 2];
+    if (!nm_in_range(a, b, c, V)) return;
+    const Tmap na = map[a], nb = map[b], nc = map[c];
+    if (na < 0 || nb < 0 || nc < 0 || na >= n_out_v || nb >= n_out_v || nc >= n_out_v) return;
+    out[3 * o] = (int32_t)na;
+    out[3 * o + 1] = (int32_t)nb;
+    out[3 * o + 2] = (int32_t)nc;
+}

@@ -1,0 +1,142 @@
+// nfl_geom_layout.h -- the scratch of the geometry entry points (surface, mesh, occupancy, simplify): every layout is
+// written ONCE, as an ordered list of regions, and one routine walks it.  Without a base the walk gives the size (what
+// the nfl_*_bytes functions return); with the caller's buffer it gives the pointers (what the entry points launch on),
+// so the two cannot disagree.  Plain C++ with no HIP in it: tests/geom_layout_sweep.cpp builds it with g++ under the
+// sanitizers.  DESIGN.md section 22.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/nerf_fl_amd.h"
+
+typedef int64_t i64;
+
+#define NG_MAX_POINTS (1ll << 30)
+#define NG_MAX_DIM 65535                                    // rows and planes of a lattice are grid dimensions
+#define NS_TILE 256                                         // points of an x-row in one slab of the surface kernels
+#define NM_SCAN_THREADS 512
+#define NM_SCAN_ITEMS 4
+#define NM_SCAN_TILE (NM_SCAN_THREADS * NM_SCAN_ITEMS)      // 2048: 2^31 elements -> 2^20 -> 2^9 -> 1 tile sums
+#define NM_SCAN_LEVELS 3
+
+static inline size_t ng_pad(size_t bytes) { return (bytes + 15) / 16 * 16; }
+static inline i64 ng_cdiv(i64 a, i64 b) { return (a + b - 1) / b; }
+static inline size_t ng_max(size_t a, size_t b) { return a > b ? a : b; }
+
+// a lattice the surface and occupancy kernels take
+static inline bool ng_dims_ok(int nx, int ny, int nz) {
+    if (nx < 2 || ny < 2 || nz < 2 || ny > NG_MAX_DIM || nz > NG_MAX_DIM) return false;
+    return (long long)nx * ny <= NG_MAX_POINTS && (long long)nx * ny * nz <= NG_MAX_POINTS;
+}
+// a mesh the mesh and simplify kernels take: int32 indices
+static inline bool nm_sizes_ok(i64 V, i64 T) { return V >= 0 && T >= 0 && V <= INT32_MAX && T <= INT32_MAX / 3; }
+
+// what nm_scan (nfl_mesh_scan.hip) needs for n elements: the tile sums of all levels above the elements, 8 B each
+static inline size_t nm_scan_bytes(i64 n) {
+    size_t entries = 0;
+    for (i64 m = ng_cdiv(n, NM_SCAN_TILE); m > 1; m = ng_cdiv(m, NM_SCAN_TILE)) entries += (size_t)m;
+    return ng_pad(entries * 8);
+}
+// slots of a simplify hash table: the power of two >= 2 n (at least 2); 0 for n == 0
+static inline uint64_t nc_cap(i64 n) {
+    if (n <= 0) return 0;
+    uint64_t c = 2;
+    while (c < 2 * (uint64_t)n) c <<= 1;
+    return c;
+}
+static inline int ns_ntx(int nx) { return (nx + NS_TILE - 1) / NS_TILE; }      // slabs per x-row
+static inline int no_words(int n) { return (n + 31) / 32; }
+
+struct NgRegion { size_t elem, count; };                    // bytes per element, elements
+
+// N regions in the order they lie in the scratch, each padded to 16 B
+template <int N>
+struct NgLayout {
+    NgRegion r[N];
+    char* at[N];            // where region i starts: set by ng_carve
+    template <typename T>
+    T* get(int i) const { return reinterpret_cast<T*>(at[i]); }
+};
+
+// The one walk.  Returns the offset at which the last region ends; with a base also at[i] = the start of region i.
+static inline size_t ng_walk(const NgRegion* r, int n, void* base, char** at) {
+    size_t off = 0;
+    for (int i = 0; i < n; ++i) {
+        if (base) at[i] = static_cast<char*>(base) + off;
+        off += ng_pad(r[i].elem * r[i].count);
+    }
+    return off;
+}
+
+template <int N>
+static inline size_t ng_bytes(const NgLayout<N>& L) { return ng_walk(L.r, N, nullptr, nullptr); }
+
+// The check every entry point makes of the caller's scratch, then the carve.  A buffer that is both misaligned and too
+// small is NFL_EINVAL, except for the surface calls (`size_first`), which have always looked at the size first.
+template <int N>
+static inline int ng_carve(NgLayout<N>& L, void* scratch, size_t scratch_bytes, bool size_first = false) {
+    if (!scratch) return NFL_EINVAL;
+    const bool misaligned = reinterpret_cast<uintptr_t>(scratch) % 8 != 0, small = scratch_bytes < ng_bytes(L);
+    if (small && (size_first || !misaligned)) return NFL_ESMALL;
+    if (misaligned) return NFL_EINVAL;
+    ng_walk(L.r, N, scratch, L.at);
+    return NFL_OK;
+}
+
+// ---- surface: nfl_surface_count / nfl_surface_emit
+enum { NS_REC, NS_SUMS, NS_REGIONS };
+static inline NgLayout<NS_REGIONS> ns_layout(int nx, int ny, int nz) {
+    return {{{4, (size_t)nx * ny * nz},                     // uint32 per point: mask << 16 | vertex offset inside the slab
+             {16, (size_t)ns_ntx(nx) * ny * nz}}, {}};      // (vertices, triangles) int64 per slab, then their prefix sums
+}
+
+// ---- occupancy: nfl_occ_build
+enum { NO_P, NO_X, NO_REGIONS };
+static inline NgLayout<NO_REGIONS> no_layout(int nx, int ny, int nz) {
+    return {{{4, (size_t)nz * ny * no_words(nx)},           // (nz, ny, wpx) point flags; after the y pass (nz, cy, wx)
+             {4, (size_t)nz * ny * no_words(nx - 1)}}, {}}; // (nz, ny, wx)
+}
+
+// ---- mesh: nfl_mesh_label
+enum { NM_L_PARENT, NM_L_FLAG, NM_L_RANK, NM_L_SUMS, NM_L_REGIONS };
+static inline NgLayout<NM_L_REGIONS> nm_label_layout(i64 V) {
+    const size_t v = (size_t)V;
+    return {{{4, v},                                        // int32 parent of the union-find
+             {4, v},                                        // int32 1 = root
+             {8, v},                                        // int64 roots before v
+             {1, nm_scan_bytes(V)}}, {}};                   // tile sums of the scan
+}
+
+// ---- mesh: nfl_mesh_compact_count / nfl_mesh_compact_emit.  ONE region of tile sums, sized for the longer of the two
+// scans: the vertex scan has finished with it (its sums are added back) before the triangle scan, next in the stream, starts.
+enum { NM_C_FLAG_V, NM_C_OFF_V, NM_C_FLAG_T, NM_C_OFF_T, NM_C_SUMS, NM_C_REGIONS };
+static inline NgLayout<NM_C_REGIONS> nm_compact_layout(i64 V, i64 T) {
+    const size_t v = (size_t)V, t = (size_t)T;
+    return {{{4, v},                                        // int32 1 = kept
+             {8, v},                                        // int64 kept vertices before v
+             {4, t},
+             {8, t},
+             {1, ng_max(nm_scan_bytes(V), nm_scan_bytes(T))}}, {}};
+}
+
+// ---- simplify: nfl_mesh_simplify_count / nfl_mesh_simplify_emit
+enum { NC_VKEY, NC_VMIN, NC_VSLOT, NC_FLAG_V, NC_RANK, NC_CANON, NC_TOWNER, NC_TMIN, NC_TSLOT, NC_FLAG_T, NC_OFF_T, NC_SUMS,
+       NC_COUNT, NC_FIXED, NC_QUADRIC, NC_REGIONS };
+static inline NgLayout<NC_REGIONS> nc_layout(i64 V, i64 T) {
+    const size_t v = (size_t)V, t = (size_t)T, cv = (size_t)nc_cap(V), ct = (size_t)nc_cap(T);
+    return {{{8, cv},                                       // uint64 keys, NC_EMPTY_KEY when free
+             {4, cv},                                       // int32 smallest vertex index of the slot
+             {4, v},                                        // uint32 slot of the vertex
+             {4, v},                                        // int32 1 = leader of its cluster
+             {8, v},                                        // int64 leaders before v
+             {12, t},                                       // int32 x 3 new ids, smallest first; [0] = -1: dropped
+             {4, ct},                                       // int32 the triangle that claimed the slot, -1 when free
+             {4, ct},                                       // int32 smallest triangle index of the slot
+             {4, t},                                        // uint32 slot of the triangle, NC_NO_SLOT when dropped
+             {4, t},                                        // int32 1 = survivor
+             {8, t},                                        // int64 survivors before t
+             {1, ng_max(nm_scan_bytes(V), nm_scan_bytes(T))},       // tile sums of the longer of the two scans
+             {4, v},                                        // int32 members of cluster c -- emit; the first V' are used
+             {72, v},                                       // int64 x 9 position, normal, colour sums
+             {72, v}}, {}};                                 // double x 9 A (xx xy xz yy yz zz), b
+}

@@ -14,22 +14,12 @@
 // Clip.  A thread per ray: slab test, entry cell, Amanatides-Woo walk with the plane parameters recomputed from integer
 // plane indices.  The walk of a wave is as long as its longest ray (neighbouring pixels of a frame walk alike); the last
 // fetched word stays in a register while the walk moves along x inside it.
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdint.h>
 
-#include "../../include/nerf_fl_amd.h"
+#include "nfl_geom.h"
 
 #define NO_TILE 256
-#define NO_MAX_POINTS (1ll << 30)
-#define NO_MAX_DIM 65535            // rows and planes are grid dimensions of the flag pass
 #define NO_MAX_DILATE 8
-
-static bool no_dims_ok(int nx, int ny, int nz) {
-    if (nx < 2 || ny < 2 || nz < 2 || ny > NO_MAX_DIM || nz > NO_MAX_DIM) return false;
-    return (long long)nx * ny <= NO_MAX_POINTS && (long long)nx * ny * nz <= NO_MAX_POINTS;
-}
-static inline int no_words(int n) { return (n + 31) / 32; }
 
 // what the build kernels get
 struct NoBuild {
@@ -89,32 +79,30 @@ __global__ __launch_bounds__(NO_TILE) void nfl_occ_or_kernel(const uint32_t* __r
     out[t] = v;
 }
 
-static inline size_t no_align16(size_t n) { return (n + 15) / 16 * 16; }
-static inline size_t no_p_bytes(int nx, int ny, int nz) { return no_align16((size_t)nz * ny * no_words(nx) * 4); }
-
 extern "C" size_t nfl_occ_bytes(int32_t nx, int32_t ny, int32_t nz) {
-    if (!no_dims_ok(nx, ny, nz)) return 0;
+    if (!ng_dims_ok(nx, ny, nz)) return 0;
     return (size_t)(nz - 1) * (ny - 1) * no_words(nx - 1) * 4;
 }
 
 extern "C" size_t nfl_occ_build_bytes(int32_t nx, int32_t ny, int32_t nz, int32_t dilate) {
-    if (!no_dims_ok(nx, ny, nz) || dilate < 0 || dilate > NO_MAX_DILATE) return 0;
-    return no_p_bytes(nx, ny, nz) + no_align16((size_t)nz * ny * no_words(nx - 1) * 4);
+    if (!ng_dims_ok(nx, ny, nz) || dilate < 0 || dilate > NO_MAX_DILATE) return 0;
+    return ng_bytes(no_layout(nx, ny, nz));
 }
 
 extern "C" int nfl_occ_build(const nfl_occ_build_args* a, void* stream) {
     if (!a || !a->d_lattice || !a->d_scratch || !a->d_bits) return NFL_EINVAL;
-    if (!no_dims_ok(a->nx, a->ny, a->nz) || a->dilate < 0 || a->dilate > NO_MAX_DILATE) return NFL_EINVAL;
-    if (reinterpret_cast<uintptr_t>(a->d_lattice) % 4 || reinterpret_cast<uintptr_t>(a->d_bits) % 4 ||
-        reinterpret_cast<uintptr_t>(a->d_scratch) % 8) return NFL_EINVAL;
-    if (a->scratch_bytes < nfl_occ_build_bytes(a->nx, a->ny, a->nz, a->dilate)) return NFL_ESMALL;
+    if (!ng_dims_ok(a->nx, a->ny, a->nz) || a->dilate < 0 || a->dilate > NO_MAX_DILATE) return NFL_EINVAL;
+    if (reinterpret_cast<uintptr_t>(a->d_lattice) % 4 || reinterpret_cast<uintptr_t>(a->d_bits) % 4) return NFL_EINVAL;
+    auto L = no_layout(a->nx, a->ny, a->nz);
+    const int rc = ng_carve(L, a->d_scratch, a->scratch_bytes);
+    if (rc != NFL_OK) return rc;
     NoBuild A;
     A.lattice = a->d_lattice;
     A.nx = a->nx, A.ny = a->ny, A.nz = a->nz, A.d = a->dilate;
     A.wpx = no_words(a->nx), A.wx = no_words(a->nx - 1);
     A.threshold = a->threshold;
-    A.P = static_cast<uint32_t*>(a->d_scratch);
-    A.X = reinterpret_cast<uint32_t*>(static_cast<char*>(a->d_scratch) + no_p_bytes(a->nx, a->ny, a->nz));
+    A.P = L.get<uint32_t>(NO_P);
+    A.X = L.get<uint32_t>(NO_X);
     A.bits = a->d_bits;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int cy = a->ny - 1, cz = a->nz - 1;
@@ -127,7 +115,7 @@ extern "C" int nfl_occ_build(const nfl_occ_build_args* a, void* stream) {
     // z: (nz, cy * wx) -> bits (cz, cy * wx)
     hipLaunchKernelGGL(nfl_occ_or_kernel, blocks((long long)cz * cy * A.wx), dim3(NO_TILE), 0, s,
                        (const uint32_t*)A.P, A.bits, 1ll, a->nz, (long long)cy * A.wx, A.d);
-    return hipGetLastError() == hipSuccess ? NFL_OK : NFL_ELAUNCH;
+    return ng_launched() ? NFL_OK : NFL_ELAUNCH;
 }
 
 // ---- clip ----------------------------------------------------------------------------------------------------------------
@@ -217,7 +205,7 @@ __global__ __launch_bounds__(NO_TILE) void nfl_occ_clip_kernel(const nfl_occ_cli
 
 extern "C" int nfl_occ_clip_rays(const nfl_occ_clip_args* a, void* stream) {
     if (!a || a->n_rays < 0 || a->n_rays > INT32_MAX) return NFL_EINVAL;
-    if (!no_dims_ok(a->nx, a->ny, a->nz)) return NFL_EINVAL;
+    if (!ng_dims_ok(a->nx, a->ny, a->nz)) return NFL_EINVAL;
     for (int k = 0; k < 3; ++k)
         if (!(a->spacing[k] > 0.f) || !(a->spacing[k] < __builtin_huge_valf()) || !(a->lo[k] - a->lo[k] == 0.f)) return NFL_EINVAL;
     if (a->n_rays == 0) return NFL_OK;
@@ -226,5 +214,5 @@ extern "C" int nfl_occ_clip_rays(const nfl_occ_clip_args* a, void* stream) {
         reinterpret_cast<uintptr_t>(a->d_near_far) % 8) return NFL_EINVAL;
     const unsigned blocks = (unsigned)((a->n_rays + NO_TILE - 1) / NO_TILE);
     hipLaunchKernelGGL(nfl_occ_clip_kernel, dim3(blocks), dim3(NO_TILE), 0, static_cast<hipStream_t>(stream), *a);
-    return hipGetLastError() == hipSuccess ? NFL_OK : NFL_ELAUNCH;
+    return ng_launched() ? NFL_OK : NFL_ELAUNCH;
 }

@@ -7,7 +7,7 @@
 //                    probe sequence ends at the key or at the first empty slot; the table is at most half full, so one
 //                    exists, and the loop is bounded by the capacity besides.  Nobody waits for anybody.
 //          leader    cluster[v] = the smallest vertex index of v's slot, flag[v] = (that is v)
-//          scan      exclusive scan of the flags (nm_scan of nfl_mesh.hip): the rank of every leader; the total is V'
+//          scan      exclusive scan of the flags (nm_scan of nfl_mesh_scan.hip): the rank of every leader; the total is V'
 //          rank      cluster[v] = rank[cluster[v]]
 //          map       a thread per triangle: the three new ids; dropped (canon[3 t] = -1) when out of range, on a vertex
 //                    without a cluster or with two equal ids; else the triple rotated so that its smallest id comes first
@@ -23,124 +23,66 @@
 // Table loads and stores that race are agent-scope atomics; everything compared or copied is an integer or a bit pattern,
 // and only the nine quadric sums depend on the order of arrival.  Nothing here allocates, sets or copies memory through
 // the runtime.
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdint.h>
 
-#include "../../include/nerf_fl_amd.h"
-#include "nfl_mesh_scan.h"
+#include "nfl_geom.h"
 
 typedef unsigned long long u64;
 
-#define NS_EMPTY_KEY 0xFFFFFFFFFFFFFFFFull                  // a key has 63 bits
-#define NS_NO_SLOT 0xFFFFFFFFu                              // the triangle table has at most 2^31 slots
-#define NS_HALF 1048576                                     // 2^20 cells either side of the origin
-#define NS_FIX 1073741824.0                                 // 2^30
+#define NC_EMPTY_KEY 0xFFFFFFFFFFFFFFFFull                  // a key has 63 bits
+#define NC_NO_SLOT 0xFFFFFFFFu                              // the triangle table has at most 2^31 slots
+#define NC_HALF 1048576                                     // 2^20 cells either side of the origin
+#define NC_FIX 1073741824.0                                 // 2^30
 
-struct NsGrid {
+struct NcGrid {
     double cell;
     double origin[3];
 };
 
-struct NsScratch {
-    u64* vkey;              // (cap_v) keys, NS_EMPTY_KEY when free
-    int32_t* vmin;          // (cap_v) smallest vertex index of the slot
-    uint32_t* vslot;        // (V) slot of the vertex
-    int32_t* flag_v;        // (V) 1 = leader of its cluster
-    i64* rank;              // (V) leaders before v
-    int32_t* canon;         // (T, 3) new ids, smallest first; canon[3 t] = -1: dropped
-    int32_t* towner;        // (cap_t) the triangle that claimed the slot, -1 when free
-    int32_t* tmin;          // (cap_t) smallest triangle index of the slot
-    uint32_t* tslot;        // (T) slot of the triangle, NS_NO_SLOT when dropped
-    int32_t* flag_t;        // (T) 1 = survivor
-    i64* off_t;             // (T) survivors before t
-    i64* sums;              // tile sums of the longer of the two scans (they run one after the other)
-    int32_t* count;         // (V) members of cluster c              -- emit; the first V' entries are used
-    i64* fixed;             // (V, 9) position, normal, colour sums
-    double* quadric;        // (V, 9) A (xx xy xz yy yz zz), b
-    u64 cap_v, cap_t;
-};
-
-// the power of two >= 2 n (at least 2); 0 for n == 0
-static inline u64 ns_cap(i64 n) {
-    if (n <= 0) return 0;
-    u64 c = 2;
-    while (c < 2 * (u64)n) c <<= 1;
-    return c;
-}
+// the scratch of count and emit: nc_layout (nfl_geom_layout.h)
+typedef NgLayout<NC_REGIONS> NcScratch;
 
 extern "C" size_t nfl_mesh_simplify_bytes(int64_t V, int64_t T) {
     if (!nm_sizes_ok(V, T)) return 0;
-    const size_t cv = (size_t)ns_cap(V), ct = (size_t)ns_cap(T), v = (size_t)V, t = (size_t)T;
-    return nm_pad(cv * 8) + nm_pad(cv * 4) + nm_pad(v * 4) * 2 + nm_pad(v * 8)
-           + nm_pad(t * 12) + nm_pad(ct * 4) * 2 + nm_pad(t * 4) * 2 + nm_pad(t * 8)
-           + nm_max(nm_scan_bytes(V), nm_scan_bytes(T))
-           + nm_pad(v * 4) + nm_pad(v * 72) * 2;
-}
-
-template <typename P>
-static inline void ns_take(char*& p, P*& out, size_t bytes) {
-    out = reinterpret_cast<P*>(p);
-    p += nm_pad(bytes);
+    return ng_bytes(nc_layout(V, T));
 }
 
 // Checks shared by count and emit.  NFL_OK with V == 0 means: nothing to do.
-static int ns_carve(const nfl_mesh_simplify_args* a, NsScratch& S) {
+static int nc_carve(const nfl_mesh_simplify_args* a, NcScratch& S) {
     if (!a || !nm_sizes_ok(a->n_vertices, a->n_triangles)) return NFL_EINVAL;
     if (!(a->cell > 0.0) || !isfinite(a->cell)) return NFL_EINVAL;
     for (int k = 0; k < 3; ++k)
         if (!isfinite(a->origin[k])) return NFL_EINVAL;
     if (a->placement != NFL_SIMPLIFY_MEAN && a->placement != NFL_SIMPLIFY_QUADRIC) return NFL_EINVAL;
-    const size_t V = (size_t)a->n_vertices, T = (size_t)a->n_triangles;
-    if (T && !a->d_triangles) return NFL_EINVAL;
-    if (V == 0) return NFL_OK;
+    S = nc_layout(a->n_vertices, a->n_triangles);
+    if (a->n_triangles && !a->d_triangles) return NFL_EINVAL;
+    if (a->n_vertices == 0) return NFL_OK;
     if (!a->d_vertices || !a->d_cluster) return NFL_EINVAL;
-    if (!a->d_scratch || reinterpret_cast<uintptr_t>(a->d_scratch) % 8) return NFL_EINVAL;
-    if (a->scratch_bytes < nfl_mesh_simplify_bytes(a->n_vertices, a->n_triangles)) return NFL_ESMALL;
-    S.cap_v = ns_cap(a->n_vertices);
-    S.cap_t = ns_cap(a->n_triangles);
-    char* p = static_cast<char*>(a->d_scratch);
-    ns_take(p, S.vkey, (size_t)S.cap_v * 8);
-    ns_take(p, S.vmin, (size_t)S.cap_v * 4);
-    ns_take(p, S.vslot, V * 4);
-    ns_take(p, S.flag_v, V * 4);
-    ns_take(p, S.rank, V * 8);
-    ns_take(p, S.canon, T * 12);
-    ns_take(p, S.towner, (size_t)S.cap_t * 4);
-    ns_take(p, S.tmin, (size_t)S.cap_t * 4);
-    ns_take(p, S.tslot, T * 4);
-    ns_take(p, S.flag_t, T * 4);
-    ns_take(p, S.off_t, T * 8);
-    S.sums = reinterpret_cast<i64*>(p);
-    p += nm_max(nm_scan_bytes(a->n_vertices), nm_scan_bytes(a->n_triangles));
-    ns_take(p, S.count, V * 4);
-    ns_take(p, S.fixed, V * 72);
-    ns_take(p, S.quadric, V * 72);
-    return NFL_OK;
+    return ng_carve(S, a->d_scratch, a->scratch_bytes);
 }
 
 // --------------------------------------------------------------------------------------------------------------- cells
 
 // The cell of vertex v: pd = the position in fp64, ijk = its cell.  False when the vertex belongs to no cluster.
-__device__ __forceinline__ bool ns_cell(const float* pos, i64 v, const NsGrid& G, double pd[3], i64 ijk[3]) {
+__device__ __forceinline__ bool nc_cell(const float* pos, i64 v, const NcGrid& G, double pd[3], i64 ijk[3]) {
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const float f = pos[3 * v + k];
         pd[k] = (double)f;
         const double fi = floor((pd[k] - G.origin[k]) / G.cell);
-        ok = ok && isfinite(f) && fi >= -(double)NS_HALF && fi < (double)NS_HALF;       // a NaN fails both comparisons
+        ok = ok && isfinite(f) && fi >= -(double)NC_HALF && fi < (double)NC_HALF;       // a NaN fails both comparisons
         ijk[k] = ok ? (i64)fi : 0;
     }
     return ok;
 }
 
-__device__ __forceinline__ double ns_centre(const NsGrid& G, int k, i64 i) {
+__device__ __forceinline__ double nc_centre(const NcGrid& G, int k, i64 i) {
     return G.origin[k] + ((double)i + 0.5) * G.cell;
 }
 
 // the finaliser of splitmix64: every input bit reaches every output bit
-__device__ __forceinline__ u64 ns_mix(u64 x) {
+__device__ __forceinline__ u64 nc_mix(u64 x) {
     x ^= x >> 30;
     x *= 0xBF58476D1CE4E5B9ull;
     x ^= x >> 27;
@@ -149,19 +91,13 @@ __device__ __forceinline__ u64 ns_mix(u64 x) {
     return x;
 }
 
-// adds the wave's number of `bad` lanes to *counter: one atomic per wave that has any.  Every lane must call it.
-__device__ __forceinline__ void ns_count_bad(bool bad, i64* counter) {
-    const unsigned long long m = __ballot(bad);
-    if (m && (threadIdx.x & 63) == __ffsll(m) - 1) atomicAdd(reinterpret_cast<u64*>(counter), (u64)__popcll(m));
-}
-
 // --------------------------------------------------------------------------------------------------------------- count
 
 __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_init_kernel(u64* vkey, int32_t* vmin, u64 cap_v, int32_t* towner,
                                                                        int32_t* tmin, u64 cap_t, i64* totals) {
     const u64 i = (u64)blockIdx.x * NM_THREADS + threadIdx.x;
     if (i < cap_v) {
-        vkey[i] = NS_EMPTY_KEY;
+        vkey[i] = NC_EMPTY_KEY;
         vmin[i] = INT32_MAX;
     }
     if (i < cap_t) {
@@ -171,7 +107,7 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_init_kernel(u64* vkey
     if (i == 0) totals[2] = totals[3] = 0;
 }
 
-__global__ __launch_bounds__(NM_THREADS) void nfl_simplify_vertices_kernel(const float* pos, i64 V, const NsGrid G, u64* vkey,
+__global__ __launch_bounds__(NM_THREADS) void nfl_simplify_vertices_kernel(const float* pos, i64 V, const NcGrid G, u64* vkey,
                                                                            int32_t* vmin, u64 cap_v, uint32_t* vslot,
                                                                            int32_t* cluster, i64* n_invalid) {
     const i64 v = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
@@ -181,15 +117,15 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_vertices_kernel(const
         i64 ijk[3];
         bool placed = false;
         u64 s = 0;
-        if (ns_cell(pos, v, G, pd, ijk)) {
-            const u64 key = (u64)(ijk[0] + NS_HALF) | (u64)(ijk[1] + NS_HALF) << 21 | (u64)(ijk[2] + NS_HALF) << 42;
+        if (nc_cell(pos, v, G, pd, ijk)) {
+            const u64 key = (u64)(ijk[0] + NC_HALF) | (u64)(ijk[1] + NC_HALF) << 21 | (u64)(ijk[2] + NC_HALF) << 42;
             const u64 mask = cap_v - 1;
-            s = ns_mix(key) & mask;
+            s = nc_mix(key) & mask;
             for (u64 n = 0; n < cap_v; ++n) {
                 u64 cur = NM_LOAD(vkey + s);
-                if (cur == NS_EMPTY_KEY) {                  // free when read: claim it, or learn who did
-                    cur = atomicCAS(vkey + s, NS_EMPTY_KEY, key);
-                    if (cur == NS_EMPTY_KEY) cur = key;
+                if (cur == NC_EMPTY_KEY) {                  // free when read: claim it, or learn who did
+                    cur = atomicCAS(vkey + s, NC_EMPTY_KEY, key);
+                    if (cur == NC_EMPTY_KEY) cur = key;
                 }
                 if (cur == key) {
                     placed = true;
@@ -207,7 +143,7 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_vertices_kernel(const
             bad = true;
         }
     }
-    ns_count_bad(bad, n_invalid);
+    ng_count_bad(bad, n_invalid);
 }
 
 __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_leader_kernel(int32_t* cluster, i64 V, const int32_t* vmin,
@@ -217,14 +153,6 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_leader_kernel(int32_t
     const int32_t l = cluster[v] < 0 ? -1 : vmin[vslot[v]];
     cluster[v] = l;
     flag[v] = l == v ? 1 : 0;
-}
-
-// cluster holds leaders on entry; a thread touches its own element only
-__global__ __launch_bounds__(NM_THREADS) void nfl_simplify_rank_kernel(int32_t* cluster, i64 V, const i64* rank) {
-    const i64 v = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
-    if (v >= V) return;
-    const int32_t l = cluster[v];
-    if (l >= 0) cluster[v] = (int32_t)rank[l];
 }
 
 __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_map_kernel(const int32_t* tri, const int32_t* cluster, i64 V, i64 T,
@@ -248,7 +176,7 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_map_kernel(const int3
         canon[3 * t + 1] = m1;
         canon[3 * t + 2] = m2;
     }
-    ns_count_bad(bad, n_out_of_range);
+    ng_count_bad(bad, n_out_of_range);
 }
 
 __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_triangles_kernel(const int32_t* canon, i64 T, int32_t* towner,
@@ -260,7 +188,7 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_triangles_kernel(cons
     u64 s = 0;
     if (m0 >= 0) {
         const u64 mask = cap_t - 1;
-        s = ns_mix(ns_mix((u64)(uint32_t)m0 | (u64)(uint32_t)m1 << 32) + (u64)(uint32_t)m2) & mask;
+        s = nc_mix(nc_mix((u64)(uint32_t)m0 | (u64)(uint32_t)m1 << 32) + (u64)(uint32_t)m2) & mask;
         for (u64 n = 0; n < cap_t; ++n) {
             int32_t cur = NM_LOAD(towner + s);
             if (cur == -1) {
@@ -278,7 +206,7 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_triangles_kernel(cons
         }
     }
     if (placed && NM_LOAD(tmin + s) > (int32_t)t) atomicMin(tmin + s, (int32_t)t);
-    tslot[t] = placed ? (uint32_t)s : NS_NO_SLOT;
+    tslot[t] = placed ? (uint32_t)s : NC_NO_SLOT;
 }
 
 __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_survive_kernel(const uint32_t* tslot, const int32_t* tmin, i64 T,
@@ -286,35 +214,40 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_survive_kernel(const 
     const i64 t = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
     if (t >= T) return;
     const uint32_t s = tslot[t];
-    flag[t] = (s != NS_NO_SLOT && tmin[s] == t) ? 1 : 0;
+    flag[t] = (s != NC_NO_SLOT && tmin[s] == t) ? 1 : 0;
 }
 
 extern "C" int nfl_mesh_simplify_count(const nfl_mesh_simplify_args* a, void* stream) {
-    NsScratch S;
-    const int rc = ns_carve(a, S);
+    NcScratch S;
+    const int rc = nc_carve(a, S);
     if (rc != NFL_OK) return rc;
     const i64 V = a->n_vertices, T = a->n_triangles;
     if (V == 0) return NFL_OK;
     if (!a->d_totals) return NFL_EINVAL;
-    const NsGrid G = {a->cell, {a->origin[0], a->origin[1], a->origin[2]}};
+    const NcGrid G = {a->cell, {a->origin[0], a->origin[1], a->origin[2]}};
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const u64 cap = S.cap_v > S.cap_t ? S.cap_v : S.cap_t;
-    hipLaunchKernelGGL(nfl_simplify_init_kernel, dim3(nm_grid((i64)cap)), dim3(NM_THREADS), 0, s, S.vkey, S.vmin, S.cap_v, S.towner,
-                       S.tmin, S.cap_t, a->d_totals);
-    hipLaunchKernelGGL(nfl_simplify_vertices_kernel, dim3(nm_grid(V)), dim3(NM_THREADS), 0, s, a->d_vertices, V, G, S.vkey, S.vmin,
-                       S.cap_v, S.vslot, a->d_cluster, a->d_totals + 3);
-    hipLaunchKernelGGL(nfl_simplify_leader_kernel, dim3(nm_grid(V)), dim3(NM_THREADS), 0, s, a->d_cluster, V, S.vmin, S.vslot, S.flag_v);
-    nm_scan(S.flag_v, S.rank, V, S.sums, a->d_totals, s);
-    hipLaunchKernelGGL(nfl_simplify_rank_kernel, dim3(nm_grid(V)), dim3(NM_THREADS), 0, s, a->d_cluster, V, S.rank);
+    const u64 cap_v = nc_cap(V), cap_t = nc_cap(T), cap = cap_v > cap_t ? cap_v : cap_t;
+    u64* vkey = S.get<u64>(NC_VKEY);
+    int32_t *vmin = S.get<int32_t>(NC_VMIN), *flag_v = S.get<int32_t>(NC_FLAG_V), *canon = S.get<int32_t>(NC_CANON);
+    int32_t *towner = S.get<int32_t>(NC_TOWNER), *tmin = S.get<int32_t>(NC_TMIN), *flag_t = S.get<int32_t>(NC_FLAG_T);
+    uint32_t *vslot = S.get<uint32_t>(NC_VSLOT), *tslot = S.get<uint32_t>(NC_TSLOT);
+    i64 *rank = S.get<i64>(NC_RANK), *off_t = S.get<i64>(NC_OFF_T), *sums = S.get<i64>(NC_SUMS);
+    hipLaunchKernelGGL(nfl_simplify_init_kernel, dim3(nm_grid((i64)cap)), dim3(NM_THREADS), 0, s, vkey, vmin, cap_v, towner,
+                       tmin, cap_t, a->d_totals);
+    hipLaunchKernelGGL(nfl_simplify_vertices_kernel, dim3(nm_grid(V)), dim3(NM_THREADS), 0, s, a->d_vertices, V, G, vkey, vmin,
+                       cap_v, vslot, a->d_cluster, a->d_totals + 3);
+    hipLaunchKernelGGL(nfl_simplify_leader_kernel, dim3(nm_grid(V)), dim3(NM_THREADS), 0, s, a->d_cluster, V, vmin, vslot, flag_v);
+    nm_scan(flag_v, rank, V, sums, a->d_totals, s);
+    nm_rank(a->d_cluster, V, rank, s);
     if (T) {
         hipLaunchKernelGGL(nfl_simplify_map_kernel, dim3(nm_grid(T)), dim3(NM_THREADS), 0, s, a->d_triangles, a->d_cluster, V, T,
-                           S.canon, a->d_totals + 2);
-        hipLaunchKernelGGL(nfl_simplify_triangles_kernel, dim3(nm_grid(T)), dim3(NM_THREADS), 0, s, S.canon, T, S.towner, S.tmin,
-                           S.cap_t, S.tslot);
-        hipLaunchKernelGGL(nfl_simplify_survive_kernel, dim3(nm_grid(T)), dim3(NM_THREADS), 0, s, S.tslot, S.tmin, T, S.flag_t);
+                           canon, a->d_totals + 2);
+        hipLaunchKernelGGL(nfl_simplify_triangles_kernel, dim3(nm_grid(T)), dim3(NM_THREADS), 0, s, canon, T, towner, tmin,
+                           cap_t, tslot);
+        hipLaunchKernelGGL(nfl_simplify_survive_kernel, dim3(nm_grid(T)), dim3(NM_THREADS), 0, s, tslot, tmin, T, flag_t);
     }
-    nm_scan(S.flag_t, S.off_t, T, S.sums, a->d_totals + 1, s);
-    return nm_launched() ? NFL_OK : NFL_ELAUNCH;
+    nm_scan(flag_t, off_t, T, sums, a->d_totals + 1, s);
+    return ng_launched() ? NFL_OK : NFL_ELAUNCH;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- emit
@@ -332,12 +265,12 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_zero_kernel(i64 n_out
     }
 }
 
-__device__ __forceinline__ void ns_add_fixed(i64* dst, double x) {
-    atomicAdd(reinterpret_cast<u64*>(dst), (u64)llrint(x * NS_FIX));                   // two's complement: the signed sum
+__device__ __forceinline__ void nc_add_fixed(i64* dst, double x) {
+    atomicAdd(reinterpret_cast<u64*>(dst), (u64)llrint(x * NC_FIX));                   // two's complement: the signed sum
 }
 
 __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_accumulate_kernel(const float* pos, const float* nrm, const float* col,
-                                                                             const int32_t* cluster, i64 V, i64 n_out, const NsGrid G,
+                                                                             const int32_t* cluster, i64 V, i64 n_out, const NcGrid G,
                                                                              int32_t* count, i64* fixed) {
     const i64 v = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
     if (v >= V) return;
@@ -345,22 +278,22 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_accumulate_kernel(con
     if (c < 0 || c >= n_out) return;
     double pd[3];
     i64 ijk[3];
-    if (!ns_cell(pos, v, G, pd, ijk)) return;
+    if (!nc_cell(pos, v, G, pd, ijk)) return;
     atomicAdd(count + c, 1);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        ns_add_fixed(fixed + 9 * (i64)c + k, (pd[k] - ns_centre(G, k, ijk[k])) / G.cell);
+        nc_add_fixed(fixed + 9 * (i64)c + k, (pd[k] - nc_centre(G, k, ijk[k])) / G.cell);
         const float n = nrm[3 * v + k];
-        if (isfinite(n)) ns_add_fixed(fixed + 9 * (i64)c + 3 + k, (double)n);
+        if (isfinite(n)) nc_add_fixed(fixed + 9 * (i64)c + 3 + k, (double)n);
         if (col) {
             const float q = col[3 * v + k];
-            if (isfinite(q)) ns_add_fixed(fixed + 9 * (i64)c + 6 + k, (double)q);
+            if (isfinite(q)) nc_add_fixed(fixed + 9 * (i64)c + 6 + k, (double)q);
         }
     }
 }
 
 __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_quadric_kernel(const float* pos, const int32_t* tri, const int32_t* cluster,
-                                                                          i64 V, i64 T, i64 n_out, const NsGrid G, double* quadric) {
+                                                                          i64 V, i64 T, i64 n_out, const NcGrid G, double* quadric) {
     const i64 t = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
     if (t >= T) return;
     const int32_t idx[3] = {tri[3 * t], tri[3 * t + 1], tri[3 * t + 2]};
@@ -371,7 +304,7 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_quadric_kernel(const 
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         cl[j] = cluster[idx[j]];
-        if (cl[j] < 0 || cl[j] >= n_out || !ns_cell(pos, idx[j], G, p[j], ijk[j])) return;
+        if (cl[j] < 0 || cl[j] >= n_out || !nc_cell(pos, idx[j], G, p[j], ijk[j])) return;
     }
     const double e1[3] = {p[1][0] - p[0][0], p[1][1] - p[0][1], p[1][2] - p[0][2]};
     const double e2[3] = {p[2][0] - p[0][0], p[2][1] - p[0][1], p[2][2] - p[0][2]};
@@ -385,7 +318,7 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_quadric_kernel(const 
     for (int j = 0; j < 3; ++j) {
         double u0[3];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) u0[k] = (p[0][k] - ns_centre(G, k, ijk[j][k])) / G.cell;
+        for (int k = 0; k < 3; ++k) u0[k] = (p[0][k] - nc_centre(G, k, ijk[j][k])) / G.cell;
         const double d = -((n[0] * u0[0] + n[1] * u0[1]) + n[2] * u0[2]);
         double* q = quadric + 9 * (i64)cl[j];
         atomicAdd(q + 0, w * n[0] * n[0]);
@@ -401,7 +334,7 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_quadric_kernel(const 
 }
 
 // (A + mu I) u = mu ub - b by cofactors; false when there is nothing to solve or the result is not finite
-__device__ __forceinline__ bool ns_solve(const double* q, const double ub[3], double u[3]) {
+__device__ __forceinline__ bool nc_solve(const double* q, const double ub[3], double u[3]) {
     const double tr = (q[0] + q[3]) + q[5];
     if (tr == 0.0) return false;
     const double mu = NFL_SIMPLIFY_LAMBDA * tr;
@@ -416,18 +349,9 @@ __device__ __forceinline__ bool ns_solve(const double* q, const double ub[3], do
     return isfinite(u[0]) && isfinite(u[1]) && isfinite(u[2]);
 }
 
-struct NsRows {
-    const float* pos;
-    const float* nrm;
-    const float* col;
-    float* out_pos;
-    float* out_nrm;
-    float* out_col;
-};
-
 __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_finish_kernel(const int32_t* flag, const int32_t* cluster, i64 V, i64 n_out,
-                                                                         const NsGrid G, const int32_t* count, const i64* fixed,
-                                                                         const double* quadric, const NsRows R) {
+                                                                         const NcGrid G, const int32_t* count, const i64* fixed,
+                                                                         const double* quadric, const NgRows R) {
     const i64 v = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
     if (v >= V || !flag[v]) return;                         // the leader of a cluster writes the cluster's rows
     const i64 c = cluster[v];
@@ -436,22 +360,22 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_finish_kernel(const i
     if (n <= 1) {                                           // alone: its own bits
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            R.out_pos[3 * c + k] = R.pos[3 * v + k];
-            R.out_nrm[3 * c + k] = R.nrm[3 * v + k];
-            if (R.col) R.out_col[3 * c + k] = R.col[3 * v + k];
+            R.out[0][3 * c + k] = R.in[0][3 * v + k];
+            R.out[1][3 * c + k] = R.in[1][3 * v + k];
+            if (R.in[2]) R.out[2][3 * c + k] = R.in[2][3 * v + k];
         }
         return;
     }
     double pd[3];
     i64 ijk[3];
-    if (!ns_cell(R.pos, v, G, pd, ijk)) return;
+    if (!nc_cell(R.in[0], v, G, pd, ijk)) return;
     const i64* f = fixed + 9 * c;
-    const double scale = (double)n * NS_FIX;
+    const double scale = (double)n * NC_FIX;
     double ub[3], u[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) u[k] = ub[k] = (double)f[k] / scale;
     double uq[3];
-    if (quadric && ns_solve(quadric + 9 * c, ub, uq)) {
+    if (quadric && nc_solve(quadric + 9 * c, ub, uq)) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) u[k] = fmin(fmax(uq[k], -0.5), 0.5);
     }
@@ -459,33 +383,15 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_finish_kernel(const i
     const double len = sqrt((s[0] * s[0] + s[1] * s[1]) + s[2] * s[2]);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        R.out_pos[3 * c + k] = (float)(ns_centre(G, k, ijk[k]) + G.cell * u[k]);
-        R.out_nrm[3 * c + k] = len > 0.0 ? (float)(s[k] / len) : 0.0f;
-        if (R.col) R.out_col[3 * c + k] = (float)((double)f[6 + k] / scale);
+        R.out[0][3 * c + k] = (float)(nc_centre(G, k, ijk[k]) + G.cell * u[k]);
+        R.out[1][3 * c + k] = len > 0.0 ? (float)(s[k] / len) : 0.0f;
+        if (R.in[2]) R.out[2][3 * c + k] = (float)((double)f[6 + k] / scale);
     }
 }
 
-// What is read from the scratch, d_cluster and d_triangles is checked like any other index, so a scratch that is not the
-// count call's makes a row be skipped, never read or written out of range.
-__global__ __launch_bounds__(NM_THREADS) void nfl_simplify_emit_triangles_kernel(const int32_t* flag, const i64* off, const int32_t* tri,
-                                                                                 const int32_t* cluster, i64 V, i64 T, i64 n_out_v,
-                                                                                 i64 n_out_t, int32_t* out) {
-    const i64 t = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
-    if (t >= T || !flag[t]) return;
-    const i64 o = off[t];
-    if (o < 0 || o >= n_out_t) return;
-    const int32_t a = tri[3 * t], b = tri[3 * t + 1], c = tri[3 * t + 2];
-    if (!nm_in_range(a, b, c, V)) return;
-    const int32_t na = cluster[a], nb = cluster[b], nc = cluster[c];
-    if (na < 0 || nb < 0 || nc < 0 || na >= n_out_v || nb >= n_out_v || nc >= n_out_v) return;
-    out[3 * o] = na;
-    out[3 * o + 1] = nb;
-    out[3 * o + 2] = nc;
-}
-
 extern "C" int nfl_mesh_simplify_emit(const nfl_mesh_simplify_args* a, void* stream) {
-    NsScratch S;
-    const int rc = ns_carve(a, S);
+    NcScratch S;
+    const int rc = nc_carve(a, S);
     if (rc != NFL_OK) return rc;
     const i64 V = a->n_vertices, T = a->n_triangles, Vo = a->n_out_vertices, To = a->n_out_triangles;
     if (V == 0) return NFL_OK;
@@ -493,21 +399,24 @@ extern "C" int nfl_mesh_simplify_emit(const nfl_mesh_simplify_args* a, void* str
     if (Vo == 0 && To == 0) return NFL_OK;
     if (Vo && (!a->d_normals || !a->d_out_vertices || !a->d_out_normals || (a->d_colors && !a->d_out_colors))) return NFL_EINVAL;
     if (To && !a->d_out_triangles) return NFL_EINVAL;
-    const NsGrid G = {a->cell, {a->origin[0], a->origin[1], a->origin[2]}};
+    const NcGrid G = {a->cell, {a->origin[0], a->origin[1], a->origin[2]}};
     const int with_quadric = a->placement == NFL_SIMPLIFY_QUADRIC;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (Vo) {
-        const NsRows R = {a->d_vertices, a->d_normals, a->d_colors, a->d_out_vertices, a->d_out_normals, a->d_out_colors};
-        hipLaunchKernelGGL(nfl_simplify_zero_kernel, dim3(nm_grid(Vo)), dim3(NM_THREADS), 0, s, Vo, S.count, S.fixed, S.quadric, with_quadric);
+        int32_t* count = S.get<int32_t>(NC_COUNT);
+        i64* fixed = S.get<i64>(NC_FIXED);
+        double* quadric = S.get<double>(NC_QUADRIC);
+        const NgRows R = {{a->d_vertices, a->d_normals, a->d_colors}, {a->d_out_vertices, a->d_out_normals, a->d_out_colors}};
+        hipLaunchKernelGGL(nfl_simplify_zero_kernel, dim3(nm_grid(Vo)), dim3(NM_THREADS), 0, s, Vo, count, fixed, quadric, with_quadric);
         hipLaunchKernelGGL(nfl_simplify_accumulate_kernel, dim3(nm_grid(V)), dim3(NM_THREADS), 0, s, a->d_vertices, a->d_normals,
-                           a->d_colors, a->d_cluster, V, Vo, G, S.count, S.fixed);
+                           a->d_colors, a->d_cluster, V, Vo, G, count, fixed);
         if (with_quadric && T)
             hipLaunchKernelGGL(nfl_simplify_quadric_kernel, dim3(nm_grid(T)), dim3(NM_THREADS), 0, s, a->d_vertices, a->d_triangles,
-                               a->d_cluster, V, T, Vo, G, S.quadric);
-        hipLaunchKernelGGL(nfl_simplify_finish_kernel, dim3(nm_grid(V)), dim3(NM_THREADS), 0, s, S.flag_v, a->d_cluster, V, Vo, G, S.count,
-                           S.fixed, with_quadric ? S.quadric : nullptr, R);
+                               a->d_cluster, V, T, Vo, G, quadric);
+        hipLaunchKernelGGL(nfl_simplify_finish_kernel, dim3(nm_grid(V)), dim3(NM_THREADS), 0, s, S.get<int32_t>(NC_FLAG_V), a->d_cluster, V, Vo, G, count,
+                           fixed, with_quadric ? quadric : nullptr, R);
     }
-    if (To) hipLaunchKernelGGL(nfl_simplify_emit_triangles_kernel, dim3(nm_grid(T)), dim3(NM_THREADS), 0, s, S.flag_t, S.off_t,
+    if (To) hipLaunchKernelGGL(nfl_mesh_emit_triangles_kernel<int32_t>, dim3(nm_grid(T)), dim3(NM_THREADS), 0, s, S.get<int32_t>(NC_FLAG_T), S.get<i64>(NC_OFF_T),
                                a->d_triangles, a->d_cluster, V, T, Vo, To, a->d_out_triangles);
-    return nm_launched() ? NFL_OK : NFL_ELAUNCH;
+    return ng_launched() ? NFL_OK : NFL_ELAUNCH;
 }

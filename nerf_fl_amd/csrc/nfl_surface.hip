@@ -20,17 +20,12 @@
 //           for the thread's own edges and for the edges its tetrahedra borrow from the seven neighbouring points alike.
 // Vertices come out ordered by (owner point, edge type), triangles by (cell, tetrahedron, place in the table).  Every
 // result is written by a plain vector store; nothing is zeroed (every scratch element that is read was written first).
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdint.h>
 
-#include "../../include/nerf_fl_amd.h"
+#include "nfl_geom.h"
 
-#define NS_TILE 256
 #define NS_SCAN_THREADS 1024
 #define NS_SCAN_ITEMS 4
-#define NS_MAX_POINTS (1ll << 30)
-#define NS_MAX_DIM 65535            // rows and planes are grid dimensions
 
 // corners (0, a, a | b, 7) of the six tetrahedra
 __constant__ uint8_t NS_TET[6][4] = {{0, 1, 3, 7}, {0, 1, 5, 7}, {0, 2, 3, 7}, {0, 2, 6, 7}, {0, 4, 5, 7}, {0, 4, 6, 7}};
@@ -50,7 +45,13 @@ __constant__ uint8_t NS_TRI[6][16][6] = {
     {{ 0, 0, 0, 0, 0, 0}, { 4, 7, 6, 0, 0, 0}, { 4,34,35, 0, 0, 0}, { 6,35, 7, 6,34,35}, { 6,49,34, 0, 0, 0}, { 4, 7,49, 4,49,34}, { 4,49,35, 4, 6,49}, { 7,49,35, 0, 0, 0},
      { 7,35,49, 0, 0, 0}, { 4,49, 6, 4,35,49}, { 4,34,49, 4,49, 7}, { 6,34,49, 0, 0, 0}, { 6,35,34, 6, 7,35}, { 4,35,34, 0, 0, 0}, { 4, 6, 7, 0, 0, 0}, { 0, 0, 0, 0, 0, 0}}};
 
-// what the kernels get: the caller's arguments and the scratch, carved up
+// (vertices, triangles) of a slab, as they lie in NsArgs::sums: what the scan kernel sums
+struct NsPair { long long v, t; };
+__device__ __forceinline__ NsPair operator+(NsPair a, NsPair b) { return {a.v + b.v, a.t + b.t}; }
+__device__ __forceinline__ NsPair operator-(NsPair a, NsPair b) { return {a.v - b.v, a.t - b.t}; }
+__device__ __forceinline__ NsPair ng_shfl_up(NsPair p, int off) { return {__shfl_up(p.v, off), __shfl_up(p.t, off)}; }
+
+// what the kernels get: the caller's arguments and the scratch (ns_layout of nfl_geom_layout.h), carved up
 struct NsArgs {
     nfl_surface_args a;
     uint32_t* rec;          // (points) mask << 16 | vertex offset inside the slab
@@ -58,13 +59,6 @@ struct NsArgs {
     int ntx;                // slabs per x-row
     long long n_slabs;
 };
-
-static inline size_t ns_rec_bytes(long long points) { return ((size_t)points * 4 + 15) / 16 * 16; }
-static inline int ns_ntx(int nx) { return (nx + NS_TILE - 1) / NS_TILE; }
-static bool ns_dims_ok(int nx, int ny, int nz) {
-    if (nx < 2 || ny < 2 || nz < 2 || ny > NS_MAX_DIM || nz > NS_MAX_DIM) return false;
-    return (long long)nx * ny <= NS_MAX_POINTS && (long long)nx * ny * nz <= NS_MAX_POINTS;
-}
 
 // the 2 x 2 rows (y + dy, z + dz), row r = dy + 2 dz, of NS_TILE + 1 values from x0 on; 0 where the lattice ends
 __device__ __forceinline__ void ns_stage(const NsArgs& A, int x0, int y, int z, float (*val)[NS_TILE + 1]) {
@@ -101,28 +95,6 @@ __device__ __forceinline__ void ns_classify(const NsArgs& A, int x, int y, int z
     }
 }
 
-// exclusive scan of v over the NS_TILE threads (4 waves); total = sum over the workgroup
-__device__ __forceinline__ uint32_t ns_block_scan(uint32_t v, uint32_t* wave_sum, uint32_t& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t n = __shfl_up(incl, off);
-        if (lane >= off) incl += n;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < NS_TILE / 64; ++w) {
-        const uint32_t s = wave_sum[w];
-        if (w < wave) before += s;
-        total += s;
-    }
-    return before + incl - v;
-}
-
 __global__ __launch_bounds__(NS_TILE) void nfl_surface_count_kernel(const NsArgs A) {
     __shared__ float val[4][NS_TILE + 1];
     __shared__ uint32_t wave_sum[NS_TILE / 64];
@@ -132,7 +104,7 @@ __global__ __launch_bounds__(NS_TILE) void nfl_surface_count_kernel(const NsArgs
     uint32_t corners, edges, n_tri, total;
     ns_classify(A, x, y, z, val, corners, edges, n_tri);
     // vertices in the low half, triangles in the high half: at most 7 * 256 and 12 * 256 per slab
-    const uint32_t excl = ns_block_scan((n_tri << 16) | __popc(edges), wave_sum, total);
+    const uint32_t excl = ng_block_scan<uint32_t, NS_TILE>((n_tri << 16) | __popc(edges), wave_sum, total);
     if (x < A.a.nx) A.rec[((size_t)z * A.a.ny + y) * A.a.nx + x] = (edges << 16) | (excl & 0xFFFFu);
     if (threadIdx.x == 0) {
         long long* s = A.sums + 2 * (((size_t)z * A.a.ny + y) * A.ntx + blockIdx.x);
@@ -143,48 +115,31 @@ __global__ __launch_bounds__(NS_TILE) void nfl_surface_count_kernel(const NsArgs
 
 // one workgroup: sums (n, 2) -> exclusive prefix sums in place, the two totals to d_totals
 __global__ __launch_bounds__(NS_SCAN_THREADS) void nfl_surface_scan_kernel(const NsArgs A) {
-    __shared__ long long wave_sum[2][NS_SCAN_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    long long carry[2] = {0, 0};
+    __shared__ NsPair wave_sum[NS_SCAN_THREADS / 64];
+    NsPair* sums = reinterpret_cast<NsPair*>(A.sums);
+    const int tid = threadIdx.x;
+    NsPair carry = {0, 0};
     for (long long base = 0; base < A.n_slabs; base += NS_SCAN_THREADS * NS_SCAN_ITEMS) {
         const long long i0 = base + (long long)tid * NS_SCAN_ITEMS;
-        long long v[NS_SCAN_ITEMS][2], incl[2] = {0, 0};
+        NsPair v[NS_SCAN_ITEMS], mine = {0, 0}, all;
 #pragma unroll
-        for (int j = 0; j < NS_SCAN_ITEMS; ++j)
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                v[j][k] = i0 + j < A.n_slabs ? A.sums[2 * (i0 + j) + k] : 0;
-                incl[k] += v[j][k];
-            }
-        const long long mine[2] = {incl[0], incl[1]};
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1)
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const long long n = __shfl_up(incl[k], off);
-                if (lane >= off) incl[k] += n;
-            }
-        __syncthreads();                                    // the previous round's wave_sum has been read
-        if (lane == 63) { wave_sum[0][wave] = incl[0]; wave_sum[1][wave] = incl[1]; }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            long long before = carry[k], all = 0;
-            for (int w = 0; w < NS_SCAN_THREADS / 64; ++w) {
-                const long long s = wave_sum[k][w];
-                if (w < wave) before += s;
-                all += s;
-            }
-            long long run = before + incl[k] - mine[k];
-#pragma unroll
-            for (int j = 0; j < NS_SCAN_ITEMS; ++j) {
-                if (i0 + j < A.n_slabs) A.sums[2 * (i0 + j) + k] = run;
-                run += v[j][k];
-            }
-            carry[k] += all;
+        for (int j = 0; j < NS_SCAN_ITEMS; ++j) {
+            v[j] = i0 + j < A.n_slabs ? sums[i0 + j] : NsPair{0, 0};
+            mine = mine + v[j];
         }
+        __syncthreads();                                    // the previous round's wave_sum has been read
+        NsPair run = carry + ng_block_scan<NsPair, NS_SCAN_THREADS>(mine, wave_sum, all);
+#pragma unroll
+        for (int j = 0; j < NS_SCAN_ITEMS; ++j) {
+            if (i0 + j < A.n_slabs) sums[i0 + j] = run;
+            run = run + v[j];
+        }
+        carry = carry + all;
     }
-    if (tid < 2) A.a.d_totals[tid] = carry[tid];
+    if (tid == 0) {
+        A.a.d_totals[0] = carry.v;
+        A.a.d_totals[1] = carry.t;
+    }
 }
 
 // -grad of the lattice at point (x, y, z): central differences, one-sided at the border
@@ -220,7 +175,7 @@ __global__ __launch_bounds__(NS_TILE) void nfl_surface_emit_kernel(const NsArgs 
     __syncthreads();
     uint32_t corners, edges, n_tri, total;
     ns_classify(A, x, y, z, val, corners, edges, n_tri);
-    const uint32_t tri_excl = ns_block_scan(n_tri, wave_sum, total);
+    const uint32_t tri_excl = ng_block_scan<uint32_t, NS_TILE>(n_tri, wave_sum, total);
 
     // ---- the vertices of this point's crossing edges
     if (edges) {
@@ -278,21 +233,21 @@ __global__ __launch_bounds__(NS_TILE) void nfl_surface_emit_kernel(const NsArgs 
 
 static int ns_carve(const nfl_surface_args* a, NsArgs& A) {
     if (!a || !a->d_lattice || !a->d_scratch) return NFL_EINVAL;
-    if (!ns_dims_ok(a->nx, a->ny, a->nz)) return NFL_EINVAL;
-    if (a->scratch_bytes < nfl_surface_bytes(a->nx, a->ny, a->nz)) return NFL_ESMALL;
-    if (reinterpret_cast<uintptr_t>(a->d_scratch) % 8) return NFL_EINVAL;
-    const long long points = (long long)a->nx * a->ny * a->nz;
+    if (!ng_dims_ok(a->nx, a->ny, a->nz)) return NFL_EINVAL;
+    auto L = ns_layout(a->nx, a->ny, a->nz);
+    const int rc = ng_carve(L, a->d_scratch, a->scratch_bytes, true);
+    if (rc != NFL_OK) return rc;
     A.a = *a;
     A.ntx = ns_ntx(a->nx);
     A.n_slabs = (long long)A.ntx * a->ny * a->nz;
-    A.rec = static_cast<uint32_t*>(a->d_scratch);
-    A.sums = reinterpret_cast<long long*>(static_cast<char*>(a->d_scratch) + ns_rec_bytes(points));
+    A.rec = L.get<uint32_t>(NS_REC);
+    A.sums = L.get<long long>(NS_SUMS);
     return NFL_OK;
 }
 
 extern "C" size_t nfl_surface_bytes(int32_t nx, int32_t ny, int32_t nz) {
-    if (!ns_dims_ok(nx, ny, nz)) return 0;
-    return ns_rec_bytes((long long)nx * ny * nz) + (size_t)ns_ntx(nx) * ny * nz * 16;
+    if (!ng_dims_ok(nx, ny, nz)) return 0;
+    return ng_bytes(ns_layout(nx, ny, nz));
 }
 
 extern "C" int nfl_surface_count(const nfl_surface_args* args, void* stream) {
@@ -303,7 +258,7 @@ extern "C" int nfl_surface_count(const nfl_surface_args* args, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(nfl_surface_count_kernel, dim3(A.ntx, args->ny, args->nz), dim3(NS_TILE), 0, s, A);
     hipLaunchKernelGGL(nfl_surface_scan_kernel, dim3(1), dim3(NS_SCAN_THREADS), 0, s, A);
-    return hipGetLastError() == hipSuccess ? NFL_OK : NFL_ELAUNCH;
+    return ng_launched() ? NFL_OK : NFL_ELAUNCH;
 }
 
 extern "C" int nfl_surface_emit(const nfl_surface_args* args, void* stream) {
@@ -316,5 +271,5 @@ extern "C" int nfl_surface_emit(const nfl_surface_args* args, void* stream) {
     if (!args->d_vertices || !args->d_normals || (args->n_triangles && !args->d_triangles)) return NFL_EINVAL;
     hipLaunchKernelGGL(nfl_surface_emit_kernel, dim3(A.ntx, args->ny, args->nz), dim3(NS_TILE), 0,
                        static_cast<hipStream_t>(stream), A);
-    return hipGetLastError() == hipSuccess ? NFL_OK : NFL_ELAUNCH;
+    return ng_launched() ? NFL_OK : NFL_ELAUNCH;
 }

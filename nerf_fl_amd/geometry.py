@@ -51,6 +51,50 @@ def _box(lo, hi, res):
     return lo, [(h - l) / (n - 1) for l, h, n in zip(lo, hi, res)], res
 
 
+def _ptr(t):
+    return C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
+
+
+def _row(v, n, what, dev):
+    v = torch.as_tensor(v, dtype=torch.float32, device=dev).detach().reshape(1, -1)
+    if v.shape[1] != n:
+        raise ValueError(f"{what}: expected {n} numbers, got {v.shape[1]}")
+    return v
+
+
+def _scratch(nbytes, dev):
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+
+
+def _on_device(*tensors):
+    for t in tensors:
+        if not torch.is_tensor(t) or t.device.type != "cuda":
+            raise RuntimeError("nerf_fl_amd.geometry needs tensors on a ROCm device (this build has no CPU path)")
+
+
+def _is(t, dtype, dim, tail=(), device=None, contiguous=True):
+    """Whether `t` has this dtype and `dim` axes, the last ones `tail` long, is contiguous and (when given) on `device`."""
+    return (t.dtype == dtype and t.dim() == dim and t.shape[dim - len(tail):] == tail
+            and (t.is_contiguous() or not contiguous) and (device is None or t.device == device))
+
+
+def _lattice(lattice, lo, hi):
+    """(nx, ny, nz, lo, spacing) of a lattice tensor over the box [lo, hi], checked."""
+    _on_device(lattice)
+    if not _is(lattice, torch.float32, 3):
+        raise ValueError("lattice: expected a contiguous fp32 (nz, ny, nx) tensor")
+    nz, ny, nx = lattice.shape
+    lo, sp, _ = _box(lo, hi, (nx, ny, nz))
+    return nx, ny, nz, lo, sp
+
+
+def _empty_mesh(V, T, colors, dev):
+    """A mesh dict of V vertices and T triangles to be written by a kernel, with a colour row when `colors`."""
+    rows = lambda: torch.empty(V, 3, dtype=torch.float32, device=dev)
+    mesh = {"vertices": rows(), "normals": rows(), "triangles": torch.empty(T, 3, dtype=torch.int32, device=dev)}
+    return dict(mesh, colors=rows()) if colors else mesh
+
+
 def _axis(lo, spacing, n, device):
     """fp32 positions lo + i * spacing of one axis: the product and the sum rounded separately, as the kernels do."""
     return torch.arange(n, dtype=torch.float32, device=device) * np.float32(spacing) + np.float32(lo)
@@ -145,17 +189,6 @@ def density_lattice(model, embeddings, lo, hi, res, chunk=1 << 20, a_embedded=No
     return (sigma, rgb) if color else sigma
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
-
-
-def _row(v, n, what, dev):
-    v = torch.as_tensor(v, dtype=torch.float32, device=dev).detach().reshape(1, -1)
-    if v.shape[1] != n:
-        raise ValueError(f"{what}: expected {n} numbers, got {v.shape[1]}")
-    return v
-
-
 def extract_surface(lattice, iso, lo, hi):
     """The surface {value == iso} of `lattice` ((nz, ny, nx) fp32, contiguous, on the device) over the box [lo, hi] as a
     dict: vertices (V, 3) fp32 world coordinates, normals (V, 3) fp32 (unit, pointing from inside -- value >= iso -- to
@@ -164,23 +197,17 @@ def extract_surface(lattice, iso, lo, hi):
     type, triangles by cell and tetrahedron) and two calls give the same bits.
 
     ONE host synchronisation: the two totals are read from the device to size the outputs."""
-    if not torch.is_tensor(lattice) or lattice.device.type != "cuda":
-        raise RuntimeError("nerf_fl_amd.geometry needs tensors on a ROCm device (this build has no CPU path)")
-    if lattice.dtype != torch.float32 or lattice.dim() != 3 or not lattice.is_contiguous():
-        raise ValueError("lattice: expected a contiguous fp32 (nz, ny, nx) tensor")
-    nz, ny, nx = lattice.shape
-    lo, sp, _ = _box(lo, hi, (nx, ny, nz))
+    nx, ny, nz, lo, sp = _lattice(lattice, lo, hi)
     dev = lattice.device
     lib = _lib.lib()
     nbytes = lib.nfl_surface_bytes(nx, ny, nz)
     if nbytes == 0:
         raise ValueError(f"lattice {nx} x {ny} x {nz}: at most 2^30 points, and 65535 rows and planes")
-    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    scratch = _scratch(nbytes, dev)
     totals = torch.empty(2, dtype=torch.int64, device=dev)
     a = _lib.SurfaceArgs()
     a.d_lattice, a.nx, a.ny, a.nz, a.iso = _ptr(lattice), nx, ny, nz, float(iso)
-    for k in range(3):
-        a.lo[k], a.spacing[k] = lo[k], sp[k]
+    a.lo[:], a.spacing[:] = lo, sp
     a.d_scratch, a.scratch_bytes, a.d_totals = _ptr(scratch), scratch.numel() * 8, _ptr(totals)
     with torch.cuda.device(dev):
         stream = rendering._stream()
@@ -188,9 +215,7 @@ def extract_surface(lattice, iso, lo, hi):
         V, T = (int(v) for v in totals.tolist())                       # the host synchronisation
         if V > 2 ** 31 - 1 or 3 * T > 2 ** 31 - 1:
             raise ValueError(f"the surface has {V} vertices and {T} triangles: more than int32 indices address")
-        mesh = {"vertices": torch.empty(V, 3, dtype=torch.float32, device=dev),
-                "normals": torch.empty(V, 3, dtype=torch.float32, device=dev),
-                "triangles": torch.empty(T, 3, dtype=torch.int32, device=dev)}
+        mesh = _empty_mesh(V, T, False, dev)
         a.n_vertices, a.n_triangles = V, T
         a.d_vertices, a.d_normals, a.d_triangles = _ptr(mesh["vertices"]), _ptr(mesh["normals"]), _ptr(mesh["triangles"])
         _lib.check(lib.nfl_surface_emit(C.byref(a), stream), "nfl_surface_emit")
@@ -202,9 +227,8 @@ def surface_colors(model, embeddings, vertices, normals, a_embedded=None):
     surface head-on), through nfl_posenc and the fused field kernel; `a_embedded` (n_a,) for a model that encodes
     appearance.  The transient head is not evaluated."""
     for t, what in ((vertices, "vertices"), (normals, "normals")):
-        if not torch.is_tensor(t) or t.device.type != "cuda":
-            raise RuntimeError("nerf_fl_amd.geometry needs tensors on a ROCm device (this build has no CPU path)")
-        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous():
+        _on_device(t)
+        if not _is(t, torch.float32, 2, (3,)):
             raise ValueError(f"{what}: expected a contiguous fp32 (V, 3) tensor")
     if vertices.shape != normals.shape or vertices.device != normals.device:
         raise ValueError("vertices and normals differ in shape or device")
@@ -261,13 +285,11 @@ def _mesh_tensors(mesh):
     except (TypeError, KeyError):
         raise ValueError("mesh: a dict with vertices (V, 3), normals (V, 3) and triangles (T, 3)") from None
     col = mesh.get("colors")
-    for t in (ver, nrm, tri) + (() if col is None else (col,)):
-        if not torch.is_tensor(t) or t.device.type != "cuda":
-            raise RuntimeError("nerf_fl_amd.geometry needs tensors on a ROCm device (this build has no CPU path)")
+    _on_device(ver, nrm, tri, *(() if col is None else (col,)))
     for t, what in ((ver, "vertices"), (nrm, "normals"), (col, "colors")):
-        if t is not None and (t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous()):
+        if t is not None and not _is(t, torch.float32, 2, (3,)):
             raise ValueError(f"mesh: {what}: expected a contiguous fp32 (V, 3) tensor")
-    if tri.dtype != torch.int32 or tri.dim() != 2 or tri.shape[1] != 3 or not tri.is_contiguous():
+    if not _is(tri, torch.int32, 2, (3,)):
         raise ValueError("mesh: triangles: expected a contiguous int32 (T, 3) tensor")
     if nrm.shape != ver.shape or (col is not None and col.shape != ver.shape):
         raise ValueError("mesh: vertices, normals and colors differ in shape")
@@ -276,10 +298,6 @@ def _mesh_tensors(mesh):
     if ver.shape[0] > 2 ** 31 - 1 or 3 * tri.shape[0] > 2 ** 31 - 1:
         raise ValueError(f"mesh: {ver.shape[0]} vertices and {tri.shape[0]} triangles: more than int32 indices address")
     return ver, nrm, col, tri
-
-
-def _scratch(nbytes, dev):
-    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
 
 
 def mesh_components(mesh):
@@ -333,11 +351,10 @@ def filter_mesh(mesh, keep, components=None):
         components = mesh_components(mesh)
     component, n_comp = components["component"], int(components["n_components"])
     dev, V, T = ver.device, ver.shape[0], tri.shape[0]
-    if not torch.is_tensor(keep) or keep.device.type != "cuda":
-        raise RuntimeError("nerf_fl_amd.geometry needs tensors on a ROCm device (this build has no CPU path)")
-    if keep.dtype != torch.bool or keep.shape != (n_comp,) or not keep.is_contiguous() or keep.device != dev:
+    _on_device(keep)
+    if not _is(keep, torch.bool, 1, (n_comp,), dev):
         raise ValueError(f"keep: expected a contiguous bool ({n_comp},) tensor on the mesh's device")
-    if component.dtype != torch.int32 or component.shape != (V,) or not component.is_contiguous() or component.device != dev:
+    if not _is(component, torch.int32, 1, (V,), dev):
         raise ValueError(f"components: component: expected a contiguous int32 ({V},) tensor on the mesh's device")
     lib = _lib.lib()
     keep8 = keep.view(torch.uint8)
@@ -354,11 +371,7 @@ def filter_mesh(mesh, keep, components=None):
             Vk, Tk = (int(v) for v in totals.tolist())                     # the host synchronisation
         else:
             Vk, Tk = 0, 0
-        out = {"vertices": torch.empty(Vk, 3, dtype=torch.float32, device=dev),
-               "normals": torch.empty(Vk, 3, dtype=torch.float32, device=dev),
-               "triangles": torch.empty(Tk, 3, dtype=torch.int32, device=dev)}
-        if col is not None:
-            out["colors"] = torch.empty(Vk, 3, dtype=torch.float32, device=dev)
+        out = _empty_mesh(Vk, Tk, col is not None, dev)
         a.n_kept_vertices, a.n_kept_triangles = Vk, Tk
         a.d_vertices, a.d_normals, a.d_colors = _ptr(ver), _ptr(nrm), _ptr(col)
         a.d_out_vertices, a.d_out_normals = _ptr(out["vertices"]), _ptr(out["normals"])
@@ -450,13 +463,11 @@ def simplify_mesh(mesh, cell, origin=(0.0, 0.0, 0.0), placement="mean", return_m
         a = _lib.MeshSimplifyArgs()
         if V:
             stream = rendering._stream()
-            nbytes = lib.nfl_mesh_simplify_bytes(V, T)
-            scratch = _scratch(nbytes, dev)
+            scratch = _scratch(lib.nfl_mesh_simplify_bytes(V, T), dev)
             totals = torch.empty(4, dtype=torch.int64, device=dev)
             a.d_vertices, a.d_normals, a.d_colors, a.d_triangles = _ptr(ver), _ptr(nrm), _ptr(col), _ptr(tri)
             a.n_vertices, a.n_triangles, a.cell, a.placement = V, T, cell, code
-            for k in range(3):
-                a.origin[k] = origin[k]
+            a.origin[:] = origin
             a.d_scratch, a.scratch_bytes = _ptr(scratch), scratch.numel() * 8
             a.d_totals, a.d_cluster = _ptr(totals), _ptr(cluster)
             _lib.check(lib.nfl_mesh_simplify_count(C.byref(a), stream), "nfl_mesh_simplify_count")
@@ -465,11 +476,7 @@ def simplify_mesh(mesh, cell, origin=(0.0, 0.0, 0.0), placement="mean", return_m
             Vo, To, outside = 0, 0, T
         if outside:
             raise ValueError(f"mesh: {outside} of {T} triangles have an index outside [0, {V})")
-        out = {"vertices": torch.empty(Vo, 3, dtype=torch.float32, device=dev),
-               "normals": torch.empty(Vo, 3, dtype=torch.float32, device=dev),
-               "triangles": torch.empty(To, 3, dtype=torch.int32, device=dev)}
-        if col is not None:
-            out["colors"] = torch.empty(Vo, 3, dtype=torch.float32, device=dev)
+        out = _empty_mesh(Vo, To, col is not None, dev)
         if V:
             a.n_out_vertices, a.n_out_triangles = Vo, To
             a.d_out_vertices, a.d_out_normals = _ptr(out["vertices"]), _ptr(out["normals"])
@@ -538,12 +545,7 @@ def occupancy_grid(lattice, threshold, lo, hi, dilate=1):
     The default of ONE cell of dilation is the usual practice and not a measured choice: the density between lattice
     points is not bounded by the corner values, so a thin structure that passes between the points of a cell is missed
     at any threshold, and the dilation only makes that less likely.  Choose the lattice fine enough for the scene."""
-    if not torch.is_tensor(lattice) or lattice.device.type != "cuda":
-        raise RuntimeError("nerf_fl_amd.geometry needs tensors on a ROCm device (this build has no CPU path)")
-    if lattice.dtype != torch.float32 or lattice.dim() != 3 or not lattice.is_contiguous():
-        raise ValueError("lattice: expected a contiguous fp32 (nz, ny, nx) tensor")
-    nz, ny, nx = lattice.shape
-    lo, sp, _ = _box(lo, hi, (nx, ny, nz))
+    nx, ny, nz, lo, sp = _lattice(lattice, lo, hi)
     dilate = int(dilate)
     if not 0 <= dilate <= 8:
         raise ValueError("dilate: 0 .. 8 cells")
@@ -574,9 +576,8 @@ def clip_rays(grid, rays):
     there.  A ray with a NaN in it hits nothing.  No host synchronisation."""
     if not isinstance(grid, OccupancyGrid):
         raise ValueError("clip_rays: `grid` is what occupancy_grid returns")
-    if not torch.is_tensor(rays) or rays.device.type != "cuda":
-        raise RuntimeError("nerf_fl_amd.geometry needs tensors on a ROCm device (this build has no CPU path)")
-    if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+    _on_device(rays)
+    if not _is(rays, torch.float32, 2, (8,), contiguous=False):
         raise ValueError("rays: expected an fp32 (R, 8) tensor")
     dev = grid.bits.device
     if rays.device != dev:
@@ -588,8 +589,7 @@ def clip_rays(grid, rays):
     cx, cy, cz = grid.cells
     a = _lib.OccClipArgs()
     a.d_rays, a.n_rays, a.d_bits, a.nx, a.ny, a.nz = _ptr(out), R, _ptr(grid.bits), cx + 1, cy + 1, cz + 1
-    for k in range(3):
-        a.lo[k], a.spacing[k] = grid.lo[k], grid.spacing[k]
+    a.lo[:], a.spacing[:] = grid.lo, grid.spacing
     a.d_near_far, a.d_hit = _ptr(near_far), _ptr(hit)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().nfl_occ_clip_rays(C.byref(a), rendering._stream()), "nfl_occ_clip_rays")

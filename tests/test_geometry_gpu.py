@@ -76,10 +76,11 @@ def test_centre_inside_is_closed():
     assert len(got["vertices"]) == 14                                        # one crossing per edge that leaves the centre
 
 
-@pytest.mark.parametrize("shape", [(3, 4, 5), (7, 9, 33), (2, 3, 65), (5, 6, 300)])
+@pytest.mark.parametrize("shape", [(3, 4, 5), (7, 9, 33), (2, 3, 65), (5, 6, 300), (67, 62, 3), (91, 91, 3)])
 def test_random_lattices(shape):
     """(nz, ny, nx): distinct sizes so that strides are not interchangeable; 33 and 65 cross wave boundaries, 300 the
-    256-point slab of a workgroup."""
+    256-point slab of a workgroup.  The two thin ones have 4154 and 8281 slabs: nfl_surface_scan_kernel takes 4096 a round,
+    so it carries its sums over a full and a ragged round, and over three."""
     rng = np.random.default_rng(sum(shape))
     lat = rng.standard_normal(shape).astype(np.float32)
     _check(lat, 0.25, (-1.0, 0.5, 2.0), (2.0, 1.5, 2.75), f"random {shape}")

@@ -1,6 +1,7 @@
 """The layering of the device headers (file map): nfl_math.h is a leaf, nfl_mlp.h the MLP engine on top of it,
 nfl_render_impl.h the forward kernel on top of that.  Every header compiles from a one-line includer, and no translation
-unit reaches above the layer it needs."""
+unit reaches above the layer it needs.  The geometry layer stands beside them: nfl_geom_layout.h (plain C++) under
+nfl_geom.h, which its five translation units include and which takes nothing from the render path."""
 import os
 import re
 import shutil
@@ -19,7 +20,8 @@ def includes(name):
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-@pytest.mark.parametrize("header", ["nfl_math.h", "nfl_dev.h", "nfl_pixel.h", "nfl_mlp.h", "nfl_render_impl.h"])
+@pytest.mark.parametrize("header", ["nfl_math.h", "nfl_dev.h", "nfl_pixel.h", "nfl_mlp.h", "nfl_render_impl.h",
+                                    "nfl_geom_layout.h", "nfl_geom.h"])
 def test_header_compiles_on_its_own(header, tmp_path):
     src = tmp_path / "includer.hip"
     src.write_text('#include "%s"\n' % header)
@@ -42,3 +44,28 @@ def test_small_kernels_take_the_math_only(unit):
 def test_dgrad_takes_the_engine_without_the_render_kernel():
     assert "nfl_mlp.h" in includes("nfl_dgrad.hip")
     assert "nfl_render_impl.h" not in includes("nfl_dgrad.hip")
+
+
+GEOMETRY_UNITS = ["nfl_surface.hip", "nfl_mesh.hip", "nfl_occupancy.hip", "nfl_simplify.hip", "nfl_mesh_scan.hip"]
+
+
+@pytest.mark.parametrize("unit", GEOMETRY_UNITS)
+def test_geometry_units_take_the_shared_header_only(unit):
+    assert "nfl_geom.h" in includes(unit)
+    assert not includes(unit) & {"nfl_mlp.h", "nfl_render_impl.h", "nfl_math.h", "nfl_plan.h"}
+
+
+def test_geometry_headers_stand_beside_the_render_path():
+    assert includes("nfl_geom.h") == {"nfl_geom_layout.h"}
+    assert includes("nfl_geom_layout.h") == {"../../include/nerf_fl_amd.h"}
+    with open(os.path.join(CSRC, "nfl_geom_layout.h")) as f:
+        assert "hip" not in re.sub(r"//.*", "", f.read())                   # host arithmetic: g++ builds it
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_layout_header_is_plain_cpp(tmp_path):
+    src = tmp_path / "includer.cpp"
+    src.write_text('#include "nfl_geom_layout.h"\nint main() { return (int)ng_bytes(nm_label_layout(0)); }\n')
+    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", CSRC, str(src)], capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]

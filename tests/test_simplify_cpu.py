@@ -293,6 +293,29 @@ def test_simplify_scratch_size(L):
         assert fn(V, T) == exp, (V, T)
 
 
+def test_simplify_scratch_layout_over_the_mesh_grid(L):
+    """The 15 regions restated here, over the grid of (V, T) test_mesh_cpu.py holds the mesh formulas to and over the
+    sizes at which a scan gains a level (2048, 2048^2) or a hash table doubles."""
+    pad = lambda b: -(-b // 16) * 16
+    fn = L.nfl_mesh_simplify_bytes
+
+    def restated(V, T):
+        regions = [8 * _cap(V), 4 * _cap(V), 4 * V, 4 * V, 8 * V,                  # vertex table, slots, flags, ranks
+                   12 * T, 4 * _cap(T), 4 * _cap(T), 4 * T, 4 * T, 8 * T,          # triples, triangle table, slots, flags, offsets
+                   max(_tiles(V), _tiles(T)), 4 * V, 72 * V, 72 * V]               # tile sums, counts, fixed-point sums, quadrics
+        return sum(pad(b) for b in regions)
+
+    sizes = (1, 2047, 2048, 2049, 2048 ** 2 + 1)
+    grid = [(1, 0), (3, 1), (2048, 7), (2049, 5000), (5_000_000, 9_000_000)] + [(V, T) for V in sizes for T in (0,) + sizes]
+    for V, T in grid:
+        assert fn(V, T) == restated(V, T), (V, T)
+        assert fn(V, T) % 16 == 0
+    big_t = (2 ** 31 - 1) // 3
+    assert fn(2 ** 31 - 1, big_t) == restated(2 ** 31 - 1, big_t)
+    for V, T in ((-1, 0), (0, -1), (-1, -1), (2 ** 31, 0), (0, big_t + 1), (2 ** 31, big_t + 1), (2 ** 63 - 1, 1), (1, 2 ** 63 - 1)):
+        assert fn(V, T) == 0, (V, T)                                           # what nm_sizes_ok refuses
+
+
 def test_simplify_calls_validate_arguments(L):
     from nerf_fl_amd import _lib
     P = 64                                                                 # never dereferenced: every call below is refused

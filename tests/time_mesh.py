@@ -17,41 +17,14 @@ import argparse
 import ctypes as C
 import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [os.path.dirname(HERE), HERE]
-
-
-def timed(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return {"median": statistics.median(ms), "min": min(ms), "max": max(ms)}
-
-
-def host_timed(fn, iters):
-    ms = []
-    for _ in range(iters):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ms.append((time.perf_counter() - t0) * 1e3)
-    return {"median": statistics.median(ms), "min": min(ms), "max": max(ms)}
+from geom_timing import host_timed, timed  # noqa: E402
 
 
 def lattice(n, blobs, dev):
@@ -117,7 +90,7 @@ def measure(name, lat, a, rec):
     t_emit = timed(lambda: _lib.check(lib.nfl_mesh_compact_emit(C.byref(ca), stream()), "emit"), a.warmup, a.iters)
     cleaned = geometry.clean_mesh(mesh, largest=1)
     assert torch.equal(cleaned["vertices"], out[0]) and torch.equal(cleaned["triangles"], out[2])
-    t_clean = host_timed(lambda: geometry.clean_mesh(mesh, largest=1), a.iters)
+    t_clean = host_timed(lambda: geometry.clean_mesh(mesh, largest=1), 0, a.iters)
 
     # the host route: indices to the host, components there, a vertex mask back
     def host_route():
@@ -127,8 +100,8 @@ def measure(name, lat, a, rec):
         return torch.from_numpy(comp == big).to(dev), comp
     mask, h_comp = host_route()
     assert np.array_equal(h_comp, component.cpu().numpy()) and int(mask.sum().item()) == Vk
-    t_host = host_timed(lambda: host_route(), a.host_iters)
-    t_copy = host_timed(lambda: tri.cpu(), a.iters)
+    t_host = host_timed(lambda: host_route(), 0, a.host_iters)
+    t_copy = host_timed(lambda: tri.cpu(), 0, a.iters)
 
     b_label = 12 * T + 44 * V
     b_stats = 16 * V + 8 * T + 32 * n_comp

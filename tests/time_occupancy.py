@@ -19,42 +19,13 @@ import ctypes as C
 import json
 import math
 import os
-import statistics
 import sys
-import time
 
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [os.path.dirname(HERE), HERE]
-
-
-def timed(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return {"median": statistics.median(ms), "min": min(ms), "max": max(ms)}
-
-
-def host_timed(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    ms = []
-    for _ in range(iters):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ms.append((time.perf_counter() - t0) * 1e3)
-    return {"median": statistics.median(ms), "min": min(ms), "max": max(ms)}
+from geom_timing import host_timed, timed  # noqa: E402
 
 
 def psnr(a, b):
