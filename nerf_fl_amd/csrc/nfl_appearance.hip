@@ -15,11 +15,11 @@
 
 #include "../../include/nerf_fl_amd.h"
 #include "nfl_dev.h"
+#include "nfl_launch.h"      // the cache entry's checks, NFL_AF_MAXCH
 
 extern "C" int nfl_launch_zcache_x3(const NflPlan*, const void*, const void*, const nfl_pass_args*, float*, int, void*);
 
 #define NFL_AF_F 128          // output width of dir_encoding.0
-#define NFL_AF_MAXCH 4        // n_pad <= 256 samples: 4 chunks of 64
 
 typedef float nfl_af4 __attribute__((ext_vector_type(4)));
 
@@ -187,16 +187,9 @@ extern "C" {
 int nfl_appearance_cache(const void* h_plan, const void* d_plan, const void* d_packed, const nfl_pass_args* a,
                          float* d_zcache, int32_t n_pad, void* stream) {
     const NflPlan* hp = static_cast<const NflPlan*>(h_plan);
-    if (!hp || hp->magic != NFL_PLAN_MAGIC || hp->is_bwd || !d_plan || !d_packed || !a || !d_zcache) return NFL_EINVAL;
-    if (hp->prec != NFL_PREC_F16X3 || !hp->has_a) return NFL_EINVAL;
-    if (a->n_rays < 0 || a->n_samples < 1 || n_pad < a->n_samples || n_pad % 64 != 0 || n_pad > 64 * NFL_AF_MAXCH)
-        return NFL_EINVAL;
-    if (!a->d_rays || a->h_cam || a->d_cam || !a->d_a_emb || a->d_t_emb || a->sigma_only || a->d_act_stash ||
-        a->d_loss_target || a->d_embedded)
-        return NFL_EINVAL;
-    if (!a->d_z && !a->d_lin) return NFL_EINVAL;
-    if (a->perturb > 0.f && !a->d_z && !a->d_perturb_rand) return NFL_EINVAL;
-    if (a->n_rays == 0) return NFL_OK;
+    int launch = 0;
+    const int rc = nfl_render_check(NFL_ENTRY_CACHE, hp, d_plan, d_packed, a, d_zcache, n_pad, &launch);
+    if (!launch) return rc;
     return nfl_launch_zcache_x3(hp, d_plan, d_packed, a, d_zcache, n_pad, stream);
 }
 

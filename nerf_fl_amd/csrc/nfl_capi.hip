@@ -1,9 +1,7 @@
 // nfl_capi.hip -- the extern "C" surface declared in include/nerf_fl_amd.h.
 #include <hip/hip_runtime.h>
-#include <string.h>
-
 #include "../../include/nerf_fl_amd.h"
-#include "nfl_plan.h"
+#include "nfl_launch.h"
 
 extern "C" int nfl_launch_render_x3(const NflPlan*, const void*, const void*, const nfl_pass_args*, void*);
 extern "C" int nfl_launch_render_x1(const NflPlan*, const void*, const void*, const nfl_pass_args*, void*);
@@ -61,48 +59,28 @@ size_t nfl_bwd_packed_bytes(const nfl_field_desc* desc, int32_t rays_grad, int32
     return (size_t)p.packed_bytes;
 }
 
+static int launch_render(const NflPlan* hp, const void* d_plan, const void* d_packed, const nfl_pass_args* a, void* stream) {
+    if (hp->prec == NFL_PREC_F16X3) return nfl_launch_render_x3(hp, d_plan, d_packed, a, stream);
+    return nfl_launch_render_x1(hp, d_plan, d_packed, a, stream);
+}
+
 int nfl_render_pass(const void* h_plan, const void* d_plan, const void* d_packed,
                     const nfl_pass_args* a, void* stream) {
     const NflPlan* hp = static_cast<const NflPlan*>(h_plan);
-    if (!hp || hp->magic != NFL_PLAN_MAGIC || !d_plan || !d_packed || !a) return NFL_EINVAL;
-    if (a->n_rays < 0 || a->n_samples < 1 || (!a->d_rays && !a->h_cam && !a->d_cam)) return NFL_EINVAL;
-    if (a->d_cam && a->d_act_stash) return NFL_EINVAL;
-    if (a->h_cam && (a->d_act_stash || a->h_cam->width < 1 || a->h_cam->fx == 0.f || a->h_cam->fy == 0.f || a->h_cam->pix0 < 0))
-        return NFL_EINVAL;
-    if (!a->d_z && !a->d_lin) return NFL_EINVAL;
-    if (a->perturb > 0.f && !a->d_z && !a->d_perturb_rand) return NFL_EINVAL;
-    if (!a->sigma_only && hp->has_a && !a->d_a_emb) return NFL_EINVAL;
-    if (hp->is_bwd) return NFL_EINVAL;
-    if (a->d_loss_target && (!a->d_losses || !a->d_seed_rgb || a->loss_slot < 0 || a->loss_slot > 1 || a->sigma_only ||
-                             a->test_extras)) return NFL_EINVAL;
-    if (a->n_rays == 0) return NFL_OK;
-    if (hp->prec == NFL_PREC_F16X3) return nfl_launch_render_x3(hp, d_plan, d_packed, a, stream);
-    return nfl_launch_render_x1(hp, d_plan, d_packed, a, stream);
+    int launch = 0;
+    const int rc = nfl_render_check(NFL_ENTRY_PASS, hp, d_plan, d_packed, a, nullptr, 0, &launch);
+    return launch ? launch_render(hp, d_plan, d_packed, a, stream) : rc;
 }
 
 int nfl_field_forward(const void* h_plan, const void* d_plan, const void* d_packed, const float* d_x,
                       int32_t n_points, int32_t row_stride, int32_t sigma_only, int32_t output_transient,
                       float* d_out, void* stream) {
     const NflPlan* hp = static_cast<const NflPlan*>(h_plan);
-    if (!hp || hp->magic != NFL_PLAN_MAGIC || hp->is_bwd || !d_plan || !d_packed || !d_x || !d_out) return NFL_EINVAL;
-    const int cx = 6 * hp->n_emb_xyz + 3, cd = hp->ld[NFL_P_DIR] - NFL_W - hp->n_a;
-    const int need = sigma_only ? cx : cx + cd + hp->n_a + ((output_transient && hp->has_t) ? hp->n_tau : 0);
-    if (n_points < 0 || row_stride < need) return NFL_EINVAL;
-    if (n_points == 0) return NFL_OK;
     nfl_pass_args a;
-    memset(&a, 0, sizeof(a));
-    a.d_embedded = d_x;
-    a.n_points = n_points;
-    a.embedded_stride = row_stride;
-    a.n_rays = (n_points + 31) / 32;
-    a.n_samples = 32;
-    a.sigma_only = sigma_only ? 1 : 0;
-    a.d_t_emb = (output_transient && hp->has_t && !sigma_only) ? d_x : nullptr;     // flag only
-    a.d_a_emb = d_x;                                                                  // flag only
-    a.d_rays = d_x;
-    a.d_field_raw = d_out;
-    if (hp->prec == NFL_PREC_F16X3) return nfl_launch_render_x3(hp, d_plan, d_packed, &a, stream);
-    return nfl_launch_render_x1(hp, d_plan, d_packed, &a, stream);
+    nfl_field_forward_args(hp, d_x, n_points, row_stride, sigma_only, output_transient, d_out, &a);
+    int launch = 0;
+    const int rc = nfl_render_check(NFL_ENTRY_FIELD, hp, d_plan, d_packed, &a, nullptr, 0, &launch);
+    return launch ? launch_render(hp, d_plan, d_packed, &a, stream) : rc;
 }
 
 int nfl_abi_version(void) { return NFL_ABI_VERSION; }
@@ -123,8 +101,9 @@ const char* nfl_strerror(int code) {
 }
 
 const char* nfl_render_kernel_name(int prec, int n_emb_xyz) {
-    if (prec == NFL_PREC_F16X3) return n_emb_xyz > 10 ? "nfl_render_kernel<3, 1, 15, 0>" : "nfl_render_kernel<3, 1, 10, 0>";
-    return n_emb_xyz > 10 ? "nfl_render_kernel<1, 1, 15, 0>" : "nfl_render_kernel<1, 1, 10, 0>";
+    const bool wide = nfl_kernel_nfx(n_emb_xyz) != 10;
+    if (prec == NFL_PREC_F16X3) return wide ? "nfl_render_kernel<3, 1, 15, 0>" : "nfl_render_kernel<3, 1, 10, 0>";
+    return wide ? "nfl_render_kernel<1, 1, 15, 0>" : "nfl_render_kernel<1, 1, 10, 0>";
 }
 
 }  // extern "C"

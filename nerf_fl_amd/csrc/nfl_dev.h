@@ -1,6 +1,7 @@
-// nfl_dev.h -- the small device-side helpers that kernels of different translation units share: wave reductions, the
-// kernarg re-read, the gradient-maximum word.  Defines no device globals, so any translation unit may include it.
+// nfl_dev.h -- the small helpers that kernels of different translation units share: wave reductions, the kernarg re-read,
+// the gradient-maximum word; their launchers' two runtime queries.  Defines no device globals: any unit may include it.
 #pragma once
+#include "../../include/nerf_fl_amd.h"
 #include "nfl_macros.h"
 #include "nfl_plan.h"
 
@@ -49,4 +50,26 @@ NFL_DEV unsigned nfl_gmax_bits(const float* d_gmax) {
             v = o > v ? o : v;
         }
     return __builtin_amdgcn_readfirstlane(nfl_wave_max(v));
+}
+
+// ---- the two runtime queries of the launchers with dynamic LDS (forward, dgrad, wgrad) ----
+struct NflDevice {
+    int ordinal, n_cu;        // the current device and its CU count (256 where the runtime does not say)
+};
+static inline NflDevice nfl_device() {
+    NflDevice d = {0, 256};
+    if (hipGetDevice(&d.ordinal) == hipSuccess) (void)hipDeviceGetAttribute(&d.n_cu, hipDeviceAttributeMultiprocessorCount, d.ordinal);
+    return d;
+}
+// Raises KERNEL's dynamic-LDS limit to `bytes` on the current device, `ordinal`, once per device: the attribute is per
+// device.  (Two threads may both make the first call; it is idempotent.  Ordinals beyond 63 make it every time.)
+template <auto KERNEL>
+static int nfl_lds_attr(int ordinal, int bytes) {
+    static unsigned long long done = 0ull;
+    const unsigned long long bit = (unsigned)ordinal < 64u ? 1ull << ordinal : 0ull;
+    if (done & bit) return NFL_OK;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
+        return NFL_ENODEV;
+    done |= bit;
+    return NFL_OK;
 }

@@ -18,6 +18,7 @@
 // order) to the gradient stash for the weight-gradient GEMMs (nfl_wgrad.hip).  The
 // appearance / transient latent gradients are the extra rows of W_dir^T / W_t0^T,
 // reduced over the samples of the ray with wave shuffles and accumulated with fp32 atomics.
+#include "nfl_launch.h"
 #include "nfl_mlp.h"
 #ifdef NFL_STAMPS
 #include "nfl_stamps.h"      // make diag DIAGTU=nfl_dgrad: this unit carries the stamp buffer instead of nfl_render_x3
@@ -46,18 +47,6 @@ struct DgMode {
 #else
     static constexpr int PRODS = NP_ == 2 ? 3 : (NWP_ == 2 ? 5 : 0);     // nfl_tile_p: bit 2 = hi + lo weight fragments under single-image operands
 #endif
-};
-
-struct DgradArgs {
-    const NflPlan* plan;
-    const char* packed;
-    nfl_dgrad_args a;
-    int n_chunks, c_start;
-    int has_a, has_t, use_t;
-    int spr, rays_per_wg, nkp, n_seg_total;
-    int rays_tiles;           // the stream carries the encoded-position / direction rows (gradient w.r.t. rays)
-    int nfx_rt, ndir_rt;      // the field's frequency counts (<= the instantiation's; nfl_plan.h, "Encoder widths")
-    int n_a, n_tau;           // widths of the latent codes (<= 48 / 16)
 };
 
 typedef NflKernarg<DgradArgs> NflDgKArgs;
@@ -689,44 +678,18 @@ __global__ __launch_bounds__(256, 1) void nfl_dgrad_kernel(const DgradArgs A) {
 #endif
 }
 
+// Host side: the checks, the argument block and the grid are nfl_launch.cpp's; here the plan's arithmetic picks the
+// instantiation, which sets its LDS attribute and launches.
 template <int NFX, int NP, int NWP>
 static int launch_dgrad(const NflPlan* hp, const void* d_plan, const void* d_packed, const nfl_dgrad_args* args,
                         hipStream_t stream) {
     using C = NflDgradCfg<NFX, DgMode<NP, NWP>>;
-    constexpr int NCB_ = C::NCB;
+    const NflDevice dev = nfl_device();
     DgradArgs A;
-    A.plan = static_cast<const NflPlan*>(d_plan);
-    A.packed = static_cast<const char*>(d_packed);
-    A.a = *args;
-    A.has_a = hp->has_a;
-    A.has_t = hp->has_t;
-    A.use_t = (hp->has_t && args->use_transient) ? 1 : 0;
-    A.n_chunks = hp->n_chunks;
-    A.c_start = (hp->has_t && !A.use_t) ? hp->n_chunks_sigma : 0;     // skip the transient head's chunks
-    if (args->d_g_rays && (!A.rays_tiles || !args->d_rays || !args->d_z)) return NFL_EINVAL;
-    A.spr = (args->n_samples + 31) / 32;
-    A.nkp = hp->nkp;
-    A.n_seg_total = args->n_rays * A.spr;
-    A.rays_tiles = hp->reserved_flags & 1;
-    A.nfx_rt = hp->n_emb_xyz;
-    A.ndir_rt = (hp->reserved_flags >> 8) & 0xff;
-    A.n_a = hp->n_a;
-    A.n_tau = hp->n_tau;
-    int dev = 0, ncu = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    int rpw = (args->n_rays + ncu - 1) / ncu;
-    const int rays_per_tile = 4 * NCB_ / A.spr;
-    if (rays_per_tile > 1) rpw = (rpw + rays_per_tile - 1) / rays_per_tile * rays_per_tile;
-    if (rpw < 1) rpw = 1;
-    A.rays_per_wg = rpw;
-    const int grid = (args->n_rays + rpw - 1) / rpw;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&nfl_dgrad_kernel<NFX, NP, NWP>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES) != hipSuccess)
-            return NFL_ENODEV;
-        attr_set = true;
-    }
+    int grid;
+    const int rc = nfl_dgrad_fill(hp, d_plan, d_packed, args, dev.n_cu, C::NCB, &A, &grid);
+    if (rc != NFL_OK) return rc;
+    if (nfl_lds_attr<&nfl_dgrad_kernel<NFX, NP, NWP>>(dev.ordinal, C::LDS_BYTES) != NFL_OK) return NFL_ENODEV;
     hipLaunchKernelGGL((nfl_dgrad_kernel<NFX, NP, NWP>), dim3(grid), dim3(256), C::LDS_BYTES, stream, A);
     return hipGetLastError() == hipSuccess ? NFL_OK : NFL_ELAUNCH;
 }
@@ -736,14 +699,19 @@ static int launch_dgrad(const NflPlan* hp, const void* d_plan, const void* d_pac
 #ifndef NFL_DGRAD_WIDE
 #define NFL_DGRAD_WIDE 0
 #endif
+static constexpr int DG_NFX = nfl_kernel_nfx(NFL_DGRAD_WIDE ? NFL_MAX_EMB_XYZ : 1);       // this half's encoder width
+static int dgrad_by_prec(const NflPlan* hp, const void* d_bwd_plan, const void* d_bwd_packed, const nfl_dgrad_args* args,
+                         void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (hp->prec == NFL_PREC_F16 && hp->nsplit == 1) return launch_dgrad<DG_NFX, 1, 1>(hp, d_bwd_plan, d_bwd_packed, args, s);
+    if (hp->prec == NFL_PREC_F16W && hp->nsplit == 3) return launch_dgrad<DG_NFX, 1, 2>(hp, d_bwd_plan, d_bwd_packed, args, s);
+    if (hp->prec == NFL_PREC_F16X3 && hp->nsplit == 3) return launch_dgrad<DG_NFX, 2, 2>(hp, d_bwd_plan, d_bwd_packed, args, s);
+    return NFL_EINVAL;
+}
 #if NFL_DGRAD_WIDE
 extern "C" int nfl_mlp_dgrad_wide(const NflPlan* hp, const void* d_bwd_plan, const void* d_bwd_packed, const nfl_dgrad_args* args,
                                   void* stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (hp->prec == NFL_PREC_F16 && hp->nsplit == 1) return launch_dgrad<15, 1, 1>(hp, d_bwd_plan, d_bwd_packed, args, s);
-    if (hp->prec == NFL_PREC_F16W && hp->nsplit == 3) return launch_dgrad<15, 1, 2>(hp, d_bwd_plan, d_bwd_packed, args, s);
-    if (hp->prec == NFL_PREC_F16X3 && hp->nsplit == 3) return launch_dgrad<15, 2, 2>(hp, d_bwd_plan, d_bwd_packed, args, s);
-    return NFL_EINVAL;
+    return dgrad_by_prec(hp, d_bwd_plan, d_bwd_packed, args, stream);
 }
 #else
 extern "C" int nfl_mlp_dgrad_wide(const NflPlan*, const void*, const void*, const nfl_dgrad_args*, void*);
@@ -751,16 +719,10 @@ extern "C" int nfl_mlp_dgrad_wide(const NflPlan*, const void*, const void*, cons
 extern "C" int nfl_mlp_dgrad(const void* h_bwd_plan, const void* d_bwd_plan, const void* d_bwd_packed,
                              const nfl_dgrad_args* args, void* stream) {
     const NflPlan* hp = static_cast<const NflPlan*>(h_bwd_plan);
-    if (!hp || hp->magic != NFL_PLAN_MAGIC || !hp->is_bwd || !d_bwd_plan || !d_bwd_packed || !args) return NFL_EINVAL;
-    if (!args->d_head_grads || !args->d_act_stash || !args->d_grad_stash || !args->d_gmax) return NFL_EINVAL;
-    if (args->n_rays < 0 || args->n_samples < 1) return NFL_EINVAL;
-    if (args->n_rays == 0) return NFL_OK;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (hp->n_emb_xyz < 1 || hp->n_emb_xyz > NFL_MAX_EMB_XYZ) return NFL_EINVAL;
-    if (hp->n_emb_xyz > 10) return nfl_mlp_dgrad_wide(hp, d_bwd_plan, d_bwd_packed, args, stream);      // encoder widths: nfl_plan.h
-    if (hp->prec == NFL_PREC_F16 && hp->nsplit == 1) return launch_dgrad<10, 1, 1>(hp, d_bwd_plan, d_bwd_packed, args, s);
-    if (hp->prec == NFL_PREC_F16W && hp->nsplit == 3) return launch_dgrad<10, 1, 2>(hp, d_bwd_plan, d_bwd_packed, args, s);
-    if (hp->prec == NFL_PREC_F16X3 && hp->nsplit == 3) return launch_dgrad<10, 2, 2>(hp, d_bwd_plan, d_bwd_packed, args, s);
-    return NFL_EINVAL;
+    int launch = 0;
+    const int rc = nfl_dgrad_check(hp, d_bwd_plan, d_bwd_packed, args, &launch);
+    if (!launch) return rc;
+    if (nfl_kernel_nfx(hp->n_emb_xyz) != DG_NFX) return nfl_mlp_dgrad_wide(hp, d_bwd_plan, d_bwd_packed, args, stream);  // encoder widths: nfl_plan.h
+    return dgrad_by_prec(hp, d_bwd_plan, d_bwd_packed, args, stream);
 }
 #endif

@@ -18,34 +18,11 @@
 //     transmittance, so segments (and tiles) of one ray are folded through a tiny LDS
 //     record.  Nothing per-sample except the API's own (R,N) outputs is written.
 #pragma once
-#include <string.h>
-
+#include "nfl_launch.h"
 #include "nfl_mlp.h"
 
 #define NFL_NST 20            // floats in a segment / ray compositing record
 #define NFL_REC 32            // record stride (floats)
-
-struct RenderArgs {
-    const NflPlan* plan;      // device copy of the plan
-    const char* packed;       // fragment stream, then bias table at plan->bias_off
-    nfl_pass_args a;
-    int n_chunks;             // chunks per tile consumed by this pass (prefix of the stream)
-    int n_rt;                 // row tiles consumed by this pass
-    int bias_off;
-    int has_a;                // field has the appearance input
-    int use_t;                // transient head evaluated in this pass
-    int spr;                  // 32-sample segments per ray
-    int rays_per_wg;
-    float beta_min;
-    int n_points, emb_stride;   // NFL_MODE_EMBED: rows / row stride (floats) of a.d_embedded
-    int nfx_rt, ndir_rt;        // the field's frequency counts (<= the instantiation's: nfl_plan.h, "Encoder widths")
-    int cx, cd;                 // 6 nfx_rt + 3, 6 ndir_rt + 3: widths of the encoded position / direction
-    int n_a, n_tau;             // widths of the appearance / transient codes (<= 48 / 16; narrower: the k-steps are zero-padded)
-    int gen_rays;               // rays come from `cam` (nfl_pass_args::h_cam), not from a.d_rays
-    nfl_camera cam;
-    float* zcache;              // NFL_MODE_ZCACHE: the appearance cache (nfl_appearance_cache), else null
-    int zpad;                   // its padded sample count
-};
 
 // ---------------------------------------------------------------------------------
 // depths (reference models/rendering.py:243-259); every operation separately rounded
@@ -117,13 +94,6 @@ typedef const __attribute__((address_space(4))) nfl_camera* NflKCam;
 NFL_DEV NflKCam nfl_kcam(NflKArgs K) {
     return K->a.d_cam ? (NflKCam)(unsigned long long)K->a.d_cam : &K->cam;
 }
-
-#define NFL_MODE_RENDER 0
-#define NFL_MODE_STASH 1      // render + fp16 activation stash for the backward
-#define NFL_MODE_STASH2 3     // as STASH, with split (hi + lo) activation records for the three-product backward
-#define NFL_MODE_EMBED 2      // NeRF.forward on already-encoded inputs (reference models/nerf.py:153-212): no
-                              // depth generation / encoding / compositing, 32 points per segment
-#define NFL_MODE_ZCACHE 4     // render + the pre-activation of dir_encoding.0 to the appearance cache (nfl_appearance_cache)
 
 template <int NSPLIT, int NCB, int NFX, int MODE>
 __global__ __launch_bounds__(256, 1) void nfl_render_kernel(const RenderArgs A) {
@@ -640,91 +610,38 @@ __global__ __launch_bounds__(256, 1) void nfl_render_kernel(const RenderArgs A) 
 #endif
 }
 
+// Host side: nfl_launch.cpp decides everything (mode, argument block, grid); here the mode picks the instantiation, which
+// sets its LDS attribute and launches.  zcache != null: the cache-building pass of nfl_appearance_cache.
 template <int NSPLIT, int NCB, int NFX, int MODE>
-static int nfl_launch_render_t(const NflPlan* hp, const void* d_plan, const void* d_packed,
-                             const nfl_pass_args* args, hipStream_t stream, float* zcache = nullptr, int zpad = 0) {
+static int nfl_launch_render_t(const NflPlan* hp, const void* d_plan, const void* d_packed, const nfl_pass_args* args,
+                               hipStream_t stream, float* zcache, int zpad) {
     using C = NflRenderCfg<NSPLIT, NCB, NFX>;
+    const NflDevice dev = nfl_device();
     RenderArgs A;
-    A.zcache = zcache;
-    A.zpad = zpad;
-    A.plan = static_cast<const NflPlan*>(d_plan);
-    A.packed = static_cast<const char*>(d_packed);
-    A.a = *args;
-    A.has_a = hp->has_a;
-    A.use_t = (hp->has_t && args->d_t_emb != nullptr && !args->sigma_only) ? 1 : 0;
-    A.n_points = 0;
-    A.emb_stride = 0;
-    A.gen_rays = 0;
-    A.nfx_rt = hp->n_emb_xyz;
-    A.ndir_rt = (hp->ld[NFL_P_DIR] - NFL_W - hp->n_a - 3) / 6;
-    A.cx = 6 * A.nfx_rt + 3;
-    A.cd = 6 * A.ndir_rt + 3;
-    A.n_a = hp->n_a;
-    A.n_tau = hp->n_tau;
-    memset(&A.cam, 0, sizeof(A.cam));
-    if ((args->h_cam != nullptr || args->d_cam != nullptr) && MODE != NFL_MODE_EMBED) {
-        A.gen_rays = 1;
-        if (args->h_cam != nullptr && args->d_cam == nullptr) A.cam = *args->h_cam;
-    }
-    A.a.h_cam = nullptr;                  // a host pointer has no business on the device
-    if (MODE == NFL_MODE_EMBED) {      // n_rays = segments of 32 points; d_t_emb != NULL only flags "transient head on"
-        A.n_points = args->n_points;
-        A.emb_stride = args->embedded_stride;
-    }
-    A.n_chunks = args->sigma_only ? hp->n_chunks_sigma : (A.use_t ? hp->n_chunks : hp->n_chunks_static);
-    A.n_rt = args->sigma_only ? hp->n_rt_sigma : (A.use_t ? hp->n_rt : hp->n_rt_static);
-    A.bias_off = hp->bias_off;
-    A.spr = (args->n_samples + 31) / 32;
-    A.beta_min = hp->beta_min;
-    // contiguous ray ranges, one workgroup per CU where there is enough work
-    int dev = 0, ncu = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    }
-    int rpw = (args->n_rays + ncu - 1) / ncu;
-    // keep whole tiles per workgroup where possible: rays per tile = NSLOT / spr (if >= 1)
-    const int rays_per_tile = C::NSLOT / A.spr;
-    if (rays_per_tile > 1) rpw = (rpw + rays_per_tile - 1) / rays_per_tile * rays_per_tile;
-    if (rpw < 1) rpw = 1;
-    A.rays_per_wg = rpw;
-    const int grid = (args->n_rays + rpw - 1) / rpw;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&nfl_render_kernel<NSPLIT, NCB, NFX, MODE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES) != hipSuccess)
-            return NFL_ENODEV;
-        attr_set = true;
-    }
+    int grid;
+    nfl_render_fill(hp, d_plan, d_packed, args, MODE, zcache, zpad, dev.n_cu, C::NSLOT, &A, &grid);
+    if (nfl_lds_attr<&nfl_render_kernel<NSPLIT, NCB, NFX, MODE>>(dev.ordinal, C::LDS_BYTES) != NFL_OK) return NFL_ENODEV;
     hipLaunchKernelGGL((nfl_render_kernel<NSPLIT, NCB, NFX, MODE>), dim3(grid), dim3(256), C::LDS_BYTES, stream, A);
     return hipGetLastError() == hipSuccess ? NFL_OK : NFL_ELAUNCH;
 }
-
 template <int NSPLIT, int NCB, int NFX>
-static int nfl_launch_render(const NflPlan* hp, const void* d_plan, const void* d_packed,
-                             const nfl_pass_args* args, hipStream_t stream) {
-#ifdef NFL_DIAG_INFERENCE_ONLY      // sweep builds (nfl_diag.h): only the inference instantiation is compiled
-    if (args->d_embedded || args->d_act_stash) return NFL_EINVAL;
-    return nfl_launch_render_t<NSPLIT, NCB, NFX, NFL_MODE_RENDER>(hp, d_plan, d_packed, args, stream);
-#endif
-    if (args->d_embedded) return nfl_launch_render_t<NSPLIT, NCB, NFX, NFL_MODE_EMBED>(hp, d_plan, d_packed, args, stream);
-    if (args->d_act_stash) {
-        if (NSPLIT != 3) return NFL_EINVAL;        // the training stash is written by the accurate mode only
-        if (args->stash_split)
-            return nfl_launch_render_t<NSPLIT, NCB, NFX, (NSPLIT == 3 ? NFL_MODE_STASH2 : NFL_MODE_RENDER)>(hp, d_plan, d_packed, args, stream);
-        return nfl_launch_render_t<NSPLIT, NCB, NFX, (NSPLIT == 3 ? NFL_MODE_STASH : NFL_MODE_RENDER)>(hp, d_plan, d_packed, args, stream);
-    }
-    return nfl_launch_render_t<NSPLIT, NCB, NFX, NFL_MODE_RENDER>(hp, d_plan, d_packed, args, stream);
-}
-
-// the cache-building pass of nfl_appearance_cache (three-product arithmetic only: the cache is fp32-class)
-template <int NSPLIT, int NCB, int NFX>
-static int nfl_launch_zcache(const NflPlan* hp, const void* d_plan, const void* d_packed, const nfl_pass_args* args,
-                             float* zcache, int zpad, hipStream_t stream) {
-#ifdef NFL_DIAG_INFERENCE_ONLY
-    return NFL_EINVAL;
+static int nfl_launch_render(const NflPlan* hp, const void* d_plan, const void* d_packed, const nfl_pass_args* args,
+                             hipStream_t stream, float* zcache = nullptr, int zpad = 0) {
+    const int mode = nfl_render_mode(hp, args, zcache != nullptr);
+#define NFL_LAUNCH_MODE(M) \
+    if (mode == M) return nfl_launch_render_t<NSPLIT, NCB, NFX, M>(hp, d_plan, d_packed, args, stream, zcache, zpad)
+#ifdef NFL_DIAG_INFERENCE_ONLY       // sweep builds (nfl_diag.h): only the inference instantiation is compiled
+    constexpr bool ALL = false;
 #else
-    if (NSPLIT != 3) return NFL_EINVAL;
-    return nfl_launch_render_t<NSPLIT, NCB, NFX, (NSPLIT == 3 ? NFL_MODE_ZCACHE : NFL_MODE_RENDER)>(hp, d_plan, d_packed, args,
-                                                                                                 stream, zcache, zpad);
+    constexpr bool ALL = true;
 #endif
+    // STASH, STASH2 and ZCACHE are modes of the three-product kernels alone (nfl_render_mode) and instantiated only there;
+    // the order is the one the kernels have always been emitted in
+    if constexpr (ALL) NFL_LAUNCH_MODE(NFL_MODE_EMBED);
+    if constexpr (ALL && NSPLIT == 3) NFL_LAUNCH_MODE(NFL_MODE_STASH2);
+    if constexpr (ALL && NSPLIT == 3) NFL_LAUNCH_MODE(NFL_MODE_STASH);
+    NFL_LAUNCH_MODE(NFL_MODE_RENDER);
+    if constexpr (ALL && NSPLIT == 3) NFL_LAUNCH_MODE(NFL_MODE_ZCACHE);
+#undef NFL_LAUNCH_MODE
+    return NFL_EINVAL;
 }

@@ -530,11 +530,11 @@ extern "C" int nfl_mlp_wgrad(const void* h_wplan, const void* d_wplan, const cha
     if (n_rays < 0 || n_samples < 1) return NFL_EINVAL;
     if (bwd_prec != NFL_PREC_F16 && bwd_prec != NFL_PREC_F16W && bwd_prec != NFL_PREC_F16X3) return NFL_EINVAL;
     const int mult = bwd_prec == NFL_PREC_F16X3 ? 2 : 1;       // split stashes: [hi record | lo record] per segment
-    int dev = 0, ncu = 256, n_wg = 0, red_blocks = 0;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    int n_wg = 0, red_blocks = 0;
+    const NflDevice dev = nfl_device();
     WgArgs A;
     memset(&A, 0, sizeof(A));
-    const int rc = nfl_wgrad_schedule(hp, n_rays * ((n_samples + 31) / 32), ncu, mult, &A, &n_wg, &red_blocks);
+    const int rc = nfl_wgrad_schedule(hp, n_rays * ((n_samples + 31) / 32), dev.n_cu, mult, &A, &n_wg, &red_blocks);
     if (rc != NFL_OK) return rc;
     A.plan = static_cast<const WgPlan*>(d_wplan);
     A.act = d_act_stash;
@@ -542,15 +542,9 @@ extern "C" int nfl_mlp_wgrad(const void* h_wplan, const void* d_wplan, const cha
     A.g = *grads;
     A.scratch = d_scratch;
     A.partial = d_scratch + NFL_W * NFL_W;       // the parts lie behind G
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&nfl_wgrad_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 2 * WG_SLOT) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&nfl_wgrad_kernel<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 4 * WG_SLOT) != hipSuccess)
-            return NFL_ENODEV;
-        attr_set = true;
-    }
+    if (nfl_lds_attr<&nfl_wgrad_kernel<false>>(dev.ordinal, 2 * WG_SLOT) != NFL_OK ||
+        nfl_lds_attr<&nfl_wgrad_kernel<true>>(dev.ordinal, 4 * WG_SLOT) != NFL_OK)
+        return NFL_ENODEV;
     WgTensors T;
     for (int L = 0; L < NFL_NUM_LAYERS; ++L) {
         T.ptr[L] = grads->weight[L];

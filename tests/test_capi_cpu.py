@@ -186,6 +186,32 @@ def test_auxiliary_entry_points_validate_arguments(L):
     assert L.nfl_pack_fields(1, job, None) == -1
 
 
+def test_dgrad_refuses_a_ray_gradient_it_cannot_compute(L):
+    """nfl_mlp_dgrad with d_g_rays needs a stream with the ray tiles (rays_grad = 1), the rays and the depths: the kernel reads
+    d_rays and d_z whenever it writes d_g_rays.  Refused with NFL_EINVAL on the host, before any runtime call (a real host
+    plan, dummy device pointers)."""
+    d = _lib.FieldDesc(10, 4, 1, 48, 1, 16, 0.1, 0)
+    n = L.nfl_plan_bytes(C.byref(d))
+    plans = {}
+    for rays_grad in (0, 1):
+        plans[rays_grad] = C.create_string_buffer(n)
+        assert L.nfl_bwd_plan_build(C.byref(d), rays_grad, _lib.NFL_PREC_F16, plans[rays_grad], n) == 0
+    dev = C.c_void_p(4096)
+
+    def call(rays_grad, **fields):
+        a = _lib.DgradArgs()
+        a.d_head_grads = a.d_act_stash = a.d_grad_stash = a.d_gmax = 4096
+        a.n_rays, a.n_samples = 64, 64
+        for k, v in fields.items():
+            setattr(a, k, v)
+        return L.nfl_mlp_dgrad(plans[rays_grad], dev, dev, C.byref(a), None)
+
+    assert call(0, d_g_rays=4096, d_rays=4096, d_z=4096) == -1      # the stream has no ray tiles
+    assert call(1, d_g_rays=4096, d_rays=4096, d_z=None) == -1
+    assert call(1, d_g_rays=4096, d_rays=None, d_z=4096) == -1
+    assert call(1, d_g_rays=4096, d_rays=4096, d_z=4096, n_rays=0) == 0         # complete, and empty: nothing launched
+
+
 def test_adam_step_dev_validates_arguments(L):
     t = _lib.AdamTensors()
     assert L.nfl_adam_step_dev(None, 1, C.c_void_p(16), C.c_void_p(16), 1, None) == -1

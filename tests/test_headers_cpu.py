@@ -1,7 +1,9 @@
 """The layering of the device headers (file map): nfl_math.h is a leaf, nfl_mlp.h the MLP engine on top of it,
 nfl_render_impl.h the forward kernel on top of that.  Every header compiles from a one-line includer, and no translation
 unit reaches above the layer it needs.  The geometry layer stands beside them: nfl_geom_layout.h (plain C++) under
-nfl_geom.h, which its five translation units include and which takes nothing from the render path."""
+nfl_geom.h, which its five translation units include and which takes nothing from the render path.  nfl_launch.h (plain C++,
+the launchers' host side) sits under the render kernel and the dgrad unit; the two runtime queries a launcher makes are
+written once, in nfl_dev.h."""
 import os
 import re
 import shutil
@@ -21,7 +23,7 @@ def includes(name):
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 @pytest.mark.parametrize("header", ["nfl_math.h", "nfl_dev.h", "nfl_pixel.h", "nfl_mlp.h", "nfl_render_impl.h",
-                                    "nfl_geom_layout.h", "nfl_geom.h"])
+                                    "nfl_geom_layout.h", "nfl_geom.h", "nfl_launch.h"])
 def test_header_compiles_on_its_own(header, tmp_path):
     src = tmp_path / "includer.hip"
     src.write_text('#include "%s"\n' % header)
@@ -69,3 +71,34 @@ def test_layout_header_is_plain_cpp(tmp_path):
     r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", CSRC, str(src)], capture_output=True, text=True,
                        timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
+
+
+def test_launch_header_sits_under_the_kernels():
+    assert includes("nfl_launch.h") == {"../../include/nerf_fl_amd.h", "nfl_plan.h"}
+    assert includes("nfl_launch.cpp") == {"nfl_launch.h"}
+    for user in ("nfl_render_impl.h", "nfl_dgrad.hip", "nfl_capi.hip", "nfl_appearance.hip"):
+        assert "nfl_launch.h" in includes(user)
+    for name in ("nfl_launch.h", "nfl_launch.cpp"):
+        with open(os.path.join(CSRC, name)) as f:
+            assert "hip" not in re.sub(r"//.*", "", f.read())                   # host arithmetic: g++ builds it
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_launch_header_is_plain_cpp(tmp_path):
+    src = tmp_path / "includer.cpp"
+    src.write_text('#include "nfl_launch.h"\nint main() { return (int)sizeof(RenderArgs) + (int)sizeof(DgradArgs); }\n')
+    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", CSRC, str(src)], capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+
+
+def test_runtime_queries_are_written_once():
+    """The CU count and the dynamic-LDS attribute go through nfl_device() / nfl_lds_attr() of nfl_dev.h: no other source
+    names the runtime calls."""
+    for name in sorted(os.listdir(CSRC)):
+        if not name.endswith((".hip", ".h", ".cpp")):
+            continue
+        with open(os.path.join(CSRC, name)) as f:
+            text = f.read()
+        for call in ("hipDeviceGetAttribute", "hipFuncSetAttribute"):
+            assert text.count(call) == (1 if name == "nfl_dev.h" else 0), (name, call)

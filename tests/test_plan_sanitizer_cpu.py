@@ -1,7 +1,8 @@
 """The host-side plan builder under AddressSanitizer + UBSan (GPU sanitizers are not available on this pool; the host code is
 where fixed-size tables are filled by configuration-dependent loops): tests/plan_sweep.cpp builds forward and backward plans
 for every encoder / latent width combination, accepted or rejected, and for every accepted one the weight-gradient job list
-(csrc/nfl_wgrad_plan.cpp) and its launch schedule over segment counts, CU counts and both stash multipliers."""
+(csrc/nfl_wgrad_plan.cpp) and its launch schedule over segment counts, CU counts and both stash multipliers, and the host side
+of the render and dgrad launchers (csrc/nfl_launch.cpp): ray split, argument-block fills, the entry points' refusals."""
 import os
 import shutil
 import subprocess
@@ -17,7 +18,8 @@ def test_plan_builder_is_clean_under_asan_ubsan(tmp_path):
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
            "-fno-omit-frame-pointer", os.path.join(ROOT, "tests", "plan_sweep.cpp"),
            os.path.join(ROOT, "nerf_fl_amd", "csrc", "nfl_plan.cpp"),
-           os.path.join(ROOT, "nerf_fl_amd", "csrc", "nfl_wgrad_plan.cpp"), "-o", exe]
+           os.path.join(ROOT, "nerf_fl_amd", "csrc", "nfl_wgrad_plan.cpp"),
+           os.path.join(ROOT, "nerf_fl_amd", "csrc", "nfl_launch.cpp"), "-o", exe]
     b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
     if b.returncode != 0 and "sanitize" in b.stderr and "cannot find" in b.stderr:
         pytest.skip("sanitizer runtime not installed")
@@ -33,3 +35,7 @@ def test_plan_builder_is_clean_under_asan_ubsan(tmp_path):
     n_wplans, n_sched = (int(r.stdout.split(k)[1].split()[0]) for k in ("wgrad plans", "schedules"))
     assert n_wplans > 10000 and n_sched == 72 * n_wplans
     assert "wgrad rows reached" in r.stdout
+    # the launchers' host side: 13 x 4 x 9 x 2 ray splits once; per accepted field its argument-block fills and the refusal table
+    assert "launch invariant broken" not in r.stdout
+    n_splits, n_fills, n_refusals = (int(r.stdout.split(k)[1].split()[0]) for k in ("launch splits", "fills", "refusals"))
+    assert n_splits == 936 and n_fills > 20 * n_wplans // 2 and n_refusals > 80 * n_wplans // 2
