@@ -19,6 +19,7 @@ import torch
 
 from . import _lib
 from . import rendering as rnd
+from .eval import _chunks
 from .train import Adam
 
 __all__ = ["AppearanceFit"]
@@ -131,16 +132,10 @@ class AppearanceFit:
         f_c = rnd._field(models["coarse"], n_xyz, n_dir, dev, pack=False, prec=f16x3)
         f_f = rnd._field(models["fine"], n_xyz, n_dir, dev, pack=False, prec=f16x3)
         rnd._pack_streams([f_c, f_f])
-        pe_w_xyz = pe_w_dir = None
-        if getattr(models["coarse"], "refine_pose", False):     # BARF weights, as render_rays takes them
-            if kwargs.get("barf_weights") is not None:
-                pe_w_xyz, pe_w_dir = (w.detach().to(dev, torch.float32).contiguous() for w in kwargs["barf_weights"])
-            else:
-                epoch = kwargs.get("current_epoch")
-                if epoch is None:
-                    raise KeyError("current_epoch")
-                pe_w_xyz = rnd._barf_weights(embeddings["xyz"], epoch).to(dev)
-                pe_w_dir = rnd._barf_weights(embeddings["dir"], epoch).to(dev)
+        if kwargs.get("barf_weights") is not None:      # as render_rays takes them, but from any device or dtype
+            kwargs = dict(kwargs, barf_weights=tuple(rnd._f32c(w.detach().to(dev, torch.float32), f"barf_weights[{k}]")
+                                                     for k, w in enumerate(kwargs["barf_weights"])))
+        pe_w_xyz, pe_w_dir = rnd._pe_weights(models, embeddings, kwargs, dev)
         view_dir = kwargs.get("view_dir")
         if view_dir is not None:
             view_dir = rnd._f32c(view_dir.to(dev), "view_dir", (R, 3)).index_select(0, self.order).contiguous()
@@ -152,12 +147,10 @@ class AppearanceFit:
         self.opacity = torch.empty(R, dtype=torch.float32, device=dev)
         self.z_sorted = torch.empty(R, F, dtype=torch.float32, device=dev)
         zeros_a = torch.zeros(min(chunk, R), self.n_a, dtype=torch.float32, device=dev)
-        for lo in range(0, R, chunk):
-            hi = min(lo + chunk, R)
-            r = rays_s[lo:hi]
-            vd = None if view_dir is None else view_dir[lo:hi]
+        for lo, hi, r, _, kw in _chunks(rays_s, None, chunk, dict(view_dir=view_dir, z_fine=z_in)):
+            vd = kw.get("view_dir")
             if z_in is not None:
-                self.z_sorted[lo:hi] = z_in[lo:hi]
+                self.z_sorted[lo:hi] = kw["z_fine"]
             else:
                 oc = rnd._run_pass(f_c, r, S, lin=rnd._linspace(S, dev), use_disp=use_disp, view_dir=vd, sigma_only=True,
                                    white_back=white_back, want_z=True, pe_w_xyz=pe_w_xyz, pe_w_dir=pe_w_dir)
@@ -211,7 +204,7 @@ class AppearanceFit:
                 done = 1
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph(keep_graph=True)     # kept after instantiation, so that its nodes can be inspected
-                with torch.cuda.graph(g):
+                with torch.cuda.graph(g, **rnd._capture_mode()):
                     self._iteration()
                 g.instantiate()
                 self._graph = g

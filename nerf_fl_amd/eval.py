@@ -13,10 +13,36 @@ per-key results.  Differences that matter on MI355X:
 import torch
 
 from . import parallel
+from . import rendering as rnd
 from .rendering import CameraRays, render_rays
 
 __all__ = ["batched_inference", "GraphedChunk", "frame_rays", "to_uint8", "dolly_path", "render_frame", "render_video",
            "fit_and_evaluate_halves", "evaluate_bank", "clipped_inference"]
+
+
+def _chunks(rays, ts, chunk, per_ray=None):
+    """Walk B rays in chunks of at most `chunk`: yields (lo, hi, rays chunk, ts chunk, per-ray kwargs of the chunk).
+    `rays`: a CameraRays (CameraRays.slice) or a matrix (row slice); `ts` may be None (reference eval.py:94).  A per-ray
+    kwarg follows its chunk: a (B, C) tensor is sliced, a (1, C) one (one latent code for the whole frame,
+    test_phototourism.ipynb cell 11) is expanded to the chunk's length; None entries are dropped."""
+    B = rays.shape[0]
+    for lo in range(0, B, chunk):
+        hi = min(lo + chunk, B)
+        r = rays.slice(lo, hi) if isinstance(rays, CameraRays) else rays[lo:hi]
+        kw = {k: v[lo:hi] if v.shape[0] == B and B != 1 else v.expand(hi - lo, -1)
+              for k, v in (per_ray or {}).items() if v is not None}
+        yield lo, hi, r, None if ts is None else ts[lo:hi], kw
+
+
+def _fill_padded(buf, v, n):
+    """Fill the static buffer `buf` from the n rows `v` of a (possibly ragged) chunk: rows [0, n) are v, the rest repeat
+    its last row; a 1-row `v` fills every row."""
+    if v.shape[0] == 1:
+        buf.copy_(v.expand_as(buf))
+        return
+    buf[:n].copy_(v)
+    if n < buf.shape[0]:
+        buf[n:].copy_(v[-1:].expand(buf.shape[0] - n, *v.shape[1:]))
 
 
 class GraphedChunk:
@@ -34,8 +60,6 @@ class GraphedChunk:
     def __init__(self, models, embeddings, chunk, device, N_samples, use_disp, N_importance, white_back, camera=False,
                  **kwargs):
         import weakref
-
-        from . import rendering as rnd
         self.chunk, self.device = chunk, torch.device(device)
         self.camera = bool(camera)
         self.model_refs = {k: weakref.ref(m) for k, m in models.items()}
@@ -67,10 +91,7 @@ class GraphedChunk:
         n_xyz, n_dir = rnd._n_freqs(embeddings["xyz"]), rnd._n_freqs(embeddings["dir"])
         self.fields = [rnd._field(m, n_xyz, n_dir, self.device, pack=False) for m in models.values()]
         self.graph = torch.cuda.CUDAGraph()
-        import torch.distributed as dist
-        # a process group's watchdog thread may query events while we capture: confine the capture checks to this thread
-        mode = dict(capture_error_mode="thread_local") if dist.is_available() and dist.is_initialized() else {}
-        with torch.no_grad(), torch.cuda.graph(self.graph, **mode):
+        with torch.no_grad(), torch.cuda.graph(self.graph, **rnd._capture_mode()):
             self.out = run()
 
     def alive_for(self, models):
@@ -78,7 +99,6 @@ class GraphedChunk:
         return set(models) == set(self.model_refs) and all(self.model_refs[k]() is m for k, m in models.items())
 
     def __call__(self, rays, ts, **per_ray):
-        from . import rendering as rnd
         n = rays.shape[0]
         if n > self.chunk:
             raise ValueError(f"GraphedChunk captured for {self.chunk} rays, got {n}")
@@ -90,25 +110,15 @@ class GraphedChunk:
         elif self.camera:
             raise ValueError("this GraphedChunk was captured for CameraRays input")
         if not isinstance(rays, CameraRays):
-            self.rays[:n].copy_(rays)
-            if n < self.chunk:                                   # ragged tail: repeat the last ray
-                self.rays[n:].copy_(rays[-1:].expand(self.chunk - n, -1))
+            _fill_padded(self.rays, rays, n)
         if ts is not None:
-            self.ts[:n].copy_(ts)
-            if n < self.chunk:
-                self.ts[n:].copy_(ts[-1:].expand(self.chunk - n))
+            _fill_padded(self.ts, ts, n)
         if set(per_ray) - set(self.kw_static):
             raise ValueError(f"per-ray kwargs {sorted(set(per_ray) - set(self.kw_static))} were not part of the capture")
         for k, buf in self.kw_static.items():
             if k not in per_ray:
                 raise ValueError(f"this GraphedChunk was captured with `{k}`: pass it on every call")
-            v = per_ray[k]
-            if v.shape[0] == 1:
-                buf.copy_(v.expand(self.chunk, -1))
-            else:                                            # per-ray values of a (possibly ragged) chunk
-                buf[:n].copy_(v)
-                if n < self.chunk:
-                    buf[n:].copy_(v[-1:].expand(self.chunk - n, -1))
+            _fill_padded(buf, per_ray[k], n)
         # weights moved since the streams were packed (optimizer step, load_state_dict)?  re-pack eagerly: the captured
         # kernels read the same buffers
         rnd._pack_streams(self.fields, bwd=False, rays_grad=False)
@@ -121,7 +131,6 @@ _GRAPH_CACHE = {}      # default cache of batched_inference(use_graph=True): one
 
 def _graph_key(models, embeddings, rays, chunk, N_samples, N_importance, use_disp, white_back, kwargs):
     """Everything that changes the captured launch sequence or the buffers it reads."""
-    from . import rendering as rnd
     return (chunk, N_samples, N_importance, bool(use_disp), bool(white_back), str(rays.device), isinstance(rays, CameraRays),
             tuple(sorted((k, id(m)) for k, m in models.items())), tuple(sorted((k, id(e)) for k, e in embeddings.items())),
             tuple(sorted(k for k in kwargs if kwargs[k] is not None and k in GraphedChunk.PER_RAY)),
@@ -136,7 +145,6 @@ def batched_inference(models, embeddings, rays, ts, N_samples, N_importance, use
     Returns a dict of GPU tensors covering all `rays`.  With `use_graph` the chunk is captured once per distinct call
     signature (models, kwargs present, `output_transient`, shapes, precision) and kept in `_graph_cache` (default: a
     module-level cache), so repeated calls replay instead of re-capturing."""
-    B = rays.shape[0]
     results = {}
     runner = None
     if use_graph:
@@ -146,17 +154,7 @@ def batched_inference(models, embeddings, rays, ts, N_samples, N_importance, use
             cache[key] = GraphedChunk(models, embeddings, chunk, rays.device, N_samples, use_disp, N_importance,
                                       white_back, camera=isinstance(rays, CameraRays), **kwargs)
         runner = cache[key]
-    for i in range(0, B, chunk):
-        r = rays.slice(i, i + chunk) if isinstance(rays, CameraRays) else rays[i:i + chunk]
-        t = ts[i:i + chunk] if ts is not None else None         # reference eval.py:94
-        n = r.shape[0]
-        # per-ray kwargs follow their chunk: a (B, C) tensor is sliced, a (1, C) one (one latent code for the whole
-        # frame, test_phototourism.ipynb cell 11) is broadcast
-        per_ray = {}
-        for k in GraphedChunk.PER_RAY:
-            v = kwargs.get(k)
-            if v is not None:
-                per_ray[k] = v[i:i + chunk] if v.shape[0] == B and B != 1 else v.expand(n, -1)
+    for _, _, r, t, per_ray in _chunks(rays, ts, chunk, {k: kwargs.get(k) for k in GraphedChunk.PER_RAY}):
         if runner is not None:
             out = {k: v.clone() for k, v in runner(r, t, **per_ray).items()}
         else:
@@ -257,29 +255,48 @@ def fit_and_evaluate_halves(models, embeddings, c2w, K, H, W, near, far, rgb, N_
     `view_dir` is given for the whole image (H*W, 3) and split into the halves; any other kwarg (max_cache_bytes, ...)
     goes to AppearanceFit."""
     import math
-
-    from .appearance import AppearanceFit
     dev = torch.device(device)
     rays = frame_rays(c2w, K, H, W, near, far, dev)
     rgb = torch.as_tensor(rgb).to(dev, torch.float32).reshape(H * W, 3)
-    left = torch.arange(H * W, device=dev) % W < W // 2
-    rays_l, rgb_l, rays_r, rgb_r = rays[left], rgb[left], rays[~left], rgb[~left]
-    start = None if init is None else torch.as_tensor(init, dtype=torch.float32).reshape(1, -1)
-    shared = {k: kwargs.pop(k) for k in ("barf_weights", "current_epoch") if kwargs.get(k) is not None}
-    fit_kw, render_kw = dict(kwargs, **shared), dict(shared)
-    if kwargs.get("view_dir") is not None:
-        view_dir = torch.as_tensor(kwargs["view_dir"]).to(dev, torch.float32).reshape(H * W, 3)
-        fit_kw["view_dir"], render_kw["view_dir"] = view_dir[left], view_dir[~left]
-    fit = AppearanceFit(models, embeddings, rays_l, rgb_l, torch.zeros(rays_l.shape[0], dtype=torch.int64, device=dev),
-                        N_samples, N_importance, use_disp=use_disp, white_back=white_back, init=start, lr=lr, chunk=chunk,
-                        **fit_kw)
-    code = fit.fit(n_iters, use_graph=use_graph)[0].clone()
-    del fit                                 # the cache is 512 B per padded sample: free it before the right half
+    render_kw = {k: kwargs.pop(k) for k in ("barf_weights", "current_epoch", "view_dir") if kwargs.get(k) is not None}
+    if "view_dir" in render_kw:
+        render_kw["view_dir"] = torch.as_tensor(render_kw["view_dir"]).to(dev, torch.float32).reshape(H * W, 3)
+    code = _fit_left_half(models, embeddings, rays, rgb, H, W, N_samples, N_importance,
+                          dict(kwargs, n_iters=n_iters, lr=lr, init=init), render_kw, use_disp=use_disp,
+                          white_back=white_back, chunk=chunk, use_graph=use_graph)
+    right = torch.arange(H * W, device=dev) % W >= W // 2
+    if "view_dir" in render_kw:
+        render_kw["view_dir"] = render_kw["view_dir"][right]
     with torch.no_grad():
-        res = batched_inference(models, embeddings, rays_r, None, N_samples, N_importance, use_disp, chunk, white_back,
-                                output_transient=False, a_embedded=code[None], **render_kw)
-    mse = ((res["rgb_fine"] - rgb_r) ** 2).mean().item()
+        res = batched_inference(models, embeddings, rays[right], None, N_samples, N_importance, use_disp, chunk, white_back,
+                                **render_kw)
+    mse = ((res["rgb_fine"] - rgb[right]) ** 2).mean().item()
     return code, (-10.0 * math.log10(mse) if mse > 0 else float("inf"))
+
+
+def _fit_left_half(models, embeddings, rays, rgbs, H, W, N_samples, N_importance, fit_kw, render_kw, *, use_disp,
+                   white_back, chunk, use_graph):
+    """Fit the appearance code of one H x W image (rays (H*W, 8), colours rgbs (H*W, 3)) on its left half, for the render
+    that follows.  fit_kw: `n_iters` (default 300), `lr` (0.05), `init` ((N_a,); default the mean of the table) and any
+    other AppearanceFit argument.  render_kw: the kwargs of that render: its `barf_weights` / `current_epoch` go to the
+    fit as well, of its `view_dir` (H*W, 3) the fit takes the left half, and it GAINS output_transient=False and
+    a_embedded=code[None].  Returns the code (N_a,); the fit's cache (512 B per padded sample) is free by then."""
+    from .appearance import AppearanceFit
+    dev = rays.device
+    left = torch.arange(H * W, device=dev) % W < W // 2
+    fit_kw = dict(fit_kw)
+    n_iters, init = fit_kw.pop("n_iters", 300), fit_kw.pop("init", None)
+    fit_kw.setdefault("lr", 0.05)
+    fit_kw.update({k: render_kw[k] for k in ("barf_weights", "current_epoch") if render_kw.get(k) is not None})
+    if render_kw.get("view_dir") is not None:
+        fit_kw["view_dir"] = render_kw["view_dir"][left]
+    rays_l = rays[left]
+    fitter = AppearanceFit(models, embeddings, rays_l, rgbs[left], torch.zeros(rays_l.shape[0], dtype=torch.int64, device=dev),
+                           N_samples, N_importance, use_disp=use_disp, white_back=white_back, chunk=chunk,
+                           init=None if init is None else torch.as_tensor(init, dtype=torch.float32).reshape(1, -1), **fit_kw)
+    code = fitter.fit(n_iters, use_graph=use_graph)[0].clone()
+    render_kw.update(output_transient=False, a_embedded=code[None])
+    return code
 
 
 def evaluate_bank(models, embeddings, bank, N_samples, N_importance, *, images=None, ts=None, halves=False, fit=None,
@@ -307,7 +324,6 @@ def evaluate_bank(models, embeddings, bank, N_samples, N_importance, *, images=N
     return_images / return_depth, `frames` / `depths`: lists of uint8 (h, w, 3) device tensors of the shard's images
     (the scored region; depths through metrics.depth_image)."""
     from . import metrics
-    from .appearance import AppearanceFit
     if bank.device is None:
         raise RuntimeError("evaluate_bank: the bank is not on a device (this build has no CPU path)")
     dev = bank.device
@@ -346,25 +362,12 @@ def evaluate_bank(models, embeddings, bank, N_samples, N_importance, *, images=N
                 rays, rgbs, _ = bank.frame(i)
             else:
                 rays, rgbs = frame_rays(c2w, K, H, W, near, far, dev), bank.frame(i)[1]
-            left = torch.arange(H * W, device=dev) % W < W // 2
-            fit_kw = dict(fit)
-            n_iters, init = fit_kw.pop("n_iters", 300), fit_kw.pop("init", None)
-            fit_kw.setdefault("lr", 0.05)
-            shared = {key: kwargs[key] for key in ("barf_weights", "current_epoch") if kwargs.get(key) is not None}
-            if kwargs.get("view_dir") is not None:
-                fit_kw["view_dir"] = kwargs["view_dir"][left]
-            rays_l = rays[left]
-            fitter = AppearanceFit(models, embeddings, rays_l, rgbs[left],
-                                   torch.zeros(rays_l.shape[0], dtype=torch.int64, device=dev), N_samples, N_importance,
-                                   use_disp=use_disp, white_back=white_back, chunk=chunk,
-                                   init=None if init is None else torch.as_tensor(init, dtype=torch.float32).reshape(1, -1),
-                                   **fit_kw, **shared)
-            code = fitter.fit(n_iters, use_graph=use_graph)[0].clone()
-            del fitter, rays, rgbs, rays_l                       # the cache is 512 B per padded sample: free it first
+            code = _fit_left_half(models, embeddings, rays, rgbs, H, W, N_samples, N_importance, fit, render_kw,
+                                  use_disp=use_disp, white_back=white_back, chunk=chunk, use_graph=use_graph)
+            del rays, rgbs
             if codes is None:
                 codes = torch.zeros(n, code.shape[0], dtype=torch.float32, device=dev)
             codes[k] = code
-            render_kw.update(output_transient=False, a_embedded=code[None])
         else:
             t_id = int(rec["id"]) if ts is None else (ts if isinstance(ts, int) else ts[k])
             t = torch.full((H * W,), t_id, dtype=torch.long, device=dev)

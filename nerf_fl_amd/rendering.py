@@ -193,6 +193,37 @@ def fill_barf_weights(embeddings, epoch, buffers):
     return buffers
 
 
+def _pe_weights(models, embeddings, kwargs, dev):
+    """(pe_w_xyz, pe_w_dir): the BARF per-frequency weights of both encodings on `dev` for a refine_pose field, (None,
+    None) for any other."""
+    if not getattr(models["coarse"], "refine_pose", False):
+        return None, None
+    if kwargs.get("barf_weights") is not None:
+        # build-defined: the BARF weights as device buffers the caller owns and refills per epoch (fill_barf_weights),
+        # so that a captured step reads the current epoch's weights without a host -> device copy of its own
+        w_xyz, w_dir = kwargs["barf_weights"]
+        for name, w, key in (("barf_weights[0]", w_xyz, "xyz"), ("barf_weights[1]", w_dir, "dir")):
+            n = _n_freqs(embeddings[key])
+            if not (isinstance(w, torch.Tensor) and w.device == dev and w.dtype == torch.float32
+                    and tuple(w.shape) == (n,) and w.is_contiguous() and w.data_ptr() % 16 == 0):
+                raise ValueError(f"`{name}` must be a 16-byte aligned, contiguous fp32 ({n},) tensor on {dev}")
+        return w_xyz.detach(), w_dir.detach()
+    # BARF (reference rendering.py:105-108, 235-238): coarse-to-fine weights of both encodings
+    epoch = kwargs.get("current_epoch")
+    if epoch is None:
+        raise KeyError("current_epoch")
+    return _barf_weights(embeddings["xyz"], epoch).to(dev), _barf_weights(embeddings["dir"], epoch).to(dev)
+
+
+def _capture_mode():
+    """kwargs of torch.cuda.graph for every capture of this package.  With a process group alive, its watchdog thread
+    polls the events of earlier collectives (hipEventQuery) at any time; under the default "global" capture mode such a
+    call from ANOTHER thread invalidates the capture ("operation not permitted when stream is capturing").  thread_local
+    confines the checks to the capturing thread."""
+    import torch.distributed as dist
+    return dict(capture_error_mode="thread_local") if dist.is_available() and dist.is_initialized() else {}
+
+
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -585,45 +616,104 @@ def _g(grads, keys, name):
     return None if g is None else g.contiguous()
 
 
+def _run_compbwd(field_raw, z, n_rays, n_samples, *, noise, noise_std, use_t, white_back, grads, go, g_tsig_const,
+                 head=None, gmax=None):
+    """One nfl_composite_backward.  `grads`: the eight upstream gradients in the struct's order (weights, opacity, rgb,
+    depth, transient_sigmas, beta, rgb_static, rgb_transient), each a tensor or None; `go`: the device scalar everything is
+    scaled by (fused loss) or None.  Returns (head (R N, 9) fp32, gmax (NFL_GMAX_SLOTS) fp32 -- the loss scale source of
+    this pass, zeroed by the call); a caller that times the call passes its own."""
+    dev = field_raw.device
+    if head is None:
+        head = torch.empty(n_rays * n_samples, 9, dtype=torch.float32, device=dev)
+    if gmax is None:
+        gmax = torch.empty(_lib.NFL_GMAX_SLOTS, dtype=torch.float32, device=dev)
+    a = _lib.CompBwdArgs()
+    a.d_field_raw, a.d_z, a.d_noise = _ptr(field_raw), _ptr(z), _ptr(noise)
+    a.noise_std, a.n_rays, a.n_samples = float(noise_std), n_rays, n_samples
+    a.use_transient, a.white_back = int(bool(use_t)), int(bool(white_back))
+    (a.g_weights, a.g_opacity, a.g_rgb, a.g_depth, a.g_transient_sigmas, a.g_beta, a.g_rgb_static,
+     a.g_rgb_transient) = [_ptr(g) for g in grads]
+    a.g_tsig_const, a.d_go = float(g_tsig_const), _ptr(go)
+    a.d_head_grads, a.d_gmax = _ptr(head), _ptr(gmax)
+    _lib.check(_lib.lib().nfl_composite_backward(C.byref(a), _stream()), "nfl_composite_backward")
+    return head, gmax
+
+
+def _grad_stash(field, n_rays, n_samples, bprec, dev):
+    nb = _lib.lib().nfl_grad_stash_bytes(C.byref(field.desc), n_rays, n_samples, bprec)
+    return torch.empty(nb, dtype=torch.uint8, device=dev)
+
+
+def _run_dgrad(field, act_stash, head, gmax, n_rays, n_samples, *, use_t, bprec, rays_grad=False, grad_stash=None,
+               g_a=None, g_t=None, latent_row=None, g_rays=None, rays=None, z=None, dir_is_data=False, pe_w_xyz=None,
+               pe_w_dir=None):
+    """One nfl_mlp_dgrad on the stream field.bwd_plan(rays_grad, bprec) (packed by the caller).  g_a / g_t: the latent
+    gradients, per ray or -- with `latent_row` (R,) int64 -- the tables' (scatter-added in the kernel); g_rays with `rays`
+    and `z`: the ray gradient.  Returns grad_stash (nfl_grad_stash_bytes; allocated when None)."""
+    if grad_stash is None:
+        grad_stash = _grad_stash(field, n_rays, n_samples, bprec, head.device)
+    a = _lib.DgradArgs()
+    a.d_head_grads, a.d_act_stash, a.d_grad_stash = _ptr(head), _ptr(act_stash), _ptr(grad_stash)
+    a.n_rays, a.n_samples, a.use_transient = n_rays, n_samples, int(bool(use_t))
+    a.d_g_a_emb, a.d_g_t_emb, a.d_gmax = _ptr(g_a), _ptr(g_t), _ptr(gmax)
+    a.rounding_seed = _rounding_seed
+    a.d_latent_row = _ptr(latent_row)
+    if g_rays is not None:
+        a.d_g_rays, a.d_rays, a.d_z = _ptr(g_rays), _ptr(rays), _ptr(z)
+        a.dir_is_data = int(bool(dir_is_data))
+        a.d_pe_w_xyz, a.d_pe_w_dir = _ptr(pe_w_xyz), _ptr(pe_w_dir)
+    bp = field.bwd_plan(rays_grad, bprec)
+    _lib.check(_lib.lib().nfl_mlp_dgrad(bp["h"], _ptr(bp["d"]), _ptr(bp["packed"]), C.byref(a), _stream()), "nfl_mlp_dgrad")
+    return grad_stash
+
+
+def _wg_scratch(field):
+    """nfl_mlp_wgrad's workspace (G + the workgroups' partial sums, 68 MB): one per field, reused by every step."""
+    if field.wg_scratch is None:
+        field.wg_scratch = torch.empty(_lib.lib().nfl_wgrad_scratch_bytes() // 4, dtype=torch.float32, device=field.device)
+    return field.wg_scratch
+
+
+def _run_wgrad(field, act_stash, grad_stash, gmax, n_rays, n_samples, *, use_t, bprec, targets, scratch=None):
+    """One nfl_mlp_wgrad.  `targets`: layer index (NFL_P_* order, field.param_list()) -> (weight gradient or None, bias
+    gradient or None), tensors the call writes; a layer left out gets NULL pointers.  `scratch`: default the field's own."""
+    fg = _lib.FieldGrads()
+    for i, (gw, gb) in targets.items():
+        fg.weight[i], fg.bias[i] = _ptr(gw), _ptr(gb)
+    scratch = _wg_scratch(field) if scratch is None else scratch
+    h_wp, d_wp = field.wgrad_plan(use_t)
+    fp, _keep = field._field_params()          # the fp32 weights the forward ran with (read by the composition)
+    _lib.check(_lib.lib().nfl_mlp_wgrad(h_wp, _ptr(d_wp), _ptr(act_stash), _ptr(grad_stash), _ptr(gmax), n_rays, n_samples,
+                                        bprec, C.byref(fp), _ptr(scratch), C.byref(fg), _stream()), "nfl_mlp_wgrad")
+
+
 def _backward_pass(field, rays, st, typ, keys, grads, cfg, want_latents, g_rays=None):
     """One pass (coarse or fine) of the hand-written backward.  Returns (flat fp32 parameter
     gradient arena views per parameter, g_a_emb, g_t_emb)."""
-    L = _lib.lib()
     R, N, dev = rays.shape[0], st["n"], rays.device
     use_t = bool(st["use_t"])
+    # head, grad_stash and the wgrad scratch are allocated here, not by the wrappers' defaults: the order of this
+    # function's allocations (head, upstream copies, gmax, grad_stash, latents, scratch, block) is the one it always had
     head = torch.empty(R * N, 9, dtype=torch.float32, device=dev)
-    ca = _lib.CompBwdArgs()
-    ca.d_field_raw, ca.d_z, ca.d_noise = _ptr(st["field_raw"]), _ptr(st["z"]), _ptr(st["noise"])
-    ca.noise_std, ca.n_rays, ca.n_samples = float(cfg["noise_std"]), R, N
-    ca.use_transient, ca.white_back = int(use_t), int(bool(cfg["white_back"]))
+    go, g_tsig_const = None, 0.0
     if cfg["loss"] is not None:
         # fused NerfWLoss: the forward epilogue left d loss / d rgb (and d beta) per ray; s_l's gradient w.r.t. every
         # transient density is the constant coef * lambda_u / (R N); everything is scaled by the upstream gradient of
         # the total on the device (d_go)
-        keep = [None, None, st["seed_rgb"], None, None, st["seed_beta"] if use_t else None, None, None]
+        up = [None, None, st["seed_rgb"], None, None, st["seed_beta"] if use_t else None, None, None]
         go = _g(grads, keys, "_nerfw_loss")
         if go is None:
             go = torch.zeros((), dtype=torch.float32, device=dev)
-        keep.append(go)
-        ca.d_go = _ptr(go)
         if use_t:
-            ca.g_tsig_const = float(cfg["loss"]["coef"]) * float(cfg["loss"]["lambda_u"]) / float(R * N)
+            g_tsig_const = float(cfg["loss"]["coef"]) * float(cfg["loss"]["lambda_u"]) / float(R * N)
     else:
-        keep = [_g(grads, keys, f"weights_{typ}"), _g(grads, keys, f"opacity_{typ}"), _g(grads, keys, f"rgb_{typ}"),
-                _g(grads, keys, f"depth_{typ}")]
-        if use_t:
-            keep += [_g(grads, keys, "transient_sigmas"), _g(grads, keys, "beta"), _g(grads, keys, "_rgb_fine_static"),
-                     _g(grads, keys, "_rgb_fine_transient")]
-        else:
-            keep += [None, None, None, None]
-    (ca.g_weights, ca.g_opacity, ca.g_rgb, ca.g_depth, ca.g_transient_sigmas, ca.g_beta, ca.g_rgb_static,
-     ca.g_rgb_transient) = [_ptr(k) for k in keep[:8]]
-    ca.d_head_grads = _ptr(head)
-    gmax = torch.empty(_lib.NFL_GMAX_SLOTS, dtype=torch.float32, device=dev)   # loss scale source of this pass (zeroed by the call)
-    ca.d_gmax = _ptr(gmax)
-    _lib.check(L.nfl_composite_backward(C.byref(ca), _stream()), "nfl_composite_backward")
+        names = [f"weights_{typ}", f"opacity_{typ}", f"rgb_{typ}", f"depth_{typ}"]
+        names += ["transient_sigmas", "beta", "_rgb_fine_static", "_rgb_fine_transient"] if use_t else []
+        up = [_g(grads, keys, k) for k in names] + [None] * (8 - len(names))
+    head, gmax = _run_compbwd(st["field_raw"], st["z"], R, N, noise=st["noise"], noise_std=cfg["noise_std"], use_t=use_t,
+                              white_back=cfg["white_back"], grads=up, go=go, g_tsig_const=g_tsig_const, head=head)
 
-    grad_stash = torch.empty(L.nfl_grad_stash_bytes(C.byref(field.desc), R, N, cfg["bprec"]), dtype=torch.uint8, device=dev)
+    grad_stash = _grad_stash(field, R, N, cfg["bprec"], dev)
     g_a = g_t = None
     tables = cfg["latent_tables"]
     arena = cfg["arena"]
@@ -639,49 +729,31 @@ def _backward_pass(field, rays, st, typ, keys, grads, cfg, want_latents, g_rays=
         g_a = latent_grad(cfg.get("table_a"), cfg.get("n_vocab_a"), field.desc.n_a)
     if want_latents and use_t:
         g_t = latent_grad(cfg.get("table_t"), cfg.get("n_vocab_t"), field.desc.n_tau)
-    da = _lib.DgradArgs()
-    da.d_head_grads, da.d_act_stash, da.d_grad_stash = _ptr(head), _ptr(st["act"]), _ptr(grad_stash)
-    da.n_rays, da.n_samples, da.use_transient = R, N, int(use_t)
-    da.d_g_a_emb, da.d_g_t_emb, da.d_gmax = _ptr(g_a), _ptr(g_t), _ptr(gmax)
-    da.rounding_seed = _rounding_seed
-    if tables and want_latents:
-        da.d_latent_row = _ptr(cfg["ts"])       # the scatter-add into the table gradients happens in the kernel
-    if g_rays is not None:
-        da.d_g_rays, da.d_rays, da.d_z = _ptr(g_rays), _ptr(rays), _ptr(st["z"])
-        da.dir_is_data = int(cfg["view_dir"] is not None)
-        da.d_pe_w_xyz, da.d_pe_w_dir = _ptr(cfg["pe_w_xyz"]), _ptr(cfg["pe_w_dir"])
-    bp = field.bwd_plan(cfg["rays_grad"], cfg["bprec"])      # packed by render_rays; the weights are the forward's
-    _lib.check(L.nfl_mlp_dgrad(bp["h"], _ptr(bp["d"]), _ptr(bp["packed"]), C.byref(da), _stream()), "nfl_mlp_dgrad")
+    ray_kw = {} if g_rays is None else dict(g_rays=g_rays, rays=rays, z=st["z"], dir_is_data=cfg["view_dir"] is not None,
+                                            pe_w_xyz=cfg["pe_w_xyz"], pe_w_dir=cfg["pe_w_dir"])
+    # (the dgrad stream was packed by render_rays; the weights are the forward's.  With tables the scatter-add into the
+    # table gradients happens in the kernel)
+    _run_dgrad(field, st["act"], head, gmax, R, N, use_t=use_t, bprec=cfg["bprec"], rays_grad=cfg["rays_grad"],
+               grad_stash=grad_stash, g_a=g_a, g_t=g_t, latent_row=cfg["ts"] if tables and want_latents else None, **ray_kw)
 
     plist = field.param_list()
-    n_scr = L.nfl_wgrad_scratch_bytes() // 4       # composition scratch (G: include/nerf_fl_amd.h, nfl_mlp_wgrad)
-    fg = _lib.FieldGrads()
-    views = []
-    # the call's workspace (G + the workgroups' partial sums, 68 MB): one per field, reused by every step
-    if field.wg_scratch is None:
-        field.wg_scratch = torch.empty(n_scr, dtype=torch.float32, device=dev)
-    scratch = field.wg_scratch
+    scratch = _wg_scratch(field)
     if arena is not None and all(arena.view(p) is not None for _, w, b in plist for p in (w, b)):
         # the caller's GradArena owns the gradient memory (p.grad are views of it): written in place, nothing returned
-        for i, w, b in plist:
-            fg.weight[i], fg.bias[i] = arena.view(w).data_ptr(), arena.view(b).data_ptr()
-            views += [None, None]
+        targets = {i: (arena.view(w), arena.view(b)) for i, w, b in plist}
+        views = [None] * (2 * len(plist))
     else:
         n_par = sum((w.numel() + 3) // 4 * 4 + (b.numel() + 3) // 4 * 4 for _, w, b in plist)
         block = torch.empty(n_par, dtype=torch.float32, device=dev)      # one allocation for the field's gradients (written by the call)
-        off = 0
+        targets, views, off = {}, [], 0
         for i, w, b in plist:
             gw = block[off:off + w.numel()].view_as(w)
             off += (w.numel() + 3) // 4 * 4
             gb = block[off:off + b.numel()].view_as(b)
             off += (b.numel() + 3) // 4 * 4
-            fg.weight[i], fg.bias[i] = gw.data_ptr(), gb.data_ptr()
+            targets[i] = (gw, gb)
             views += [gw, gb]
-    h_wp, d_wp = field.wgrad_plan(use_t)
-    fp, _keep = field._field_params()          # the fp32 weights the forward ran with (read by the composition)
-    _lib.check(L.nfl_mlp_wgrad(h_wp, _ptr(d_wp), _ptr(st["act"]), _ptr(grad_stash), _ptr(gmax), R, N, cfg["bprec"], C.byref(fp),
-                               C.c_void_p(scratch.data_ptr()), C.byref(fg), _stream()),
-               "nfl_mlp_wgrad")
+    _run_wgrad(field, st["act"], grad_stash, gmax, R, N, use_t=use_t, bprec=cfg["bprec"], targets=targets, scratch=scratch)
     return views, g_a, g_t
 
 
@@ -776,22 +848,7 @@ def render_rays(models, embeddings, rays, ts, N_samples=64, use_disp=False, pert
             cfg["loss"] = dict(target=_f32c(kwargs["loss_target"], "loss_target", (R, 3)),
                                losses=torch.zeros(4, dtype=torch.float32, device=dev),
                                coef=float(kwargs.get("loss_coef", 1.0)), lambda_u=float(kwargs.get("lambda_u", 0.01)))
-        if getattr(models["coarse"], "refine_pose", False) and kwargs.get("barf_weights") is not None:
-            # build-defined: the BARF weights as device buffers the caller owns and refills per epoch (fill_barf_weights),
-            # so that a captured step reads the current epoch's weights without a host -> device copy of its own
-            w_xyz, w_dir = kwargs["barf_weights"]
-            for name, w, n in (("barf_weights[0]", w_xyz, n_xyz), ("barf_weights[1]", w_dir, n_dir)):
-                if not (isinstance(w, torch.Tensor) and w.device == dev and w.dtype == torch.float32
-                        and tuple(w.shape) == (n,) and w.is_contiguous() and w.data_ptr() % 16 == 0):
-                    raise ValueError(f"`{name}` must be a 16-byte aligned, contiguous fp32 ({n},) tensor on {dev}")
-            cfg["pe_w_xyz"], cfg["pe_w_dir"] = w_xyz.detach(), w_dir.detach()
-        elif getattr(models["coarse"], "refine_pose", False):
-            # BARF (reference rendering.py:105-108, 235-238): coarse-to-fine weights of both encodings
-            epoch = kwargs.get("current_epoch")
-            if epoch is None:
-                raise KeyError("current_epoch")
-            cfg["pe_w_xyz"] = _barf_weights(embeddings["xyz"], epoch).to(dev)
-            cfg["pe_w_dir"] = _barf_weights(embeddings["dir"], epoch).to(dev)
+        cfg["pe_w_xyz"], cfg["pe_w_dir"] = _pe_weights(models, embeddings, kwargs, dev)
         if kwargs.get("view_dir") is not None:
             if kwargs["view_dir"].requires_grad and torch.is_grad_enabled():
                 raise NotImplementedError("gradient w.r.t. `view_dir` (no caller of the reference asks for it); detach it")

@@ -24,6 +24,7 @@ import torch
 from torch import nn
 
 from . import _lib, parallel
+from .eval import _chunks
 from .nerf import BarfPosEmbedding, NeRF, PosEmbedding
 from .poses import LearnPose, posed_rays, row_table
 from .rendering import fill_barf_weights, render_rays
@@ -609,10 +610,7 @@ class GraphedTrainStep:
         self.graph_opt = None
         from . import rendering
         self.rounding_seed = rendering._rounding_seed      # a by-value kernel argument: replays keep this one
-        # With a process group alive, its watchdog thread polls the events of earlier collectives (hipEventQuery) at any
-        # time; under the default "global" capture mode such a call from ANOTHER thread invalidates the capture
-        # ("operation not permitted when stream is capturing").  thread_local confines the checks to this thread.
-        mode = dict(capture_error_mode="thread_local") if dist.is_initialized() else {}
+        mode = rendering._capture_mode()
         with torch.cuda.graph(self.graph, **mode):
             self.out = fwd_bwd()
             if self.all_reduce and self.captured_collective:
@@ -923,11 +921,10 @@ class RayTrainer:
         hp = self.hp
         self._sync_barf()
         outs = []
-        for i in range(0, rays.shape[0], chunk):
-            r = rays[i:i + chunk]
+        for _, _, r, t, _ in _chunks(rays, ts, chunk):
             if self.refine_pose and r.shape[1] != 8:      # the training layout, through the learned poses
-                r = posed_rays(self.pose, r, ts[i:i + chunk], self.row_of_id)
-            res = render_rays(self.models, self.embeddings, r, ts[i:i + chunk], hp["N_samples"], hp["use_disp"], 0, 0,
+                r = posed_rays(self.pose, r, t, self.row_of_id)
+            res = render_rays(self.models, self.embeddings, r, t, hp["N_samples"], hp["use_disp"], 0, 0,
                               hp["N_importance"], chunk, hp["white_back"], False, barf_weights=self.barf_w)
             outs.append(res["rgb_fine" if "rgb_fine" in res else "rgb_coarse"])
         return torch.cat(outs)

@@ -19,7 +19,7 @@ m = NeRF("fine")
 m.load_state_dict(orc.make_field_params(orc.FieldSpec("fine"), 12, "sharp"))
 m = m.to(dev)
 f = rnd._field(m, 10, 4, dev)
-bp = f.ensure_bwd_packed(False)
+f.ensure_bwd_packed(False, _lib.NFL_PREC_F16)
 rays = orc.make_rays(R, 100).to(dev)
 z = torch.sort(2 + 4 * torch.rand(R, F, device=dev), dim=1)[0]
 noise = torch.randn(R, F, device=dev)
@@ -28,10 +28,7 @@ L = _lib.lib()
 head = torch.randn(R * F, 9, device=dev) * 1e-3
 gmax = torch.full((1024,), 4e-3, device=dev)
 grad_stash = torch.empty(L.nfl_grad_stash_bytes(C.byref(f.desc), R, F, _lib.NFL_PREC_F16), dtype=torch.uint8, device=dev)
-da = _lib.DgradArgs()
-da.d_head_grads, da.d_act_stash, da.d_grad_stash = rnd._ptr(head), rnd._ptr(out["act_stash"]), rnd._ptr(grad_stash)
-da.n_rays, da.n_samples, da.use_transient, da.d_gmax = R, F, 0, rnd._ptr(gmax)
-run = lambda: _lib.check(L.nfl_mlp_dgrad(bp["h"], rnd._ptr(bp["d"]), rnd._ptr(bp["packed"]), C.byref(da), rnd._stream()), "dg")
+run = lambda: rnd._run_dgrad(f, out["act_stash"], head, gmax, R, F, use_t=False, bprec=_lib.NFL_PREC_F16, grad_stash=grad_stash)
 for _ in range(10):
     run()
 torch.cuda.synchronize()

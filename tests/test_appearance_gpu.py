@@ -101,6 +101,29 @@ def test_render_matches_render_rays_on_photo_rays():
     assert err <= 1e-5
 
 
+@pytest.mark.parametrize("inject", [False, True])
+def test_cache_is_the_same_whatever_the_chunk(inject):
+    """150 rays of 3 images with a per-ray view_dir: built in chunks of 64 + 64 + 22 rays, the cache, the weights, the
+    opacity and the fine depths are bit-identical to the ones built in one pass; with injected fine depths as well."""
+    cfg, a, specs, kw, models, emb, extra = _setup("g17_trained_cfg3", "trained")
+    R, S, I = 150, 32, 32
+    rays = orc.make_rays(R, 23).to(DEV)
+    gen = torch.Generator().manual_seed(29)
+    more = dict(view_dir=torch.nn.functional.normalize(torch.randn(R, 3, generator=gen), dim=1).to(DEV))
+    if inject:
+        more["z_fine"] = torch.sort(2.0 + 4.0 * torch.rand(R, S + I, generator=gen), dim=1)[0].to(DEV)
+    idx = _ragged_images(R, [70, 13, 67], 4).to(DEV)
+    rgb = torch.zeros(R, 3, device=DEV)
+    init = gu.embedding_table(cfg, "a")[[2, 3, 9]].to(DEV)
+    fits = [AppearanceFit(models, emb, rays, rgb, idx, S, I, white_back=True, init=init, chunk=chunk, **more)
+            for chunk in (64, 1024)]
+    for name in ("zcache", "weights", "opacity", "z_fine"):
+        assert torch.equal(getattr(fits[0], name), getattr(fits[1], name)), name
+    assert fits[0].zcache.shape[0] == R and float(fits[0].weights.abs().sum()) > 0
+    if inject:
+        assert torch.equal(fits[0].z_fine, more["z_fine"])
+
+
 # ---- 2. gradient ----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,regime", [("g17_trained_cfg3", "trained"), ("g14_barf_e9", None)])
 def test_gradient_matches_fp64_autograd(name, regime):

@@ -170,6 +170,31 @@ def test_graph_cache_is_keyed_by_everything_that_changes_the_launches():
     assert sizes == [1, 2, 3, 4, 5, 5]
 
 
+def test_per_ray_kwargs_follow_a_ragged_chunk():
+    """B = chunk + 37 rays with a B-row a_embedded and a B-row view_dir together: the chunk walk slices both, the graphed
+    chunk pads both; graphed == chunked without a graph == one direct render_rays on every key."""
+    import gpu_util
+    from nerf_fl_amd import render_rays
+    from nerf_fl_amd.eval import batched_inference
+    dev = gpu_util.DEV
+    models, emb = _nerfw_models(dev)
+    chunk, S, I = 128, 32, 32
+    B = chunk + 37
+    rays = orc.make_rays(B, 9, near=0.3, far=5.0).to(dev)
+    gen = torch.Generator().manual_seed(19)
+    kw = dict(a_embedded=torch.randn(B, 48, generator=gen).to(dev), output_transient=False,
+              view_dir=torch.nn.functional.normalize(torch.randn(B, 3, generator=gen), dim=1).to(dev))
+    graphed = batched_inference(models, emb, rays, None, S, I, chunk=chunk, white_back=True, use_graph=True, _graph_cache={},
+                                **kw)
+    chunked = batched_inference(models, emb, rays, None, S, I, chunk=chunk, white_back=True, **kw)
+    with torch.no_grad():
+        direct = render_rays(models, emb, rays, None, S, False, 0, 0, I, chunk, True, True, **kw)
+    assert list(graphed) == list(chunked) == list(direct)
+    for k in direct:
+        assert graphed[k].shape[0] == B
+        assert torch.equal(graphed[k], direct[k]) and torch.equal(chunked[k], direct[k]), k
+
+
 def test_graph_replay_follows_the_weights():
     """A cached capture must not render with the weights it was captured on (VERDICT r2 weak #10b): after
     load_state_dict and after an in-place optimizer-style update, with NO eager render in between, replay == eager."""

@@ -43,6 +43,20 @@ def test_fit_and_checkpoint(tmp_path):
     assert abs(tr2.validate(val, vrgb, vts) - p1) < 1e-4
 
 
+def test_validate_is_the_same_whatever_the_chunk():
+    """150 rays rendered as 64 + 64 + 22 give the PSNR of one pass exactly: the prediction is concatenated before it."""
+    import math
+
+    import gpu_util
+    from nerf_fl_amd.train import RayTrainer
+    dev = gpu_util.DEV
+    tr = RayTrainer(dev, N_samples=32, N_importance=32, encode_a=True, encode_t=True, N_vocab=8, batch_size=512, seed=3)
+    gen = torch.Generator().manual_seed(41)
+    val, rgbs = orc.make_rays(150, 33).to(dev), torch.rand(150, 3, generator=gen).to(dev)
+    ts = torch.randint(0, 8, (150,), generator=gen).to(dev)
+    whole = tr.validate(val, rgbs, ts, chunk=32768)
+    assert math.isfinite(whole) and tr.validate(val, rgbs, ts, chunk=64) == whole
+
 
 def test_trainer_with_graphed_steps_fits_like_the_eager_one():
     """RayTrainer(use_graph=True): every step of fit_epoch replayed from one captured HIP graph (what the README batch of 1024

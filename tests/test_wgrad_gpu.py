@@ -147,23 +147,14 @@ def run_wgrad(f, use_t, act, grd, gmax_value, n_rays, n_samples, backward, leave
             where[_lib.LAYER_NAMES[i] + suffix] = (off, p.numel(), tuple(p.shape), i)
             off += (p.numel() + 3) // 4 * 4 + GUARD
     arena = torch.full((off,), SENT, dtype=torch.float32, device=dev)
-    fg = _lib.FieldGrads()
-    for name, (o, n, _, i) in where.items():
-        if _lib.LAYER_NAMES[i] in leave_out:
-            continue
-        ptr = arena[o:o + n].data_ptr()
-        if name.endswith(".weight"):
-            fg.weight[i] = ptr
-        else:
-            fg.bias[i] = ptr
+    place = lambda name: arena[where[name][0]:where[name][0] + where[name][1]]
+    targets = {i: (place(_lib.LAYER_NAMES[i] + ".weight"), place(_lib.LAYER_NAMES[i] + ".bias"))
+               for i, _, _ in plist if _lib.LAYER_NAMES[i] not in leave_out}
     gmax = torch.zeros(_lib.NFL_GMAX_SLOTS, dtype=torch.float32, device=dev)
     gmax[GMAX_SLOT] = gmax_value
-    h_wp, d_wp = f.wgrad_plan(use_t)
-    fpar, _keep = f._field_params()
     scratch = torch.empty(L.nfl_wgrad_scratch_bytes() // 4, dtype=torch.float32, device=dev)
-    _lib.check(L.nfl_mlp_wgrad(h_wp, rnd._ptr(d_wp), rnd._ptr(act), rnd._ptr(grd), rnd._ptr(gmax), n_rays, n_samples,
-                               rnd._BPREC[backward], C.byref(fpar), rnd._ptr(scratch), C.byref(fg), rnd._stream()),
-               "nfl_mlp_wgrad")
+    rnd._run_wgrad(f, act, grd, gmax, n_rays, n_samples, use_t=use_t, bprec=rnd._BPREC[backward], targets=targets,
+                   scratch=scratch)
     torch.cuda.synchronize()
     host = arena.cpu()
     got = {name: host[o:o + n].view(shape).clone() for name, (o, n, shape, _) in where.items()}
@@ -292,7 +283,6 @@ def test_wgrad_on_real_stashes(R, N, kind, backward):
     import nerf_fl_amd
     from nerf_fl_amd import _lib, rendering as rnd
     dev = gpu_util.DEV
-    L = _lib.lib()
     lat = kind == "nerfw"
     BP = rnd._BPREC[backward]
     mult = 2 if backward == "f16x3" else 1
@@ -300,7 +290,7 @@ def test_wgrad_on_real_stashes(R, N, kind, backward):
     P = orc.make_field_params(spec, 81 + lat, "sharp")
     model = gpu_util.module_from(spec, P)
     f = rnd._field(model, 10, 4, torch.device(dev), prec=rnd._PREC["f16x3"])
-    bp = f.ensure_bwd_packed(False, BP)
+    f.ensure_bwd_packed(False, BP)
     rays, z = exact_rays(R, N, 5 * R + N)
     gen = torch.Generator().manual_seed(R + N)
     a_emb = torch.randn(R, 48, generator=gen).to(dev) if lat else None
@@ -311,22 +301,11 @@ def test_wgrad_on_real_stashes(R, N, kind, backward):
     # composite backward with a generic upstream gradient on every output the pass has
     g = {k: (torch.randn(*s, generator=gen) * 1e-2).to(dev) for k, s in
          dict(weights=(R, N), opacity=(R,), rgb=(R, 3), depth=(R,), tsig=(R, N), beta=(R,), rgb_s=(R, 3), rgb_t=(R, 3)).items()}
-    head = torch.empty(R * N, 9, dtype=torch.float32, device=dev)
+    up = [g[k] for k in ("weights", "opacity", "rgb", "depth")] + ([g[k] for k in ("tsig", "beta", "rgb_s", "rgb_t")] if lat else [None] * 4)
     gmax = torch.zeros(_lib.NFL_GMAX_SLOTS, dtype=torch.float32, device=dev)
-    ca = _lib.CompBwdArgs()
-    ca.d_field_raw, ca.d_z, ca.d_noise = rnd._ptr(out["field_raw"]), rnd._ptr(z_d), rnd._ptr(None)
-    ca.noise_std, ca.n_rays, ca.n_samples, ca.use_transient, ca.white_back = 0.0, R, N, int(lat), 1
-    ca.g_weights, ca.g_opacity, ca.g_rgb, ca.g_depth = (rnd._ptr(g[k]) for k in ("weights", "opacity", "rgb", "depth"))
-    if lat:
-        ca.g_transient_sigmas, ca.g_beta = rnd._ptr(g["tsig"]), rnd._ptr(g["beta"])
-        ca.g_rgb_static, ca.g_rgb_transient = rnd._ptr(g["rgb_s"]), rnd._ptr(g["rgb_t"])
-    ca.d_head_grads, ca.d_gmax = rnd._ptr(head), rnd._ptr(gmax)
-    _lib.check(L.nfl_composite_backward(C.byref(ca), rnd._stream()), "nfl_composite_backward")
-    grad_stash = torch.empty(L.nfl_grad_stash_bytes(C.byref(f.desc), R, N, BP), dtype=torch.uint8, device=dev)
-    da = _lib.DgradArgs()
-    da.d_head_grads, da.d_act_stash, da.d_grad_stash = rnd._ptr(head), rnd._ptr(out["act_stash"]), rnd._ptr(grad_stash)
-    da.n_rays, da.n_samples, da.use_transient, da.d_gmax = R, N, int(lat), rnd._ptr(gmax)
-    _lib.check(L.nfl_mlp_dgrad(bp["h"], rnd._ptr(bp["d"]), rnd._ptr(bp["packed"]), C.byref(da), rnd._stream()), "nfl_mlp_dgrad")
+    head, gmax = rnd._run_compbwd(out["field_raw"], z_d, R, N, noise=None, noise_std=0.0, use_t=lat, white_back=True, grads=up,
+                                  go=None, g_tsig_const=0.0, gmax=gmax)
+    grad_stash = rnd._run_dgrad(f, out["act_stash"], head, gmax, R, N, use_t=lat, bprec=BP)
     torch.cuda.synchronize()
     gmax_value = float(gmax.max())
     assert gmax_value > 0

@@ -22,7 +22,7 @@ f = rnd._field(m, 10, 4, dev)
 BWD = sys.argv[sys.argv.index("--backward") + 1] if "--backward" in sys.argv else "f16"      # f16 | f16x3
 nerf_fl_amd.set_precision(backward=BWD)
 BP = rnd._BPREC[BWD]
-bp = f.ensure_bwd_packed(False, BP)
+f.ensure_bwd_packed(False, BP)
 rays = orc.make_rays(R, 100).to(dev)
 z = torch.sort(2 + 4 * torch.rand(R, F, device=dev), dim=1)[0]
 noise = torch.randn(R, F, device=dev)
@@ -48,35 +48,25 @@ if prec == "f16x3":
     def fwd_stash():
         out.update(rnd._run_pass(f, rays, F, z=z, noise=noise, noise_std=1.0, white_back=True, stash=True, bprec=BP))
     print("fwd  (training stash) %.3f ms" % timeit(fwd_stash))
-    st = dict(z=z, field_raw=out["field_raw"], act=out["act_stash"], noise=noise, use_t=False, n=F)
-    cfg = dict(noise_std=1.0, white_back=True)
-    keys = ["weights_fine", "opacity_fine", "rgb_fine", "depth_fine"]
-    grads = [None, None, torch.randn(R, 3, device=dev) * 1e-3, None]
+    act = out["act_stash"]
+    up = [None, None, torch.randn(R, 3, device=dev) * 1e-3] + [None] * 5          # d rgb_fine only
     L = _lib.lib()
+    # every buffer a timed call touches exists before it: the wrappers allocate nothing then
     head = torch.empty(R * F, 9, device=dev)
-    grad_stash = torch.empty(L.nfl_grad_stash_bytes(C.byref(f.desc), R, F, BP), dtype=torch.uint8, device=dev)
-    ca = _lib.CompBwdArgs()
-    ca.d_field_raw, ca.d_z, ca.d_noise = rnd._ptr(st["field_raw"]), rnd._ptr(z), rnd._ptr(noise)
-    ca.noise_std, ca.n_rays, ca.n_samples, ca.use_transient, ca.white_back = 1.0, R, F, 0, 1
-    ca.g_rgb = rnd._ptr(grads[2])
-    ca.d_head_grads = rnd._ptr(head)
     gmax = torch.zeros(1024, device=dev)
-    ca.d_gmax = rnd._ptr(gmax)
-    print("composite backward    %.3f ms" % timeit(lambda: _lib.check(L.nfl_composite_backward(C.byref(ca), rnd._stream()), "cb")))
-    da = _lib.DgradArgs()
-    da.d_head_grads, da.d_act_stash, da.d_grad_stash = rnd._ptr(head), rnd._ptr(st["act"]), rnd._ptr(grad_stash)
-    da.n_rays, da.n_samples, da.use_transient = R, F, 0
-    da.d_gmax = rnd._ptr(gmax)
-    print("dgrad                 %.3f ms" % timeit(lambda: _lib.check(L.nfl_mlp_dgrad(bp['h'], rnd._ptr(bp['d']), rnd._ptr(bp['packed']), C.byref(da), rnd._stream()), "dg")))
+    grad_stash = torch.empty(L.nfl_grad_stash_bytes(C.byref(f.desc), R, F, BP), dtype=torch.uint8, device=dev)
+    print("composite backward    %.3f ms" % timeit(lambda: rnd._run_compbwd(
+        out["field_raw"], z, R, F, noise=noise, noise_std=1.0, use_t=False, white_back=True, grads=up, go=None,
+        g_tsig_const=0.0, head=head, gmax=gmax)))
+    print("dgrad                 %.3f ms" % timeit(lambda: rnd._run_dgrad(
+        f, act, head, gmax, R, F, use_t=False, bprec=BP, grad_stash=grad_stash)))
     plist = f.param_list()
     arena = torch.zeros(sum(w.numel() + b.numel() for _, w, b in plist), device=dev)
-    fg = _lib.FieldGrads()
-    off = 0
+    targets, off = {}, 0
     for i, w, b in plist:
-        fg.weight[i] = arena[off:off + w.numel()].data_ptr(); off += w.numel()
-        fg.bias[i] = arena[off:off + b.numel()].data_ptr(); off += b.numel()
-    h_wp, d_wp = f.wgrad_plan(False)
-    fpar, _keep = f._field_params()
+        targets[i] = (arena[off:off + w.numel()], arena[off + w.numel():off + w.numel() + b.numel()])
+        off += w.numel() + b.numel()
     scratch = torch.empty(L.nfl_wgrad_scratch_bytes() // 4, device=dev)
-    print("wgrad                 %.3f ms" % timeit(lambda: _lib.check(L.nfl_mlp_wgrad(h_wp, rnd._ptr(d_wp), rnd._ptr(st["act"]), rnd._ptr(grad_stash), rnd._ptr(gmax), R, F, BP, C.byref(fpar), rnd._ptr(scratch), C.byref(fg), rnd._stream()), "wg")))
-    print("act stash %.2f GB, grad stash %.2f GB" % (st["act"].numel() / 1e9, grad_stash.numel() / 1e9))
+    print("wgrad                 %.3f ms" % timeit(lambda: rnd._run_wgrad(
+        f, act, grad_stash, gmax, R, F, use_t=False, bprec=BP, targets=targets, scratch=scratch)))
+    print("act stash %.2f GB, grad stash %.2f GB" % (act.numel() / 1e9, grad_stash.numel() / 1e9))
