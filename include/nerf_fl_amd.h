@@ -949,6 +949,81 @@ typedef struct nfl_occ_clip_args {
 } nfl_occ_clip_args;
 int nfl_occ_clip_rays(const nfl_occ_clip_args* args, void* stream);
 
+/* ---- mesh colour: a depth map of a mesh per camera, and the bank's pixels blended into per-vertex colours (the line of
+ * projects this one follows colours an exported mesh the same way: project, test visibility, average) ------------------------
+ * Every operation below is fp32 and rounded on its own; dot(a, x) stands for (a0 * x0 + a1 * x1) + a2 * x2 and cross for
+ * (a1 * b2 - a2 * b1, a2 * b0 - a0 * b2, a0 * b1 - a1 * b0).  Divisions and square roots are correctly rounded.
+ * The CAMERA is one nfl_image_rec: R[r][c] = c2w[4 r + c], t[r] = c2w[4 r + 3].  A world point p has the camera coordinates
+ *   q[c] = dot((R[0][c], R[1][c], R[2][c]), p - t),
+ * and pixel (i, j), column i and row j, has the camera-space ray d = ((i - cx) / fx, -(j - cy) / fy, -1): the expressions of
+ * nfl_gather_batch's camera layout, pixel centres on the integers.  A run is the images first .. first + count - 1 of a table;
+ * pixel (i, j) of image n of the run is word pix0[n] - pix0[first] + j * width + i of the run's depth buffer.
+ *
+ * nfl_mesh_depth   two launches (fill, raster).  The value of a pixel is the minimum over all triangles its ray hits of the
+ *   distance from the camera centre to the hit, +inf when there is none.  With a, b, c the camera coordinates of a triangle's
+ *   vertices (Moeller-Trumbore from the origin): tv = -a, e1 = b - a, e2 = c - a, qv = cross(tv, e1), tnum = dot(e2, qv);
+ *   per pixel pv = cross(d, e2), det = dot(e1, pv), a miss when det == 0 (or NaN), inv = 1 / det, u = dot(tv, pv) * inv,
+ *   v = dot(d, qv) * inv, tau = tnum * inv; a HIT when u >= 0, v >= 0, u + v <= 1 and tau > 0 (two-sided, edges included),
+ *   its distance tau * sqrt((dx dx + dy dy) + dz dz).  A triangle with a non-finite camera coordinate, or an index outside
+ *   [0, n_vertices) (indices are NOT trusted), hits nothing.  Which pixels a triangle is tried against is the kernel's
+ *   business: none when all three vertices have -q.z <= 0; the bounding box of the projections cx + fx * (q.x / s),
+ *   cy - fy * (q.y / s), s = -q.z, widened by one pixel each way and cut to the frame, when all three have s > 0 and finite
+ *   projections; the whole frame otherwise.  Boxes of more than 64 pixels are walked by a whole wave, in the same launch.
+ *   A hit is an atomicMin on the word as uint32 (non-negative floats order as their bits): the result does not depend on the
+ *   order.  Only words below n_depth are written; n_depth = the pixels of the run.  V == 0 or T == 0 or count == 0: the fill
+ *   alone.  NFL_EINVAL (nothing launched): args / d_table NULL or d_table not 8-byte aligned, n_images < 1, a run outside the
+ *   table, a negative size, V > INT32_MAX or 3 T > INT32_MAX, n_depth above 2^38, a NULL or misaligned (4 B) pointer that a
+ *   non-zero size needs, more than 2^31 workgroups of 256 (triangle, image) pairs.
+ *
+ * nfl_mesh_blend   one launch, one thread per vertex, the images of the run in increasing n inside.  For vertex p with normal
+ *   nrm, image n contributes when all of these hold:
+ *     1  wi = d_image_weights[n] > 0 (NULL: 1 for every image; the array is indexed by the TABLE's n);
+ *     2  s = -q.z > 0;
+ *     3  u = cx + fx * (q.x / s), v = cy - fy * (q.y / s) with 0 <= u <= width - 1 and 0 <= v <= height - 1 (NaN fails);
+ *     4  e = t - p, dist = sqrt(dot(e, e)), cos = dot(nrm, e) / dist > min_cos; a normal of three zeros counts as cos = 1;
+ *     5  dist <= depth[floorf(u + 0.5f), floorf(v + 0.5f)] + depth_tol, the depth word of this run's nfl_mesh_depth;
+ *     6  with d_center: max_k |c_k - center_k| <= reject.
+ *   c is the bilinear sample at (u, v): x = floorf(u), tx = u - x, sx = 1 - tx, likewise y, ty, sy; the neighbours x + 1 and
+ *   y + 1 are clamped to the last column and row; c = (c00 * sx + c10 * tx) * sy + (c01 * sx + c11 * tx) * ty with c00 at
+ *   (x, y), c10 at (x + 1, y), c01 at (x, y + 1), every pixel converted by the device function of nfl_gather_batch
+ *   (c / 255.0f; RGBA: rgb * a + (1 - a)).  The image adds w * c to d_sum[v][0..2], w to d_sum[v][3] and 1 to d_views[v],
+ *   w = wi * cos (NFL_BLEND_COS) or wi (NFL_BLEND_UNIFORM).  start != 0 begins the accumulators at zero, start == 0 continues
+ *   what the caller's arrays hold, so a bank may be walked in runs; the result does not depend on the split.  No atomics.
+ *   NFL_EINVAL (nothing launched): args NULL, V < 0 or above INT32_MAX, d_table / run as above, an unknown weighting,
+ *   depth_tol negative or NaN, min_cos NaN (or negative with NFL_BLEND_COS: a weight is never negative), reject negative or NaN
+ *   when d_center is given, n_depth as above, and for V > 0 a NULL d_vertices / d_normals / d_sum / d_views (d_pixels, d_depth
+ *   when count > 0) or a misaligned pointer (d_sum 16 B, the others 4 B).  V == 0, or count == 0 with start == 0: NFL_OK, no
+ *   launch. */
+enum { NFL_BLEND_COS = 0, NFL_BLEND_UNIFORM = 1 };
+typedef struct nfl_mesh_depth_args {
+    const float*   d_vertices;        /* (V, 3) world */
+    const int32_t* d_triangles;       /* (T, 3) */
+    int64_t  n_vertices, n_triangles;
+    const nfl_image_rec* d_table;     /* (n_images) */
+    int32_t  n_images, first, count, reserved;
+    float*   d_depth;                 /* out (n_depth) */
+    int64_t  n_depth;                 /* pixels of the run */
+} nfl_mesh_depth_args;
+int nfl_mesh_depth(const nfl_mesh_depth_args* args, void* stream);
+
+typedef struct nfl_mesh_blend_args {
+    const float*   d_vertices;        /* (V, 3) */
+    const float*   d_normals;         /* (V, 3) */
+    int64_t  n_vertices;
+    const uint8_t* d_pixels;
+    const nfl_image_rec* d_table;     /* (n_images) */
+    int32_t  n_images, first, count, weighting;
+    const float*   d_depth;           /* (n_depth): nfl_mesh_depth of the same run */
+    int64_t  n_depth;
+    const float*   d_image_weights;   /* (n_images) or NULL */
+    const float*   d_center;          /* (V, 3) or NULL */
+    float    min_cos, depth_tol, reject;
+    int32_t  start;                   /* != 0: the accumulators begin at zero */
+    float*   d_sum;                   /* in/out (V, 4): sum of w * rgb, sum of w */
+    int32_t* d_views;                 /* in/out (V) */
+} nfl_mesh_blend_args;
+int nfl_mesh_blend(const nfl_mesh_blend_args* args, void* stream);
+
 /* ---- hierarchical sampling (reference sample_pdf, rendering.py:7-46, plus the
  * concat + sort of rendering.py:267-272) -------------------------------------
  * d_z_coarse (R,S), d_weights_coarse (R,S); d_u (R,I) or NULL with d_u_row (I)

@@ -255,6 +255,24 @@ class OccClipArgs(C.Structure):
                 ("reserved", C.c_int32), ("d_near_far", C.c_void_p), ("d_hit", C.c_void_p)]
 
 
+# nfl_mesh_depth / nfl_mesh_blend (nerf_fl_amd.geometry: mesh colour from the images) likewise: two new symbols and structs
+BLEND_WEIGHTINGS = {"cos": 0, "uniform": 1}
+
+
+class MeshDepthArgs(C.Structure):
+    _fields_ = [("d_vertices", C.c_void_p), ("d_triangles", C.c_void_p), ("n_vertices", C.c_int64),
+                ("n_triangles", C.c_int64), ("d_table", C.c_void_p), ("n_images", C.c_int32), ("first", C.c_int32),
+                ("count", C.c_int32), ("reserved", C.c_int32), ("d_depth", C.c_void_p), ("n_depth", C.c_int64)]
+
+
+class MeshBlendArgs(C.Structure):
+    _fields_ = [("d_vertices", C.c_void_p), ("d_normals", C.c_void_p), ("n_vertices", C.c_int64), ("d_pixels", C.c_void_p),
+                ("d_table", C.c_void_p), ("n_images", C.c_int32), ("first", C.c_int32), ("count", C.c_int32),
+                ("weighting", C.c_int32), ("d_depth", C.c_void_p), ("n_depth", C.c_int64), ("d_image_weights", C.c_void_p),
+                ("d_center", C.c_void_p), ("min_cos", C.c_float), ("depth_tol", C.c_float), ("reject", C.c_float),
+                ("start", C.c_int32), ("d_sum", C.c_void_p), ("d_views", C.c_void_p)]
+
+
 # every symbol include/nerf_fl_amd.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("nfl_plan_bytes", C.c_size_t, [C.POINTER(FieldDesc)]),
@@ -322,6 +340,8 @@ SYMBOLS = [
     ("nfl_occ_build_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     ("nfl_occ_build", C.c_int, [C.POINTER(OccBuildArgs), C.c_void_p]),
     ("nfl_occ_clip_rays", C.c_int, [C.POINTER(OccClipArgs), C.c_void_p]),
+    ("nfl_mesh_depth", C.c_int, [C.POINTER(MeshDepthArgs), C.c_void_p]),
+    ("nfl_mesh_blend", C.c_int, [C.POINTER(MeshBlendArgs), C.c_void_p]),
     ("nfl_abi_version", C.c_int, []),
     ("nfl_version", C.c_char_p, []),
     ("nfl_strerror", C.c_char_p, [C.c_int]),

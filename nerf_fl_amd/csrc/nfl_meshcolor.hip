@@ -1,0 +1,250 @@
+// nfl_meshcolor.hip -- colour a mesh from the images that see it (include/nerf_fl_amd.h, "mesh colour"): a depth map of the
+// mesh per camera (fill + raster) and a blend of the bank's pixels into per-vertex accumulators.  DESIGN.md section 25.
+//
+// Fill.    A thread per depth word of the run: +inf.
+// Raster.  A thread per (triangle, image) of the run.  It transforms the three vertices once, culls (all behind the camera
+//          plane, a non-finite coordinate, an index out of range) and takes a pixel box: the projections' bounding box
+//          widened by one pixel and clamped to the frame, or the whole frame when the triangle straddles the camera plane.
+//          A box of at most NMC_SMALL_BOX pixels is walked by its own lane.  A larger one is NOT: one lane walking
+//          thousands of pixels holds its 63 neighbours for as long, so after the small boxes the wave ballots its large
+//          ones and takes them in turn, all 64 lanes striding the box (the triangle goes round by __shfl, 14 words).  One
+//          launch, no list, no second kernel.  A hit is an atomicMin on the depth word as uint32: the depths are
+//          non-negative floats, which order as their bits, and +inf is the largest.
+// Blend.   A thread per vertex, the image loop inside: the records are read by every thread in the same order and stay in
+//          cache; per contributing image 4 pixels through nfl_pixel_rgb and one depth word.  The thread owns its row of the
+//          accumulators: no atomics, the same bits every time.
+#include <math.h>
+
+#include "nfl_geom.h"
+#include "nfl_pixel.h"
+
+#ifndef NMC_SMALL_BOX
+#define NMC_SMALL_BOX 64                                    // pixels: boxes above this are walked by the whole wave
+#endif
+#define NMC_MAX_WORDS (1ll << 38)                           // depth words of one run (a grid of 2^30 workgroups)
+
+// (a * x + b * y) + c * z, every operation rounded on its own (the unit is built with -ffp-contract=off)
+NFL_DEV float nmc_dot(float a, float b, float c, float x, float y, float z) { return (a * x + b * y) + c * z; }
+
+// camera coordinates of the world point p: q = R^T (p - t)
+NFL_DEV void nmc_to_camera(const nfl_image_rec& im, const float p[3], float q[3]) {
+    const float wx = p[0] - im.c2w[3], wy = p[1] - im.c2w[7], wz = p[2] - im.c2w[11];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) q[c] = nmc_dot(im.c2w[c], im.c2w[4 + c], im.c2w[8 + c], wx, wy, wz);
+}
+
+NFL_DEV bool nmc_finite(float v) { return v - v == 0.f; }
+
+// what a triangle's pixel tests share: the Moeller-Trumbore terms that do not depend on the ray (origin 0: tvec = -a)
+struct NmcTri {
+    float tv[3], e1[3], e2[3], qv[3], tnum;
+};
+
+NFL_DEV void nmc_setup(const float a[3], const float b[3], const float c[3], NmcTri& t) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t.tv[k] = -a[k], t.e1[k] = b[k] - a[k], t.e2[k] = c[k] - a[k];
+    t.qv[0] = t.tv[1] * t.e1[2] - t.tv[2] * t.e1[1];
+    t.qv[1] = t.tv[2] * t.e1[0] - t.tv[0] * t.e1[2];
+    t.qv[2] = t.tv[0] * t.e1[1] - t.tv[1] * t.e1[0];
+    t.tnum = nmc_dot(t.e2[0], t.e2[1], t.e2[2], t.qv[0], t.qv[1], t.qv[2]);
+}
+
+// the ray of pixel (i, j) against the triangle: true and the distance from the camera centre on a hit
+NFL_DEV bool nmc_test(const NmcTri& t, const nfl_image_rec& im, int i, int j, float& depth) {
+    const float dx = ((float)i - im.cx) / im.fx, dy = -((float)j - im.cy) / im.fy, dz = -1.f;
+    const float px = dy * t.e2[2] - dz * t.e2[1], py = dz * t.e2[0] - dx * t.e2[2], pz = dx * t.e2[1] - dy * t.e2[0];
+    const float det = nmc_dot(t.e1[0], t.e1[1], t.e1[2], px, py, pz);
+    if (!(det != 0.f)) return false;                        // 0 or NaN
+    const float inv = 1.f / det;
+    const float u = nmc_dot(t.tv[0], t.tv[1], t.tv[2], px, py, pz) * inv;
+    const float v = nmc_dot(dx, dy, dz, t.qv[0], t.qv[1], t.qv[2]) * inv;
+    const float tau = t.tnum * inv;
+    if (!(u >= 0.f && v >= 0.f && u + v <= 1.f && tau > 0.f)) return false;
+    depth = tau * sqrtf((dx * dx + dy * dy) + dz * dz);
+    return true;
+}
+
+__global__ __launch_bounds__(NM_THREADS) void nfl_mesh_depth_fill_kernel(float* depth, i64 n) {
+    const i64 w = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
+    if (w < n) depth[w] = __builtin_huge_valf();
+}
+
+NFL_DEV void nmc_pixel(const NmcTri& t, const nfl_image_rec& im, int i, int j, float* depth, i64 base, i64 n_depth) {
+    float d;
+    if (!nmc_test(t, im, i, j, d)) return;
+    const i64 w = base + (i64)j * im.width + i;
+    if (w >= 0 && w < n_depth) atomicMin(reinterpret_cast<unsigned int*>(depth) + w, __float_as_uint(d));
+}
+
+__global__ __launch_bounds__(NM_THREADS) void nfl_mesh_depth_raster_kernel(const nfl_mesh_depth_args a) {
+    const i64 item = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
+    const i64 T = a.n_triangles, V = a.n_vertices;
+    // every lane stays to the end: the wave's large boxes are walked by all of its lanes
+    int n = 0, x0 = 0, x1 = -1, y0 = 0, y1 = -1;
+    float q[3][3] = {};
+    if (item < T * a.count) {
+        n = (int)(item / T);
+        const i64 tr = item - (i64)n * T;
+        const int32_t ia = a.d_triangles[3 * tr], ib = a.d_triangles[3 * tr + 1], ic = a.d_triangles[3 * tr + 2];
+        const nfl_image_rec& im = a.d_table[a.first + n];
+        if (nm_in_range(ia, ib, ic, V) && im.width > 0 && im.height > 0) {
+            const int32_t idx[3] = {ia, ib, ic};
+            bool finite = true, all_front = true, any_front = false, boxed = true;
+            float bx0 = __builtin_huge_valf(), bx1 = -__builtin_huge_valf(), by0 = bx0, by1 = bx1;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float p[3] = {a.d_vertices[3 * (i64)idx[k]], a.d_vertices[3 * (i64)idx[k] + 1], a.d_vertices[3 * (i64)idx[k] + 2]};
+                nmc_to_camera(im, p, q[k]);
+                finite = finite && nmc_finite(q[k][0]) && nmc_finite(q[k][1]) && nmc_finite(q[k][2]);
+                const float s = -q[k][2];
+                if (s > 0.f) {
+                    any_front = true;
+                    const float u = im.cx + im.fx * (q[k][0] / s), v = im.cy - im.fy * (q[k][1] / s);
+                    boxed = boxed && nmc_finite(u) && nmc_finite(v);
+                    bx0 = fminf(bx0, u), bx1 = fmaxf(bx1, u), by0 = fminf(by0, v), by1 = fmaxf(by1, v);
+                } else all_front = false;
+            }
+            if (finite && any_front) {
+                const float wmax = (float)(im.width - 1), hmax = (float)(im.height - 1);
+                if (all_front && boxed) {                   // clamped as floats: a projection may lie far outside int range
+                    x0 = (int)fminf(fmaxf(floorf(bx0) - 1.f, 0.f), wmax + 1.f), x1 = (int)fmaxf(fminf(ceilf(bx1) + 1.f, wmax), -1.f);
+                    y0 = (int)fminf(fmaxf(floorf(by0) - 1.f, 0.f), hmax + 1.f), y1 = (int)fmaxf(fminf(ceilf(by1) + 1.f, hmax), -1.f);
+                } else {                                    // straddles the camera plane: no box to trust
+                    x0 = 0, x1 = im.width - 1, y0 = 0, y1 = im.height - 1;
+                }
+            }
+        }
+    }
+    const int bw = x1 - x0 + 1, bh = y1 - y0 + 1;
+    const i64 area = bw > 0 && bh > 0 ? (i64)bw * bh : 0;
+    const i64 pix_first = a.d_table[a.first].pix0;
+    if (area > 0 && area <= NMC_SMALL_BOX) {
+        const nfl_image_rec& im = a.d_table[a.first + n];
+        NmcTri t;
+        nmc_setup(q[0], q[1], q[2], t);
+        const i64 base = im.pix0 - pix_first;
+        for (int j = y0; j <= y1; ++j)
+            for (int i = x0; i <= x1; ++i) nmc_pixel(t, im, i, j, a.d_depth, base, a.n_depth);
+    }
+    unsigned long long big = __ballot(area > NMC_SMALL_BOX);
+    const int lane = threadIdx.x & 63;
+    while (big) {
+        const int src = __ffsll(big) - 1;
+        big &= big - 1;
+        float g[3][3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) g[k][c] = __shfl(q[k][c], src);
+        const int gn = __shfl(n, src), gx0 = __shfl(x0, src), gy0 = __shfl(y0, src), gw = __shfl(bw, src), gh = __shfl(bh, src);
+        const nfl_image_rec& im = a.d_table[a.first + gn];
+        NmcTri t;
+        nmc_setup(g[0], g[1], g[2], t);
+        const i64 base = im.pix0 - pix_first;
+        // pixels lane, lane + 64, ... of the box in row-major order, kept as (row, column) and advanced by
+        // (64 / gw, 64 % gw) with a carry: no division per pixel
+        const int dj = 64 / gw, di = 64 - dj * gw;
+        for (int j = lane / gw, i = lane - j * gw; j < gh; j += dj) {
+            nmc_pixel(t, im, gx0 + i, gy0 + j, a.d_depth, base, a.n_depth);
+            i += di;
+            if (i >= gw) i -= gw, ++j;
+        }
+    }
+}
+
+static bool nmc_run_ok(const void* table, int32_t n_images, int32_t first, int32_t count) {
+    if (!table || reinterpret_cast<uintptr_t>(table) % 8) return false;
+    return n_images >= 1 && first >= 0 && count >= 0 && (long long)first + count <= n_images;
+}
+
+extern "C" int nfl_mesh_depth(const nfl_mesh_depth_args* a, void* stream) {
+    if (!a || !nm_sizes_ok(a->n_vertices, a->n_triangles)) return NFL_EINVAL;
+    if (!nmc_run_ok(a->d_table, a->n_images, a->first, a->count)) return NFL_EINVAL;
+    if (a->n_depth < 0 || a->n_depth > NMC_MAX_WORDS) return NFL_EINVAL;
+    if (a->n_depth && (!a->d_depth || reinterpret_cast<uintptr_t>(a->d_depth) % 4)) return NFL_EINVAL;
+    if (a->n_vertices && (!a->d_vertices || reinterpret_cast<uintptr_t>(a->d_vertices) % 4)) return NFL_EINVAL;
+    if (a->n_triangles && (!a->d_triangles || reinterpret_cast<uintptr_t>(a->d_triangles) % 4)) return NFL_EINVAL;
+    const i64 items = a->n_triangles * a->count;
+    if (ng_cdiv(items, NM_THREADS) > INT32_MAX) return NFL_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (a->n_depth) hipLaunchKernelGGL(nfl_mesh_depth_fill_kernel, dim3(nm_grid(a->n_depth)), dim3(NM_THREADS), 0, s, a->d_depth, a->n_depth);
+    if (items && a->n_vertices && a->n_depth)
+        hipLaunchKernelGGL(nfl_mesh_depth_raster_kernel, dim3(nm_grid(items)), dim3(NM_THREADS), 0, s, *a);
+    return ng_launched() ? NFL_OK : NFL_ELAUNCH;
+}
+
+// ---- blend -----------------------------------------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(NM_THREADS) void nfl_mesh_blend_kernel(const nfl_mesh_blend_args a) {
+    const i64 v = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
+    if (v >= a.n_vertices) return;
+    const float p[3] = {a.d_vertices[3 * v], a.d_vertices[3 * v + 1], a.d_vertices[3 * v + 2]};
+    const float nr[3] = {a.d_normals[3 * v], a.d_normals[3 * v + 1], a.d_normals[3 * v + 2]};
+    const bool flat = nr[0] == 0.f && nr[1] == 0.f && nr[2] == 0.f;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    int32_t views = 0;
+    if (!a.start) acc = reinterpret_cast<const float4*>(a.d_sum)[v], views = a.d_views[v];
+    float centre[3] = {0.f, 0.f, 0.f};
+    if (a.d_center) centre[0] = a.d_center[3 * v], centre[1] = a.d_center[3 * v + 1], centre[2] = a.d_center[3 * v + 2];
+    const i64 pix_first = a.count ? a.d_table[a.first].pix0 : 0;
+    for (int n = a.first; n < a.first + a.count; ++n) {
+        const float wi = a.d_image_weights ? a.d_image_weights[n] : 1.f;
+        if (!(wi > 0.f)) continue;                                                      // 1
+        const nfl_image_rec& im = a.d_table[n];
+        if (im.width < 1 || im.height < 1) continue;
+        float q[3];
+        nmc_to_camera(im, p, q);
+        const float s = -q[2];
+        if (!(s > 0.f)) continue;                                                       // 2
+        const float wmax = (float)(im.width - 1), hmax = (float)(im.height - 1);
+        const float u = im.cx + im.fx * (q[0] / s), w = im.cy - im.fy * (q[1] / s);
+        if (!(u >= 0.f && u <= wmax && w >= 0.f && w <= hmax)) continue;                // 3
+        const float ex = im.c2w[3] - p[0], ey = im.c2w[7] - p[1], ez = im.c2w[11] - p[2];
+        const float dist = sqrtf((ex * ex + ey * ey) + ez * ez);
+        const float cosv = flat ? 1.f : nmc_dot(nr[0], nr[1], nr[2], ex, ey, ez) / dist;
+        if (!(cosv > a.min_cos)) continue;                                              // 4
+        const int ix = (int)floorf(u + 0.5f), iy = (int)floorf(w + 0.5f);
+        const i64 word = (im.pix0 - pix_first) + (i64)iy * im.width + ix;
+        if (word < 0 || word >= a.n_depth) continue;                    // a depth buffer that is not this run's: nothing read
+        if (!(dist <= a.d_depth[word] + a.depth_tol)) continue;                         // 5
+        const float xf = floorf(u), yf = floorf(w), tx = u - xf, ty = w - yf, sx = 1.f - tx, sy = 1.f - ty;
+        const int xa = (int)xf, ya = (int)yf;
+        const int xb = xa + 1 < im.width ? xa + 1 : im.width - 1, yb = ya + 1 < im.height ? ya + 1 : im.height - 1;
+        float c00[3], c10[3], c01[3], c11[3], c[3];
+        nfl_pixel_rgb(a.d_pixels, im, (i64)ya * im.width + xa, c00);
+        nfl_pixel_rgb(a.d_pixels, im, (i64)ya * im.width + xb, c10);
+        nfl_pixel_rgb(a.d_pixels, im, (i64)yb * im.width + xa, c01);
+        nfl_pixel_rgb(a.d_pixels, im, (i64)yb * im.width + xb, c11);
+        float off = 0.f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            c[k] = (c00[k] * sx + c10[k] * tx) * sy + (c01[k] * sx + c11[k] * tx) * ty;
+            off = fmaxf(off, fabsf(c[k] - centre[k]));
+        }
+        if (a.d_center && !(off <= a.reject)) continue;                                 // 6
+        const float wt = a.weighting == NFL_BLEND_COS ? wi * cosv : wi;
+        acc.x += wt * c[0], acc.y += wt * c[1], acc.z += wt * c[2], acc.w += wt;
+        ++views;
+    }
+    reinterpret_cast<float4*>(a.d_sum)[v] = acc;
+    a.d_views[v] = views;
+}
+
+extern "C" int nfl_mesh_blend(const nfl_mesh_blend_args* a, void* stream) {
+    if (!a || a->n_vertices < 0 || a->n_vertices > INT32_MAX) return NFL_EINVAL;
+    if (!nmc_run_ok(a->d_table, a->n_images, a->first, a->count)) return NFL_EINVAL;
+    if (a->weighting != NFL_BLEND_COS && a->weighting != NFL_BLEND_UNIFORM) return NFL_EINVAL;
+    if (!(a->depth_tol >= 0.f) || !(a->min_cos == a->min_cos)) return NFL_EINVAL;
+    if (a->weighting == NFL_BLEND_COS && !(a->min_cos >= 0.f)) return NFL_EINVAL;       // a weight is never negative
+    if (a->d_center && !(a->reject >= 0.f)) return NFL_EINVAL;
+    if (a->n_depth < 0 || a->n_depth > NMC_MAX_WORDS) return NFL_EINVAL;
+    if (a->n_vertices == 0) return NFL_OK;
+    if (!a->d_vertices || !a->d_normals || !a->d_sum || !a->d_views) return NFL_EINVAL;
+    if (reinterpret_cast<uintptr_t>(a->d_vertices) % 4 || reinterpret_cast<uintptr_t>(a->d_normals) % 4 ||
+        reinterpret_cast<uintptr_t>(a->d_sum) % 16 || reinterpret_cast<uintptr_t>(a->d_views) % 4 ||
+        reinterpret_cast<uintptr_t>(a->d_center) % 4 || reinterpret_cast<uintptr_t>(a->d_image_weights) % 4) return NFL_EINVAL;
+    if (a->count && (!a->d_pixels || !a->d_depth || reinterpret_cast<uintptr_t>(a->d_depth) % 4)) return NFL_EINVAL;
+    if (a->count == 0 && !a->start) return NFL_OK;
+    hipLaunchKernelGGL(nfl_mesh_blend_kernel, dim3(nm_grid(a->n_vertices)), dim3(NM_THREADS), 0, static_cast<hipStream_t>(stream), *a);
+    return ng_launched() ? NFL_OK : NFL_ELAUNCH;
+}

@@ -11,6 +11,8 @@
     extract_mesh      all of it in a row
     occupancy_grid    one bit per cell of a lattice: occupied where a corner reaches a threshold, dilated (csrc/nfl_occupancy.hip)
     clip_rays         rays walked through such a grid: a tightened [near, far] per ray and a flag for rays that hit nothing
+    mesh_depth        the depth map of a mesh seen by a camera: a z-buffer on the device (csrc/nfl_meshcolor.hip)
+    color_mesh_from_images   vertex colours from the images of an ImageBank that see each vertex, hidden views left out
 
 Conventions: `lo`, `hi` and `res` are 3 numbers in (x, y, z) order; a lattice is a (nz, ny, nx) fp32 tensor, x fastest,
 whose point (x, y, z) lies at lo + (x, y, z) * spacing with spacing = (hi - lo) / (res - 1): `lattice_points` returns
@@ -27,7 +29,8 @@ import torch
 from . import _lib, rendering
 
 __all__ = ["density_lattice", "extract_surface", "surface_colors", "write_ply", "extract_mesh", "lattice_points",
-           "mesh_components", "filter_mesh", "clean_mesh", "simplify_mesh", "OccupancyGrid", "occupancy_grid", "clip_rays"]
+           "mesh_components", "filter_mesh", "clean_mesh", "simplify_mesh", "OccupancyGrid", "occupancy_grid", "clip_rays",
+           "mesh_depth", "color_mesh_from_images"]
 
 # Longest piece of an x-row handed to the render pass as one ray.  nfl_render_pass accepts any n_samples >= 1; the cut is
 # a scheduling choice, not a limit of the ABI: the kernel gives whole rays to workgroups (contiguous ray ranges, one
@@ -485,10 +488,193 @@ def simplify_mesh(mesh, cell, origin=(0.0, 0.0, 0.0), placement="mean", return_m
     return (out, cluster) if return_map else out
 
 
+def _run_depth(lib, stream, ver, tri, table, n_images, first, count, depth):
+    """nfl_mesh_depth of images first .. first + count - 1 of `table` into `depth` (the run's pixels, fp32)."""
+    a = _lib.MeshDepthArgs()
+    a.d_vertices, a.d_triangles, a.n_vertices, a.n_triangles = _ptr(ver), _ptr(tri), ver.shape[0], tri.shape[0]
+    a.d_table, a.n_images, a.first, a.count = _ptr(table), n_images, first, count
+    a.d_depth, a.n_depth = _ptr(depth), depth.numel()
+    _lib.check(lib.nfl_mesh_depth(C.byref(a), stream), "nfl_mesh_depth")
+
+
+def mesh_depth(mesh, c2w=None, K=None, H=None, W=None, *, bank=None, image=None):
+    """The depth map of `mesh` seen by one camera: (H, W) fp32, per pixel the distance from the camera centre to the
+    nearest triangle its ray hits (the quantity rays[:, 6:8] and depth_fine are measured in when |rays_d| = 1), +inf
+    where it hits none.  The surface occludes from both sides, pixel centres lie on the integers, and the definition is
+    written out in include/nerf_fl_amd.h, "mesh colour".  Two forms:
+
+        mesh_depth(mesh, c2w, K, H, W)          a free camera: c2w (3|4, 4), K (3, 3), tensors or arrays
+        mesh_depth(mesh, bank=bank, image=i)    image i of a data.ImageBank on the mesh's device
+
+    Besides a depth image of the geometry to set beside depth_fine, it is a per-pixel near / far tighter than an
+    occupancy grid's.  The bank form never synchronises with the host.  The free-camera form does not either when `c2w`
+    and `K` are tensors on the mesh's device (its record is then written by device-side fills and copies); an array, a
+    list or a CPU tensor is uploaded first, and that copy waits for the stream."""
+    ver, _, _, tri = _mesh_tensors(mesh)
+    dev = ver.device
+    lib = _lib.lib()
+    if bank is not None:
+        if c2w is not None or K is not None or H is not None or W is not None or image is None:
+            raise ValueError("mesh_depth: either (c2w, K, H, W) or (bank=, image=)")
+        if bank.device != dev:
+            raise ValueError("mesh_depth: the bank and the mesh are on different devices")
+        image = int(image)
+        if not 0 <= image < bank.n_images:
+            raise ValueError(f"image: 0 .. {bank.n_images - 1}")
+        H, W = int(bank.host_table[image]["height"]), int(bank.host_table[image]["width"])
+        table, n_images = bank.table, bank.n_images
+    else:
+        if c2w is None or K is None or H is None or W is None or image is not None:
+            raise ValueError("mesh_depth: either (c2w, K, H, W) or (bank=, image=)")
+        H, W = int(H), int(W)
+        if H < 1 or W < 1 or H * W > 1 << 38:
+            raise ValueError("mesh_depth: H and W are positive, and H * W is at most 2^38 pixels")
+        c2w = torch.as_tensor(c2w, dtype=torch.float32, device=dev).detach()
+        K = torch.as_tensor(K, dtype=torch.float32, device=dev).detach()
+        if c2w.dim() != 2 or c2w.shape[0] not in (3, 4) or c2w.shape[1] != 4 or K.shape != (3, 3):
+            raise ValueError("mesh_depth: c2w (3|4, 4) and K (3, 3)")
+        # one nfl_image_rec that owns no pixels, written on the device: 26 words, the integers first
+        words = torch.zeros(26, dtype=torch.int32, device=dev)
+        for at, value in ((4, W), (5, H), (6, 3)):                     # fill kernels: an indexed assignment of a Python
+            words[at:at + 1].fill_(value)                               # number goes through a blocking copy instead
+        f = words.view(torch.float32)
+        f[8:12] = torch.stack([K[0, 0], K[1, 1], K[0, 2], K[1, 2]])
+        f[14:26] = c2w[:3].reshape(12)
+        table, n_images, image = words, 1, 0
+    depth = torch.empty(H, W, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _run_depth(lib, rendering._stream(), ver, tri, table, n_images, image, 1, depth)
+    return depth
+
+
+def _image_runs(bank, images, batch_pixels):
+    """[(first, count, pixels)]: the selected images of `bank` in ascending order, cut into runs of consecutive images whose
+    pixels stay within `batch_pixels` (an image larger than that is a run of its own)."""
+    n = bank.n_images
+    if images is None:
+        sel = list(range(n))
+    else:
+        sel = sorted({int(i) for i in images})
+        if sel and not 0 <= sel[0] <= sel[-1] < n:
+            raise ValueError(f"images: indices in 0 .. {n - 1}")
+    size = lambda i: int(bank.host_table[i]["width"]) * int(bank.host_table[i]["height"])
+    runs = []
+    for i in sel:
+        if runs and runs[-1][0] + runs[-1][1] == i and runs[-1][2] + size(i) <= batch_pixels:
+            runs[-1] = (runs[-1][0], runs[-1][1] + 1, runs[-1][2] + size(i))
+        else:
+            runs.append((i, 1, size(i)))
+    return runs
+
+
+def color_mesh_from_images(mesh, bank, depth_tol, *, images=None, image_weights=None, min_cos=0.0, weighting="cos",
+                           reject=None, fallback=None, batch_pixels=1 << 26):
+    """Colour the vertices of `mesh` from the images of `bank` (a data.ImageBank on the mesh's device) that see them:
+    every vertex is projected into every selected image, the views in which it lies inside the frame, faces the camera
+    (cos of the angle between its normal and the direction to the camera > `min_cos`; a zero normal passes) and is not
+    hidden behind the mesh are kept, and their bilinear samples are averaged.  The definition is written out in
+    include/nerf_fl_amd.h, "mesh colour".  Returns a dict:
+
+        colors (V, 3) fp32 in [0, 1]; weight (V,) fp32, the sum of the weights; views (V,) int32; seen (V,) bool
+
+    depth_tol     a vertex counts as visible in an image when its distance to the camera is at most the mesh depth map's
+                  value at its nearest pixel plus `depth_tol` (world units).  It has no default, as occupancy_grid's
+                  threshold has none.  Too small and vertices lose their own views: the depth map is sampled at a pixel
+                  centre, up to half a pixel from where the vertex projects, and on a slanted surface that is a depth
+                  difference of its own.  Too large and what lies behind a thin structure shows through it.
+    images        indices of the images to use (default all); an unselected image costs no raster work.
+    image_weights (n_images,) non-negative weights (default 1); a zero weight drops the image from the blend.
+    weighting     "cos": a view counts by image weight x cos (head-on views dominate; needs min_cos >= 0); "uniform".
+    reject        r: the blend runs twice, and the second pass keeps, for a vertex seen in the first, only the samples
+                  within r (largest channel difference) of the first pass's colour: a passer-by in 3 of 40 photographs does
+                  not tint the wall.  When the depth maps of all selected images fit in `batch_pixels` they are kept for
+                  the second pass; otherwise they are rasterised again.
+                  A vertex seen in the first pass whose samples are ALL rejected in the second (two views further than r
+                  from their own mean, say) keeps its first-pass colour; its views and weight are 0 and seen is False.
+    fallback      colours of the vertices no image sees: (V, 3) or 3 numbers (default 0.5 grey).
+    batch_pixels  depth words held at a time: the images are walked in runs of consecutive images within it, each run
+                  a fill, a raster and a blend that continues the accumulators.
+
+    No host synchronisation of its own: `image_weights` and `fallback` given as tensors on the device (or left at their
+    defaults) are used as they are; given as lists, arrays or CPU tensors they are uploaded first, and that copy waits
+    for the stream."""
+    ver, nrm, _, tri = _mesh_tensors(mesh)
+    dev, V = ver.device, ver.shape[0]
+    if getattr(bank, "device", None) != dev or bank.table is None:
+        raise ValueError("color_mesh_from_images: `bank` is a data.ImageBank on the mesh's device")
+    if weighting not in _lib.BLEND_WEIGHTINGS:
+        raise ValueError(f"weighting: one of {sorted(_lib.BLEND_WEIGHTINGS)}, got {weighting!r}")
+    depth_tol, min_cos = float(depth_tol), float(min_cos)
+    if not depth_tol >= 0.0:
+        raise ValueError("depth_tol: a non-negative number")
+    if not (min_cos >= 0.0 or (weighting != "cos" and min_cos == min_cos)):
+        raise ValueError("min_cos: a number, not negative with weighting='cos' (a weight is never negative)")
+    if reject is not None and not float(reject) >= 0.0:
+        raise ValueError("reject: a non-negative number")
+    batch_pixels = int(batch_pixels)
+    if batch_pixels < 1:
+        raise ValueError("batch_pixels must be positive")
+    runs = _image_runs(bank, images, batch_pixels)
+    weights = None
+    if image_weights is not None:
+        weights = torch.as_tensor(image_weights, dtype=torch.float32, device=dev).detach().contiguous()
+        if weights.shape != (bank.n_images,):
+            raise ValueError(f"image_weights: expected ({bank.n_images},)")
+    if fallback is None:
+        fallback = torch.full((3,), 0.5, dtype=torch.float32, device=dev)
+    fallback = torch.as_tensor(fallback, dtype=torch.float32, device=dev).detach()
+    if fallback.shape not in ((3,), (V, 3)):
+        raise ValueError(f"fallback: 3 numbers or ({V}, 3)")
+    lib = _lib.lib()
+    keep = reject is not None and sum(r[2] for r in runs) <= batch_pixels
+    scratch = None if keep or not runs else torch.empty(max(r[2] for r in runs), dtype=torch.float32, device=dev)
+    kept = {}
+    sums = torch.empty(V, 4, dtype=torch.float32, device=dev)
+    views = torch.empty(V, dtype=torch.int32, device=dev)
+
+    def one_pass(center, fallback):
+        a = _lib.MeshBlendArgs()
+        a.d_vertices, a.d_normals, a.n_vertices, a.d_pixels = _ptr(ver), _ptr(nrm), V, _ptr(bank.pixels)
+        a.d_table, a.n_images, a.weighting = _ptr(bank.table), bank.n_images, _lib.BLEND_WEIGHTINGS[weighting]
+        a.d_image_weights, a.d_center, a.min_cos, a.depth_tol = _ptr(weights), _ptr(center), min_cos, depth_tol
+        a.reject = float(reject) if center is not None else 0.0
+        a.d_sum, a.d_views = _ptr(sums), _ptr(views)
+        for k, (first, count, pixels) in enumerate(runs or [(0, 0, 0)]):
+            if count and first in kept:
+                depth = kept[first]
+            elif count:
+                depth = torch.empty(pixels, dtype=torch.float32, device=dev) if keep else scratch[:pixels]
+                _run_depth(lib, stream, ver, tri, bank.table, bank.n_images, first, count, depth)
+                if keep:
+                    kept[first] = depth
+            else:
+                depth = None
+            a.first, a.count, a.start = first, count, int(k == 0)
+            a.d_depth, a.n_depth = _ptr(depth), pixels
+            _lib.check(lib.nfl_mesh_blend(C.byref(a), stream), "nfl_mesh_blend")
+        seen = views > 0
+        colors = torch.where(seen[:, None], (sums[:, :3] / sums[:, 3:4]).clamp(0.0, 1.0), fallback.expand(V, 3))
+        return colors.contiguous(), seen
+
+    with torch.cuda.device(dev):
+        stream = rendering._stream()
+        colors, seen = one_pass(None, fallback)
+        if reject is not None:
+            colors, seen = one_pass(colors, colors)                       # all samples rejected: the first pass's colour stays
+    return {"colors": colors, "weight": sums[:, 3].contiguous(), "views": views, "seen": seen}
+
+
 def extract_mesh(models, embeddings, lo, hi, res, iso, chunk=1 << 20, a_embedded=None, path=None, largest=None,
-                 min_triangles=None, simplify=None, placement="mean"):
+                 min_triangles=None, simplify=None, placement="mean", color_from=None, depth_tol=None, color_kwargs=None):
     """density_lattice -> extract_surface -> surface_colors (-> write_ply when `path` is given) for the fine model of
     `models` (the coarse one when there is no fine one).  Returns the mesh dict with `colors` (V, 3) added.
+
+    With `color_from` = a data.ImageBank the colours come from the images that see the surface
+    (color_mesh_from_images, after cleaning and simplifying; `color_kwargs` are passed on to it) and the mesh also gets
+    `seen` (V,) bool.  surface_colors is then the fallback for the vertices no image sees, unless the model encodes
+    appearance and no `a_embedded` is given, when they stay grey.  `depth_tol` = None means twice the largest lattice
+    spacing: that is the usual practice and not a measured choice (the extracted surface lies within a cell of the
+    field's, and a vertex should not lose its own views to that).
 
     With `largest` or `min_triangles` (as in clean_mesh) the small components are dropped BEFORE the colour pass, so the
     field is never evaluated at a discarded vertex.
@@ -505,8 +691,18 @@ def extract_mesh(models, embeddings, lo, hi, res, iso, chunk=1 << 20, a_embedded
         mesh = simplify_mesh(mesh, simplify, origin=lo, placement=placement)
     if mesh["vertices"].shape[0] == 0 and not (largest is None and min_triangles is None and simplify is None):
         mesh["colors"] = torch.empty_like(mesh["vertices"])               # the filter kept nothing: nothing to colour
-    else:
+        if color_from is not None:
+            mesh["seen"] = torch.zeros(0, dtype=torch.bool, device=mesh["vertices"].device)
+    elif color_from is None:
         mesh["colors"] = surface_colors(model, embeddings, mesh["vertices"], mesh["normals"], a_embedded=a_embedded)
+    else:
+        fallback = None
+        if a_embedded is not None or not model.encode_appearance:
+            fallback = surface_colors(model, embeddings, mesh["vertices"], mesh["normals"], a_embedded=a_embedded)
+        if depth_tol is None:
+            depth_tol = 2.0 * max(_box(lo, hi, res)[1])
+        got = color_mesh_from_images(mesh, color_from, depth_tol, **dict({"fallback": fallback}, **(color_kwargs or {})))
+        mesh["colors"], mesh["seen"] = got["colors"], got["seen"]
     if path is not None:
         write_ply(path, mesh, mesh["colors"])
     return mesh
