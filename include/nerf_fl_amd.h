@@ -109,7 +109,8 @@ int nfl_pack_field(const void* h_plan, const void* d_plan, const nfl_field_param
  * d_wdir_c (128, 256 + n_side) and d_wt0_c (128, 256 + n_tau; with has_t) must hold COPIES of dir_encoding.0.weight /
  * transient_encoding.0.weight on entry (their side columns are kept); d_bdir_c / d_bt0_c (128) are written.  Pack with a
  * nfl_field_params whose weight / bias entries NFL_P_DIR (and NFL_P_T0) point at these folded tensors; every other
- * entry point (nfl_mlp_wgrad's `params`) takes the ORIGINAL parameters.  One launch, fp32 (v_mfma_f32_32x32x2_f32). */
+ * entry point (nfl_mlp_wgrad's `params`) takes the ORIGINAL parameters.  One launch, fp32 (v_mfma_f32_32x32x2_f32).
+ * NFL_EINVAL, before anything is launched: a pointer that is needed and missing, n_side < 0 or n_tau < 0. */
 int nfl_compose_forward(const nfl_field_params* params, int32_t has_t, int32_t n_side, int32_t n_tau,
                         float* d_wdir_c, float* d_bdir_c, float* d_wt0_c, float* d_bt0_c, void* stream);
 /* Several streams in one launch (a training step re-packs the forward and the dgrad stream of both fields after every
@@ -329,9 +330,9 @@ typedef struct nfl_dgrad_args {
 int nfl_mlp_dgrad(const void* h_bwd_plan, const void* d_bwd_plan, const void* d_bwd_packed,
                   const nfl_dgrad_args* args, void* stream);
 
-/* fp32 gradient tensors in nn.Linear layout, WRITTEN by nfl_mlp_wgrad (it zeroes them, accumulates
- * with atomics, then divides the loss scale out); entries may be NULL (layer absent / gradient
- * not wanted). */
+/* fp32 gradient tensors in nn.Linear layout, WRITTEN by nfl_mlp_wgrad (it zeroes them, then a reduction
+ * launch stores the sums of its workgroups' parts, added in a fixed order and divided by the loss scale:
+ * no atomics); entries may be NULL (layer absent / gradient not wanted). */
 typedef struct nfl_field_grads {
     float* weight[NFL_NUM_LAYERS];
     float* bias[NFL_NUM_LAYERS];
@@ -354,7 +355,10 @@ int    nfl_wgrad_plan_build(const nfl_field_desc* desc, int32_t use_transient, v
  * them up in a fixed order, divides by the loss scale and writes the gradient tensors -- the weight and bias gradients are
  * therefore bit-reproducible from run to run (no atomics), and elements no job owns (heads the call leaves out) are zero.
  * The gradient tensors may be views of one caller-owned flat buffer (nerf_fl_amd.parallel.GradArena): they are written in
- * place, so a collective can run on that buffer right after this call. */
+ * place, so a collective can run on that buffer right after this call.
+ * d_scratch and params->weight[NFL_P_FINAL] must be 16-byte aligned (the composition reads rows of G and of W_fin with
+ * 16-byte loads).  Every refusal, this one included, is made before anything is launched: a call that returns NFL_EINVAL
+ * has left the gradient tensors untouched. */
 size_t nfl_wgrad_scratch_bytes(void);
 int nfl_mlp_wgrad(const void* h_wplan, const void* d_wplan, const char* d_act_stash, const char* d_grad_stash,
                   const float* d_gmax, int32_t n_rays, int32_t n_samples, int32_t bwd_prec,

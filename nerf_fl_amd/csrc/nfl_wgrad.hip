@@ -19,18 +19,20 @@
 //     dW_dir[:, :256] = G W_fin^T + db_dir (x) b_fin    (dW_t0[:, :256] likewise from Gt)
 // Neither `feat` nor `delta_feat` is ever stashed (16 KiB per 32-sample segment less written by the forward, 16 less
 // by dgrad, 24 less read here); the stream accumulates G | Gt into a 256 x 256 scratch like any other job and
-// nfl_wgrad_compose_kernel finishes the four products in fp32 (34-67 MFLOP, one launch).
+// nfl_wgrad_compose_kernel (nfl_compose.hip; the task list: nfl_compose.cpp) finishes the four products in fp32 (34-67 MFLOP, one launch).
 //
 // Roofline: HBM.  A 256x256 layer reads 32 KiB per segment for 2 x 64 MFMAs, 128 FLOP/B,
 // far under the MFMA ridge, so the kernel is a stream (wg_body_rs below), with fp32 accumulators
 // for the whole (<=256 x <=352) tile of dW in registers.  Every workgroup stores its accumulators once, as they are, and
 // nfl_wgrad_reduce_kernel adds the parts up in a fixed order and divides the loss scale out: no atomics.
 //
-// The job list of a field, the launch schedule of a call and the table of instantiations are host code: nfl_wgrad_plan.h / .cpp.
+// The job list of a field, the launch schedule of a call, the entry point's checks and the table of instantiations are host
+// code: nfl_wgrad_plan.h / .cpp.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
 #include "../../include/nerf_fl_amd.h"
+#include "nfl_compose.h"
 #include "nfl_dev.h"
 #include "nfl_diag.h"
 #include "nfl_wgrad_plan.h"
@@ -405,155 +407,40 @@ __global__ __launch_bounds__(256, 1) void nfl_wgrad_kernel(const WgArgs A) {
 #undef WG_RUN
 }
 
-// ---------------------------------------------------------------------------------
-// The four small fp32 products of the composition (file header), one launch: task t computes
-//   C[m, n] = sum_k A[m, k] B[k, n] (+ sum_k A2[m, k] B2[k, n]) (+ u[m] v[n])
-// over element strides of which one per operand is 1, 32 x 32 output tiles per 256-thread workgroup.
-// The operands are the fp32 master weights and the finished (unscaled) G / bias gradients; everything is L2-resident.
-struct WgGemm {
-    const float* A; int sam, sak;
-    const float* B; int sbk, sbn;
-    const float* A2; int sam2, sak2;
-    const float* B2; int sbk2, sbn2;
-    const float* u; const float* v;       // rank-1 term (NULL: none)
-    const float* addm;                    // + addm[m] (NULL: none)
-    int avec, bvec;                       // the k-contiguous operand may be fetched with 16-byte loads (rows 16-byte aligned)
-    float* Cp; int ldc;
-    int M, N, K, K2;                      // K2 = 0: no second product
-    int tiles_n, tile0;                   // tiles across N; index of this task's first workgroup
-};
-#define WG_MAX_GEMM 4
-struct WgCompose {
-    int n_tasks, n_wg;
-    WgGemm t[WG_MAX_GEMM];
-};
-// One 32 x 32 output tile per workgroup on the fp32 matrix cores (v_mfma_f32_32x32x2_f32: exact products, fp32
-// accumulation): the four waves split K, every lane fetches its operands straight from global memory (float4 along k where
-// k is the contiguous index, one dword per k otherwise; all loads of a wave are in flight before its first MFMA), the
-// partial tiles meet in LDS.  MFMA j of a wave takes, in lane half h, k = k_wave + 8 (j / 4) + 4 h + (j % 4): any pairing
-// of the two k of a step is as good as another as long as A and B agree.  (The first version staged 32 x 128 operand
-// blocks through LDS for scalar FMAs and was LDS-bound: 20-30 us; this one is one memory round trip and 16-32 MFMAs per wave.)
-template <int NJ>       // MFMAs per wave = (K / 4) / 2
-__device__ __forceinline__ void wg_compose_pass(f16v& acc, const float* A, int sam, int sak, const float* B, int sbk, int sbn,
-                                                int m, int n, bool n_ok, int k_wave, int h, bool avec, bool bvec) {
-    float ra[NJ], rb[NJ];
-#pragma unroll
-    for (int g = 0; g < NJ / 4; ++g) {
-        const int kq = k_wave + 8 * g + 4 * h;
-        if (sak == 1 && avec) {
-            const wg_f4 v = *reinterpret_cast<const wg_f4*>(A + (size_t)m * sam + kq);
-            ra[4 * g] = v[0]; ra[4 * g + 1] = v[1]; ra[4 * g + 2] = v[2]; ra[4 * g + 3] = v[3];
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ra[4 * g + e] = A[(size_t)m * sam + (size_t)(kq + e) * sak];
-        }
-        if (!n_ok) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) rb[4 * g + e] = 0.f;
-        } else if (sbk == 1 && sbn != 1 && bvec) {
-            const wg_f4 v = *reinterpret_cast<const wg_f4*>(B + (size_t)n * sbn + kq);
-            rb[4 * g] = v[0]; rb[4 * g + 1] = v[1]; rb[4 * g + 2] = v[2]; rb[4 * g + 3] = v[3];
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) rb[4 * g + e] = B[(size_t)(kq + e) * sbk + (size_t)n * sbn];
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ra[j], rb[j], acc, 0, 0, 0);
-}
-
-__global__ __launch_bounds__(256) void nfl_wgrad_compose_kernel(const WgCompose Cc) {
-    __shared__ float red[4][16][64];
-    int ti = 0;
-    while (ti + 1 < Cc.n_tasks && (int)blockIdx.x >= Cc.t[ti + 1].tile0) ++ti;
-    const WgGemm& T = Cc.t[ti];
-    const int tile = blockIdx.x - T.tile0, m0 = 32 * (tile / T.tiles_n), n0 = 32 * (tile % T.tiles_n);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
-    const int m = m0 + (lane & 31), n = n0 + (lane & 31);      // M is a multiple of 32 (256 or 128); N is 256 or 1
-    const bool n_ok = n < T.N;
-    f16v acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    // K and K2 are 128 or 256 (host-checked): 32 or 64 per wave
-    if (T.K == 256) wg_compose_pass<32>(acc, T.A, T.sam, T.sak, T.B, T.sbk, T.sbn, m, n, n_ok, 64 * wave, h, T.avec, T.bvec);
-    else wg_compose_pass<16>(acc, T.A, T.sam, T.sak, T.B, T.sbk, T.sbn, m, n, n_ok, 32 * wave, h, T.avec, T.bvec);
-    if (T.K2 == 256) wg_compose_pass<32>(acc, T.A2, T.sam2, T.sak2, T.B2, T.sbk2, T.sbn2, m, n, n_ok, 64 * wave, h, T.avec, T.bvec);
-    else if (T.K2 == 128) wg_compose_pass<16>(acc, T.A2, T.sam2, T.sak2, T.B2, T.sbk2, T.sbn2, m, n, n_ok, 32 * wave, h, T.avec, T.bvec);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) red[wave][r][lane] = acc[r];
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int r = 4 * wave + q;                             // accumulator register r: row 8 (r / 4) + 4 h + (r % 4), column lane % 32
-        const float c = red[0][r][lane] + red[1][r][lane] + red[2][r][lane] + red[3][r][lane];
-        const int row = m0 + 8 * (r >> 2) + 4 * h + (r & 3);
-        if (n_ok) T.Cp[(size_t)row * T.ldc + n] = (T.u ? __builtin_fmaf(T.u[row], T.v[n], c) : c) + (T.addm ? T.addm[row] : 0.f);
-    }
-}
-
 // Zeroes the gradient tensors and the composition scratch before the stream: the reduction stores only the elements a job owns.
 // blockIdx.y = tensor, blockIdx.x strides over its elements.
-#define WG_NTENS (2 * NFL_NUM_LAYERS + 1)     // weights, biases, the composition scratch
-struct WgTensors {
-    float* ptr[WG_NTENS];
-    int n[WG_NTENS];
-};
 __global__ __launch_bounds__(256) void nfl_wgrad_zero_kernel(const WgTensors T) {
     float* p = T.ptr[blockIdx.y];
     if (p == nullptr) return;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < T.n[blockIdx.y]; i += gridDim.x * 256) p[i] = 0.f;
 }
 
-// appends a task to a composition launch; vec: its k-contiguous operands have 16-byte aligned rows
-static void wg_add(WgCompose& Cc, WgGemm g, int vec) {
-    g.avec = g.bvec = vec;
-    g.tiles_n = (g.N + 31) / 32;
-    g.tile0 = Cc.n_wg;
-    Cc.n_wg += g.tiles_n * ((g.M + 31) / 32);
-    Cc.t[Cc.n_tasks++] = g;
-}
+void nfl_compose_launch(const WgCompose& Cc, hipStream_t s);      // nfl_compose.hip
 
+// Every refusal (nfl_wgrad_check, the schedule, the composition's task list) comes before the first launch: a refused call
+// leaves the gradient tensors as they were.
 extern "C" int nfl_mlp_wgrad(const void* h_wplan, const void* d_wplan, const char* d_act_stash,
                              const char* d_grad_stash, const float* d_gmax, int32_t n_rays, int32_t n_samples,
                              int32_t bwd_prec, const nfl_field_params* params, float* d_scratch,
                              const nfl_field_grads* grads, void* stream) {
+    int rc = nfl_wgrad_check(h_wplan, d_wplan, d_act_stash, d_grad_stash, d_gmax, n_rays, n_samples, bwd_prec, params, d_scratch, grads);
+    if (rc != NFL_OK) return rc;
     const WgPlan* hp = static_cast<const WgPlan*>(h_wplan);
-    if (!hp || hp->magic != WG_PLAN_MAGIC || !d_wplan || !d_act_stash || !d_grad_stash || !d_gmax || !grads
-        || !params || !d_scratch)
-        return NFL_EINVAL;
-    // the composition reads these master weights; the side-input job of a layer needs its bias gradient as well
-    if (!params->weight[NFL_P_FINAL] || !params->bias[NFL_P_FINAL] || !params->weight[NFL_P_DIR]) return NFL_EINVAL;
-    const bool ut = hp->n_jobs > 0 && hp->job[hp->n_jobs - 1].layer == NFL_P_TSIGMA;
-    if (ut && !params->weight[NFL_P_T0]) return NFL_EINVAL;
-    if ((grads->weight[NFL_P_DIR] || grads->weight[NFL_P_FINAL]) && !grads->bias[NFL_P_DIR]) return NFL_EINVAL;
-    if (ut && (grads->weight[NFL_P_T0] || grads->weight[NFL_P_FINAL]) && !grads->bias[NFL_P_T0]) return NFL_EINVAL;
-    if (n_rays < 0 || n_samples < 1) return NFL_EINVAL;
-    if (bwd_prec != NFL_PREC_F16 && bwd_prec != NFL_PREC_F16W && bwd_prec != NFL_PREC_F16X3) return NFL_EINVAL;
     const int mult = bwd_prec == NFL_PREC_F16X3 ? 2 : 1;       // split stashes: [hi record | lo record] per segment
     int n_wg = 0, red_blocks = 0;
     const NflDevice dev = nfl_device();
     WgArgs A;
     memset(&A, 0, sizeof(A));
-    const int rc = nfl_wgrad_schedule(hp, n_rays * ((n_samples + 31) / 32), dev.n_cu, mult, &A, &n_wg, &red_blocks);
+    rc = nfl_wgrad_schedule(hp, n_rays * ((n_samples + 31) / 32), dev.n_cu, mult, &A, &n_wg, &red_blocks);
     if (rc != NFL_OK) return rc;
-    A.plan = static_cast<const WgPlan*>(d_wplan);
-    A.act = d_act_stash;
-    A.grd = d_grad_stash;
-    A.g = *grads;
-    A.scratch = d_scratch;
-    A.partial = d_scratch + NFL_W * NFL_W;       // the parts lie behind G
+    WgTensors T;
+    nfl_wgrad_fill(hp, d_wplan, d_act_stash, d_grad_stash, grads, d_scratch, &A, &T);
+    WgCompose Cc;      // the composition through xyz_encoding_final (file header)
+    rc = nfl_compose_backward_tasks(hp, params, grads, d_scratch, &Cc);
+    if (rc != NFL_OK) return rc;
     if (nfl_lds_attr<&nfl_wgrad_kernel<false>>(dev.ordinal, 2 * WG_SLOT) != NFL_OK ||
         nfl_lds_attr<&nfl_wgrad_kernel<true>>(dev.ordinal, 4 * WG_SLOT) != NFL_OK)
         return NFL_ENODEV;
-    WgTensors T;
-    for (int L = 0; L < NFL_NUM_LAYERS; ++L) {
-        T.ptr[L] = grads->weight[L];
-        T.n[L] = hp->w_numel[L];
-        T.ptr[NFL_NUM_LAYERS + L] = grads->bias[L];
-        T.n[NFL_NUM_LAYERS + L] = hp->b_numel[L];
-    }
-    T.ptr[2 * NFL_NUM_LAYERS] = d_scratch;
-    T.n[2 * NFL_NUM_LAYERS] = NFL_W * NFL_W;
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(nfl_wgrad_zero_kernel, dim3(16, WG_NTENS), dim3(256), 0, s, T);
     if (n_rays == 0) return hipGetLastError() == hipSuccess ? NFL_OK : NFL_ELAUNCH;
@@ -565,81 +452,6 @@ extern "C" int nfl_mlp_wgrad(const void* h_wplan, const void* d_wplan, const cha
     // parts -> gradient tensors and G, summed in a fixed order and divided by the loss scale (what the tensors' zeroing above
     // still covers: elements no job owns, i.e. the heads a call leaves out)
     hipLaunchKernelGGL(nfl_wgrad_reduce_kernel, dim3(red_blocks), dim3(256), 0, s, A, d_gmax);
-
-    // the composition through xyz_encoding_final (file header); G, db_dir, db_t0 are final (unscaled) by now
-    const int W = NFL_W, H = NFL_W / 2;
-    const int ld_dir = hp->w_numel[NFL_P_DIR] / H, ld_t0 = ut ? hp->w_numel[NFL_P_T0] / H : 0;
-    const float* Wd = params->weight[NFL_P_DIR];
-    const float* Wt = ut ? params->weight[NFL_P_T0] : nullptr;
-    const float* Wf = params->weight[NFL_P_FINAL];
-    const float* G = d_scratch;
-    const float* Gt = d_scratch + (size_t)H * W;
-    WgCompose Cc;
-    memset(&Cc, 0, sizeof(Cc));
-    WgGemm g;
-    if (grads->weight[NFL_P_FINAL]) {       // dW_fin[i, j] = sum_r Wd[r, i] G[r, j] (+ sum_r Wt[r, i] Gt[r, j])
-        memset(&g, 0, sizeof(g));
-        g.A = Wd; g.sam = 1; g.sak = ld_dir; g.B = G; g.sbk = W; g.sbn = 1; g.K = H;
-        if (ut) { g.A2 = Wt; g.sam2 = 1; g.sak2 = ld_t0; g.B2 = Gt; g.sbk2 = W; g.sbn2 = 1; g.K2 = H; }
-        g.Cp = grads->weight[NFL_P_FINAL]; g.ldc = W; g.M = W; g.N = W;
-        wg_add(Cc, g, 1);      // G and W_fin rows are 1 KiB (checked below): float4 loads
-    }
-    if (grads->bias[NFL_P_FINAL]) {         // db_fin[i] = sum_r Wd[r, i] db_dir[r] (+ sum_r Wt[r, i] db_t0[r]): a 256 x 1 product
-        memset(&g, 0, sizeof(g));
-        g.A = Wd; g.sam = 1; g.sak = ld_dir; g.B = grads->bias[NFL_P_DIR]; g.sbk = 1; g.sbn = 1; g.K = H;
-        if (ut) { g.A2 = Wt; g.sam2 = 1; g.sak2 = ld_t0; g.B2 = grads->bias[NFL_P_T0]; g.sbk2 = 1; g.sbn2 = 1; g.K2 = H; }
-        g.Cp = grads->bias[NFL_P_FINAL]; g.ldc = 1; g.M = W; g.N = 1;
-        wg_add(Cc, g, 1);
-    }
-    if (grads->weight[NFL_P_DIR]) {         // dW_dir[r, i] = sum_j G[r, j] W_fin[i, j] + db_dir[r] b_fin[i], i < 256
-        memset(&g, 0, sizeof(g));
-        g.A = G; g.sam = W; g.sak = 1; g.B = Wf; g.sbk = 1; g.sbn = W; g.K = W;
-        g.u = grads->bias[NFL_P_DIR]; g.v = params->bias[NFL_P_FINAL];
-        g.Cp = grads->weight[NFL_P_DIR]; g.ldc = ld_dir; g.M = H; g.N = W;
-        wg_add(Cc, g, 1);
-    }
-    if (ut && grads->weight[NFL_P_T0]) {
-        memset(&g, 0, sizeof(g));
-        g.A = Gt; g.sam = W; g.sak = 1; g.B = Wf; g.sbk = 1; g.sbn = W; g.K = W;
-        g.u = grads->bias[NFL_P_T0]; g.v = params->bias[NFL_P_FINAL];
-        g.Cp = grads->weight[NFL_P_T0]; g.ldc = ld_t0; g.M = H; g.N = W;
-        wg_add(Cc, g, 1);
-    }
-    if (((uintptr_t)d_scratch | (uintptr_t)Wf) & 15) return NFL_EINVAL;      // float4 loads along k (G, W_fin rows)
-    if (Cc.n_wg > 0) hipLaunchKernelGGL(nfl_wgrad_compose_kernel, dim3(Cc.n_wg), dim3(256), 0, s, Cc);
-    return hipGetLastError() == hipSuccess ? NFL_OK : NFL_ELAUNCH;
-}
-
-// Fold xyz_encoding_final into the layers that read its output, for the PACKED streams only (the parameters stay what
-// they are): W_dir' = [W_dir[:, :256] W_fin | W_dir[:, 256:]], b_dir' = b_dir + W_dir[:, :256] b_fin, likewise for
-// transient_encoding.0.  The caller hands in copies of W_dir / W_t0 (the side columns are kept, the first 256 columns
-// overwritten) and receives the folded biases; nfl_pack_field(s) is then given these in place of the originals, and
-// the streams carry no tiles for xyz_encoding_final (nfl_plan.cpp): one 256 x 256 layer less in the forward and in dgrad.
-extern "C" int nfl_compose_forward(const nfl_field_params* params, int32_t has_t, int32_t n_side, int32_t n_tau,
-                                   float* d_wdir_c, float* d_bdir_c, float* d_wt0_c, float* d_bt0_c, void* stream) {
-    if (!params || !d_wdir_c || !d_bdir_c || (has_t && (!d_wt0_c || !d_bt0_c))) return NFL_EINVAL;
-    const float* Wf = params->weight[NFL_P_FINAL];
-    const float* bf = params->bias[NFL_P_FINAL];
-    if (!Wf || !bf || !params->weight[NFL_P_DIR] || !params->bias[NFL_P_DIR]) return NFL_EINVAL;
-    if (has_t && (!params->weight[NFL_P_T0] || !params->bias[NFL_P_T0])) return NFL_EINVAL;
-    const int W = NFL_W, H = NFL_W / 2;
-    WgCompose Cc;
-    memset(&Cc, 0, sizeof(Cc));
-    for (int which = 0; which < (has_t ? 2 : 1); ++which) {
-        const int L = which ? NFL_P_T0 : NFL_P_DIR;
-        const int ld = W + (which ? n_tau : n_side);
-        const float* Ws = params->weight[L];
-        WgGemm g;
-        memset(&g, 0, sizeof(g));          // W'[r, i] = sum_j W[r, j] W_fin[j, i]   (rows of W are not 16-byte aligned: scalar loads)
-        g.A = Ws; g.sam = ld; g.sak = 1; g.B = Wf; g.sbk = W; g.sbn = 1; g.K = W;
-        g.Cp = which ? d_wt0_c : d_wdir_c; g.ldc = ld; g.M = H; g.N = W;
-        wg_add(Cc, g, 0);
-        memset(&g, 0, sizeof(g));          // b'[r] = b[r] + sum_j W[r, j] b_fin[j]
-        g.A = Ws; g.sam = ld; g.sak = 1; g.B = bf; g.sbk = 1; g.sbn = 1; g.K = W;
-        g.addm = params->bias[L];
-        g.Cp = which ? d_bt0_c : d_bdir_c; g.ldc = 1; g.M = H; g.N = 1;
-        wg_add(Cc, g, 0);
-    }
-    hipLaunchKernelGGL(nfl_wgrad_compose_kernel, dim3(Cc.n_wg), dim3(256), 0, static_cast<hipStream_t>(stream), Cc);
+    if (Cc.n_wg > 0) nfl_compose_launch(Cc, s);      // G, db_dir, db_t0 are final (unscaled) by now
     return hipGetLastError() == hipSuccess ? NFL_OK : NFL_ELAUNCH;
 }

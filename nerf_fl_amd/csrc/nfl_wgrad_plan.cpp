@@ -1,6 +1,7 @@
 // nfl_wgrad_plan.cpp -- host planner of the weight-gradient pass: the per-layer job list of a field and the launch schedule
-// of a call.  Plain C++ (no HIP), so that tests/plan_sweep.cpp can run it under ASan + UBSan over every configuration:
-// fixed-size tables (WG_MAX_JOBS, WG_MAX_OT, WG_MAX_IT) filled by configuration-dependent loops.
+// of a call, the entry point's refusals and the fill of its pointer arguments.  Plain C++ (no HIP), so that
+// tests/plan_sweep.cpp can run it under ASan + UBSan over every configuration: fixed-size tables (WG_MAX_JOBS, WG_MAX_OT,
+// WG_MAX_IT) filled by configuration-dependent loops.
 #include "nfl_wgrad_plan.h"
 
 #include <string.h>
@@ -215,4 +216,41 @@ extern "C" int nfl_wgrad_schedule(const WgPlan* hp, int n_seg, int n_cu, int mul
     *n_wg_out = acc_wg;
     *n_red_out = red_blocks;
     return NFL_OK;
+}
+
+int nfl_wgrad_check(const void* h_wplan, const void* d_wplan, const char* d_act_stash, const char* d_grad_stash,
+                    const float* d_gmax, int32_t n_rays, int32_t n_samples, int32_t bwd_prec, const nfl_field_params* params,
+                    const float* d_scratch, const nfl_field_grads* grads) {
+    const WgPlan* hp = static_cast<const WgPlan*>(h_wplan);
+    if (!hp || hp->magic != WG_PLAN_MAGIC || !d_wplan || !d_act_stash || !d_grad_stash || !d_gmax || !grads
+        || !params || !d_scratch)
+        return NFL_EINVAL;
+    // the composition reads these master weights; the side-input job of a layer needs its bias gradient as well
+    if (!params->weight[NFL_P_FINAL] || !params->bias[NFL_P_FINAL] || !params->weight[NFL_P_DIR]) return NFL_EINVAL;
+    const bool ut = wg_plan_transient(hp);
+    if (ut && !params->weight[NFL_P_T0]) return NFL_EINVAL;
+    if ((grads->weight[NFL_P_DIR] || grads->weight[NFL_P_FINAL]) && !grads->bias[NFL_P_DIR]) return NFL_EINVAL;
+    if (ut && (grads->weight[NFL_P_T0] || grads->weight[NFL_P_FINAL]) && !grads->bias[NFL_P_T0]) return NFL_EINVAL;
+    if (n_rays < 0 || n_samples < 1) return NFL_EINVAL;
+    if (bwd_prec != NFL_PREC_F16 && bwd_prec != NFL_PREC_F16W && bwd_prec != NFL_PREC_F16X3) return NFL_EINVAL;
+    if (((uintptr_t)d_scratch | (uintptr_t)params->weight[NFL_P_FINAL]) & 15) return NFL_EINVAL;      // float4 loads along k (G, W_fin rows)
+    return NFL_OK;
+}
+
+void nfl_wgrad_fill(const WgPlan* hp, const void* d_wplan, const char* d_act_stash, const char* d_grad_stash,
+                    const nfl_field_grads* grads, float* d_scratch, WgArgs* args, WgTensors* zero) {
+    args->plan = static_cast<const WgPlan*>(d_wplan);
+    args->act = d_act_stash;
+    args->grd = d_grad_stash;
+    args->g = *grads;
+    args->scratch = d_scratch;
+    args->partial = d_scratch + NFL_W * NFL_W;       // the parts lie behind G
+    for (int L = 0; L < NFL_NUM_LAYERS; ++L) {
+        zero->ptr[L] = grads->weight[L];
+        zero->n[L] = hp->w_numel[L];
+        zero->ptr[NFL_NUM_LAYERS + L] = grads->bias[L];
+        zero->n[NFL_NUM_LAYERS + L] = hp->b_numel[L];
+    }
+    zero->ptr[2 * NFL_NUM_LAYERS] = d_scratch;
+    zero->n[2 * NFL_NUM_LAYERS] = NFL_W * NFL_W;
 }

@@ -1,6 +1,7 @@
 // nfl_wgrad_plan.h -- what the host planner of the weight-gradient pass (nfl_wgrad_plan.cpp, plain C++) and its kernels
-// (nfl_wgrad.hip) share: the job list of a field, the launch schedule of a call, and the ONE table of the stream kernel's
-// instantiations.  Read by g++ and hipcc alike; the kernels read the structs and the caller keeps a device copy of the plan.
+// (nfl_wgrad.hip) share: the job list of a field, the launch schedule of a call, the ONE table of the stream kernel's
+// instantiations, and the checks and pointer fill of nfl_mlp_wgrad.  Read by g++ and hipcc alike; the kernels read the
+// structs and the caller keeps a device copy of the plan.
 #pragma once
 #include "../../include/nerf_fl_amd.h"
 #include "nfl_plan.h"
@@ -96,3 +97,22 @@ NFL_HD_EARLY int wg_nitw(int n_it, int n_wi) { return (n_it + n_wi - 1) / n_wi; 
 //   n_seg  32-sample segments of the call;  n_cu  compute units of the device;  mult  2 with split (hi + lo) stashes, else 1
 // NFL_EINVAL: a plan that nfl_wgrad_plan_build did not make, or one whose parts / LDS slots exceed what the library sizes.
 extern "C" int nfl_wgrad_schedule(const WgPlan* h_plan, int n_seg, int n_cu, int mult, WgArgs* args, int* n_wg, int* n_red);
+
+// What nfl_wgrad_zero_kernel clears before the stream (the reduction stores only the elements a job owns).
+#define WG_NTENS (2 * NFL_NUM_LAYERS + 1)     // weights, biases, the composition scratch
+struct WgTensors {
+    float* ptr[WG_NTENS];
+    int n[WG_NTENS];
+};
+// the plan has the transient jobs (its last job is then the transient heads'): the composition takes W_t0 and Gt in
+inline bool wg_plan_transient(const WgPlan* hp) {
+    return hp->n_jobs > 0 && hp->n_jobs <= WG_MAX_JOBS && hp->job[hp->n_jobs - 1].layer == NFL_P_TSIGMA;
+}
+// Every refusal of nfl_mlp_wgrad (its arguments; NFL_OK or NFL_EINVAL), the last one the 16-byte alignment of d_scratch and
+// params->weight[NFL_P_FINAL] that the composition's float4 loads need.  No runtime call: the entry point makes it first.
+int nfl_wgrad_check(const void* h_wplan, const void* d_wplan, const char* d_act_stash, const char* d_grad_stash,
+                    const float* d_gmax, int32_t n_rays, int32_t n_samples, int32_t bwd_prec, const nfl_field_params* params,
+                    const float* d_scratch, const nfl_field_grads* grads);
+// The pointer fields of *args (nfl_wgrad_schedule fills the others) and the zero list of a checked call.
+void nfl_wgrad_fill(const WgPlan* h_plan, const void* d_wplan, const char* d_act_stash, const char* d_grad_stash,
+                    const nfl_field_grads* grads, float* d_scratch, WgArgs* args, WgTensors* zero);

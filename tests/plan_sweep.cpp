@@ -10,11 +10,18 @@
 // counts against the twelve lines it replaced; for every accepted field the argument blocks of every mode and backward
 // plan, filled over 0x00 and over 0xFF; and the table of refusals of the four entry points.  Prints
 // "launch splits <n> fills <m> refusals <k>".
+// The composition through xyz_encoding_final (csrc/nfl_compose.cpp) and the entry half of the weight-gradient pass
+// (nfl_wgrad_check, nfl_wgrad_fill) are the fourth: every task list the two builders make, for every distinct shape the
+// descriptor sweep yields, is evaluated on exactly-sized heap blocks by a reference interpreter of the kernel's stated
+// meaning and compared, exactly (integer data), with the composition's formulas written directly; a table of refusals,
+// one and more rows per `return`.  Prints "compose forward cases <n> backward cases <m> refusal rows <k> wgrad fills <l>".
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <initializer_list>
 
 #include "../include/nerf_fl_amd.h"
+#include "../nerf_fl_amd/csrc/nfl_compose.h"
 #include "../nerf_fl_amd/csrc/nfl_launch.h"
 #include "../nerf_fl_amd/csrc/nfl_plan.h"
 #include "../nerf_fl_amd/csrc/nfl_wgrad_plan.h"
@@ -436,6 +443,452 @@ static bool check_refusals(const NflPlan& fx3, const NflPlan& fx1, const NflPlan
     return ok;
 }
 
+// ---------------------------------------------------------------------------------
+// csrc/nfl_compose.cpp and the entry half of csrc/nfl_wgrad_plan.cpp
+// ---------------------------------------------------------------------------------
+#define CP_CHECK(cond)                                                 \
+    do {                                                               \
+        if (!(cond)) {                                                 \
+            printf("compose invariant broken: %s (%s)\n", #cond, cp_where); \
+            return false;                                              \
+        }                                                              \
+    } while (0)
+static char cp_where[200];
+static int n_cp_fwd, n_cp_bwd, n_cp_refusals, n_wg_fills;
+static const float CP_SENTINEL = 12345.f;
+
+// an operand or an output of exactly its size on the heap: one element past it is an ASan report
+struct Blk {
+    float* p;
+    size_t n;
+    explicit Blk(size_t n_) : p(new float[n_]), n(n_) {}
+    Blk(const Blk& o) : p(new float[o.n]), n(o.n) { memcpy(p, o.p, n * sizeof(float)); }
+    Blk& operator=(const Blk&) = delete;
+    ~Blk() { delete[] p; }
+    Blk& ints(unsigned seed) {          // integers in [-2, 2]: every partial sum is an integer far below 2^24, exact in any order
+        for (size_t i = 0; i < n; ++i) {
+            seed = seed * 1664525u + 1013904223u;
+            p[i] = (float)((int)((seed >> 16) % 5u) - 2);
+        }
+        return *this;
+    }
+    Blk& fill(float v) {
+        for (size_t i = 0; i < n; ++i) p[i] = v;
+        return *this;
+    }
+    bool same(const Blk& o) const { return n == o.n && memcmp(p, o.p, n * sizeof(float)) == 0; }
+};
+
+// The two pieces of arithmetic that form no address of a task are built without the sanitizers and optimised (the sweep
+// makes ~4 x 10^10 multiply-adds): the dense product below, whose operands cp_gather has read one by one under the
+// sanitizers, and the expected values of the gradient composition.
+#define CP_FAST __attribute__((optimize("O3"), no_sanitize("address", "undefined")))
+// C (M x N, dense) += A (M x K, dense) B (K x N, dense)
+CP_FAST static void cp_dense(float* C, const float* A, const float* B, int M, int N, int K) {
+    for (int m = 0; m < M; ++m)
+        for (int k = 0; k < K; ++k) {
+            const float a = A[(size_t)m * K + k];
+            for (int n = 0; n < N; ++n) C[(size_t)m * N + n] += a * B[(size_t)k * N + n];
+        }
+}
+// rows x cols elements of P at element strides (sr, sc), read one by one, into a dense block
+static Blk cp_gather(const float* P, int rows, int cols, long sr, long sc) {
+    Blk d((size_t)rows * cols);
+    for (int r = 0; r < rows; ++r)
+        for (int c = 0; c < cols; ++c) d.p[(size_t)r * cols + c] = P[r * sr + c * sc];
+    return d;
+}
+
+// The reference interpreter: a task list on host memory by the kernel's stated meaning (csrc/nfl_compose.h),
+//   C[m*ldc + n] = sum_k A[m*sam + k*sak] B[k*sbk + n*sbn] (+ second product) (+ u[m] v[n]) (+ addm[m]),  m < M, n < N,
+// written workgroup by workgroup as tiles_n and tile0 say: workgroup w belongs to the last task whose tile0 is <= w and
+// writes the 32 rows from 32 (tile / tiles_n) on, columns 32 (tile % tiles_n) + 0..31 below N.
+static bool cp_run(const WgCompose& Cc) {
+    CP_CHECK(Cc.n_tasks >= 0 && Cc.n_tasks <= WG_MAX_GEMM);
+    int wg = 0;
+    for (int ti = 0; ti < Cc.n_tasks; ++ti) {
+        const WgGemm& T = Cc.t[ti];
+        CP_CHECK(T.tile0 == wg);
+        Blk C((size_t)T.M * T.N);
+        C.fill(0.f);
+        cp_dense(C.p, cp_gather(T.A, T.M, T.K, T.sam, T.sak).p, cp_gather(T.B, T.K, T.N, T.sbk, T.sbn).p, T.M, T.N, T.K);
+        if (T.K2) cp_dense(C.p, cp_gather(T.A2, T.M, T.K2, T.sam2, T.sak2).p, cp_gather(T.B2, T.K2, T.N, T.sbk2, T.sbn2).p, T.M, T.N, T.K2);
+        const int end = ti + 1 < Cc.n_tasks ? Cc.t[ti + 1].tile0 : Cc.n_wg;
+        int written = 0;
+        for (; wg < end; ++wg) {
+            const int tile = wg - T.tile0, m0 = 32 * (tile / T.tiles_n), n0 = 32 * (tile % T.tiles_n);
+            CP_CHECK(m0 + 32 <= T.M);          // the kernel does not test m
+            for (int m = m0; m < m0 + 32; ++m)
+                for (int n = n0; n < n0 + 32 && n < T.N; ++n, ++written)
+                    T.Cp[(size_t)m * T.ldc + n] = C.p[(size_t)m * T.N + n] + (T.u ? T.u[m] * T.v[n] : 0.f) + (T.addm ? T.addm[m] : 0.f);
+        }
+        CP_CHECK(written == T.M * T.N);        // every element of the block by exactly one workgroup
+    }
+    CP_CHECK(wg == Cc.n_wg);
+    return true;
+}
+
+// out[:, :cols] of a (rows x ld) block equals the dense `exp`; every other column still holds what `before` holds
+static bool cp_block_is(const Blk& out, const Blk& before, int rows, int ld, int cols, const Blk& exp) {
+    for (int r = 0; r < rows; ++r)
+        for (int c = 0; c < ld; ++c) {
+            const size_t i = (size_t)r * ld + c;
+            if (c < cols ? out.p[i] != exp.p[(size_t)r * cols + c] : memcmp(&out.p[i], &before.p[i], sizeof(float)) != 0) {
+                printf("compose invariant broken: element (%d, %d) is %g (%s)\n", r, c, out.p[i], cp_where);
+                return false;
+            }
+        }
+    return true;
+}
+
+struct CpShape { int n_side, has_t, n_tau; };      // of a field: side columns of dir_encoding.0, transient layers, their code width
+
+// The forward fold against  W' = [W[:, :256] W_fin | W[:, 256:]],  b' = b + W[:, :256] b_fin.
+CP_FAST static void cp_expect_forward(int ld, const float* Wl, const float* bl, const float* Wfin, const float* bfin, float* eW, float* eb) {
+    const int W = NFL_W, H = NFL_W / 2;
+    for (int r = 0; r < H; ++r) {
+        for (int c = 0; c < W; ++c) eW[r * W + c] = 0.f;
+        for (int j = 0; j < W; ++j)
+            for (int c = 0; c < W; ++c) eW[r * W + c] += Wl[r * ld + j] * Wfin[j * W + c];
+        eb[r] = bl[r];
+        for (int j = 0; j < W; ++j) eb[r] += Wl[r * ld + j] * bfin[j];
+    }
+}
+static bool check_compose_forward(const CpShape& s) {
+    const int W = NFL_W, H = NFL_W / 2, ld[2] = {W + s.n_side, W + s.n_tau};
+    snprintf(cp_where, sizeof(cp_where), "forward: n_side %d has_t %d n_tau %d", s.n_side, s.has_t, s.n_tau);
+    Blk Wfin((size_t)W * W), bfin(W);
+    Wfin.ints(1); bfin.ints(2);
+    Blk Wl[2] = {Blk((size_t)H * ld[0]), Blk((size_t)H * ld[1])}, bl[2] = {Blk(H), Blk(H)};
+    for (int i = 0; i < 2; ++i) { Wl[i].ints(3 + i); bl[i].ints(5 + i); }
+    nfl_field_params P;
+    memset(&P, 0, sizeof(P));
+    P.weight[NFL_P_FINAL] = Wfin.p; P.bias[NFL_P_FINAL] = bfin.p;
+    P.weight[NFL_P_DIR] = Wl[0].p; P.bias[NFL_P_DIR] = bl[0].p;
+    P.weight[NFL_P_T0] = Wl[1].p; P.bias[NFL_P_T0] = bl[1].p;
+    Blk Wc[2] = {Wl[0], Wl[1]}, bc[2] = {Blk(H), Blk(H)};       // the API takes copies of the weights and writes the biases
+    if (!s.has_t) Wc[1].fill(CP_SENTINEL);                      // ... and leaves the transient pair alone without has_t
+    bc[0].fill(CP_SENTINEL); bc[1].fill(CP_SENTINEL);
+    const Blk Wc0[2] = {Wc[0], Wc[1]}, bc0[2] = {bc[0], bc[1]}, in0[6] = {Wfin, bfin, Wl[0], Wl[1], bl[0], bl[1]};
+    WgCompose* Cc = new WgCompose;
+    memset(Cc, 0xFF, sizeof(*Cc));
+    bool ok = [&]() {
+        CP_CHECK(nfl_compose_forward_tasks(&P, s.has_t, s.n_side, s.n_tau, Wc[0].p, bc[0].p, Wc[1].p, bc[1].p, Cc) == NFL_OK);
+        CP_CHECK(Cc->n_tasks == (s.has_t ? 4 : 2));
+        if (!cp_run(*Cc)) return false;
+        for (int i = 0; i < 2; ++i) {
+            if (i && !s.has_t) {
+                CP_CHECK(Wc[1].same(Wc0[1]) && bc[1].same(bc0[1]));
+                continue;
+            }
+            Blk eW((size_t)H * W), eb(H);
+            cp_expect_forward(ld[i], Wl[i].p, bl[i].p, Wfin.p, bfin.p, eW.p, eb.p);
+            if (!cp_block_is(Wc[i], Wc0[i], H, ld[i], W, eW) || !cp_block_is(bc[i], bc0[i], H, 1, 1, eb)) return false;
+        }
+        CP_CHECK(Wfin.same(in0[0]) && bfin.same(in0[1]) && Wl[0].same(in0[2]) && Wl[1].same(in0[3]) && bl[0].same(in0[4]) && bl[1].same(in0[5]));
+        return true;
+    }();
+    delete Cc;
+    ++n_cp_fwd;
+    return ok;
+}
+
+// The gradient composition of one plan and one subset of the four composed gradients (bit 0 dW_fin, 1 db_fin, 2 dW_dir,
+// 3 dW_t0) against the formulas of the header of csrc/nfl_wgrad.hip, written directly.
+CP_FAST static void cp_expect_backward(int ut, int ld_d, int ld_t, const float* Wfin, const float* bfin, const float* Wdir, const float* Wt0,
+                                       const float* G, const float* db_dir, const float* db_t0, float* eWfin, float* ebfin, float* eWdir, float* eWt0) {
+    const int W = NFL_W, H = NFL_W / 2;
+    // dW_fin = Wd^T G (+ Wt^T Gt),  db_fin = Wd^T db_dir (+ Wt^T db_t0);  Wd = W_dir[:, :256], Gt = rows 128.. of the scratch
+    for (int i = 0; i < W; ++i) {
+        ebfin[i] = 0.f;
+        for (int j = 0; j < W; ++j) eWfin[i * W + j] = 0.f;
+    }
+    for (int t = 0; t < (ut ? 2 : 1); ++t) {
+        const float* Ws = t ? Wt0 : Wdir;
+        const float* Gs = G + (size_t)t * H * W;
+        const float* dbs = t ? db_t0 : db_dir;
+        const int ld = t ? ld_t : ld_d;
+        for (int r = 0; r < H; ++r)
+            for (int i = 0; i < W; ++i) {
+                for (int j = 0; j < W; ++j) eWfin[i * W + j] += Ws[r * ld + i] * Gs[r * W + j];
+                ebfin[i] += Ws[r * ld + i] * dbs[r];
+            }
+    }
+    // dW_dir[:, :256] = G W_fin^T + db_dir (x) b_fin, the same for W_t0 from Gt and db_t0
+    for (int t = 0; t < 2; ++t) {
+        const float* Gs = G + (size_t)t * H * W;
+        const float* dbs = t ? db_t0 : db_dir;
+        float* e = t ? eWt0 : eWdir;
+        for (int r = 0; r < H; ++r)
+            for (int i = 0; i < W; ++i) {
+                float a = dbs[r] * bfin[i];
+                for (int j = 0; j < W; ++j) a += Gs[r * W + j] * Wfin[i * W + j];
+                e[r * W + i] = a;
+            }
+    }
+}
+
+static bool check_compose_backward(const WgPlan& P, const CpShape& s, int ut, int subset, const Blk* in, const Blk* in0, const Blk* exp,
+                                   const Blk* out0) {
+    const int W = NFL_W, H = NFL_W / 2, ld_d = W + s.n_side, ld_t = W + s.n_tau;
+    snprintf(cp_where, sizeof(cp_where), "backward: n_side %d has_t %d n_tau %d transient %d subset %d", s.n_side, s.has_t, s.n_tau, ut, subset);
+    const Blk &Wfin = in[0], &bfin = in[1], &Wdir = in[2], &Wt0 = in[3], &G = in[4], &db_dir = in[5], &db_t0 = in[6];
+    Blk gWfin(out0[0]), gbfin(out0[1]), gWdir(out0[2]), gWt0(out0[3]);        // copies of the sentinel-filled blocks
+    nfl_field_params prm;
+    nfl_field_grads gr;
+    memset(&prm, 0, sizeof(prm));
+    memset(&gr, 0, sizeof(gr));
+    prm.weight[NFL_P_FINAL] = Wfin.p; prm.bias[NFL_P_FINAL] = bfin.p; prm.weight[NFL_P_DIR] = Wdir.p;
+    if (s.has_t) prm.weight[NFL_P_T0] = Wt0.p;
+    gr.bias[NFL_P_DIR] = db_dir.p; gr.bias[NFL_P_T0] = db_t0.p;
+    if (subset & 1) gr.weight[NFL_P_FINAL] = gWfin.p;
+    if (subset & 2) gr.bias[NFL_P_FINAL] = gbfin.p;
+    if (subset & 4) gr.weight[NFL_P_DIR] = gWdir.p;
+    if (subset & 8) gr.weight[NFL_P_T0] = gWt0.p;
+    WgCompose* Cc = new WgCompose;
+    memset(Cc, 0xFF, sizeof(*Cc));
+    bool ok = [&]() {
+        CP_CHECK(nfl_wgrad_check(&P, DP, DC, DC, DP, 64, 64, NFL_PREC_F16, &prm, G.p, &gr) == NFL_OK);
+        CP_CHECK(nfl_compose_backward_tasks(&P, &prm, &gr, G.p, Cc) == NFL_OK);
+        CP_CHECK(wg_plan_transient(&P) == (ut != 0));
+        CP_CHECK(Cc->n_tasks == !!(subset & 1) + !!(subset & 2) + !!(subset & 4) + (ut && (subset & 8)));
+        if (!cp_run(*Cc)) return false;
+        // a gradient that is not given, or not composed by this plan, keeps its sentinel in every byte
+        if (subset & 1 ? !cp_block_is(gWfin, out0[0], W, W, W, exp[0]) : !gWfin.same(out0[0])) return false;
+        if (subset & 2 ? !cp_block_is(gbfin, out0[1], W, 1, 1, exp[1]) : !gbfin.same(out0[1])) return false;
+        if (subset & 4 ? !cp_block_is(gWdir, out0[2], H, ld_d, W, exp[2]) : !gWdir.same(out0[2])) return false;
+        if (ut && (subset & 8) ? !cp_block_is(gWt0, out0[3], H, ld_t, W, exp[3]) : !gWt0.same(out0[3])) return false;
+        CP_CHECK(Wfin.same(in0[0]) && bfin.same(in0[1]) && Wdir.same(in0[2]) && Wt0.same(in0[3]) && G.same(in0[4]) && db_dir.same(in0[5]) && db_t0.same(in0[6]));
+        return true;
+    }();
+    delete Cc;
+    ++n_cp_bwd;
+    return ok;
+}
+
+// nfl_wgrad_fill: the zero list whatever *zero held before, the pointer fields of *args and nothing else of it
+static bool check_wgrad_fill(const WgPlan& P) {
+    snprintf(cp_where, sizeof(cp_where), "nfl_wgrad_fill");
+    nfl_field_grads gr;
+    memset(&gr, 0, sizeof(gr));
+    for (int L = 0; L < NFL_NUM_LAYERS; L += 2) { gr.weight[L] = DP + 1; gr.bias[L] = DP + 2; }
+    WgTensors* T[2] = {new WgTensors, new WgTensors};
+    WgArgs* A[2] = {new WgArgs, new WgArgs};
+    for (int i = 0; i < 2; ++i) {
+        memset(T[i], i ? 0xFF : 0x00, sizeof(WgTensors));
+        memset(A[i], i ? 0xFF : 0x00, sizeof(WgArgs));
+        nfl_wgrad_fill(&P, DP, DC, DC + 1, &gr, DP, A[i], T[i]);
+    }
+    bool ok = [&]() {
+        for (int i = 0; i < 2; ++i) {
+            for (int L = 0; L < NFL_NUM_LAYERS; ++L) {
+                CP_CHECK(T[i]->ptr[L] == gr.weight[L] && T[i]->n[L] == P.w_numel[L]);
+                CP_CHECK(T[i]->ptr[NFL_NUM_LAYERS + L] == gr.bias[L] && T[i]->n[NFL_NUM_LAYERS + L] == P.b_numel[L]);
+            }
+            CP_CHECK(T[i]->ptr[WG_NTENS - 1] == DP && T[i]->n[WG_NTENS - 1] == NFL_W * NFL_W);
+            CP_CHECK(A[i]->plan == (const WgPlan*)DP && A[i]->act == DC && A[i]->grd == DC + 1 && A[i]->scratch == DP);
+            CP_CHECK(A[i]->partial == DP + NFL_W * NFL_W && memcmp(&A[i]->g, &gr, sizeof(gr)) == 0);
+            CP_CHECK(A[i]->n_seg == (i ? -1 : 0) && A[i]->slot_bytes == (i ? -1 : 0) && A[i]->red_start[WG_MAX_JOBS] == (i ? -1 : 0));
+        }
+        return true;
+    }();
+    for (int i = 0; i < 2; ++i) { delete T[i]; delete A[i]; }
+    ++n_wg_fills;
+    return ok;
+}
+
+// One call of nfl_wgrad_check or of a builder: valid arguments, until a row's edit.
+enum { C_CHECK, C_FWD, C_BWD };
+struct CCase {
+    const WgPlan *hp, *plan_t, *plan_not;      // hp: the plan with the transient jobs; plan_not: the same field without
+    WgPlan* edited;
+    const void* d_wplan;
+    const char *act, *grd;
+    const float* gmax;
+    int n_rays, n_samples, prec;
+    nfl_field_params prm;
+    const nfl_field_params* params;
+    nfl_field_grads gr;
+    const nfl_field_grads* grads;
+    float* scratch;
+    int has_t, n_side, n_tau;
+    float *wdir_c, *bdir_c, *wt0_c, *bt0_c;
+    WgCompose* out;
+};
+struct CRow {
+    int entry;
+    const char* what;
+    void (*edit)(CCase&);
+    int rc, n_tasks;          // n_tasks: of the builders' list (-1: not looked at)
+};
+#define BAD NFL_EINVAL
+static const CRow CROWS[] = {
+    // nfl_wgrad_check, in the order of its refusals
+    {C_CHECK, "valid", [](CCase&) {}, NFL_OK, -1},
+    {C_CHECK, "no plan", [](CCase& c) { c.hp = nullptr; }, BAD, -1},
+    {C_CHECK, "bad magic", [](CCase& c) { c.edited->magic = NFL_PLAN_MAGIC; c.hp = c.edited; }, BAD, -1},
+    {C_CHECK, "no device plan", [](CCase& c) { c.d_wplan = nullptr; }, BAD, -1},
+    {C_CHECK, "no activation stash", [](CCase& c) { c.act = nullptr; }, BAD, -1},
+    {C_CHECK, "no gradient stash", [](CCase& c) { c.grd = nullptr; }, BAD, -1},
+    {C_CHECK, "no gmax", [](CCase& c) { c.gmax = nullptr; }, BAD, -1},
+    {C_CHECK, "no gradient tensors", [](CCase& c) { c.grads = nullptr; }, BAD, -1},
+    {C_CHECK, "no parameters", [](CCase& c) { c.params = nullptr; }, BAD, -1},
+    {C_CHECK, "no scratch", [](CCase& c) { c.scratch = nullptr; }, BAD, -1},
+    {C_CHECK, "no W_fin", [](CCase& c) { c.prm.weight[NFL_P_FINAL] = nullptr; }, BAD, -1},
+    {C_CHECK, "no b_fin", [](CCase& c) { c.prm.bias[NFL_P_FINAL] = nullptr; }, BAD, -1},
+    {C_CHECK, "no W_dir", [](CCase& c) { c.prm.weight[NFL_P_DIR] = nullptr; }, BAD, -1},
+    {C_CHECK, "transient plan without W_t0", [](CCase& c) { c.prm.weight[NFL_P_T0] = nullptr; }, BAD, -1},
+    {C_CHECK, "... which a plan without the transient jobs does not need", [](CCase& c) { c.hp = c.plan_not; c.prm.weight[NFL_P_T0] = nullptr; }, NFL_OK, -1},
+    {C_CHECK, "dW_dir without db_dir", [](CCase& c) { c.gr.weight[NFL_P_FINAL] = nullptr; c.gr.bias[NFL_P_DIR] = nullptr; }, BAD, -1},
+    {C_CHECK, "dW_fin without db_dir", [](CCase& c) { c.gr.weight[NFL_P_DIR] = nullptr; c.gr.bias[NFL_P_DIR] = nullptr; }, BAD, -1},
+    {C_CHECK, "neither, no db_dir", [](CCase& c) { c.gr.weight[NFL_P_DIR] = c.gr.weight[NFL_P_FINAL] = nullptr; c.gr.bias[NFL_P_DIR] = nullptr; }, NFL_OK, -1},
+    {C_CHECK, "dW_t0 without db_t0", [](CCase& c) { c.gr.weight[NFL_P_FINAL] = nullptr; c.gr.bias[NFL_P_T0] = nullptr; }, BAD, -1},
+    {C_CHECK, "dW_fin without db_t0", [](CCase& c) { c.gr.weight[NFL_P_T0] = nullptr; c.gr.bias[NFL_P_T0] = nullptr; }, BAD, -1},
+    {C_CHECK, "... which a plan without the transient jobs does not need", [](CCase& c) { c.hp = c.plan_not; c.gr.bias[NFL_P_T0] = nullptr; }, NFL_OK, -1},
+    {C_CHECK, "n_rays < 0", [](CCase& c) { c.n_rays = -1; }, BAD, -1},
+    {C_CHECK, "n_samples < 1", [](CCase& c) { c.n_samples = 0; }, BAD, -1},
+    {C_CHECK, "no rays", [](CCase& c) { c.n_rays = 0; }, NFL_OK, -1},
+    {C_CHECK, "precision 7", [](CCase& c) { c.prec = 7; }, BAD, -1},
+    {C_CHECK, "precision -1", [](CCase& c) { c.prec = -1; }, BAD, -1},
+    {C_CHECK, "exact-weight chain", [](CCase& c) { c.prec = NFL_PREC_F16W; }, NFL_OK, -1},
+    {C_CHECK, "three products", [](CCase& c) { c.prec = NFL_PREC_F16X3; }, NFL_OK, -1},
+    {C_CHECK, "scratch off by 4 bytes", [](CCase& c) { c.scratch += 1; }, BAD, -1},
+    {C_CHECK, "W_fin off by 4 bytes", [](CCase& c) { c.prm.weight[NFL_P_FINAL] += 1; }, BAD, -1},
+    {C_CHECK, "both off by 4 bytes", [](CCase& c) { c.scratch += 1; c.prm.weight[NFL_P_FINAL] += 1; }, BAD, -1},
+    {C_CHECK, "scratch off by 8 bytes", [](CCase& c) { c.scratch += 2; }, BAD, -1},
+    {C_CHECK, "misaligned, no rays: refused all the same", [](CCase& c) { c.scratch += 1; c.n_rays = 0; }, BAD, -1},
+    // nfl_compose_forward_tasks
+    {C_FWD, "valid", [](CCase&) {}, NFL_OK, 4},
+    {C_FWD, "valid, no transient layers", [](CCase& c) { c.has_t = 0; }, NFL_OK, 2},
+    {C_FWD, "... which need neither their outputs nor their parameters", [](CCase& c) { c.has_t = 0; c.wt0_c = c.bt0_c = nullptr; c.prm.weight[NFL_P_T0] = c.prm.bias[NFL_P_T0] = nullptr; }, NFL_OK, 2},
+    {C_FWD, "no task list", [](CCase& c) { c.out = nullptr; }, BAD, -1},
+    {C_FWD, "no parameters", [](CCase& c) { c.params = nullptr; }, BAD, 0},
+    {C_FWD, "no W_dir copy", [](CCase& c) { c.wdir_c = nullptr; }, BAD, 0},
+    {C_FWD, "no b_dir output", [](CCase& c) { c.bdir_c = nullptr; }, BAD, 0},
+    {C_FWD, "no W_t0 copy", [](CCase& c) { c.wt0_c = nullptr; }, BAD, 0},
+    {C_FWD, "no b_t0 output", [](CCase& c) { c.bt0_c = nullptr; }, BAD, 0},
+    {C_FWD, "no W_fin", [](CCase& c) { c.prm.weight[NFL_P_FINAL] = nullptr; }, BAD, 0},
+    {C_FWD, "no b_fin", [](CCase& c) { c.prm.bias[NFL_P_FINAL] = nullptr; }, BAD, 0},
+    {C_FWD, "no W_dir", [](CCase& c) { c.prm.weight[NFL_P_DIR] = nullptr; }, BAD, 0},
+    {C_FWD, "no b_dir", [](CCase& c) { c.prm.bias[NFL_P_DIR] = nullptr; }, BAD, 0},
+    {C_FWD, "no W_t0", [](CCase& c) { c.prm.weight[NFL_P_T0] = nullptr; }, BAD, 0},
+    {C_FWD, "no b_t0", [](CCase& c) { c.prm.bias[NFL_P_T0] = nullptr; }, BAD, 0},
+    {C_FWD, "n_side -1", [](CCase& c) { c.n_side = -1; }, BAD, 0},
+    {C_FWD, "n_tau -1", [](CCase& c) { c.n_tau = -1; }, BAD, 0},
+    {C_FWD, "n_tau -1 without the transient layers", [](CCase& c) { c.has_t = 0; c.n_tau = -1; }, BAD, 0},
+    {C_FWD, "no side columns", [](CCase& c) { c.n_side = 0; }, NFL_OK, 4},
+    {C_FWD, "misaligned operands: scalar loads", [](CCase& c) { c.prm.weight[NFL_P_FINAL] += 1; c.wdir_c += 1; }, NFL_OK, 4},
+    // nfl_compose_backward_tasks
+    {C_BWD, "valid", [](CCase&) {}, NFL_OK, 4},
+    {C_BWD, "valid, no transient jobs", [](CCase& c) { c.hp = c.plan_not; }, NFL_OK, 3},
+    {C_BWD, "no composed gradient wanted", [](CCase& c) { c.gr.weight[NFL_P_FINAL] = c.gr.bias[NFL_P_FINAL] = c.gr.weight[NFL_P_DIR] = c.gr.weight[NFL_P_T0] = nullptr; }, NFL_OK, 0},
+    {C_BWD, "no task list", [](CCase& c) { c.out = nullptr; }, BAD, -1},
+    {C_BWD, "no plan", [](CCase& c) { c.hp = nullptr; }, BAD, 0},
+    {C_BWD, "bad magic", [](CCase& c) { c.edited->magic = NFL_PLAN_MAGIC; c.hp = c.edited; }, BAD, 0},
+    {C_BWD, "no parameters", [](CCase& c) { c.params = nullptr; }, BAD, 0},
+    {C_BWD, "no gradient tensors", [](CCase& c) { c.grads = nullptr; }, BAD, 0},
+    {C_BWD, "no scratch", [](CCase& c) { c.scratch = nullptr; }, BAD, 0},
+    {C_BWD, "dW_dir without db_dir", [](CCase& c) { c.gr.bias[NFL_P_DIR] = nullptr; }, BAD, 0},
+    {C_BWD, "dW_t0 without db_t0", [](CCase& c) { c.gr.bias[NFL_P_T0] = nullptr; }, BAD, 0},
+    {C_BWD, "no W_dir", [](CCase& c) { c.prm.weight[NFL_P_DIR] = nullptr; }, BAD, -1},
+    {C_BWD, "no W_t0", [](CCase& c) { c.prm.weight[NFL_P_T0] = nullptr; }, BAD, -1},
+    {C_BWD, "no W_fin", [](CCase& c) { c.prm.weight[NFL_P_FINAL] = nullptr; }, BAD, -1},
+    {C_BWD, "no b_fin for the rank-1 term", [](CCase& c) { c.prm.bias[NFL_P_FINAL] = nullptr; }, BAD, -1},
+    {C_BWD, "db_fin alone without db_dir", [](CCase& c) { c.gr.weight[NFL_P_FINAL] = c.gr.weight[NFL_P_DIR] = c.gr.weight[NFL_P_T0] = nullptr; c.gr.bias[NFL_P_DIR] = nullptr; }, BAD, -1},
+    {C_BWD, "scratch off by 4 bytes", [](CCase& c) { c.scratch += 1; }, BAD, -1},
+    {C_BWD, "W_fin off by 4 bytes", [](CCase& c) { c.prm.weight[NFL_P_FINAL] += 1; }, BAD, -1},
+    {C_BWD, "scratch off by 4 bytes, transient columns only", [](CCase& c) { c.scratch += 1; c.gr.weight[NFL_P_FINAL] = c.gr.bias[NFL_P_FINAL] = c.gr.weight[NFL_P_DIR] = nullptr; }, BAD, -1},
+    {C_BWD, "scratch off by 4 bytes, no float4 load of it", [](CCase& c) { c.scratch += 1; c.gr.weight[NFL_P_DIR] = c.gr.weight[NFL_P_T0] = nullptr; }, NFL_OK, 2},
+    {C_BWD, "a plan whose W_dir rows are shorter than 256", [](CCase& c) { c.edited->w_numel[NFL_P_DIR] = 128 * 255; c.hp = c.edited; }, BAD, -1},
+    {C_BWD, "a plan with more jobs than its table", [](CCase& c) { c.edited->n_jobs = WG_MAX_JOBS + 1; c.hp = c.edited; }, NFL_OK, 3},
+};
+#undef BAD
+
+alignas(16) static float g_dev16[8];       // made-up device memory again, 16-byte aligned: never followed
+
+static bool check_compose_refusals(const WgPlan& plan_t, const WgPlan& plan_not) {
+    CCase* c = new CCase;
+    WgPlan* edited = new WgPlan;
+    WgCompose* out = new WgCompose;
+    float* const D = g_dev16;
+    bool ok = true;
+    for (const CRow& r : CROWS) {
+        memset(c, 0, sizeof(*c));
+        memset(out, 0xFF, sizeof(*out));
+        *edited = plan_t;
+        c->hp = c->plan_t = &plan_t; c->plan_not = &plan_not; c->edited = edited;
+        c->d_wplan = D; c->act = c->grd = reinterpret_cast<const char*>(D); c->gmax = D;
+        c->n_rays = 64; c->n_samples = 64; c->prec = NFL_PREC_F16;
+        for (int L : {NFL_P_FINAL, NFL_P_DIR, NFL_P_T0}) {
+            c->prm.weight[L] = c->gr.weight[L] = D;
+            c->prm.bias[L] = c->gr.bias[L] = D + 4;
+        }
+        c->params = &c->prm; c->grads = &c->gr; c->scratch = D;
+        c->has_t = 1; c->n_side = 75; c->n_tau = 16;
+        c->wdir_c = c->wt0_c = D; c->bdir_c = c->bt0_c = D + 4;
+        c->out = out;
+        r.edit(*c);
+        snprintf(cp_where, sizeof(cp_where), "refusals: entry %d, %s", r.entry, r.what);
+        int rc = 12345;
+        if (r.entry == C_CHECK)
+            rc = nfl_wgrad_check(c->hp, c->d_wplan, c->act, c->grd, c->gmax, c->n_rays, c->n_samples, c->prec, c->params, c->scratch, c->grads);
+        else if (r.entry == C_FWD)
+            rc = nfl_compose_forward_tasks(c->params, c->has_t, c->n_side, c->n_tau, c->wdir_c, c->bdir_c, c->wt0_c, c->bt0_c, c->out);
+        else
+            rc = nfl_compose_backward_tasks(c->hp, c->params, c->grads, c->scratch, c->out);
+        ++n_cp_refusals;
+        if (rc != r.rc || (r.n_tasks >= 0 && out->n_tasks != r.n_tasks) || (rc == NFL_OK && r.entry != C_CHECK && out->n_wg < out->n_tasks)) {
+            printf("compose invariant broken: rc %d tasks %d, expected %d %d (%s)\n", rc, out->n_tasks, r.rc, r.n_tasks, cp_where);
+            ok = false;
+            break;
+        }
+    }
+    delete out;
+    delete edited;
+    delete c;
+    return ok;
+}
+
+// the distinct shapes the descriptor sweep yields, each run once: the forward fold per shape, the gradient composition per
+// (shape, plan with / without the transient jobs) and subset of the four composed gradients
+static CpShape g_cp_fwd_seen[256];
+static struct { CpShape s; int ut; } g_cp_bwd_seen[512];
+static int n_cp_fwd_seen, n_cp_bwd_seen;
+static bool cp_same(const CpShape& a, const CpShape& b) { return a.n_side == b.n_side && a.has_t == b.has_t && a.n_tau == b.n_tau; }
+
+static bool check_compose(const NflPlan& fp, const WgPlan& P) {
+    const CpShape s = {fp.ld[NFL_P_DIR] - NFL_W, fp.has_t ? 1 : 0, fp.has_t ? fp.n_tau : 0};
+    const int ut = wg_plan_transient(&P) ? 1 : 0;
+    snprintf(cp_where, sizeof(cp_where), "shape: n_side %d has_t %d n_tau %d", s.n_side, s.has_t, s.n_tau);
+    CP_CHECK(P.w_numel[NFL_P_DIR] == (NFL_W / 2) * (NFL_W + s.n_side) && P.w_numel[NFL_P_T0] == (s.has_t ? (NFL_W / 2) * (NFL_W + s.n_tau) : 0));
+    int i = 0;
+    while (i < n_cp_fwd_seen && !cp_same(g_cp_fwd_seen[i], s)) ++i;
+    if (i == n_cp_fwd_seen) {
+        CP_CHECK(n_cp_fwd_seen < 256);
+        g_cp_fwd_seen[n_cp_fwd_seen++] = s;
+        if (!check_compose_forward(s)) return false;
+    }
+    i = 0;
+    while (i < n_cp_bwd_seen && !(cp_same(g_cp_bwd_seen[i].s, s) && g_cp_bwd_seen[i].ut == ut)) ++i;
+    if (i == n_cp_bwd_seen) {
+        CP_CHECK(n_cp_bwd_seen < 512);
+        g_cp_bwd_seen[n_cp_bwd_seen].s = s;
+        g_cp_bwd_seen[n_cp_bwd_seen++].ut = ut;
+        // the operands (W_fin, b_fin, W_dir, W_t0, G | Gt, db_dir, db_t0) and the four expected gradients, once for the 16 subsets
+        const int W = NFL_W, H = NFL_W / 2, ld_d = W + s.n_side, ld_t = W + s.n_tau;
+        Blk in[7] = {Blk((size_t)W * W), Blk(W), Blk((size_t)H * ld_d), Blk((size_t)H * ld_t), Blk((size_t)W * W), Blk(H), Blk(H)};
+        for (int k = 0; k < 7; ++k) in[k].ints(11 + k);
+        Blk exp[4] = {Blk((size_t)W * W), Blk(W), Blk((size_t)H * W), Blk((size_t)H * W)};
+        cp_expect_backward(ut, ld_d, ld_t, in[0].p, in[1].p, in[2].p, in[3].p, in[4].p, in[5].p, in[6].p, exp[0].p, exp[1].p, exp[2].p, exp[3].p);
+        const Blk in0[7] = {in[0], in[1], in[2], in[3], in[4], in[5], in[6]};          // to see that a run leaves them as they were
+        Blk out0[4] = {Blk((size_t)W * W), Blk(W), Blk((size_t)H * ld_d), Blk((size_t)H * ld_t)};       // the outputs' sentinel fill
+        for (Blk& b : out0) b.fill(CP_SENTINEL);
+        for (int subset = 0; subset < 16; ++subset)
+            if (!check_compose_backward(P, s, ut, subset, in, in0, exp, out0)) return false;
+    }
+    return true;
+}
+
 // everything above for one accepted field
 static bool check_launch(const nfl_field_desc& d) {
     NflPlan* p[6];
@@ -453,6 +906,17 @@ static bool check_launch(const nfl_field_desc& d) {
 
 int main() {
     if (!check_ray_split()) return 1;
+    {   // the refusal table of nfl_wgrad_check and the two compose builders takes no field: once, on the NeRF-W fine field's plans
+        nfl_field_desc d;
+        memset(&d, 0, sizeof(d));
+        d.n_emb_xyz = 10; d.n_emb_dir = 4; d.encode_appearance = 1; d.n_a = 48; d.encode_transient = 1; d.n_tau = 16; d.beta_min = 0.1f;
+        WgPlan* w[2] = {new WgPlan, new WgPlan};
+        const bool ok = nfl_wgrad_plan_build(&d, 1, w[0], sizeof(WgPlan)) == NFL_OK && nfl_wgrad_plan_build(&d, 0, w[1], sizeof(WgPlan)) == NFL_OK &&
+                        check_compose_refusals(*w[0], *w[1]);
+        delete w[0];
+        delete w[1];
+        if (!ok) return 1;
+    }
     int n_ok = 0, n_bad = 0, n_wplans = 0, n_sched = 0;
     for (int xyz = 0; xyz <= 16; ++xyz)
         for (int dir = 0; dir <= 5; ++dir)
@@ -476,6 +940,7 @@ int main() {
                                     }
                                 }
                             const bool accepted = nfl_plan_fill(&d, NFL_PREC_F16X3, p) == 0;
+                            const NflPlan fp = *p;               // the field's forward plan: the compose shapes are read off it
                             delete p;
                             if (accepted && !check_launch(d)) {
                                 printf("  at xyz %d dir %d a %d na %d t %d nt %d\n", xyz, dir, a, na, t, nt);
@@ -488,7 +953,7 @@ int main() {
                                 if (!ok) printf("wgrad plan: rc %d for an %s field\n", rc, accepted ? "accepted" : "rejected");
                                 if (ok && accepted) {
                                     ++n_wplans;
-                                    ok = check_wgrad_plan(*w);
+                                    ok = check_wgrad_plan(*w) && check_wgrad_fill(*w) && check_compose(fp, *w);
                                     for (int mult = 1; ok && mult <= 2; ++mult)
                                         for (int n_seg : {0, 1, 2, 7, 255, 256, 257, 65536, 1048576})
                                             for (int cu : {1, 64, 256, 304}) {
@@ -512,5 +977,6 @@ int main() {
         if (!g_row_reached[i]) printf(" (%d, %d)", WG_INST[0][i].cost, WG_INST[0][i].nitw);
     printf("\n");
     printf("launch splits %d fills %d refusals %d\n", n_splits, n_fills, n_refusals);
+    printf("compose forward cases %d backward cases %d refusal rows %d wgrad fills %d\n", n_cp_fwd, n_cp_bwd, n_cp_refusals, n_wg_fills);
     return 0;
 }

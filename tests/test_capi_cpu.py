@@ -212,6 +212,33 @@ def test_dgrad_refuses_a_ray_gradient_it_cannot_compute(L):
     assert call(1, d_g_rays=4096, d_rays=4096, d_z=4096, n_rays=0) == 0         # complete, and empty: nothing launched
 
 
+def test_wgrad_and_compose_refuse_before_any_runtime_call(L):
+    """The two refusals that come before the first launch: nfl_mlp_wgrad with d_scratch (or xyz_encoding_final's weight) off
+    the 16-byte grid -- it used to follow the zero, stream and reduce launches -- and nfl_compose_forward with a negative
+    side width.  A real host plan, made-up device pointers: both return NFL_EINVAL here, where there is no device."""
+    d = _lib.FieldDesc(10, 4, 1, 48, 1, 16, 0.1, 0)
+    n = L.nfl_wgrad_plan_bytes()
+    plan = C.create_string_buffer(n)
+    assert L.nfl_wgrad_plan_build(C.byref(d), 1, plan, n) == 0
+    dev = C.c_void_p(4096)
+    fp, fg = _lib.FieldParams(), _lib.FieldGrads()
+    for i in range(len(fp.weight)):
+        fp.weight[i] = fp.bias[i] = fg.weight[i] = fg.bias[i] = 4096
+
+    def wgrad(scratch, n_rays=64):
+        return L.nfl_mlp_wgrad(plan, dev, dev, dev, dev, n_rays, 64, _lib.NFL_PREC_F16, C.byref(fp), C.c_void_p(scratch),
+                               C.byref(fg), None)
+
+    assert wgrad(4096 + 4) == -1
+    assert wgrad(4096 + 4, n_rays=0) == -1
+    P_FINAL = 8                                       # NFL_P_FINAL: xyz_encoding_final
+    fp.weight[P_FINAL] = 4096 + 4
+    assert wgrad(4096) == -1
+    fp.weight[P_FINAL] = 4096
+    assert L.nfl_compose_forward(C.byref(fp), 1, -1, 16, dev, dev, dev, dev, None) == -1
+    assert L.nfl_compose_forward(C.byref(fp), 1, 75, -1, dev, dev, dev, dev, None) == -1
+
+
 def test_adam_step_dev_validates_arguments(L):
     t = _lib.AdamTensors()
     assert L.nfl_adam_step_dev(None, 1, C.c_void_p(16), C.c_void_p(16), 1, None) == -1

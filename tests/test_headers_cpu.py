@@ -2,8 +2,9 @@
 nfl_render_impl.h the forward kernel on top of that.  Every header compiles from a one-line includer, and no translation
 unit reaches above the layer it needs.  The geometry layer stands beside them: nfl_geom_layout.h (plain C++) under
 nfl_geom.h, which its five translation units include and which takes nothing from the render path.  nfl_launch.h (plain C++,
-the launchers' host side) sits under the render kernel and the dgrad unit; the two runtime queries a launcher makes are
-written once, in nfl_dev.h."""
+the launchers' host side) sits under the render kernel and the dgrad unit, nfl_compose.h (plain C++, the composition's task
+lists) under the weight-gradient launcher and the compose unit; the two runtime queries a launcher makes are written once,
+in nfl_dev.h."""
 import os
 import re
 import shutil
@@ -23,7 +24,7 @@ def includes(name):
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 @pytest.mark.parametrize("header", ["nfl_math.h", "nfl_dev.h", "nfl_pixel.h", "nfl_mlp.h", "nfl_render_impl.h",
-                                    "nfl_geom_layout.h", "nfl_geom.h", "nfl_launch.h"])
+                                    "nfl_geom_layout.h", "nfl_geom.h", "nfl_launch.h", "nfl_compose.h"])
 def test_header_compiles_on_its_own(header, tmp_path):
     src = tmp_path / "includer.hip"
     src.write_text('#include "%s"\n' % header)
@@ -87,6 +88,28 @@ def test_launch_header_sits_under_the_kernels():
 def test_launch_header_is_plain_cpp(tmp_path):
     src = tmp_path / "includer.cpp"
     src.write_text('#include "nfl_launch.h"\nint main() { return (int)sizeof(RenderArgs) + (int)sizeof(DgradArgs); }\n')
+    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", CSRC, str(src)], capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+
+
+def test_compose_header_sits_under_the_two_units_that_launch_it():
+    """nfl_compose.h (plain C++: the composition's task records and their builders) takes the public header and the
+    weight-gradient plan only; the unit with the kernel and the weight-gradient launcher include it."""
+    assert includes("nfl_compose.h") == {"../../include/nerf_fl_amd.h", "nfl_wgrad_plan.h"}
+    assert includes("nfl_wgrad_plan.h") == {"../../include/nerf_fl_amd.h", "nfl_plan.h"}
+    assert includes("nfl_compose.cpp") == {"nfl_compose.h"}
+    for user in ("nfl_wgrad.hip", "nfl_compose.hip"):
+        assert "nfl_compose.h" in includes(user)
+    for name in ("nfl_compose.h", "nfl_compose.cpp"):
+        with open(os.path.join(CSRC, name)) as f:
+            assert "hip" not in re.sub(r"//.*", "", f.read())                   # host arithmetic: g++ builds it
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_compose_header_is_plain_cpp(tmp_path):
+    src = tmp_path / "includer.cpp"
+    src.write_text('#include "nfl_compose.h"\nint main() { return (int)sizeof(WgCompose) + (int)sizeof(WgTensors); }\n')
     r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", CSRC, str(src)], capture_output=True, text=True,
                        timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]

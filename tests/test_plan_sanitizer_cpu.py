@@ -2,7 +2,9 @@
 where fixed-size tables are filled by configuration-dependent loops): tests/plan_sweep.cpp builds forward and backward plans
 for every encoder / latent width combination, accepted or rejected, and for every accepted one the weight-gradient job list
 (csrc/nfl_wgrad_plan.cpp) and its launch schedule over segment counts, CU counts and both stash multipliers, and the host side
-of the render and dgrad launchers (csrc/nfl_launch.cpp): ray split, argument-block fills, the entry points' refusals."""
+of the render and dgrad launchers (csrc/nfl_launch.cpp): ray split, argument-block fills, the entry points' refusals; and the
+task lists of the composition through xyz_encoding_final (csrc/nfl_compose.cpp), evaluated on exactly-sized heap blocks by a
+reference interpreter that lives in the sweep, with the refusals of nfl_mlp_wgrad (nfl_wgrad_check)."""
 import os
 import shutil
 import subprocess
@@ -19,7 +21,8 @@ def test_plan_builder_is_clean_under_asan_ubsan(tmp_path):
            "-fno-omit-frame-pointer", os.path.join(ROOT, "tests", "plan_sweep.cpp"),
            os.path.join(ROOT, "nerf_fl_amd", "csrc", "nfl_plan.cpp"),
            os.path.join(ROOT, "nerf_fl_amd", "csrc", "nfl_wgrad_plan.cpp"),
-           os.path.join(ROOT, "nerf_fl_amd", "csrc", "nfl_launch.cpp"), "-o", exe]
+           os.path.join(ROOT, "nerf_fl_amd", "csrc", "nfl_launch.cpp"),
+           os.path.join(ROOT, "nerf_fl_amd", "csrc", "nfl_compose.cpp"), "-o", exe]
     b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
     if b.returncode != 0 and "sanitize" in b.stderr and "cannot find" in b.stderr:
         pytest.skip("sanitizer runtime not installed")
@@ -39,3 +42,11 @@ def test_plan_builder_is_clean_under_asan_ubsan(tmp_path):
     assert "launch invariant broken" not in r.stdout
     n_splits, n_fills, n_refusals = (int(r.stdout.split(k)[1].split()[0]) for k in ("launch splits", "fills", "refusals"))
     assert n_splits == 936 and n_fills > 20 * n_wplans // 2 and n_refusals > 80 * n_wplans // 2
+    # the composition through xyz_encoding_final: the sweep's accepted fields have 24 side widths of dir_encoding.0 (4 direction
+    # encoders, alone or with one of 5 appearance widths) and no transient layers or 3 code widths: 24 x 4 forward folds; the
+    # gradient composition per shape and plan (no transient layers 24, transient layers unused 72, used 72) x the 16 subsets
+    # of the four composed gradients; the refusal rows of nfl_wgrad_check and the two builders once; nfl_wgrad_fill per plan
+    assert "compose invariant broken" not in r.stdout
+    n_fwd, n_bwd, n_rows, n_wfills = (int(r.stdout.split(k)[1].split()[0])
+                                      for k in ("compose forward cases", "backward cases", "refusal rows", "wgrad fills"))
+    assert n_fwd == 96 and n_bwd == 168 * 16 and n_rows == 75 and n_wfills == n_wplans
