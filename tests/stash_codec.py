@@ -148,6 +148,83 @@ class Layout:
         return tuple(out)
 
 
+# ---- the relu-mask records behind the activation records ---------------------------------------------------------------
+# Written from the documentation: nfl_plan.h (nfl_msk_h / _dirh / _g, NFL_MSK_WORDS, nfl_msk_offset, the record layout
+# [group of 4 tiles][lane][4 words] and the bit rule: bit 2p = accumulator 2p, bit 16 + 2p = accumulator 2p + 1) and the
+# 32x32 MFMA accumulator layout (lane = 32 * half + sample; accumulator r holds row (r & 3) + 8 * (r >> 2) + 4 * half of the
+# tile).  A mask is a boolean (n_seg * 32, width) tensor, sample-major like every other field; tile t covers features
+# 32 t .. 32 t + 31.  The records are the same for one-image and split activation records; only their offset differs.
+MSK_WORDS = 84
+
+
+def mask_fields(has_t=True):
+    """name -> (first word, row tiles), nfl_msk_h / nfl_msk_dirh / nfl_msk_g."""
+    m = {f"h{l}": (8 * (l - 1), 8) for l in range(1, 9)}
+    m["dirh"] = (64, 4)
+    if has_t:
+        m.update({f"g{k}": (68 + 4 * (k - 1), 4) for k in range(1, 5)})
+    return m
+
+
+def mask_offset(n_seg, nkp, mult=1):
+    """nfl_msk_offset: the records, their 4 KiB tail pad, then the masks."""
+    return n_seg * (nkp + 174) * mult * 1024 + 4096
+
+
+def mask_bit_of_row():
+    """(half, bit) of each of a tile's 32 rows: row = (r & 3) + 8 (r >> 2) + 4 half, bit = r - (r & 1) + 16 (r & 1)."""
+    row = torch.arange(32)
+    half, r = (row >> 2) & 1, (row & 3) + 4 * (row >> 3)
+    return half, (r & ~1) + 16 * (r & 1)
+
+
+def _mask_words(buf, n_seg):
+    """(n_seg, 21 groups, 64 lanes, 4 words) int32 view of the mask records at the head of `buf` (uint8)."""
+    return buf[:n_seg * MSK_WORDS * 256].view(torch.int32).view(n_seg, MSK_WORDS // 4, 64, 4)
+
+
+def encode_masks(masks, has_t=True, count=None):
+    """Boolean tensors -> mask records (uint8, n_seg * 84 * 256 bytes).  Words of fields that are not given, and the bits no
+    accumulator owns, are zero.  `count` ((84, 64, 32) int): incremented at every (word, lane, bit) written."""
+    n_seg = next(iter(masks.values())).shape[0] // 32
+    dev = next(iter(masks.values())).device
+    buf = torch.zeros(n_seg * MSK_WORDS * 256, dtype=torch.uint8, device=dev)
+    words = _mask_words(buf, n_seg)
+    half, bit = (x.to(dev) for x in mask_bit_of_row())
+    for name, (w0, tiles) in mask_fields(has_t).items():
+        if name not in masks:
+            continue
+        m = masks[name]
+        assert m.dtype == torch.bool and m.shape == (n_seg * 32, 32 * tiles), (name, tuple(m.shape))
+        m = m.view(n_seg, 32, tiles, 32).permute(0, 2, 1, 3).to(torch.int32)          # (segment, tile, sample, row)
+        for t in range(tiles):
+            w = w0 + t
+            for h in (0, 1):
+                rows = (half == h).nonzero().flatten()
+                val = (m[:, t][:, :, rows] << bit[rows].to(torch.int32)).sum(-1).to(torch.int32)      # (segment, sample)
+                words[:, w >> 2, 32 * h:32 * h + 32, w & 3] = val
+                if count is not None:
+                    count[w, 32 * h:32 * h + 32, bit[rows]] += 1
+    return buf
+
+
+def decode_masks(buf, n_seg, has_t=True):
+    """Mask records (the bytes from mask_offset on) -> name -> boolean (n_seg * 32, width)."""
+    words = _mask_words(buf, n_seg)
+    half, bit = (x.to(buf.device) for x in mask_bit_of_row())
+    out = {}
+    for name, (w0, tiles) in mask_fields(has_t).items():
+        m = torch.zeros(n_seg, tiles, 32, 32, dtype=torch.bool, device=buf.device)
+        for t in range(tiles):
+            w = w0 + t
+            for h in (0, 1):
+                rows = (half == h).nonzero().flatten()
+                val = words[:, w >> 2, 32 * h:32 * h + 32, w & 3]                              # (segment, sample)
+                m[:, t][:, :, rows] = ((val[..., None] >> bit[rows].to(torch.int32)) & 1).bool()
+        out[name] = m.permute(0, 2, 1, 3).reshape(n_seg * 32, 32 * tiles)
+    return out
+
+
 # ---- which stash operands form which gradient (the tests' oracle) ----------------------------------------------------
 # layer -> (gradient field, [(input field, first weight column it multiplies)]).  "feat" is the output of
 # xyz_encoding_final, which is never stashed: feat = W_fin h8 + b_fin, so

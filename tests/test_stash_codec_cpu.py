@@ -77,6 +77,79 @@ def test_named_bytes_written_exactly_once(widths, latents):
             assert torch.equal(v[s] == 1.0, count == 1) and torch.equal(v[s] == -7.0, count == 0)
 
 
+def random_masks(has_t, n_seg, gen):
+    return {n: torch.randint(0, 2, (n_seg * 32, 32 * tiles), generator=gen).bool() for n, (_, tiles) in sc.mask_fields(has_t).items()}
+
+
+@pytest.mark.parametrize("has_t", [False, True])
+def test_mask_roundtrip(has_t):
+    gen = torch.Generator().manual_seed(11)
+    n_seg = 3
+    masks = random_masks(has_t, n_seg, gen)
+    buf = sc.encode_masks(masks, has_t)
+    assert buf.dtype == torch.uint8 and buf.numel() == n_seg * sc.MSK_WORDS * 256
+    back = sc.decode_masks(buf, n_seg, has_t)
+    assert set(back) == set(masks) and all(torch.equal(back[n], masks[n]) for n in masks)
+    assert torch.equal(sc.encode_masks(back, has_t), buf)
+    # a longer buffer decodes the same, and without the transient head its words stay zero
+    assert all(torch.equal(v, masks[n]) for n, v in sc.decode_masks(torch.cat([buf, buf[:512]]), n_seg, has_t).items())
+    if not has_t:
+        assert not sc.decode_masks(buf, n_seg, True)["g3"].any()
+
+
+def test_mask_words_owned_exactly_once():
+    """Every one of the 84 * 64 words of a record belongs to exactly one (field, tile, lane); of its 32 bits the 16 the bit
+    rule names carry one feature each, the other 16 none."""
+    count = torch.zeros(sc.MSK_WORDS, 64, 32, dtype=torch.int32)
+    masks = {n: torch.ones(32, 32 * tiles, dtype=torch.bool) for n, (_, tiles) in sc.mask_fields(True).items()}
+    buf = sc.encode_masks(masks, True, count)
+    assert int(count.max()) == 1
+    named = [2 * p for p in range(8)] + [16 + 2 * p for p in range(8)]
+    assert torch.equal(count.sum(-1), torch.full((sc.MSK_WORDS, 64), 16, dtype=torch.int32))
+    assert int(count[:, :, named].sum()) == int(count.sum()) == sc.MSK_WORDS * 64 * 16 == 32 * sum(32 * t for _, t in sc.mask_fields(True).values())
+    words = buf.view(torch.int32)
+    assert words.numel() == sc.MSK_WORDS * 64 and bool((words == sum(1 << b for b in named)).all())
+    # the words of two fields never meet, and together they are 0 .. 83
+    owner = sorted(w0 + t for w0, tiles in sc.mask_fields(True).values() for t in range(tiles))
+    assert owner == list(range(sc.MSK_WORDS))
+
+
+def test_mask_bit_and_word_placement():
+    """One set bit at a time, against the rules of nfl_plan.h spelled out here: word w of a segment lies at byte
+    (w >> 2) * 1024 + lane * 16 + (w & 3) * 4 of its 84 * 256-byte record, lane = 32 * half + sample, and the feature in row
+    (r & 3) + 8 (r >> 2) + 4 half of tile t is bit r (r even) or 16 + r - 1 (r odd)."""
+    n_seg = 2
+    for name, seg, sample, feature in [("h1", 0, 0, 0), ("h3", 1, 31, 255), ("h8", 1, 7, 100), ("dirh", 0, 5, 37), ("g1", 1, 9, 4),
+                                       ("g4", 0, 30, 127), ("h5", 0, 17, 45)]:
+        masks = {n: torch.zeros(n_seg * 32, 32 * tiles, dtype=torch.bool) for n, (_, tiles) in sc.mask_fields(True).items()}
+        masks[name][seg * 32 + sample, feature] = True
+        words = sc.encode_masks(masks, True).view(torch.int32)
+        tile, row = feature // 32, feature % 32
+        half = (row // 4) % 2
+        r = (row % 4) + 4 * (row // 8)
+        assert (r & 3) + 8 * (r >> 2) + 4 * half == row
+        w = (64 if name == "dirh" else 68 + 4 * (int(name[1]) - 1) if name[0] == "g" else 8 * (int(name[1]) - 1)) + tile
+        at = (seg * sc.MSK_WORDS * 256 + (w >> 2) * 1024 + (32 * half + sample) * 16 + (w & 3) * 4) // 4
+        bit = r if r % 2 == 0 else 16 + r - 1
+        nz = words.nonzero().flatten().tolist()
+        assert nz == [at] and int(words[at]) == 1 << bit, (name, nz, at, int(words[at]), bit)
+
+
+@pytest.mark.parametrize("mult", [1, 2])
+@pytest.mark.parametrize("widths", WIDTHS)
+def test_mask_offset_is_the_librarys(widths, mult):
+    """nfl_msk_offset through the one exported function built on it: nfl_act_stash_bytes = nfl_msk_offset + n_seg * 84 * 256."""
+    from nerf_fl_amd import _lib
+    L = _lib.lib()
+    desc = _lib.FieldDesc(n_emb_xyz=widths[0], n_emb_dir=widths[1], encode_appearance=1, n_a=widths[2], encode_transient=1,
+                          n_tau=widths[3], beta_min=0.03, reserved=0)
+    prec = _lib.NFL_PREC_F16X3 if mult == 2 else _lib.NFL_PREC_F16
+    for n_rays, n_samples in [(1, 1), (9, 40), (3, 300)]:
+        n_seg = n_rays * ((n_samples + 31) // 32)
+        total = L.nfl_act_stash_bytes(C.byref(desc), n_rays, n_samples, prec)
+        assert total - n_seg * sc.MSK_WORDS * 256 == sc.mask_offset(n_seg, plan_nkp(widths, True), mult)
+
+
 def test_feature_orders():
     """The two k-slot -> column maps of nfl_plan.h, spelled out on a few positions."""
     act = sc.feature_of_position(sc.ACT, 64)
