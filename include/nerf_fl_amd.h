@@ -1028,6 +1028,71 @@ typedef struct nfl_mesh_blend_args {
 } nfl_mesh_blend_args;
 int nfl_mesh_blend(const nfl_mesh_blend_args* args, void* stream);
 
+/* ---- mesh render: a coloured mesh as images -- which triangle wins each pixel, and its vertex attributes interpolated there --
+ * Camera, run, pixel ray, dot, cross and the Moeller-Trumbore arithmetic are those of "mesh colour" above, word for word: every
+ * operation fp32 and rounded on its own, divisions and square roots correctly rounded.  Pixel (i, j) of image n of the run is
+ * word pix0[n] - pix0[first] + j * width + i of the run's buffers.
+ *
+ * nfl_mesh_visibility   two launches (fill, raster).  The word of a pixel is the minimum, over all triangles tr whose ray test
+ *   is a HIT (as defined for nfl_mesh_depth) with a distance d = tau * |ray| below +inf, of
+ *     ((uint64_t)bits(d) << 32) | (uint32_t)tr,
+ *   and 2^64 - 1 when there is none.  tr is the triangle's index in d_triangles (culled and refused triangles keep their
+ *   numbers).  The distance decides; among equal distances the lowest index wins, so the result does not depend on the order
+ *   of the hits.  A hit is a 64-bit atomicMin on the word.  Which triangles are tried against which pixels, the 64-pixel
+ *   threshold and the whole-wave walk of larger boxes are those of nfl_mesh_depth.  Only words below n_vis are written; n_vis
+ *   = the pixels of the run.  V == 0 or T == 0 or count == 0: the fill alone.  NFL_EINVAL (nothing launched): the refusals of
+ *   nfl_mesh_depth, with d_vis 8-byte aligned.
+ *
+ * nfl_mesh_shade   one launch, a thread per word of the run.  The image of a word is found by a binary search of pix0 (as in
+ *   nfl_gather_batch), its pixel (i, j) from the image's width.  A word is UNCOVERED when it is 2^64 - 1, when its low half is
+ *   not below n_triangles, when that triangle has an index outside [0, n_vertices), when the word lies past the pixels of its
+ *   image, count == 0, or when det == 0 (or NaN) for that triangle and pixel (the buffer is the caller's and is not trusted;
+ *   no word nfl_mesh_visibility writes is uncovered by the last three).  For a covered word the three vertices are
+ *   transformed and u, v and the distance recomputed by the expressions of the raster (the same bits); the hit conditions are
+ *   not tested again.  w0 = (1 - u) - v, and an attribute triple A, B, C of the triangle's vertices interpolates to
+ *   (w0 * A + u * B) + v * C.  mode:
+ *     NFL_SHADE_COLOR    d_attr (V, 3) interpolated; the float result is not clamped.
+ *     NFL_SHADE_NORMAL   d_attr holds vertex normals; the interpolated m becomes 0.5f * (m_k / sqrt(dot(m, m))) + 0.5f, and
+ *                        0.5 in all three when that length is zero or NaN.
+ *     NFL_SHADE_FACING   no attributes: with n = cross(e1, e2) and the pixel's ray d,
+ *                        g = |dot(n, d)| / (sqrt(dot(n, n)) * sqrt(dot(d, d))), NaN -> 0, the colour (g, g, g): a headlight.
+ *   Outputs, each skipped when NULL: d_rgb (n_vis, 3) fp32; d_rgb_u8 (n_vis, 3) = (uint8_t)(clamp(c, 0, 1) * 255), truncated,
+ *   NaN -> 0; d_depth (n_vis) fp32, the distance, bit-equal to nfl_mesh_depth of the same inputs; d_triangle (n_vis) int32.
+ *   An uncovered word gets background[3], +inf and -1.  NFL_EINVAL (nothing launched): args / d_table NULL or d_table not
+ *   8-byte aligned, n_images < 1, a run outside the table, a negative size, V > INT32_MAX or 3 T > INT32_MAX, an unknown mode,
+ *   d_attr NULL in a mode that reads it (and V > 0), n_vis above 2^38, d_vis NULL (n_vis > 0) or not 8-byte aligned, a NULL
+ *   d_vertices / d_triangles that a non-zero size needs, another pointer not 4-byte aligned (d_rgb_u8: bytes, any address).
+ *   n_vis == 0: NFL_OK, no launch. */
+enum { NFL_SHADE_COLOR = 0, NFL_SHADE_NORMAL = 1, NFL_SHADE_FACING = 2 };
+typedef struct nfl_mesh_visibility_args {
+    const float*   d_vertices;        /* (V, 3) world */
+    const int32_t* d_triangles;       /* (T, 3) */
+    int64_t  n_vertices, n_triangles;
+    const nfl_image_rec* d_table;     /* (n_images) */
+    int32_t  n_images, first, count, reserved;
+    uint64_t* d_vis;                  /* out (n_vis), 8-byte aligned */
+    int64_t  n_vis;                   /* pixels of the run */
+} nfl_mesh_visibility_args;
+int nfl_mesh_visibility(const nfl_mesh_visibility_args* args, void* stream);
+
+typedef struct nfl_mesh_shade_args {
+    const float*   d_vertices;        /* (V, 3) world */
+    const int32_t* d_triangles;       /* (T, 3) */
+    int64_t  n_vertices, n_triangles;
+    const nfl_image_rec* d_table;     /* (n_images) */
+    int32_t  n_images, first, count, mode;
+    const uint64_t* d_vis;            /* (n_vis): nfl_mesh_visibility of the same run */
+    int64_t  n_vis;
+    const float*   d_attr;            /* (V, 3) colours or normals; NULL with NFL_SHADE_FACING */
+    float    background[3];
+    int32_t  reserved;
+    float*   d_rgb;                   /* out (n_vis, 3) or NULL */
+    uint8_t* d_rgb_u8;                /* out (n_vis, 3) or NULL */
+    float*   d_depth;                 /* out (n_vis) or NULL */
+    int32_t* d_triangle;              /* out (n_vis) or NULL */
+} nfl_mesh_shade_args;
+int nfl_mesh_shade(const nfl_mesh_shade_args* args, void* stream);
+
 /* ---- hierarchical sampling (reference sample_pdf, rendering.py:7-46, plus the
  * concat + sort of rendering.py:267-272) -------------------------------------
  * d_z_coarse (R,S), d_weights_coarse (R,S); d_u (R,I) or NULL with d_u_row (I)

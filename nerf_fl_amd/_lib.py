@@ -273,6 +273,26 @@ class MeshBlendArgs(C.Structure):
                 ("start", C.c_int32), ("d_sum", C.c_void_p), ("d_views", C.c_void_p)]
 
 
+# nfl_mesh_visibility / nfl_mesh_shade (nerf_fl_amd.geometry: a coloured mesh rendered to images) likewise: two new symbols
+# and structs
+SHADE_MODES = {"color": 0, "normal": 1, "facing": 2}
+VIS_EMPTY = -1                                  # 2^64 - 1 as the int64 that torch holds the words in
+
+
+class MeshVisibilityArgs(C.Structure):
+    _fields_ = [("d_vertices", C.c_void_p), ("d_triangles", C.c_void_p), ("n_vertices", C.c_int64),
+                ("n_triangles", C.c_int64), ("d_table", C.c_void_p), ("n_images", C.c_int32), ("first", C.c_int32),
+                ("count", C.c_int32), ("reserved", C.c_int32), ("d_vis", C.c_void_p), ("n_vis", C.c_int64)]
+
+
+class MeshShadeArgs(C.Structure):
+    _fields_ = [("d_vertices", C.c_void_p), ("d_triangles", C.c_void_p), ("n_vertices", C.c_int64),
+                ("n_triangles", C.c_int64), ("d_table", C.c_void_p), ("n_images", C.c_int32), ("first", C.c_int32),
+                ("count", C.c_int32), ("mode", C.c_int32), ("d_vis", C.c_void_p), ("n_vis", C.c_int64),
+                ("d_attr", C.c_void_p), ("background", C.c_float * 3), ("reserved", C.c_int32), ("d_rgb", C.c_void_p),
+                ("d_rgb_u8", C.c_void_p), ("d_depth", C.c_void_p), ("d_triangle", C.c_void_p)]
+
+
 # every symbol include/nerf_fl_amd.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("nfl_plan_bytes", C.c_size_t, [C.POINTER(FieldDesc)]),
@@ -342,6 +362,8 @@ SYMBOLS = [
     ("nfl_occ_clip_rays", C.c_int, [C.POINTER(OccClipArgs), C.c_void_p]),
     ("nfl_mesh_depth", C.c_int, [C.POINTER(MeshDepthArgs), C.c_void_p]),
     ("nfl_mesh_blend", C.c_int, [C.POINTER(MeshBlendArgs), C.c_void_p]),
+    ("nfl_mesh_visibility", C.c_int, [C.POINTER(MeshVisibilityArgs), C.c_void_p]),
+    ("nfl_mesh_shade", C.c_int, [C.POINTER(MeshShadeArgs), C.c_void_p]),
     ("nfl_abi_version", C.c_int, []),
     ("nfl_version", C.c_char_p, []),
     ("nfl_strerror", C.c_char_p, [C.c_int]),

@@ -9,60 +9,16 @@
 //          thousands of pixels holds its 63 neighbours for as long, so after the small boxes the wave ballots its large
 //          ones and takes them in turn, all 64 lanes striding the box (the triangle goes round by __shfl, 14 words).  One
 //          launch, no list, no second kernel.  A hit is an atomicMin on the depth word as uint32: the depths are
-//          non-negative floats, which order as their bits, and +inf is the largest.
+//          non-negative floats, which order as their bits, and +inf is the largest.  The transform and the ray test are
+//          nfl_meshray.h's, shared with the visibility buffer of nfl_meshrender.hip, which has a walk of its own.
 // Blend.   A thread per vertex, the image loop inside: the records are read by every thread in the same order and stay in
 //          cache; per contributing image 4 pixels through nfl_pixel_rgb and one depth word.  The thread owns its row of the
 //          accumulators: no atomics, the same bits every time.
 #include <math.h>
 
 #include "nfl_geom.h"
+#include "nfl_meshray.h"
 #include "nfl_pixel.h"
-
-#ifndef NMC_SMALL_BOX
-#define NMC_SMALL_BOX 64                                    // pixels: boxes above this are walked by the whole wave
-#endif
-#define NMC_MAX_WORDS (1ll << 38)                           // depth words of one run (a grid of 2^30 workgroups)
-
-// (a * x + b * y) + c * z, every operation rounded on its own (the unit is built with -ffp-contract=off)
-NFL_DEV float nmc_dot(float a, float b, float c, float x, float y, float z) { return (a * x + b * y) + c * z; }
-
-// camera coordinates of the world point p: q = R^T (p - t)
-NFL_DEV void nmc_to_camera(const nfl_image_rec& im, const float p[3], float q[3]) {
-    const float wx = p[0] - im.c2w[3], wy = p[1] - im.c2w[7], wz = p[2] - im.c2w[11];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) q[c] = nmc_dot(im.c2w[c], im.c2w[4 + c], im.c2w[8 + c], wx, wy, wz);
-}
-
-NFL_DEV bool nmc_finite(float v) { return v - v == 0.f; }
-
-// what a triangle's pixel tests share: the Moeller-Trumbore terms that do not depend on the ray (origin 0: tvec = -a)
-struct NmcTri {
-    float tv[3], e1[3], e2[3], qv[3], tnum;
-};
-
-NFL_DEV void nmc_setup(const float a[3], const float b[3], const float c[3], NmcTri& t) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) t.tv[k] = -a[k], t.e1[k] = b[k] - a[k], t.e2[k] = c[k] - a[k];
-    t.qv[0] = t.tv[1] * t.e1[2] - t.tv[2] * t.e1[1];
-    t.qv[1] = t.tv[2] * t.e1[0] - t.tv[0] * t.e1[2];
-    t.qv[2] = t.tv[0] * t.e1[1] - t.tv[1] * t.e1[0];
-    t.tnum = nmc_dot(t.e2[0], t.e2[1], t.e2[2], t.qv[0], t.qv[1], t.qv[2]);
-}
-
-// the ray of pixel (i, j) against the triangle: true and the distance from the camera centre on a hit
-NFL_DEV bool nmc_test(const NmcTri& t, const nfl_image_rec& im, int i, int j, float& depth) {
-    const float dx = ((float)i - im.cx) / im.fx, dy = -((float)j - im.cy) / im.fy, dz = -1.f;
-    const float px = dy * t.e2[2] - dz * t.e2[1], py = dz * t.e2[0] - dx * t.e2[2], pz = dx * t.e2[1] - dy * t.e2[0];
-    const float det = nmc_dot(t.e1[0], t.e1[1], t.e1[2], px, py, pz);
-    if (!(det != 0.f)) return false;                        // 0 or NaN
-    const float inv = 1.f / det;
-    const float u = nmc_dot(t.tv[0], t.tv[1], t.tv[2], px, py, pz) * inv;
-    const float v = nmc_dot(dx, dy, dz, t.qv[0], t.qv[1], t.qv[2]) * inv;
-    const float tau = t.tnum * inv;
-    if (!(u >= 0.f && v >= 0.f && u + v <= 1.f && tau > 0.f)) return false;
-    depth = tau * sqrtf((dx * dx + dy * dy) + dz * dz);
-    return true;
-}
 
 __global__ __launch_bounds__(NM_THREADS) void nfl_mesh_depth_fill_kernel(float* depth, i64 n) {
     const i64 w = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
@@ -150,11 +106,6 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_mesh_depth_raster_kernel(const
             if (i >= gw) i -= gw, ++j;
         }
     }
-}
-
-static bool nmc_run_ok(const void* table, int32_t n_images, int32_t first, int32_t count) {
-    if (!table || reinterpret_cast<uintptr_t>(table) % 8) return false;
-    return n_images >= 1 && first >= 0 && count >= 0 && (long long)first + count <= n_images;
 }
 
 extern "C" int nfl_mesh_depth(const nfl_mesh_depth_args* a, void* stream) {

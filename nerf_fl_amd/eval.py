@@ -17,7 +17,7 @@ from . import rendering as rnd
 from .rendering import CameraRays, render_rays
 
 __all__ = ["batched_inference", "GraphedChunk", "frame_rays", "to_uint8", "dolly_path", "render_frame", "render_video",
-           "fit_and_evaluate_halves", "evaluate_bank", "clipped_inference"]
+           "fit_and_evaluate_halves", "evaluate_bank", "clipped_inference", "render_mesh_video", "evaluate_mesh"]
 
 
 def _chunks(rays, ts, chunk, per_ray=None):
@@ -456,3 +456,71 @@ def render_video(models, embeddings, poses, K, H, W, near, far, N_samples, N_imp
                            **kwargs)[0] for i in range(lo, hi)]
     dev = kwargs.get("device", "cuda:0")
     return lo, (torch.stack(frames) if frames else torch.empty(0, H, W, 3, dtype=torch.uint8, device=dev))
+
+
+def render_mesh_video(mesh, poses, K, H, W, rank=0, world=1, **kwargs):
+    """render_video for a mesh: the frames of a camera path through geometry.render_mesh (`kwargs`: colors, shade,
+    background), sharded over ranks with no collective.  Rank r renders the contiguous block
+    parallel.shard_bounds(n_frames, r, world) and returns (first frame index, uint8 (n_local, H, W, 3)) on the mesh's
+    device.  No host synchronisation when `poses` and `K` are tensors on that device."""
+    from . import geometry
+    lo, hi = parallel.shard_bounds(len(poses), rank, world)
+    frames = [geometry.render_mesh(mesh, poses[i], K, H, W, **kwargs)["rgb"] for i in range(lo, hi)]
+    dev = mesh["vertices"].device
+    return lo, (torch.stack(frames) if frames else torch.empty(0, int(H), int(W), 3, dtype=torch.uint8, device=dev))
+
+
+def evaluate_mesh(mesh, bank, *, colors=None, images=None, background=None, rank=0, world=1, return_images=False):
+    """evaluate_bank for a coloured mesh: every selected image of a data.ImageBank (on the mesh's device) is rendered from
+    its record's camera by geometry.render_mesh (`colors`: default the mesh's own) and scored on the device against the
+    bank's image, with one device-to-host copy after the last image.
+
+    What is scored is the 8-bit frame, byte / 255 (what `frames` holds and a viewer sees; the photographs are 8-bit
+    too), so a bank rendered from the mesh itself scores an error of exactly zero.  `psnr` and `ssim` are over the whole
+    frame, the background included (`background`: 3 numbers; default white when bank.white_back, black otherwise);
+    `psnr_valid` is over the pixels the mesh covers (metrics.image_metrics in tensor form, mask = covered).
+
+    images: indices into the bank (default all); image k of them is scored into row k of one (n, 8) fp64 table
+    (metrics.METRIC_COLUMNS) when k lies in parallel.shard_bounds(n, rank, world) -- the other rows stay zero, so one
+    all_reduce(SUM) of `table` merges the ranks.  An image is at least 2 x 2 pixels (the SSIM border is a reflection).
+
+    Returns the dict evaluate_bank returns: `table` (device), `psnr`, `psnr_valid`, `ssim` (fp64 host tensors, one per
+    image, zero outside the shard), `mean_psnr`, `mean_psnr_valid`, `mean_ssim` over this rank's shard, `first`, `count`;
+    with return_images, `frames`: a list of uint8 (h, w, 3) device tensors of the shard's images."""
+    from . import geometry, metrics
+    if bank.device is None:
+        raise RuntimeError("evaluate_mesh: the bank is not on a device (this build has no CPU path)")
+    dev = bank.device
+    images = list(range(bank.n_images)) if images is None else [int(i) for i in images]
+    n = len(images)
+    if any(not 0 <= i < bank.n_images for i in images):
+        raise ValueError(f"images outside the bank's {bank.n_images}")
+    if background is None:
+        background = (1.0, 1.0, 1.0) if bank.white_back else (0.0, 0.0, 0.0)
+    lo, hi = parallel.shard_bounds(n, rank, world)
+    table = torch.zeros(n, len(metrics.METRIC_COLUMNS), dtype=torch.float64, device=dev)
+    frames = []
+    for k in range(lo, hi):
+        i = images[k]
+        rec = bank.host_table[i]
+        H, W = int(rec["height"]), int(rec["width"])
+        out = geometry.render_mesh(mesh, bank=bank, image=i, colors=colors, background=background)
+        # byte / 255.0f as the bank's own pixels are converted (nfl_pixel.h: a correctly rounded fp32 quotient).  Taken
+        # through fp64: torch divides an fp32 tensor by a number by multiplying with its reciprocal, which is one ulp off
+        # for some bytes; the fp64 quotient is within 2^-52 of k / 255 whichever way it is formed, and no k / 255 lies
+        # within 2^-33 (relative) of a point where fp32 rounding changes, so rounding it once more gives the same bits.
+        pred = (out["rgb"].reshape(H * W, 3).to(torch.float64) / 255.0).to(torch.float32)
+        target = torch.empty(H * W, 3, dtype=torch.float32, device=dev)
+        bank.gather(int(rec["pix0"]), H * W, 0, out=(None, target, None))
+        metrics.image_metrics(pred, H, W, target=target, mask=out["covered"].reshape(H * W), clip=False, table=table, slot=k)
+        if return_images:
+            frames.append(out["rgb"])
+        del out, pred, target
+    host = table.cpu()                                              # the one device-to-host copy
+    col = {name: host[:, j] for j, name in enumerate(metrics.METRIC_COLUMNS)}
+    result = dict(table=table, first=lo, count=hi - lo, psnr=col["psnr"], psnr_valid=col["psnr_valid"], ssim=col["ssim"])
+    for name in ("psnr", "psnr_valid", "ssim"):
+        result[f"mean_{name}"] = float(col[name][lo:hi].mean()) if hi > lo else float("nan")
+    if return_images:
+        result["frames"] = frames
+    return result

@@ -13,6 +13,8 @@
     clip_rays         rays walked through such a grid: a tightened [near, far] per ray and a flag for rays that hit nothing
     mesh_depth        the depth map of a mesh seen by a camera: a z-buffer on the device (csrc/nfl_meshcolor.hip)
     color_mesh_from_images   vertex colours from the images of an ImageBank that see each vertex, hidden views left out
+    mesh_visibility   which triangle a camera sees at every pixel, and how far: a visibility buffer (csrc/nfl_meshrender.hip)
+    render_mesh       a coloured mesh as an image: vertex colours, normals or a headlight interpolated at the winning triangles
 
 Conventions: `lo`, `hi` and `res` are 3 numbers in (x, y, z) order; a lattice is a (nz, ny, nx) fp32 tensor, x fastest,
 whose point (x, y, z) lies at lo + (x, y, z) * spacing with spacing = (hi - lo) / (res - 1): `lattice_points` returns
@@ -30,7 +32,7 @@ from . import _lib, rendering
 
 __all__ = ["density_lattice", "extract_surface", "surface_colors", "write_ply", "extract_mesh", "lattice_points",
            "mesh_components", "filter_mesh", "clean_mesh", "simplify_mesh", "OccupancyGrid", "occupancy_grid", "clip_rays",
-           "mesh_depth", "color_mesh_from_images"]
+           "mesh_depth", "color_mesh_from_images", "mesh_visibility", "render_mesh"]
 
 # Longest piece of an x-row handed to the render pass as one ray.  nfl_render_pass accepts any n_samples >= 1; the cut is
 # a scheduling choice, not a limit of the ABI: the kernel gives whole rays to workgroups (contiguous ray ranges, one
@@ -497,6 +499,38 @@ def _run_depth(lib, stream, ver, tri, table, n_images, first, count, depth):
     _lib.check(lib.nfl_mesh_depth(C.byref(a), stream), "nfl_mesh_depth")
 
 
+def _camera_record(what, dev, c2w, K, H, W, bank, image):
+    """The camera forms of mesh_depth, mesh_visibility and render_mesh, checked: (table, n_images, image, H, W), the
+    record of a free camera written on the device (no synchronisation when `c2w` and `K` are tensors there)."""
+    if bank is not None:
+        if c2w is not None or K is not None or H is not None or W is not None or image is None:
+            raise ValueError(f"{what}: either (c2w, K, H, W) or (bank=, image=)")
+        if bank.device != dev:
+            raise ValueError(f"{what}: the bank and the mesh are on different devices")
+        image = int(image)
+        if not 0 <= image < bank.n_images:
+            raise ValueError(f"image: 0 .. {bank.n_images - 1}")
+        H, W = int(bank.host_table[image]["height"]), int(bank.host_table[image]["width"])
+        return bank.table, bank.n_images, image, H, W
+    if c2w is None or K is None or H is None or W is None or image is not None:
+        raise ValueError(f"{what}: either (c2w, K, H, W) or (bank=, image=)")
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or H * W > 1 << 38:
+        raise ValueError(f"{what}: H and W are positive, and H * W is at most 2^38 pixels")
+    c2w = torch.as_tensor(c2w, dtype=torch.float32, device=dev).detach()
+    K = torch.as_tensor(K, dtype=torch.float32, device=dev).detach()
+    if c2w.dim() != 2 or c2w.shape[0] not in (3, 4) or c2w.shape[1] != 4 or K.shape != (3, 3):
+        raise ValueError(f"{what}: c2w (3|4, 4) and K (3, 3)")
+    # one nfl_image_rec that owns no pixels, written on the device: 26 words, the integers first
+    words = torch.zeros(26, dtype=torch.int32, device=dev)
+    for at, value in ((4, W), (5, H), (6, 3)):                     # fill kernels: an indexed assignment of a Python
+        words[at:at + 1].fill_(value)                               # number goes through a blocking copy instead
+    f = words.view(torch.float32)
+    f[8:12] = torch.stack([K[0, 0], K[1, 1], K[0, 2], K[1, 2]])
+    f[14:26] = c2w[:3].reshape(12)
+    return words, 1, 0, H, W
+
+
 def mesh_depth(mesh, c2w=None, K=None, H=None, W=None, *, bank=None, image=None):
     """The depth map of `mesh` seen by one camera: (H, W) fp32, per pixel the distance from the camera centre to the
     nearest triangle its ray hits (the quantity rays[:, 6:8] and depth_fine are measured in when |rays_d| = 1), +inf
@@ -513,38 +547,97 @@ def mesh_depth(mesh, c2w=None, K=None, H=None, W=None, *, bank=None, image=None)
     ver, _, _, tri = _mesh_tensors(mesh)
     dev = ver.device
     lib = _lib.lib()
-    if bank is not None:
-        if c2w is not None or K is not None or H is not None or W is not None or image is None:
-            raise ValueError("mesh_depth: either (c2w, K, H, W) or (bank=, image=)")
-        if bank.device != dev:
-            raise ValueError("mesh_depth: the bank and the mesh are on different devices")
-        image = int(image)
-        if not 0 <= image < bank.n_images:
-            raise ValueError(f"image: 0 .. {bank.n_images - 1}")
-        H, W = int(bank.host_table[image]["height"]), int(bank.host_table[image]["width"])
-        table, n_images = bank.table, bank.n_images
-    else:
-        if c2w is None or K is None or H is None or W is None or image is not None:
-            raise ValueError("mesh_depth: either (c2w, K, H, W) or (bank=, image=)")
-        H, W = int(H), int(W)
-        if H < 1 or W < 1 or H * W > 1 << 38:
-            raise ValueError("mesh_depth: H and W are positive, and H * W is at most 2^38 pixels")
-        c2w = torch.as_tensor(c2w, dtype=torch.float32, device=dev).detach()
-        K = torch.as_tensor(K, dtype=torch.float32, device=dev).detach()
-        if c2w.dim() != 2 or c2w.shape[0] not in (3, 4) or c2w.shape[1] != 4 or K.shape != (3, 3):
-            raise ValueError("mesh_depth: c2w (3|4, 4) and K (3, 3)")
-        # one nfl_image_rec that owns no pixels, written on the device: 26 words, the integers first
-        words = torch.zeros(26, dtype=torch.int32, device=dev)
-        for at, value in ((4, W), (5, H), (6, 3)):                     # fill kernels: an indexed assignment of a Python
-            words[at:at + 1].fill_(value)                               # number goes through a blocking copy instead
-        f = words.view(torch.float32)
-        f[8:12] = torch.stack([K[0, 0], K[1, 1], K[0, 2], K[1, 2]])
-        f[14:26] = c2w[:3].reshape(12)
-        table, n_images, image = words, 1, 0
+    table, n_images, image, H, W = _camera_record("mesh_depth", dev, c2w, K, H, W, bank, image)
     depth = torch.empty(H, W, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         _run_depth(lib, rendering._stream(), ver, tri, table, n_images, image, 1, depth)
     return depth
+
+
+def _run_visibility(lib, stream, ver, tri, table, n_images, first, count, vis):
+    """nfl_mesh_visibility of images first .. first + count - 1 of `table` into `vis` (the run's pixels, int64 words)."""
+    a = _lib.MeshVisibilityArgs()
+    a.d_vertices, a.d_triangles, a.n_vertices, a.n_triangles = _ptr(ver), _ptr(tri), ver.shape[0], tri.shape[0]
+    a.d_table, a.n_images, a.first, a.count = _ptr(table), n_images, first, count
+    a.d_vis, a.n_vis = _ptr(vis), vis.numel()
+    _lib.check(lib.nfl_mesh_visibility(C.byref(a), stream), "nfl_mesh_visibility")
+
+
+def mesh_visibility(mesh, c2w=None, K=None, H=None, W=None, *, bank=None, image=None):
+    """The visibility buffer of `mesh` seen by one camera: (H, W) int64 words, per pixel
+    (bits of the fp32 distance << 32) | index of the nearest triangle its ray hits, the lowest index among equally near
+    ones, and -1 (all 64 bits set) where it hits none: `word & 0xFFFFFFFF` is the triangle, `(word >> 32)` viewed as fp32
+    the value mesh_depth gives.  The camera forms, and what they synchronise, are mesh_depth's; the definition is written
+    out in include/nerf_fl_amd.h, "mesh render"."""
+    ver, _, _, tri = _mesh_tensors(mesh)
+    dev = ver.device
+    lib = _lib.lib()
+    table, n_images, image, H, W = _camera_record("mesh_visibility", dev, c2w, K, H, W, bank, image)
+    vis = torch.empty(H, W, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _run_visibility(lib, rendering._stream(), ver, tri, table, n_images, image, 1, vis)
+    return vis
+
+
+def render_mesh(mesh, c2w=None, K=None, H=None, W=None, *, bank=None, image=None, colors=None, shade="color",
+                background=(1.0, 1.0, 1.0)):
+    """`mesh` rendered from one camera (the two forms of mesh_depth): the nearest triangle of every pixel
+    (nfl_mesh_visibility) and its vertex attributes interpolated there (nfl_mesh_shade); include/nerf_fl_amd.h, "mesh
+    render".  No anti-aliasing: a pixel is its centre's ray.  Returns a dict:
+
+        rgb        uint8 (H, W, 3), by eval.to_uint8's rule (clamp, x 255, truncate)
+        rgb_float  (H * W, 3) fp32, not clamped: the layout metrics.image_metrics takes
+        depth      (H, W) fp32, bit-equal to mesh_depth; +inf where nothing is hit
+        triangle   (H, W) int32, -1 where nothing is hit
+        covered    bool (H, W)
+
+    shade       "color": `colors` (V, 3) fp32 on the mesh's device, default the mesh's own `colors`; ValueError when
+                there are none.  "normal": the mesh's normals as colours, 0.5 * n + 0.5 of the interpolated, normalised
+                normal.  "facing": a headlight, |cos| between the triangle's plane normal and the pixel's ray; needs
+                neither colours nor normals.
+    background  3 numbers: the colour of the pixels that see nothing.
+
+    It synchronises as mesh_depth does: never in the bank form, not in the free-camera form when `c2w` and `K` are
+    tensors on the mesh's device."""
+    ver, nrm, col, tri = _mesh_tensors(mesh)
+    dev, V = ver.device, ver.shape[0]
+    if shade not in _lib.SHADE_MODES:
+        raise ValueError(f"shade: one of {sorted(_lib.SHADE_MODES)}, got {shade!r}")
+    attr = None
+    if shade == "color":
+        attr = col if colors is None else colors
+        if attr is None:
+            raise ValueError("render_mesh: shade='color' needs `colors` or a mesh that has them")
+        _on_device(attr)
+        if not _is(attr, torch.float32, 2, (3,), dev) or attr.shape[0] != V:
+            raise ValueError(f"colors: expected a contiguous fp32 ({V}, 3) tensor on {dev}")
+    elif shade == "normal":
+        attr = nrm
+    try:
+        background = [float(v) for v in background]
+    except TypeError:
+        raise ValueError("background: 3 numbers") from None
+    if len(background) != 3:
+        raise ValueError("background: 3 numbers")
+    lib = _lib.lib()
+    table, n_images, image, H, W = _camera_record("render_mesh", dev, c2w, K, H, W, bank, image)
+    vis = torch.empty(H * W, dtype=torch.int64, device=dev)
+    out = {"rgb": torch.empty(H, W, 3, dtype=torch.uint8, device=dev),
+           "rgb_float": torch.empty(H * W, 3, dtype=torch.float32, device=dev),
+           "depth": torch.empty(H, W, dtype=torch.float32, device=dev),
+           "triangle": torch.empty(H, W, dtype=torch.int32, device=dev)}
+    with torch.cuda.device(dev):
+        stream = rendering._stream()
+        _run_visibility(lib, stream, ver, tri, table, n_images, image, 1, vis)
+        a = _lib.MeshShadeArgs()
+        a.d_vertices, a.d_triangles, a.n_vertices, a.n_triangles = _ptr(ver), _ptr(tri), V, tri.shape[0]
+        a.d_table, a.n_images, a.first, a.count, a.mode = _ptr(table), n_images, image, 1, _lib.SHADE_MODES[shade]
+        a.d_vis, a.n_vis, a.d_attr = _ptr(vis), H * W, _ptr(attr)
+        a.background[:] = background
+        a.d_rgb, a.d_rgb_u8, a.d_depth, a.d_triangle = (_ptr(out[k]) for k in ("rgb_float", "rgb", "depth", "triangle"))
+        _lib.check(lib.nfl_mesh_shade(C.byref(a), stream), "nfl_mesh_shade")
+    out["covered"] = out["triangle"] >= 0
+    return out
 
 
 def _image_runs(bank, images, batch_pixels):
