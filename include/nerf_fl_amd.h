@@ -1093,6 +1093,102 @@ typedef struct nfl_mesh_shade_args {
 } nfl_mesh_shade_args;
 int nfl_mesh_shade(const nfl_mesh_shade_args* args, void* stream);
 
+/* ---- mesh atlas: a texture for a mesh, baked from the images and sampled by the shading pass ---------------------------------
+ * Every operation fp32 and rounded on its own, divisions and square roots correctly rounded, as in "mesh colour" and "mesh
+ * render", whose camera, run, visibility words and ray arithmetic are used word for word.
+ *
+ * THE ATLAS of a mesh of T triangles has one chart per triangle, two triangles to a square cell, all cells the same size; it
+ * needs no parameterisation solver.  cell = C texels with 6 <= C <= 1024, L = C - 5; cols >= 1, rows >= 1 and
+ * 2 * cols * rows >= T.  It is W = cols * C by H = rows * C texels, row-major, row 0 first, three colours a texel, and
+ * W * H <= INT32_MAX.  Texel e is column X = e % W of row Y = e / W; its cell is k = (Y / C) * cols + X / C, its local
+ * coordinates i = X % C, j = Y % C; its half is h = 0 when i + j <= C - 1, else 1; its triangle is tr = 2 k + h.
+ *   Barycentrics of a texel.  Half 0: u = (float)(i - 1) / (float)L, v = (float)(j - 1) / (float)L.  Half 1 is the cell turned
+ *   by 180 degrees: u = (float)((C - 2) - i) / (float)L, v = (float)((C - 2) - j) / (float)L.  w0 = (1 - u) - v, and an
+ *   attribute triple A, B, C of the triangle's vertices interpolates to (w0 * A + u * B) + v * C (nfl_mesh_shade's
+ *   expression).  Texels outside the triangle (u < 0, v < 0 or u + v > 1) keep these extrapolated barycentrics, NOT clamped:
+ *   they are the gutter, and extrapolation is what makes a bilinear lookup reproduce an affine colour up to the hypotenuse.
+ *   Surface position.  The point (u, v) of triangle tr has the local coordinates lx = 1 + u * L, ly = 1 + v * L, and in half 1
+ *   lx = (float)(C - 1) - lx, ly = (float)(C - 1) - ly.  With u >= 0, v >= 0, u + v <= 1 the bilinear lookup at (lx, ly)
+ *   reads with non-zero weight only texels of its own half, all inside the cell.  The corners of the triangle lie ON texels:
+ *   (1, 1), (C - 4, 1), (1, C - 4) in half 0; (C - 2, C - 2), (3, C - 2), (C - 2, 3) in half 1.
+ *   A texel is OWNERLESS when tr >= T or when its triangle has an index outside [0, n_vertices): indices are not trusted.
+ *
+ * nfl_atlas_points   one launch, a thread per texel first_texel .. first_texel + n_texels - 1 (a large atlas may be baked in
+ *   pieces; the result does not depend on the split).  Row n of the outputs belongs to texel first_texel + n: d_points the
+ *   interpolated position, d_normals the interpolated vertex normal m divided by sqrt(dot(m, m)), three zeros when that
+ *   length is zero or NaN (nfl_mesh_blend counts a zero normal as cos = 1).  An ownerless texel gets three NaNs and three
+ *   zeros: nfl_mesh_blend leaves a NaN point out at its condition 2, so the rows go to it as they are, with no mask.
+ *
+ * nfl_atlas_resolve   one launch, a thread per texel of the same range, d_sum (n_texels, 4) and d_views (n_texels) being what
+ *   nfl_mesh_blend left for nfl_atlas_points' rows.  Ownerless: background[3] (whatever d_views holds).  Seen, d_views > 0:
+ *   fminf(fmaxf(sum_k / sum_3, 0), 1), so NaN -> 0.  Unseen with an owner: d_vertex_colors (V, 3) interpolated by the
+ *   texel's barycentrics, not clamped, when that pointer is given; fallback[3] otherwise.  Outputs, each skipped when NULL:
+ *   d_texture (n_texels, 3) fp32; d_texture_u8 (n_texels, 3) = (uint8_t)(clamp(c, 0, 1) * 255), truncated, NaN -> 0, the rule
+ *   of nfl_mesh_shade; d_seen (n_texels) bytes, 1 for a seen texel with an owner, else 0.
+ *
+ * nfl_mesh_shade_atlas   nfl_mesh_shade in NFL_SHADE_COLOR with the colour taken from the atlas: the uncovered rules, the
+ *   recomputation of u, v and the distance, the four outputs and the background are that entry point's.  Exactly one of
+ *   d_atlas (fp32 (H, W, 3)) and d_atlas_u8 (bytes, a texel converts by c / 255.0f) is non-NULL.  For a covered word of
+ *   triangle tr, lx and ly as above, then clamped into the cell by fminf(fmaxf(., 0), C - 1) (NaN -> 0: a forged word gives
+ *   arbitrary barycentrics and still reads inside its cell); x = floorf(lx), tx = lx - x, sx = 1 - tx, likewise y, ty, sy; the
+ *   neighbours x + 1 and y + 1 are clamped to C - 1; c = (c00 * sx + c10 * tx) * sy + (c01 * sx + c11 * tx) * ty with c00 at
+ *   (x, y), c10 at (x + 1, y), c01 at (x, y + 1) -- nfl_mesh_blend's expression.  The cell's origin ((k % cols) * C,
+ *   (k / cols) * C) is added to the integers after the floor, never in floating point.
+ *
+ * NFL_EINVAL (nothing launched), all three: args NULL; a negative size, V > INT32_MAX or 3 T > INT32_MAX; cell outside
+ *   [6, 1024], cols < 1, rows < 1, W * H > INT32_MAX, 2 * cols * rows < T; a NULL or misaligned (4 B) d_vertices /
+ *   d_triangles (points: d_vertex_normals too) that a non-zero size needs.  points and resolve: a texel range that is negative
+ *   or leaves the atlas; for n_texels > 0 a NULL or misaligned output (points) or d_sum (16 B) / d_views (resolve); a
+ *   misaligned d_vertex_colors or d_texture.  nfl_mesh_shade_atlas: the table, run, n_vis, d_vis and alignment refusals of
+ *   nfl_mesh_shade; both or neither of d_atlas and d_atlas_u8.  Zero texels or zero words: NFL_OK, no launch. */
+typedef struct nfl_atlas_points_args {
+    const float*   d_vertices;        /* (V, 3) world */
+    const float*   d_vertex_normals;  /* (V, 3) */
+    const int32_t* d_triangles;       /* (T, 3) */
+    int64_t  n_vertices, n_triangles;
+    int32_t  cell, cols, rows, reserved;
+    int64_t  first_texel, n_texels;
+    float*   d_points;                /* out (n_texels, 3) */
+    float*   d_normals;               /* out (n_texels, 3) */
+} nfl_atlas_points_args;
+int nfl_atlas_points(const nfl_atlas_points_args* args, void* stream);
+
+typedef struct nfl_atlas_resolve_args {
+    const int32_t* d_triangles;       /* (T, 3) */
+    int64_t  n_vertices, n_triangles;
+    int32_t  cell, cols, rows, reserved;
+    int64_t  first_texel, n_texels;
+    const float*   d_sum;             /* (n_texels, 4): nfl_mesh_blend over nfl_atlas_points' rows */
+    const int32_t* d_views;           /* (n_texels) */
+    const float*   d_vertex_colors;   /* (V, 3) or NULL: what an unseen texel interpolates */
+    float    fallback[3];             /* an unseen texel without d_vertex_colors */
+    float    background[3];           /* an ownerless texel */
+    float*   d_texture;               /* out (n_texels, 3) or NULL */
+    uint8_t* d_texture_u8;            /* out (n_texels, 3) or NULL */
+    uint8_t* d_seen;                  /* out (n_texels) or NULL */
+} nfl_atlas_resolve_args;
+int nfl_atlas_resolve(const nfl_atlas_resolve_args* args, void* stream);
+
+typedef struct nfl_mesh_shade_atlas_args {
+    const float*   d_vertices;        /* (V, 3) world */
+    const int32_t* d_triangles;       /* (T, 3) */
+    int64_t  n_vertices, n_triangles;
+    const nfl_image_rec* d_table;     /* (n_images) */
+    int32_t  n_images, first, count, reserved;
+    const uint64_t* d_vis;            /* (n_vis): nfl_mesh_visibility of the same run */
+    int64_t  n_vis;
+    const float*   d_atlas;           /* (H, W, 3) fp32, or NULL */
+    const uint8_t* d_atlas_u8;        /* (H, W, 3) bytes, or NULL: exactly one of the two */
+    int32_t  cell, cols, rows, reserved2;
+    float    background[3];
+    int32_t  reserved3;
+    float*   d_rgb;                   /* out (n_vis, 3) or NULL */
+    uint8_t* d_rgb_u8;                /* out (n_vis, 3) or NULL */
+    float*   d_depth;                 /* out (n_vis) or NULL */
+    int32_t* d_triangle;              /* out (n_vis) or NULL */
+} nfl_mesh_shade_atlas_args;
+int nfl_mesh_shade_atlas(const nfl_mesh_shade_atlas_args* args, void* stream);
+
 /* ---- hierarchical sampling (reference sample_pdf, rendering.py:7-46, plus the
  * concat + sort of rendering.py:267-272) -------------------------------------
  * d_z_coarse (R,S), d_weights_coarse (R,S); d_u (R,I) or NULL with d_u_row (I)

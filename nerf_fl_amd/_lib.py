@@ -293,6 +293,35 @@ class MeshShadeArgs(C.Structure):
                 ("d_rgb_u8", C.c_void_p), ("d_depth", C.c_void_p), ("d_triangle", C.c_void_p)]
 
 
+# nfl_atlas_points / nfl_atlas_resolve / nfl_mesh_shade_atlas (nerf_fl_amd.geometry: a texture atlas baked from the images and
+# sampled by the shading pass) likewise: three new symbols and structs
+ATLAS_MIN_CELL, ATLAS_MAX_CELL = 6, 1024
+
+
+class AtlasPointsArgs(C.Structure):
+    _fields_ = [("d_vertices", C.c_void_p), ("d_vertex_normals", C.c_void_p), ("d_triangles", C.c_void_p),
+                ("n_vertices", C.c_int64), ("n_triangles", C.c_int64), ("cell", C.c_int32), ("cols", C.c_int32),
+                ("rows", C.c_int32), ("reserved", C.c_int32), ("first_texel", C.c_int64), ("n_texels", C.c_int64),
+                ("d_points", C.c_void_p), ("d_normals", C.c_void_p)]
+
+
+class AtlasResolveArgs(C.Structure):
+    _fields_ = [("d_triangles", C.c_void_p), ("n_vertices", C.c_int64), ("n_triangles", C.c_int64), ("cell", C.c_int32),
+                ("cols", C.c_int32), ("rows", C.c_int32), ("reserved", C.c_int32), ("first_texel", C.c_int64),
+                ("n_texels", C.c_int64), ("d_sum", C.c_void_p), ("d_views", C.c_void_p), ("d_vertex_colors", C.c_void_p),
+                ("fallback", C.c_float * 3), ("background", C.c_float * 3), ("d_texture", C.c_void_p),
+                ("d_texture_u8", C.c_void_p), ("d_seen", C.c_void_p)]
+
+
+class MeshShadeAtlasArgs(C.Structure):
+    _fields_ = [("d_vertices", C.c_void_p), ("d_triangles", C.c_void_p), ("n_vertices", C.c_int64),
+                ("n_triangles", C.c_int64), ("d_table", C.c_void_p), ("n_images", C.c_int32), ("first", C.c_int32),
+                ("count", C.c_int32), ("reserved", C.c_int32), ("d_vis", C.c_void_p), ("n_vis", C.c_int64),
+                ("d_atlas", C.c_void_p), ("d_atlas_u8", C.c_void_p), ("cell", C.c_int32), ("cols", C.c_int32),
+                ("rows", C.c_int32), ("reserved2", C.c_int32), ("background", C.c_float * 3), ("reserved3", C.c_int32),
+                ("d_rgb", C.c_void_p), ("d_rgb_u8", C.c_void_p), ("d_depth", C.c_void_p), ("d_triangle", C.c_void_p)]
+
+
 # every symbol include/nerf_fl_amd.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("nfl_plan_bytes", C.c_size_t, [C.POINTER(FieldDesc)]),
@@ -364,6 +393,9 @@ SYMBOLS = [
     ("nfl_mesh_blend", C.c_int, [C.POINTER(MeshBlendArgs), C.c_void_p]),
     ("nfl_mesh_visibility", C.c_int, [C.POINTER(MeshVisibilityArgs), C.c_void_p]),
     ("nfl_mesh_shade", C.c_int, [C.POINTER(MeshShadeArgs), C.c_void_p]),
+    ("nfl_atlas_points", C.c_int, [C.POINTER(AtlasPointsArgs), C.c_void_p]),
+    ("nfl_atlas_resolve", C.c_int, [C.POINTER(AtlasResolveArgs), C.c_void_p]),
+    ("nfl_mesh_shade_atlas", C.c_int, [C.POINTER(MeshShadeAtlasArgs), C.c_void_p]),
     ("nfl_abi_version", C.c_int, []),
     ("nfl_version", C.c_char_p, []),
     ("nfl_strerror", C.c_char_p, [C.c_int]),

@@ -460,7 +460,7 @@ def render_video(models, embeddings, poses, K, H, W, near, far, N_samples, N_imp
 
 def render_mesh_video(mesh, poses, K, H, W, rank=0, world=1, **kwargs):
     """render_video for a mesh: the frames of a camera path through geometry.render_mesh (`kwargs`: colors, shade,
-    background), sharded over ranks with no collective.  Rank r renders the contiguous block
+    background, texture), sharded over ranks with no collective.  Rank r renders the contiguous block
     parallel.shard_bounds(n_frames, r, world) and returns (first frame index, uint8 (n_local, H, W, 3)) on the mesh's
     device.  No host synchronisation when `poses` and `K` are tensors on that device."""
     from . import geometry
@@ -470,9 +470,11 @@ def render_mesh_video(mesh, poses, K, H, W, rank=0, world=1, **kwargs):
     return lo, (torch.stack(frames) if frames else torch.empty(0, int(H), int(W), 3, dtype=torch.uint8, device=dev))
 
 
-def evaluate_mesh(mesh, bank, *, colors=None, images=None, background=None, rank=0, world=1, return_images=False):
+def evaluate_mesh(mesh, bank, *, colors=None, images=None, background=None, rank=0, world=1, return_images=False,
+                  texture=None):
     """evaluate_bank for a coloured mesh: every selected image of a data.ImageBank (on the mesh's device) is rendered from
-    its record's camera by geometry.render_mesh (`colors`: default the mesh's own) and scored on the device against the
+    its record's camera by geometry.render_mesh (`colors`: default the mesh's own; `texture`: an atlas, as render_mesh
+    takes it, scores the textured render instead) and scored on the device against the
     bank's image, with one device-to-host copy after the last image.
 
     What is scored is the 8-bit frame, byte / 255 (what `frames` holds and a viewer sees; the photographs are 8-bit
@@ -504,7 +506,7 @@ def evaluate_mesh(mesh, bank, *, colors=None, images=None, background=None, rank
         i = images[k]
         rec = bank.host_table[i]
         H, W = int(rec["height"]), int(rec["width"])
-        out = geometry.render_mesh(mesh, bank=bank, image=i, colors=colors, background=background)
+        out = geometry.render_mesh(mesh, bank=bank, image=i, colors=colors, background=background, texture=texture)
         # byte / 255.0f as the bank's own pixels are converted (nfl_pixel.h: a correctly rounded fp32 quotient).  Taken
         # through fp64: torch divides an fp32 tensor by a number by multiplying with its reciprocal, which is one ulp off
         # for some bytes; the fp64 quotient is within 2^-52 of k / 255 whichever way it is formed, and no k / 255 lies

@@ -15,6 +15,9 @@
     color_mesh_from_images   vertex colours from the images of an ImageBank that see each vertex, hidden views left out
     mesh_visibility   which triangle a camera sees at every pixel, and how far: a visibility buffer (csrc/nfl_meshrender.hip)
     render_mesh       a coloured mesh as an image: vertex colours, normals or a headlight interpolated at the winning triangles
+    atlas_layout      the texture atlas of a mesh: a chart per triangle, two to a square cell (csrc/nfl_atlas.hip)
+    bake_texture      such an atlas filled from the images of an ImageBank; render_mesh(texture=) samples it
+    write_obj         OBJ + MTL + PNG of a mesh and its atlas (numpy and Pillow)
 
 Conventions: `lo`, `hi` and `res` are 3 numbers in (x, y, z) order; a lattice is a (nz, ny, nx) fp32 tensor, x fastest,
 whose point (x, y, z) lies at lo + (x, y, z) * spacing with spacing = (hi - lo) / (res - 1): `lattice_points` returns
@@ -24,6 +27,7 @@ exactly the fp32 positions both the field pass and the extraction use.  A point 
 There is no CPU path.
 """
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -32,7 +36,8 @@ from . import _lib, rendering
 
 __all__ = ["density_lattice", "extract_surface", "surface_colors", "write_ply", "extract_mesh", "lattice_points",
            "mesh_components", "filter_mesh", "clean_mesh", "simplify_mesh", "OccupancyGrid", "occupancy_grid", "clip_rays",
-           "mesh_depth", "color_mesh_from_images", "mesh_visibility", "render_mesh"]
+           "mesh_depth", "color_mesh_from_images", "mesh_visibility", "render_mesh", "atlas_layout", "atlas_uv",
+           "bake_texture", "write_obj"]
 
 # Longest piece of an x-row handed to the render pass as one ray.  nfl_render_pass accepts any n_samples >= 1; the cut is
 # a scheduling choice, not a limit of the ABI: the kernel gives whole rays to workgroups (contiguous ray ranges, one
@@ -579,8 +584,31 @@ def mesh_visibility(mesh, c2w=None, K=None, H=None, W=None, *, bank=None, image=
     return vis
 
 
+def _atlas_of(texture, T, dev):
+    """(fp32 texture or None, uint8 texture or None, cell, cols, rows) of the `texture` dict render_mesh takes, checked
+    against a mesh of T triangles on `dev`."""
+    try:
+        cell, cols = int(texture["cell"]), int(texture["cols"])
+        tex, tex8 = texture.get("texture"), texture.get("texture_u8")
+    except (TypeError, KeyError, AttributeError):
+        raise ValueError("texture: a dict with `texture` (H, W, 3) fp32 or `texture_u8`, `cell` and `cols`") from None
+    if tex is not None:
+        tex8 = None
+    t = tex if tex is not None else tex8
+    if t is None:
+        raise ValueError("texture: a dict with `texture` (H, W, 3) fp32 or `texture_u8`, `cell` and `cols`")
+    _on_device(t)
+    if not _is(t, torch.float32 if tex is not None else torch.uint8, 3, (3,), dev):
+        raise ValueError(f"texture: expected a contiguous (H, W, 3) fp32 or uint8 tensor on {dev}")
+    rows = t.shape[0] // cell if cell > 0 else 0
+    lay = atlas_layout(T, cell, cols)                                 # refuses a bad cell or cols
+    if t.shape[1] != cols * cell or t.shape[0] != rows * cell or rows < lay["rows"]:
+        raise ValueError(f"texture: {tuple(t.shape)} is not an atlas of cell {cell} and {cols} columns for {T} triangles")
+    return tex, tex8, cell, cols, rows
+
+
 def render_mesh(mesh, c2w=None, K=None, H=None, W=None, *, bank=None, image=None, colors=None, shade="color",
-                background=(1.0, 1.0, 1.0)):
+                background=(1.0, 1.0, 1.0), texture=None):
     """`mesh` rendered from one camera (the two forms of mesh_depth): the nearest triangle of every pixel
     (nfl_mesh_visibility) and its vertex attributes interpolated there (nfl_mesh_shade); include/nerf_fl_amd.h, "mesh
     render".  No anti-aliasing: a pixel is its centre's ray.  Returns a dict:
@@ -596,6 +624,10 @@ def render_mesh(mesh, c2w=None, K=None, H=None, W=None, *, bank=None, image=None
                 normal.  "facing": a headlight, |cos| between the triangle's plane normal and the pixel's ray; needs
                 neither colours nor normals.
     background  3 numbers: the colour of the pixels that see nothing.
+    texture     an atlas: the dict bake_texture returns, or any dict with `texture` ((H, W, 3) fp32) or `texture_u8`
+                (uint8, used when `texture` is absent), `cell` and `cols`.  The colour of a covered pixel is then the
+                bilinear lookup in its triangle's chart (nfl_mesh_shade_atlas; "mesh atlas" in the header) instead of
+                interpolated vertex colours; `colors` is not read, and any `shade` but the default raises.
 
     It synchronises as mesh_depth does: never in the bank form, not in the free-camera form when `c2w` and `K` are
     tensors on the mesh's device."""
@@ -603,8 +635,12 @@ def render_mesh(mesh, c2w=None, K=None, H=None, W=None, *, bank=None, image=None
     dev, V = ver.device, ver.shape[0]
     if shade not in _lib.SHADE_MODES:
         raise ValueError(f"shade: one of {sorted(_lib.SHADE_MODES)}, got {shade!r}")
-    attr = None
-    if shade == "color":
+    attr = atlas = None
+    if texture is not None:
+        if shade != "color":
+            raise ValueError("render_mesh: a texture is a colour; shade must be left at 'color'")
+        atlas = _atlas_of(texture, tri.shape[0], dev)
+    elif shade == "color":
         attr = col if colors is None else colors
         if attr is None:
             raise ValueError("render_mesh: shade='color' needs `colors` or a mesh that has them")
@@ -629,13 +665,18 @@ def render_mesh(mesh, c2w=None, K=None, H=None, W=None, *, bank=None, image=None
     with torch.cuda.device(dev):
         stream = rendering._stream()
         _run_visibility(lib, stream, ver, tri, table, n_images, image, 1, vis)
-        a = _lib.MeshShadeArgs()
+        a = _lib.MeshShadeArgs() if atlas is None else _lib.MeshShadeAtlasArgs()
         a.d_vertices, a.d_triangles, a.n_vertices, a.n_triangles = _ptr(ver), _ptr(tri), V, tri.shape[0]
-        a.d_table, a.n_images, a.first, a.count, a.mode = _ptr(table), n_images, image, 1, _lib.SHADE_MODES[shade]
-        a.d_vis, a.n_vis, a.d_attr = _ptr(vis), H * W, _ptr(attr)
+        a.d_table, a.n_images, a.first, a.count = _ptr(table), n_images, image, 1
+        a.d_vis, a.n_vis = _ptr(vis), H * W
         a.background[:] = background
         a.d_rgb, a.d_rgb_u8, a.d_depth, a.d_triangle = (_ptr(out[k]) for k in ("rgb_float", "rgb", "depth", "triangle"))
-        _lib.check(lib.nfl_mesh_shade(C.byref(a), stream), "nfl_mesh_shade")
+        if atlas is None:
+            a.mode, a.d_attr = _lib.SHADE_MODES[shade], _ptr(attr)
+            _lib.check(lib.nfl_mesh_shade(C.byref(a), stream), "nfl_mesh_shade")
+        else:
+            a.d_atlas, a.d_atlas_u8, a.cell, a.cols, a.rows = _ptr(atlas[0]), _ptr(atlas[1]), *atlas[2:]
+            _lib.check(lib.nfl_mesh_shade_atlas(C.byref(a), stream), "nfl_mesh_shade_atlas")
     out["covered"] = out["triangle"] >= 0
     return out
 
@@ -658,6 +699,70 @@ def _image_runs(bank, images, batch_pixels):
         else:
             runs.append((i, 1, size(i)))
     return runs
+
+
+class _BlendWalk:
+    """The walk over the image runs that color_mesh_from_images and bake_texture share: per run the depth map of the MESH
+    (nfl_mesh_depth; kept for later passes when `keep` and all of them fit in `batch_pixels`, otherwise rasterised again
+    into one scratch) and nfl_mesh_blend of any points with normals, continuing the caller's accumulators."""
+
+    def __init__(self, ver, tri, bank, runs, weights, weighting, min_cos, depth_tol, reject, batch_pixels, keep):
+        self.lib, self.ver, self.tri, self.bank, self.runs = _lib.lib(), ver, tri, bank, runs
+        self.weights, self.weighting, self.min_cos, self.depth_tol, self.reject = weights, weighting, min_cos, depth_tol, reject
+        dev = ver.device
+        self.keep = keep and sum(r[2] for r in runs) <= batch_pixels
+        self.scratch = None if self.keep or not runs else torch.empty(max(r[2] for r in runs), dtype=torch.float32, device=dev)
+        self.kept = {}
+
+    def blend(self, points, normals, center, sums, views):
+        """One pass over all runs: `sums` (n, 4) and `views` (n,) begin at zero; with `center` (n, 3) the samples further
+        than `reject` from it are left out.  On the current device's stream."""
+        lib, bank, dev, stream = self.lib, self.bank, self.ver.device, rendering._stream()
+        a = _lib.MeshBlendArgs()
+        a.d_vertices, a.d_normals, a.n_vertices, a.d_pixels = _ptr(points), _ptr(normals), points.shape[0], _ptr(bank.pixels)
+        a.d_table, a.n_images, a.weighting = _ptr(bank.table), bank.n_images, _lib.BLEND_WEIGHTINGS[self.weighting]
+        a.d_image_weights, a.d_center, a.min_cos, a.depth_tol = _ptr(self.weights), _ptr(center), self.min_cos, self.depth_tol
+        a.reject = float(self.reject) if center is not None else 0.0
+        a.d_sum, a.d_views = _ptr(sums), _ptr(views)
+        for k, (first, count, pixels) in enumerate(self.runs or [(0, 0, 0)]):
+            if count and first in self.kept:
+                depth = self.kept[first]
+            elif count:
+                depth = torch.empty(pixels, dtype=torch.float32, device=dev) if self.keep else self.scratch[:pixels]
+                _run_depth(lib, stream, self.ver, self.tri, bank.table, bank.n_images, first, count, depth)
+                if self.keep:
+                    self.kept[first] = depth
+            else:
+                depth = None
+            a.first, a.count, a.start = first, count, int(k == 0)
+            a.d_depth, a.n_depth = _ptr(depth), pixels
+            _lib.check(lib.nfl_mesh_blend(C.byref(a), stream), "nfl_mesh_blend")
+
+
+def _blend_arguments(what, mesh_dev, bank, depth_tol, images, image_weights, min_cos, weighting, reject, batch_pixels):
+    """The blend arguments color_mesh_from_images and bake_texture share, checked: (depth_tol, min_cos, batch_pixels, runs,
+    weights)."""
+    if getattr(bank, "device", None) != mesh_dev or bank.table is None:
+        raise ValueError(f"{what}: `bank` is a data.ImageBank on the mesh's device")
+    if weighting not in _lib.BLEND_WEIGHTINGS:
+        raise ValueError(f"weighting: one of {sorted(_lib.BLEND_WEIGHTINGS)}, got {weighting!r}")
+    depth_tol, min_cos = float(depth_tol), float(min_cos)
+    if not depth_tol >= 0.0:
+        raise ValueError("depth_tol: a non-negative number")
+    if not (min_cos >= 0.0 or (weighting != "cos" and min_cos == min_cos)):
+        raise ValueError("min_cos: a number, not negative with weighting='cos' (a weight is never negative)")
+    if reject is not None and not float(reject) >= 0.0:
+        raise ValueError("reject: a non-negative number")
+    batch_pixels = int(batch_pixels)
+    if batch_pixels < 1:
+        raise ValueError("batch_pixels must be positive")
+    runs = _image_runs(bank, images, batch_pixels)
+    weights = None
+    if image_weights is not None:
+        weights = torch.as_tensor(image_weights, dtype=torch.float32, device=mesh_dev).detach().contiguous()
+        if weights.shape != (bank.n_images,):
+            raise ValueError(f"image_weights: expected ({bank.n_images},)")
+    return depth_tol, min_cos, batch_pixels, runs, weights
 
 
 def color_mesh_from_images(mesh, bank, depth_tol, *, images=None, image_weights=None, min_cos=0.0, weighting="cos",
@@ -693,72 +798,210 @@ def color_mesh_from_images(mesh, bank, depth_tol, *, images=None, image_weights=
     for the stream."""
     ver, nrm, _, tri = _mesh_tensors(mesh)
     dev, V = ver.device, ver.shape[0]
-    if getattr(bank, "device", None) != dev or bank.table is None:
-        raise ValueError("color_mesh_from_images: `bank` is a data.ImageBank on the mesh's device")
-    if weighting not in _lib.BLEND_WEIGHTINGS:
-        raise ValueError(f"weighting: one of {sorted(_lib.BLEND_WEIGHTINGS)}, got {weighting!r}")
-    depth_tol, min_cos = float(depth_tol), float(min_cos)
-    if not depth_tol >= 0.0:
-        raise ValueError("depth_tol: a non-negative number")
-    if not (min_cos >= 0.0 or (weighting != "cos" and min_cos == min_cos)):
-        raise ValueError("min_cos: a number, not negative with weighting='cos' (a weight is never negative)")
-    if reject is not None and not float(reject) >= 0.0:
-        raise ValueError("reject: a non-negative number")
-    batch_pixels = int(batch_pixels)
-    if batch_pixels < 1:
-        raise ValueError("batch_pixels must be positive")
-    runs = _image_runs(bank, images, batch_pixels)
-    weights = None
-    if image_weights is not None:
-        weights = torch.as_tensor(image_weights, dtype=torch.float32, device=dev).detach().contiguous()
-        if weights.shape != (bank.n_images,):
-            raise ValueError(f"image_weights: expected ({bank.n_images},)")
+    depth_tol, min_cos, batch_pixels, runs, weights = _blend_arguments(
+        "color_mesh_from_images", dev, bank, depth_tol, images, image_weights, min_cos, weighting, reject, batch_pixels)
     if fallback is None:
         fallback = torch.full((3,), 0.5, dtype=torch.float32, device=dev)
     fallback = torch.as_tensor(fallback, dtype=torch.float32, device=dev).detach()
     if fallback.shape not in ((3,), (V, 3)):
         raise ValueError(f"fallback: 3 numbers or ({V}, 3)")
-    lib = _lib.lib()
-    keep = reject is not None and sum(r[2] for r in runs) <= batch_pixels
-    scratch = None if keep or not runs else torch.empty(max(r[2] for r in runs), dtype=torch.float32, device=dev)
-    kept = {}
+    walk = _BlendWalk(ver, tri, bank, runs, weights, weighting, min_cos, depth_tol, reject, batch_pixels,
+                      keep=reject is not None)
     sums = torch.empty(V, 4, dtype=torch.float32, device=dev)
     views = torch.empty(V, dtype=torch.int32, device=dev)
 
     def one_pass(center, fallback):
-        a = _lib.MeshBlendArgs()
-        a.d_vertices, a.d_normals, a.n_vertices, a.d_pixels = _ptr(ver), _ptr(nrm), V, _ptr(bank.pixels)
-        a.d_table, a.n_images, a.weighting = _ptr(bank.table), bank.n_images, _lib.BLEND_WEIGHTINGS[weighting]
-        a.d_image_weights, a.d_center, a.min_cos, a.depth_tol = _ptr(weights), _ptr(center), min_cos, depth_tol
-        a.reject = float(reject) if center is not None else 0.0
-        a.d_sum, a.d_views = _ptr(sums), _ptr(views)
-        for k, (first, count, pixels) in enumerate(runs or [(0, 0, 0)]):
-            if count and first in kept:
-                depth = kept[first]
-            elif count:
-                depth = torch.empty(pixels, dtype=torch.float32, device=dev) if keep else scratch[:pixels]
-                _run_depth(lib, stream, ver, tri, bank.table, bank.n_images, first, count, depth)
-                if keep:
-                    kept[first] = depth
-            else:
-                depth = None
-            a.first, a.count, a.start = first, count, int(k == 0)
-            a.d_depth, a.n_depth = _ptr(depth), pixels
-            _lib.check(lib.nfl_mesh_blend(C.byref(a), stream), "nfl_mesh_blend")
+        walk.blend(ver, nrm, center, sums, views)
         seen = views > 0
         colors = torch.where(seen[:, None], (sums[:, :3] / sums[:, 3:4]).clamp(0.0, 1.0), fallback.expand(V, 3))
         return colors.contiguous(), seen
 
     with torch.cuda.device(dev):
-        stream = rendering._stream()
         colors, seen = one_pass(None, fallback)
         if reject is not None:
             colors, seen = one_pass(colors, colors)                       # all samples rejected: the first pass's colour stays
     return {"colors": colors, "weight": sums[:, 3].contiguous(), "views": views, "seen": seen}
 
 
+def atlas_layout(n_triangles, cell, cols=None):
+    """The texture atlas of a mesh of `n_triangles` (include/nerf_fl_amd.h, "mesh atlas"): one chart per triangle, two
+    triangles to a square cell of `cell` x `cell` texels (6 .. 1024), `cols` cells a row (default
+    ceil(sqrt(ceil(T / 2))), a square atlas), at least one row and one column.  Returns a dict: cell, cols, rows, width,
+    height."""
+    T, cell = int(n_triangles), int(cell)
+    if T < 0 or 3 * T > 2 ** 31 - 1:
+        raise ValueError("n_triangles: 0 .. (2^31 - 1) / 3")
+    if not _lib.ATLAS_MIN_CELL <= cell <= _lib.ATLAS_MAX_CELL:
+        raise ValueError(f"cell: {_lib.ATLAS_MIN_CELL} .. {_lib.ATLAS_MAX_CELL} texels")
+    cells = max((T + 1) // 2, 1)
+    if cols is None:
+        cols = math.isqrt(cells - 1) + 1                              # ceil(sqrt(cells)) in integers
+    cols = int(cols)
+    if cols < 1:
+        raise ValueError("cols must be positive")
+    rows = (cells + cols - 1) // cols
+    if cols * cell * rows * cell > 2 ** 31 - 1:
+        raise ValueError(f"an atlas of {cols * cell} x {rows * cell} texels: more than int32 addresses")
+    return {"cell": cell, "cols": cols, "rows": rows, "width": cols * cell, "height": rows * cell}
+
+
+def atlas_uv(layout, n_triangles):
+    """(T, 3, 2) fp64 array: where the three corners of every triangle lie in the atlas, (x, y) in texel units (texel
+    centres on the integers, row 0 first).  They lie ON texels: (1, 1), (C - 4, 1), (1, C - 4) of the cell in half 0,
+    the cell turned by 180 degrees in half 1."""
+    C_, cols = int(layout["cell"]), int(layout["cols"])
+    tr = np.arange(int(n_triangles))
+    k, h = tr // 2, tr % 2
+    L = C_ - 5
+    local = np.array([[1, 1], [1 + L, 1], [1, 1 + L]], dtype=np.float64)[None, :, :].repeat(len(tr), axis=0)
+    local = np.where(h[:, None, None] == 1, (C_ - 1) - local, local)
+    origin = np.stack([(k % cols) * C_, (k // cols) * C_], axis=1).astype(np.float64)
+    return local + origin[:, None, :]
+
+
+def bake_texture(mesh, bank, depth_tol, *, cell=16, cols=None, fallback="colors", background=(0.0, 0.0, 0.0),
+                 texel_batch=1 << 24, images=None, image_weights=None, min_cos=0.0, weighting="cos", reject=None,
+                 batch_pixels=1 << 26):
+    """A texture atlas of `mesh` baked from the images of `bank`: every texel of atlas_layout(T, cell, cols) becomes a
+    point of its triangle with a normal (nfl_atlas_points), the points are coloured exactly as color_mesh_from_images
+    colours vertices -- the same projection, facing and depth tests against the depth maps of the MESH, the same
+    bilinear samples and weights, `images`, `image_weights`, `min_cos`, `weighting`, `reject` and `batch_pixels` as
+    there -- and the sums become texels (nfl_atlas_resolve).  The definition is written out in include/nerf_fl_amd.h,
+    "mesh atlas".  Returns a dict that render_mesh(texture=) and write_obj take:
+
+        texture (H, W, 3) fp32 in [0, 1] where seen; texture_u8 (H, W, 3) uint8 (clamp, x 255, truncate);
+        seen (H, W) bool; views (H, W) int32; cell, cols, rows
+
+    fallback     the colour of a texel no image sees: "colors" interpolates the mesh's vertex `colors` (ValueError when it
+                 has none), 3 numbers give a flat colour.  With `reject`, a texel seen in the first pass whose samples are
+                 all rejected in the second keeps its first-pass colour (and is not `seen`), as a vertex does.
+    background   3 numbers: texels of cells and half-cells that no triangle owns.
+    texel_batch  texels coloured at a time (each needs 44 bytes of points, normals and sums); the result does not depend
+                 on it.  With more than one batch the depth maps are kept between them when they fit in `batch_pixels`.
+
+    No host synchronisation of its own, as color_mesh_from_images."""
+    ver, nrm, col, tri = _mesh_tensors(mesh)
+    dev, V, T = ver.device, ver.shape[0], tri.shape[0]
+    depth_tol, min_cos, batch_pixels, runs, weights = _blend_arguments(
+        "bake_texture", dev, bank, depth_tol, images, image_weights, min_cos, weighting, reject, batch_pixels)
+    lay = atlas_layout(T, cell, cols)
+    cell, cols, rows, W, H = (lay[k] for k in ("cell", "cols", "rows", "width", "height"))
+    texel_batch = int(texel_batch)
+    if texel_batch < 1:
+        raise ValueError("texel_batch must be positive")
+    vcol, flat = None, [0.0, 0.0, 0.0]
+    if isinstance(fallback, str):
+        if fallback != "colors":
+            raise ValueError("fallback: 'colors' or 3 numbers")
+        if col is None:
+            raise ValueError("bake_texture: fallback='colors' needs a mesh that has `colors`")
+        vcol = col
+    else:
+        try:
+            flat = [float(v) for v in fallback]
+        except TypeError:
+            raise ValueError("fallback: 'colors' or 3 numbers") from None
+        if len(flat) != 3:
+            raise ValueError("fallback: 'colors' or 3 numbers")
+    try:
+        background = [float(v) for v in background]
+    except TypeError:
+        raise ValueError("background: 3 numbers") from None
+    if len(background) != 3:
+        raise ValueError("background: 3 numbers")
+    N = W * H
+    lib = _lib.lib()
+    walk = _BlendWalk(ver, tri, bank, runs, weights, weighting, min_cos, depth_tol, reject, batch_pixels,
+                      keep=reject is not None or N > texel_batch)
+    out = {"texture": torch.empty(H, W, 3, dtype=torch.float32, device=dev),
+           "texture_u8": torch.empty(H, W, 3, dtype=torch.uint8, device=dev),
+           "seen": torch.empty(H, W, dtype=torch.uint8, device=dev),
+           "views": torch.empty(H, W, dtype=torch.int32, device=dev)}
+    tex, tex8, seen, views = out["texture"].view(N, 3), out["texture_u8"].view(N, 3), out["seen"].view(N), out["views"].view(N)
+    n_max = min(N, texel_batch)
+    pts, nor = (torch.empty(n_max, 3, dtype=torch.float32, device=dev) for _ in range(2))
+    sums = torch.empty(n_max, 4, dtype=torch.float32, device=dev)
+
+    def resolve(first, n, texture, texture_u8, seen_):
+        r = _lib.AtlasResolveArgs()
+        r.d_triangles, r.n_vertices, r.n_triangles = _ptr(tri), V, T
+        r.cell, r.cols, r.rows, r.first_texel, r.n_texels = cell, cols, rows, first, n
+        r.d_sum, r.d_views, r.d_vertex_colors = _ptr(sums), _ptr(views[first:first + n]), _ptr(vcol)
+        r.fallback[:], r.background[:] = flat, background
+        r.d_texture, r.d_texture_u8, r.d_seen = _ptr(texture), _ptr(texture_u8), _ptr(seen_)
+        _lib.check(lib.nfl_atlas_resolve(C.byref(r), stream), "nfl_atlas_resolve")
+
+    with torch.cuda.device(dev):
+        stream = rendering._stream()
+        for first in range(0, N, texel_batch):
+            n = min(texel_batch, N - first)
+            a = _lib.AtlasPointsArgs()
+            a.d_vertices, a.d_vertex_normals, a.d_triangles, a.n_vertices, a.n_triangles = _ptr(ver), _ptr(nrm), _ptr(tri), V, T
+            a.cell, a.cols, a.rows, a.first_texel, a.n_texels = cell, cols, rows, first, n
+            a.d_points, a.d_normals = _ptr(pts), _ptr(nor)
+            _lib.check(lib.nfl_atlas_points(C.byref(a), stream), "nfl_atlas_points")
+            piece = slice(first, first + n)
+            walk.blend(pts[:n], nor[:n], None, sums[:n], views[piece])
+            resolve(first, n, tex[piece], tex8[piece], seen[piece])
+            if reject is not None:
+                first_tex, first_u8 = tex[piece].clone(), tex8[piece].clone()
+                walk.blend(pts[:n], nor[:n], first_tex, sums[:n], views[piece])
+                resolve(first, n, tex[piece], tex8[piece], seen[piece])
+                lost = (seen[piece] == 0)[:, None]                        # all samples rejected: the first pass's colour stays
+                tex[piece] = torch.where(lost, first_tex, tex[piece])
+                tex8[piece] = torch.where(lost, first_u8, tex8[piece])
+    out["seen"] = out["seen"].view(torch.bool)
+    return dict(out, cell=cell, cols=cols, rows=rows)
+
+
+def write_obj(path, mesh, atlas):
+    """Write `mesh` with its texture `atlas` (the dict bake_texture returns; tensors or arrays) as `stem`.obj,
+    `stem`.mtl and `stem`.png beside each other, `path` being any of the three or the bare stem: per vertex `v` and
+    `vn`, per CORNER a `vt` ((x + 0.5) / W, 1 - (y + 0.5) / H of atlas_uv: the PNG's row 0 is the top), faces
+    `f v/vt/vn` 1-based, the material's `map_Kd` the PNG of `texture_u8`.  Needs Pillow."""
+    import os
+    from PIL import Image
+    arr = lambda v: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v))
+    ver, nrm, tri = arr(mesh["vertices"]), arr(mesh["normals"]), arr(mesh["triangles"])
+    V, T = ver.shape[0], tri.shape[0]
+    if ver.shape != (V, 3) or nrm.shape != (V, 3) or tri.shape != (T, 3):
+        raise ValueError("mesh: vertices (V, 3), normals (V, 3), triangles (T, 3)")
+    if T and (tri.min() < 0 or tri.max() >= V):
+        raise ValueError("mesh: a triangle index lies outside the vertices")
+    try:
+        tex8, cell, cols = atlas.get("texture_u8"), int(atlas["cell"]), int(atlas["cols"])
+    except (TypeError, KeyError, AttributeError):
+        raise ValueError("atlas: a dict with `texture_u8` (H, W, 3) uint8, `cell` and `cols`") from None
+    if tex8 is None:
+        raise ValueError("atlas: a dict with `texture_u8` (H, W, 3) uint8, `cell` and `cols`")
+    tex8 = arr(tex8)
+    lay = atlas_layout(T, cell, cols)
+    if tex8.dtype != np.uint8 or tex8.ndim != 3 or tex8.shape[2] != 3 or tex8.shape[1] != lay["width"] \
+            or tex8.shape[0] % cell or tex8.shape[0] < lay["height"]:
+        raise ValueError(f"atlas: texture_u8 {tex8.shape} is not an atlas of cell {cell} and {cols} columns for {T} triangles")
+    H, W = tex8.shape[:2]
+    stem = str(path)
+    if stem.lower().endswith((".obj", ".mtl", ".png")):
+        stem = stem[:-4]
+    name = os.path.basename(stem)
+    Image.fromarray(np.ascontiguousarray(tex8), "RGB").save(stem + ".png")
+    with open(stem + ".mtl", "w") as f:
+        f.write(f"# nerf_fl_amd.geometry\nnewmtl {name}\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 0\nmap_Kd {name}.png\n")
+    uv = atlas_uv(lay, T).reshape(-1, 2)
+    vt = np.stack([(uv[:, 0] + 0.5) / W, 1.0 - (uv[:, 1] + 0.5) / H], axis=1)
+    lines = [f"# nerf_fl_amd.geometry\nmtllib {name}.mtl\nusemtl {name}\n"]
+    lines += ["".join(f"v {x!r} {y!r} {z!r}\n" for x, y, z in ver.astype(np.float64).tolist())]
+    lines += ["".join(f"vn {x!r} {y!r} {z!r}\n" for x, y, z in nrm.astype(np.float64).tolist())]
+    lines += ["".join(f"vt {u!r} {v!r}\n" for u, v in vt.tolist())]
+    lines += ["".join(f"f {a + 1}/{3 * t + 1}/{a + 1} {b + 1}/{3 * t + 2}/{b + 1} {c + 1}/{3 * t + 3}/{c + 1}\n"
+                      for t, (a, b, c) in enumerate(tri.tolist()))]
+    with open(stem + ".obj", "w") as f:
+        f.write("".join(lines))
+
+
 def extract_mesh(models, embeddings, lo, hi, res, iso, chunk=1 << 20, a_embedded=None, path=None, largest=None,
-                 min_triangles=None, simplify=None, placement="mean", color_from=None, depth_tol=None, color_kwargs=None):
+                 min_triangles=None, simplify=None, placement="mean", color_from=None, depth_tol=None, color_kwargs=None,
+                 texture=None):
     """density_lattice -> extract_surface -> surface_colors (-> write_ply when `path` is given) for the fine model of
     `models` (the coarse one when there is no fine one).  Returns the mesh dict with `colors` (V, 3) added.
 
@@ -773,7 +1016,15 @@ def extract_mesh(models, embeddings, lo, hi, res, iso, chunk=1 << 20, a_embedded
     field is never evaluated at a discarded vertex.
 
     With `simplify` = a cell size the cleaned mesh goes through simplify_mesh (origin = `lo`, `placement` as there), also
-    before the colour pass: the field is evaluated at the simplified vertices only, seen along their new normals."""
+    before the colour pass: the field is evaluated at the simplified vertices only, seen along their new normals.
+
+    With `texture` = a cell size (and `color_from`) a texture atlas is baked from the same bank after the vertex colours
+    exist (bake_texture with the `color_kwargs` that apply to it; the vertex colours are its fallback); the mesh gets
+    `atlas`, and `path` is then written as an OBJ set (write_obj) instead of a PLY."""
+    if texture is not None:
+        if color_from is None:
+            raise ValueError("extract_mesh: texture= bakes from the images; give color_from")
+        atlas_layout(0, texture)                                          # refused before anything is evaluated
     if simplify is not None:
         _simplify_arguments(simplify, lo, placement)                      # refused before anything is evaluated
     model = models["fine"] if "fine" in models else models["coarse"]
@@ -796,7 +1047,12 @@ def extract_mesh(models, embeddings, lo, hi, res, iso, chunk=1 << 20, a_embedded
             depth_tol = 2.0 * max(_box(lo, hi, res)[1])
         got = color_mesh_from_images(mesh, color_from, depth_tol, **dict({"fallback": fallback}, **(color_kwargs or {})))
         mesh["colors"], mesh["seen"] = got["colors"], got["seen"]
-    if path is not None:
+        if texture is not None:
+            kw = {k: v for k, v in (color_kwargs or {}).items() if k != "fallback"}
+            mesh["atlas"] = bake_texture(mesh, color_from, depth_tol, cell=texture, fallback="colors", **kw)
+    if path is not None and mesh.get("atlas") is not None:
+        write_obj(path, mesh, mesh["atlas"])
+    elif path is not None:
         write_ply(path, mesh, mesh["colors"])
     return mesh
 
