@@ -1,6 +1,7 @@
-"""References and comparisons for the training forward (nfl_render_kernel in NFL_MODE_STASH / NFL_MODE_STASH2) on its own.
-A plain helper (no pytest hooks) of tests/test_forward_gpu.py and tests/test_forward_refs_cpu.py; everything but
-`run_forward` works without a GPU.
+"""References and comparisons for the training forward (nfl_render_kernel in NFL_MODE_STASH / NFL_MODE_STASH2) and the
+inference passes (NFL_MODE_RENDER, NFL_MODE_EMBED) on their own.  A plain helper (no pytest hooks) of
+tests/test_forward_gpu.py, tests/test_inference_gpu.py and tests/test_forward_refs_cpu.py; everything but the runners
+(`run_forward`, `run_render`, `run_embed`) works without a GPU.
 
 * the launch geometry: `ray_split` restates nfl_ray_split (csrc/nfl_launch.cpp), `tiling` / `situation_violations` say what
   a shape makes of it on a device with a given number of CUs;
@@ -9,7 +10,11 @@ A plain helper (no pytest hooks) of tests/test_forward_gpu.py and tests/test_for
 * the runner: `run_forward` (the stash inside a sentinel-filled arena), `decode`, `unwritten`, `mismatches`;
 * Part B: `layer_table`, `check_layers` (three-product prediction from the DECODED operands, hard bound, mask, split and
   discrimination rules) and `emulate_forward`, an fp32 CPU stand-in for the kernel that writes real stash bytes;
-* Part C: `composite_ref`, float64 compositing of the pass's own field outputs with the bounds the issue derives.
+* Part C: `composite_ref`, float64 compositing of the pass's own field outputs with the bounds the issue derives;
+* the inference passes (tests/test_inference_gpu.py): `run_render` (NFL_MODE_RENDER) and `run_embed` (NFL_MODE_EMBED) with
+  every output in a guarded NaN arena, `int_embedded` and `fp16_weight_violations` for Part A on the single-product kernels,
+  `bit_differences`, and `x1_forward` / `x1_conditions` / `x1_rule`: the single-product arithmetic in float64, the
+  unrounded network, and the rule that holds the kernel between them.
 
 The stash formats come from tests/stash_codec.py, float64 compositing from tests/compbwd_ref.py.
 """
@@ -266,6 +271,41 @@ def exactness_violations(P, inp, ref, pre, widths, lat, use_t, N):
     return bad
 
 
+def fp16_weight_violations(P, fold=None):
+    """One more condition, for the single-product kernels (nfl_render_x1.hip): they read the hi image of every weight and
+    nothing else, so 'equal in every arithmetic' needs every weight to BE one fp16 -- the two folded matrices included:
+    `fold` = name -> (weight, bias) as read back from the field, or None for the fp32 fold of `P`.  The biases go to the
+    kernel as fp32.  A list of complaints."""
+    F = dict(fold_fp32(P))
+    for name, (w, b) in (fold or {}).items():
+        F[name + ".weight"] = w.detach().float().cpu()
+    bad = []
+    for name, w in F.items():
+        if name.endswith(".weight") and name != "xyz_encoding_final.weight":
+            w = w.detach().float().cpu()
+            off = w.half().float() != w
+            if bool(off.any()):
+                r, c = off.nonzero()[0].tolist()
+                bad.append(f"{name}: {int(off.sum())} weights are not one fp16, first [{r}, {c}] = {w[r, c].item()!r}")
+    return bad
+
+
+def int_embedded(inp, widths, lat, use_t, N):
+    """The encoded (R N, C) matrix NeRF.forward takes, of a Part A case: with BARF weights 0 only the raw coordinates of both
+    encodings are non-zero, so a row is [xyz, 0 ..., view, 0 ..., a, t] (a with an appearance field, t with the transient
+    head on), in (ray, sample) order.  float64."""
+    nx, nd, na, nt = widths
+    n = inp["xyz"].shape[0]
+    rep = lambda v: v.double().repeat_interleave(N, 0)
+    zeros = lambda c: torch.zeros(n, c, dtype=torch.float64)
+    cols = [inp["xyz"].double(), zeros(6 * nx), rep(inp["view"]), zeros(6 * nd)]
+    if lat:
+        cols.append(rep(inp["a"]))
+    if use_t:
+        cols.append(rep(inp["t"]))
+    return torch.cat(cols, 1)
+
+
 def head_activation(pre):
     """float64 field_raw of (n, 9) head pre-activations: softplus on sigma, sigma_t and beta, sigmoid on the colours."""
     out = torch.sigmoid(pre)
@@ -298,10 +338,24 @@ def run_forward(f, rays, z, N, *, split, a_emb=None, t_emb=None, view_dir=None, 
     out = dict(weights=new(R, N), opacity=new(R), rgb=new(R, 3), depth=new(R), field_raw=new(R * N, 9))
     if use_t:
         out.update(transient_sigmas=new(R, N), beta=new(R), rgb_static=new(R, 3), rgb_transient=new(R, 3))
+    stash = arena[GUARD:GUARD + nb]
+    a = _pass_args(out, rays, z, N, a_emb, t_emb, view_dir, pe_w, noise, noise_std, white_back)
+    a.d_act_stash = rnd._ptr(stash)
+    a.stash_split = int(bool(split))
+    _launch_pass(f, a)
+    g = arena.view(torch.int16)
+    out["guards_ok"] = bool((g[:GUARD // 2] == SENT16).all()) and bool((g[(GUARD + nb) // 2:] == SENT16).all())
+    out["stash"] = stash
+    return out
+
+
+def _pass_args(out, rays, z, N, a_emb, t_emb, view_dir, pe_w, noise, noise_std, white_back):
+    """PassArgs of one pass over given rays and depths, as rendering._run_pass builds them; d_act_stash is left null."""
+    from nerf_fl_amd import _lib, rendering as rnd
     p = rnd._ptr
     a = _lib.PassArgs()
     a.d_rays, a.d_view_dir = p(rays), p(view_dir)
-    a.n_rays, a.n_samples = R, N
+    a.n_rays, a.n_samples = rays.shape[0], N
     a.d_z = p(z)
     a.d_noise, a.noise_std = p(noise), float(noise_std)
     a.d_a_emb, a.d_t_emb = p(a_emb), p(t_emb)
@@ -310,18 +364,98 @@ def run_forward(f, rays, z, N, *, split, a_emb=None, t_emb=None, view_dir=None, 
     a.d_transient_sigmas, a.d_beta = p(out.get("transient_sigmas")), p(out.get("beta"))
     a.d_rgb_static, a.d_rgb_transient = p(out.get("rgb_static")), p(out.get("rgb_transient"))
     a.d_field_raw = p(out["field_raw"])
-    stash = arena[GUARD:GUARD + nb]
-    a.d_act_stash = p(stash)
-    a.stash_split = int(bool(split))
     if pe_w is not None:
         a.d_pe_w_xyz, a.d_pe_w_dir = p(pe_w[0]), p(pe_w[1])
-    a.d_status = p(rnd._status_word(dev))
-    _lib.check(L.nfl_render_pass(f.h_plan, p(f.d_plan), p(f.packed), C.byref(a), rnd._stream()), "nfl_render_pass")
+    a.d_status = p(rnd._status_word(rays.device))
+    return a
+
+
+def _launch_pass(f, a):
+    from nerf_fl_amd import _lib, rendering as rnd
+    p = rnd._ptr
+    _lib.check(_lib.lib().nfl_render_pass(f.h_plan, p(f.d_plan), p(f.packed), C.byref(a), rnd._stream()), "nfl_render_pass")
     torch.cuda.synchronize()
-    g = arena.view(torch.int16)
-    out["guards_ok"] = bool((g[:GUARD // 2] == SENT16).all()) and bool((g[(GUARD + nb) // 2:] == SENT16).all())
-    out["stash"] = stash
+
+
+SENTF = 0x7FC5A7E5            # an fp32 NaN with a payload: what the arenas of the inference runners are filled with
+
+
+class Arena:
+    """An fp32 output buffer of `shape` inside an allocation filled with SENTF, GUARD bytes of it on either side."""
+
+    def __init__(self, shape, dev):
+        n = 1
+        for s in shape:
+            n *= s
+        self.n = n
+        self.all = torch.full((2 * (GUARD // 4) + n,), SENTF, dtype=torch.int32, device=dev)
+        self.t = self.all[GUARD // 4:GUARD // 4 + n].view(torch.float32).view(*shape)
+
+    def guards_ok(self):
+        return bool((self.all[:GUARD // 4] == SENTF).all()) and bool((self.all[GUARD // 4 + self.n:] == SENTF).all())
+
+
+def _finish(out, arenas):
+    out["guards"] = {k: v.guards_ok() for k, v in arenas.items()}
+    out["guards_ok"] = all(out["guards"].values())
+    out["nan_left"] = [k for k, v in arenas.items() if bool(torch.isnan(v.t).any())]
     return out
+
+
+def run_render(f, rays, z, N, *, a_emb=None, t_emb=None, view_dir=None, pe_w=None, noise=None, noise_std=0.0, white_back=True):
+    """One nfl_render_pass at inference: the PassArgs of run_forward with d_act_stash null, so nfl_render_mode picks
+    NFL_MODE_RENDER -- of the three-product or the single-product kernel, as `f` was planned.  Every output buffer lies in
+    an Arena of its own.  Returns the outputs (device tensors) with `guards` (name -> intact), `guards_ok` and `nan_left`
+    (the buffers that still hold a NaN)."""
+    from nerf_fl_amd import rendering as rnd
+    R, dev = rays.shape[0], rays.device
+    rnd._pack_streams([f])
+    shapes = dict(weights=(R, N), opacity=(R,), rgb=(R, 3), depth=(R,), field_raw=(R * N, 9))
+    if t_emb is not None:
+        shapes.update(transient_sigmas=(R, N), beta=(R,), rgb_static=(R, 3), rgb_transient=(R, 3))
+    arenas = {k: Arena(s, dev) for k, s in shapes.items()}
+    out = {k: v.t for k, v in arenas.items()}
+    _launch_pass(f, _pass_args(out, rays, z, N, a_emb, t_emb, view_dir, pe_w, noise, noise_std, white_back))
+    return _finish(out, arenas)
+
+
+def run_embed(f, x, stride=None, sigma_only=False, output_transient=True):
+    """nfl_field_forward (NFL_MODE_EMBED) on the encoded (B, C) matrix `x`, laid out with a row stride of `stride` floats
+    (default C + 3: rows are then not 16-byte aligned) whose extra columns hold NaN; the (B, 9) output lies in an Arena.
+    Returns dict(raw, guards, guards_ok, nan_left)."""
+    from nerf_fl_amd import _lib, rendering as rnd
+    B, width = x.shape
+    stride = width + 3 if stride is None else stride
+    assert stride >= width and B > 0
+    dev = f.packed.device
+    rnd._pack_streams([f])
+    rows = torch.full((B, stride), float("nan"), dtype=torch.float32, device=dev)
+    rows[:, :width] = x.to(device=dev, dtype=torch.float32)
+    arenas = {"raw": Arena((B, 9), dev)}
+    p = rnd._ptr
+    _lib.check(_lib.lib().nfl_field_forward(f.h_plan, p(f.d_plan), p(f.packed), p(rows), B, stride, int(bool(sigma_only)),
+                                            int(bool(output_transient)), p(arenas["raw"].t), rnd._stream()), "nfl_field_forward")
+    torch.cuda.synchronize()
+    return _finish({"raw": arenas["raw"].t}, arenas)
+
+
+def bit_differences(a, b, names):
+    """The buffers `names` of two passes' outputs that are not bit-identical (name -> where the first difference is)."""
+    out = {}
+    for k in names:
+        x, y = a[k].contiguous().view(torch.int32), b[k].contiguous().view(torch.int32)
+        if x.shape != y.shape:
+            out[k] = f"shapes {tuple(x.shape)} and {tuple(y.shape)}"
+        elif not torch.equal(x, y):
+            at = (x != y).nonzero()[0].tolist()
+            out[k] = (f"{int((x != y).sum())} of {x.numel()} values differ, first at {at}: {a[k][tuple(at)].item()!r} against "
+                      f"{b[k][tuple(at)].item()!r}")
+    return out
+
+
+def embed_columns(sigma_only, output_transient):
+    """The columns of field_raw NeRF.forward returns (rendering.field_forward)."""
+    return [3] if sigma_only else list(range(9 if output_transient else 4))
 
 
 def decode(stash, lay, n_seg, mult, use_t):
@@ -665,6 +799,23 @@ def composite_ref(field_raw, z, *, noise, noise_std, use_t, white_back, beta_min
     return out
 
 
+def composite_violations(out, ref):
+    """A pass's composited outputs against composite_ref of its own field_raw: (complaints, name -> largest error / bound)."""
+    bad, report = [], {}
+    for name, (v, b) in ref.items():
+        got = out[name].cpu().double().view_as(v)
+        ratio = (got - v).abs() / b
+        ratio = torch.where(torch.isnan(ratio), torch.full_like(ratio, float("inf")), ratio)
+        report[name] = float(ratio.max())
+        if not float(v.abs().max()) > 0:
+            bad.append(f"{name}: the reference is zero everywhere")
+        if not float(ratio.max()) <= 1.0:
+            k = (ratio == ratio.max()).nonzero()[0].tolist()
+            bad.append(f"{name}: {float(ratio.max()):.3f} of its bound at {k} (ray first; a weight's second index is its sample): "
+                       f"got {got[tuple(k)].item()!r} float64 {v[tuple(k)].item()!r}")
+    return bad, report
+
+
 def sorted_depths(R, N, seed):
     """Sorted distinct depths on a 1/64 grid in [2, 10) (tests/test_wgrad_gpu.py::exact_rays has only 256 of them)."""
     gen = torch.Generator().manual_seed(seed)
@@ -701,3 +852,73 @@ def fold_fp32(P):
             out[n + ".weight"] = torch.cat([w[:, :W] @ P["xyz_encoding_final.weight"].float(), w[:, W:]], 1)
             out[n + ".bias"] = P[n + ".bias"].float() + w[:, :W] @ P["xyz_encoding_final.bias"].float()
     return out
+
+
+# ---- the single-product kernel on real weights ---------------------------------------------------------------------------
+def encoded_inputs(inp, widths, lat, use_t, N, pe_w=None):
+    """float64 side inputs of every live sample as a pass over rays encodes them (the view direction is the ray's): pe,
+    dir_side [direction encoding, a], tau."""
+    nx, nd, na, nt = widths
+    rays, z = inp["rays"].double(), inp["z"].double()
+    xyz = (rays[:, None, 0:3] + rays[:, None, 3:6] * z[..., None]).reshape(-1, 3)
+    rep = lambda v: v.double().repeat_interleave(N, 0)
+    w = (None, None) if pe_w is None else tuple(v.double() for v in pe_w)
+    val = {"pe": orc.posenc(xyz, nx, w[0])}
+    val["dir_side"] = rep(torch.cat([orc.posenc(rays[:, 3:6], nd, w[1])] + ([inp["a"].double()] if lat else []), 1))
+    if use_t:
+        val["tau"] = rep(inp["t"])
+    return val
+
+
+def x1_forward(F, val, widths, lat, use_t, *, acc=torch.float64, rounded=True, zero_bias=None):
+    """field_raw (n, 9), float64, of the network on the encoded inputs `val`; `F`: fp32 parameters, the two folded layers
+    folded.  rounded, acc = float64: the single-product kernel's arithmetic restated -- every layer b + half(W) half(x)
+    accumulated in float64, activations fp32 between layers (`x1_64`).  rounded, acc = float32: torch's fp32 matmul in the
+    accumulator's place, a CPU stand-in for the kernel.  not rounded: the same network on unrounded operands (`truth`).
+    `zero_bias`: the output name of a layer that loses its bias (a deliberate defect)."""
+    op = (lambda v: v.float().half().to(acc)) if rounded else (lambda v: v.to(acc))
+    val = dict(val)
+    n = val["pe"].shape[0]
+    pre = torch.zeros(n, 9, dtype=torch.float64)
+    for name, head, ins, layer in layer_table(widths, lat, use_t):
+        x = torch.cat([op(val[i]) for i in ins], 1)
+        b = F[layer + ".bias"].to(acc)
+        y = (torch.zeros_like(b) if zero_bias == name else b) + x @ op(F[layer + ".weight"]).t()
+        if head:
+            pre[:, HEAD_COLS[name]] = y.double()
+        else:
+            val[name] = torch.relu(y).float() if rounded else torch.relu(y)
+    out = head_activation(pre)
+    if not use_t:
+        out[:, 4:] = 0
+    return out
+
+
+COLUMN_NAMES = ("rgb.r", "rgb.g", "rgb.b", "sigma", "rgb_t.r", "rgb_t.g", "rgb_t.b", "sigma_t", "beta")
+
+
+def x1_conditions(x1, truth, use_t):
+    """Before the launch: in every head column the gap between the kernel's arithmetic and the truth is well above fp32
+    rounding of the column, rms(x1_64 - truth) >= 8 * 2^-24 * max|truth|.  A list of complaints."""
+    bad = []
+    for c in range(9 if use_t else 4):
+        gap, floor = rms(x1[:, c] - truth[:, c]), 8 * U24 * float(truth[:, c].abs().max())
+        if not gap >= floor:
+            bad.append(f"{COLUMN_NAMES[c]}: rms(x1_64 - truth) = {gap:.3e} is below 8 * 2^-24 * max|truth| = {floor:.3e}")
+    return bad
+
+
+def x1_rule(raw, x1, truth, use_t):
+    """The kernel is nearer to its own arithmetic than that arithmetic is to the truth, per head column over the live samples:
+    rms(kernel - x1_64) <= rms(x1_64 - truth).  Returns (complaints, column name -> ratio)."""
+    raw = raw.double()
+    bad, report = [], {}
+    for c in range(9 if use_t else 4):
+        err, gap = rms(raw[:, c] - x1[:, c]), rms(x1[:, c] - truth[:, c])
+        ratio = err / gap if gap > 0 else float("inf")
+        report[COLUMN_NAMES[c]] = ratio
+        if not ratio <= 1.0:
+            bad.append(f"{COLUMN_NAMES[c]}: rms(kernel - x1_64) = {err:.3e} is {ratio:.3f} of rms(x1_64 - truth) = {gap:.3e}")
+    if not use_t and bool(raw[:, 4:].any()):
+        bad.append("field_raw is not zero in the columns of a head the pass does not have")
+    return bad, report

@@ -186,6 +186,20 @@ def test_auxiliary_entry_points_validate_arguments(L):
     assert L.nfl_pack_fields(1, job, None) == -1
 
 
+def test_sample_pdf_refuses_sizes_it_cannot_hold(L):
+    """nfl_sample_pdf needs one interior weight (S >= 3), one draw, and S + I within the 512 entries a ray has in LDS:
+    NFL_EINVAL on the host before any runtime call (dummy device pointers), with rays or without.  The sizes at the limits
+    are accepted (no ray: nothing is launched)."""
+    d = C.c_void_p(4096)
+    call = lambda R, S, I: L.nfl_sample_pdf(d, d, d, None, R, S, I, d, None, None)
+    assert call(0, 3, 1) == 0 and call(0, 258, 254) == 0 and call(0, 3, 509) == 0
+    for R in (0, 7):
+        assert call(R, 2, 64) == -1                                  # S = 2: no interior weight
+        assert call(R, 64, 0) == -1                                  # I = 0
+        assert call(R, 258, 255) == -1 and call(R, 449, 64) == -1    # S + I = 513
+    assert call(-1, 64, 64) == -1
+
+
 def test_dgrad_refuses_a_ray_gradient_it_cannot_compute(L):
     """nfl_mlp_dgrad with d_g_rays needs a stream with the ray tiles (rays_grad = 1), the rays and the depths: the kernel reads
     d_rays and d_z whenever it writes d_g_rays.  Refused with NFL_EINVAL on the host, before any runtime call (a real host

@@ -1,7 +1,9 @@
 """tests/forward_ref.py on the CPU, no kernel involved: the launch geometry, the exactness conditions of every Part A case
 of tests/test_forward_gpu.py, and the Part B / Part C comparisons fed an fp32 emulation of the forward -- which they must
 accept -- and the same emulation with one defect of the kind the GPU tests exist to catch -- which they must reject, and
-locate."""
+locate.  The same for the helpers of tests/test_inference_gpu.py: the encoded matrix of a Part A case, the condition the
+single-product kernels add, the bitwise comparison, and the single-product rule on an fp32 stand-in with and without a lost
+bias."""
 import pytest
 import torch
 
@@ -60,6 +62,105 @@ def test_exactness_conditions_notice():
     r3["g2"][:, 32:64] = 1.0
     assert any("g2: tiles [1]" in b for b in fr.exactness_violations(P, inp, r3, pre, widths, lat, True, 40))
     assert any("head" in b for b in fr.exactness_violations(P, inp, ref, pre * 3, widths, lat, True, 40))
+
+
+# ---- the inference tests' helpers (tests/test_inference_gpu.py) ---------------------------------------------------------
+@pytest.mark.parametrize("variant", list(fr.VARIANTS))
+def test_every_integer_weight_is_one_fp16(variant):
+    """The single-product kernels drop w_lo: Part A of tests/test_inference_gpu.py needs every weight, the two folded
+    matrices included, to be exactly one fp16 -- and a weight that is not is noticed, in a layer and in a fold."""
+    widths, kind = fr.VARIANTS[variant]
+    lat = kind != "coarse"
+    P = fr.int_params(widths, lat)
+    assert not fr.fp16_weight_violations(P)
+    Q = dict(P)
+    Q["xyz_encoding_3.0.weight"] = P["xyz_encoding_3.0.weight"].clone()
+    Q["xyz_encoding_3.0.weight"][5, 7] = 2049.0
+    bad = fr.fp16_weight_violations(Q)
+    assert len(bad) == 1 and bad[0].startswith("xyz_encoding_3.0.weight: 1 weights") and "[5, 7] = 2049.0" in bad[0], bad
+    # ... in a folded matrix as read back from a field, where the parameters themselves are fine
+    F = fr.fold_fp32(P)
+    w = F["dir_encoding.0.weight"].clone()
+    w[0, 0] = 2049.0
+    bad = fr.fp16_weight_violations(P, {"dir_encoding.0": (w, F["dir_encoding.0.bias"])})
+    assert len(bad) == 1 and bad[0].startswith("dir_encoding.0.weight") and "[0, 0]" in bad[0], bad
+
+
+@pytest.mark.parametrize("variant,R,N", fr.A_CASES, ids=[f"{v}-R{R}N{N}" for v, R, N in fr.A_CASES])
+def test_int_embedded_is_the_encoding_with_zero_barf_weights(variant, R, N):
+    """int_embedded against orc.posenc with zero weights on the same points and view directions, the codes behind them."""
+    widths, kind = fr.VARIANTS[variant]
+    nx, nd, na, nt = widths
+    lat, use_t = kind != "coarse", kind == "nerfw_t"
+    inp = fr.int_inputs(R, N, widths, lat)
+    x = fr.int_embedded(inp, widths, lat, use_t, N)
+    rep = lambda v: v.repeat_interleave(N, 0)
+    exp = [orc.posenc(inp["xyz"], nx, torch.zeros(nx)), rep(orc.posenc(inp["view"], nd, torch.zeros(nd)))]
+    exp += ([rep(inp["a"])] if lat else []) + ([rep(inp["t"])] if use_t else [])
+    exp = torch.cat(exp, 1)
+    assert x.shape == (R * N, 6 * nx + 3 + 6 * nd + 3 + (na if lat else 0) + (nt if use_t else 0))
+    assert x.dtype == torch.float64 and torch.equal(x, exp)
+    # what the reference run feeds its first layer and its side inputs
+    ref, _ = fr.int_reference(fr.int_params(widths, lat), inp, widths, lat, use_t, N)
+    assert torch.equal(x[:, :6 * nx + 3], ref["pe"]) and torch.equal(x[:, 6 * nx + 3:6 * nx + 3 + ref["dir_side"].shape[1]], ref["dir_side"])
+    assert torch.equal(x.float().double(), x)
+
+
+def test_bitwise_comparison_sees_a_lost_product():
+    """Part B of the inference tests holds RENDER to STASH2 bit for bit: the emulation with one product dropped in one layer
+    does not give the bits of the emulation without."""
+    R, N = 3, 40
+    _, _, _, _, raw = emulated(R, N, True, False)
+    assert not fr.bit_differences({"field_raw": raw}, {"field_raw": emulated(R, N, True, False)[4]}, ["field_raw"])
+    for drop in (("h5", "w_lo x_hi"), ("g3", "w_hi x_lo")):
+        diff = fr.bit_differences({"field_raw": raw}, {"field_raw": emulated(R, N, True, False, drop=drop)[4]}, ["field_raw"])
+        assert list(diff) == ["field_raw"] and "values differ, first at" in diff["field_raw"], diff
+
+
+# ---- the single-product references ---------------------------------------------------------------------------------------
+def x1_case(R, N, lat, barf):
+    widths, spec, P, inp = fr.real_inputs(R, N, lat)
+    F = fr.fold_fp32(P)
+    val = fr.encoded_inputs(inp, widths, lat, lat, N, fr.BARF if barf else None)
+    run = lambda **kw: fr.x1_forward(F, val, widths, lat, lat, **kw)
+    return run, run(), run(rounded=False)
+
+
+@pytest.mark.parametrize("barf", [False, True])
+@pytest.mark.parametrize("lat", [False, True], ids=["base", "nerfw"])
+@pytest.mark.parametrize("R,N", fr.B_SHAPES)
+def test_single_product_rule_on_an_fp32_stand_in(R, N, lat, barf):
+    """torch's fp32 matmul in the accumulator's place passes the rule of Part C of tests/test_inference_gpu.py, and the gap
+    that sets the bar is above its floor in every column, on the `sharp` weights.  Measured here: ratios 0.04 .. 0.45."""
+    run, x1, truth = x1_case(R, N, lat, barf)
+    assert not fr.x1_conditions(x1, truth, lat)
+    bad, report = fr.x1_rule(run(acc=torch.float32), x1, truth, lat)
+    print({k: float(f"{v:.3f}") for k, v in report.items()})
+    assert not bad, bad
+    assert len(report) == (9 if lat else 4)
+    # unrounded operands are the oracle's network, up to the fp32 rounding of the fold
+    widths, spec, P, inp = fr.real_inputs(R, N, lat)
+    val = fr.encoded_inputs(inp, widths, lat, lat, N, fr.BARF if barf else None)
+    P64 = {k: v.double() for k, v in P.items()}
+    o = orc.field_forward(spec, P64, val["pe"], val["dir_side"], val.get("tau"))
+    assert float((o["sigma"] - truth[:, 3]).abs().max()) <= 1e-5 * float(truth[:, 3].abs().max())
+    assert float((o["rgb"] - truth[:, 0:3]).abs().max()) <= 1e-5
+    if lat:
+        assert float((o["beta"] - truth[:, 8]).abs().max()) <= 1e-5 and float((o["rgb_t"] - truth[:, 4:7]).abs().max()) <= 1e-5
+
+
+@pytest.mark.parametrize("layer,cols", [("h3", ["sigma"]), ("sigma", ["sigma"]), ("dirh", ["rgb.r", "rgb.g", "rgb.b"]),
+                                        ("g2", ["rgb_t.r", "sigma_t", "beta"]), ("beta", ["beta"])])
+def test_a_lost_bias_exceeds_the_single_product_ratio(layer, cols):
+    """The stand-in with one layer's bias zeroed reads above 1 in the columns that layer feeds."""
+    run, x1, truth = x1_case(3, 40, True, False)
+    bad, report = fr.x1_rule(run(acc=torch.float32, zero_bias=layer), x1, truth, True)
+    assert bad and all(report[c] > 1.0 for c in cols), report
+    if layer in ("sigma", "beta", "g2", "dirh"):         # ... and leaves the heads it does not feed where they were
+        clean = fr.x1_rule(run(acc=torch.float32), x1, truth, True)[1]
+        fed = {"sigma": ["sigma"], "beta": ["beta"], "dirh": ["rgb.r", "rgb.g", "rgb.b"],
+               "g2": ["rgb_t.r", "rgb_t.g", "rgb_t.b", "sigma_t", "beta"]}[layer]
+        assert all(report[c] == clean[c] for c in report if c not in fed), (report, clean)
 
 
 # ---- Part B on the emulation ---------------------------------------------------------------------------------------
