@@ -6,9 +6,9 @@
 //           interpolated normal of its triangle.  The texels are what nfl_mesh_blend then takes for "vertices".
 // Resolve.  A thread per texel of the range: the blend's sums into a colour, the fallback for an unseen texel, the background
 //           for one without an owner.
-// Shade.    nfl_mesh_shade's thread per word, restated here (nfl_meshrender.hip stays byte for byte): the same search, the
-//           same recomputation of u, v and the distance through nmc_ray<false>, and the colour a bilinear lookup in the
-//           triangle's half-cell.  The cell's integer origin is added after the floor, never in floating point.
+// Shade.    nfl_mesh_shade's thread per word over the same front (nfl_meshray.h: the search, and u, v and the distance
+//           recomputed through nmc_ray<false>) and the same four outputs; the colour is a bilinear lookup in the triangle's
+//           half-cell.  The cell's integer origin is added after the floor, never in floating point.
 //
 // The rows of three floats that points and resolve write go out through LDS: a lane that stored its own row would write 4 of
 // every 12 bytes of the wave's span per instruction; staged, consecutive lanes store consecutive words.  The stride of 3 words
@@ -19,15 +19,8 @@
 #include "nfl_meshray.h"
 #include "nfl_pixel.h"
 
-#define NMR_EMPTY 0xFFFFFFFFFFFFFFFFull
 #define NA_MIN_CELL 6
 #define NA_MAX_CELL 1024
-
-// (w0 * a + u * b) + v * c: nfl_mesh_shade's expression
-NFL_DEV float na_mix(float w0, float u, float v, float a, float b, float c) { return (w0 * a + u * b) + v * c; }
-
-// (uint8)(clamp(c, 0, 1) * 255): truncation; NaN gives 0 (nfl_mesh_shade's rule)
-NFL_DEV uint8_t na_byte(float c) { return (uint8_t)((c > 0.f ? (c < 1.f ? c : 1.f) : 0.f) * 255.f); }
 
 // Texel e of an atlas `cols` cells of C texels wide: its triangle 2 k + h and its (extrapolated, never clamped) barycentrics
 NFL_DEV void na_texel(unsigned e, int C, int cols, i64& tr, float& u, float& v) {
@@ -77,7 +70,7 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_atlas_points_kernel(const nfl_
             const float *NA = a.d_vertex_normals + 3 * (i64)idx[0], *NB = a.d_vertex_normals + 3 * (i64)idx[1],
                         *NC = a.d_vertex_normals + 3 * (i64)idx[2];
 #pragma unroll
-            for (int k = 0; k < 3; ++k) p[k] = na_mix(w0, u, v, A[k], B[k], Cc[k]), m[k] = na_mix(w0, u, v, NA[k], NB[k], NC[k]);
+            for (int k = 0; k < 3; ++k) p[k] = nmc_mix(w0, u, v, A[k], B[k], Cc[k]), m[k] = nmc_mix(w0, u, v, NA[k], NB[k], NC[k]);
             const float len = sqrtf(nmc_dot(m[0], m[1], m[2], m[0], m[1], m[2]));
 #pragma unroll
             for (int k = 0; k < 3; ++k) m[k] = len > 0.f ? m[k] / len : 0.f;                     // 0 or NaN: no normal
@@ -109,12 +102,12 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_atlas_resolve_kernel(const nfl
                 const float *A = a.d_vertex_colors + 3 * (i64)idx[0], *B = a.d_vertex_colors + 3 * (i64)idx[1],
                             *Cc = a.d_vertex_colors + 3 * (i64)idx[2];
 #pragma unroll
-                for (int k = 0; k < 3; ++k) c[k] = na_mix(w0, u, v, A[k], B[k], Cc[k]);
+                for (int k = 0; k < 3; ++k) c[k] = nmc_mix(w0, u, v, A[k], B[k], Cc[k]);
             } else {
                 c[0] = a.fallback[0], c[1] = a.fallback[1], c[2] = a.fallback[2];
             }
         }
-        if (a.d_texture_u8) a.d_texture_u8[3 * n] = na_byte(c[0]), a.d_texture_u8[3 * n + 1] = na_byte(c[1]), a.d_texture_u8[3 * n + 2] = na_byte(c[2]);
+        if (a.d_texture_u8) a.d_texture_u8[3 * n] = nmc_byte(c[0]), a.d_texture_u8[3 * n + 1] = nmc_byte(c[1]), a.d_texture_u8[3 * n + 2] = nmc_byte(c[2]);
         if (a.d_seen) a.d_seen[n] = seen ? 1 : 0;
     }
     if (a.d_texture) na_store_rows(a.d_texture, row0, rows, c, stage);                  // uniform over the workgroup
@@ -136,59 +129,30 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_mesh_shade_atlas_kernel(const 
     float rgb[3] = {a.background[0], a.background[1], a.background[2]};
     float depth = __builtin_huge_valf();
     int32_t winner = -1;
-    const unsigned long long word = reinterpret_cast<const unsigned long long*>(a.d_vis)[w];
-    const i64 tr = (i64)(word & 0xFFFFFFFFull);
-    if (word != NMR_EMPTY && tr < a.n_triangles && a.count > 0) {
-        // last image of the run whose first word is <= w
-        const i64 pix_first = a.d_table[a.first].pix0;
-        int lo = a.first, hi = a.first + a.count - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (a.d_table[mid].pix0 - pix_first <= w) lo = mid; else hi = mid - 1;
-        }
-        const nfl_image_rec& im = a.d_table[lo];
-        const i64 local = w - (im.pix0 - pix_first);
-        const int32_t ia = a.d_triangles[3 * tr], ib = a.d_triangles[3 * tr + 1], ic = a.d_triangles[3 * tr + 2];
-        if (nm_in_range(ia, ib, ic, a.n_vertices) && im.width > 0 && im.height > 0 && local >= 0 && local < (i64)im.width * im.height) {
-            const int j = (int)(local / im.width), i = (int)(local - (i64)j * im.width);
-            const int32_t idx[3] = {ia, ib, ic};
-            float q[3][3];
+    NmcCovered c;
+    if (nmc_covered(a, w, c)) {
+        depth = c.d, winner = (int32_t)c.tr;
+        // the triangle's half-cell: tr < T <= 2 cols rows, so the cell lies inside the atlas
+        const int C = a.cell, cell = (int)(c.tr >> 1);
+        const int cy = cell / a.cols, cx = cell - cy * a.cols;
+        const float L = (float)(C - 5), last = (float)(C - 1);
+        float lx = 1.f + c.u * L, ly = 1.f + c.v * L;
+        if (c.tr & 1) lx = last - lx, ly = last - ly;
+        lx = fminf(fmaxf(lx, 0.f), last), ly = fminf(fmaxf(ly, 0.f), last);            // NaN -> 0: forged words stay in the cell
+        const float xf = floorf(lx), yf = floorf(ly), tx = lx - xf, ty = ly - yf, sx = 1.f - tx, sy = 1.f - ty;
+        const int xa = (int)xf, ya = (int)yf;
+        const int xb = xa + 1 < C ? xa + 1 : C - 1, yb = ya + 1 < C ? ya + 1 : C - 1;
+        const int ox = cx * C, oy = cy * C;
+        const i64 W = (i64)a.cols * C;
+        float c00[3], c10[3], c01[3], c11[3];
+        na_fetch(a, W, ox + xa, oy + ya, c00);
+        na_fetch(a, W, ox + xb, oy + ya, c10);
+        na_fetch(a, W, ox + xa, oy + yb, c01);
+        na_fetch(a, W, ox + xb, oy + yb, c11);
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float p[3] = {a.d_vertices[3 * (i64)idx[k]], a.d_vertices[3 * (i64)idx[k] + 1], a.d_vertices[3 * (i64)idx[k] + 2]};
-                nmc_to_camera(im, p, q[k]);
-            }
-            NmcTri t;
-            nmc_setup(q[0], q[1], q[2], t);
-            float d, u, v;
-            if (nmc_ray<false>(t, im, i, j, d, u, v)) {
-                depth = d, winner = (int32_t)tr;
-                // the triangle's half-cell: tr < T <= 2 cols rows, so the cell lies inside the atlas
-                const int C = a.cell, cell = (int)(tr >> 1);
-                const int cy = cell / a.cols, cx = cell - cy * a.cols;
-                const float L = (float)(C - 5), last = (float)(C - 1);
-                float lx = 1.f + u * L, ly = 1.f + v * L;
-                if (tr & 1) lx = last - lx, ly = last - ly;
-                lx = fminf(fmaxf(lx, 0.f), last), ly = fminf(fmaxf(ly, 0.f), last);    // NaN -> 0: forged words stay in the cell
-                const float xf = floorf(lx), yf = floorf(ly), tx = lx - xf, ty = ly - yf, sx = 1.f - tx, sy = 1.f - ty;
-                const int xa = (int)xf, ya = (int)yf;
-                const int xb = xa + 1 < C ? xa + 1 : C - 1, yb = ya + 1 < C ? ya + 1 : C - 1;
-                const int ox = cx * C, oy = cy * C;
-                const i64 W = (i64)a.cols * C;
-                float c00[3], c10[3], c01[3], c11[3];
-                na_fetch(a, W, ox + xa, oy + ya, c00);
-                na_fetch(a, W, ox + xb, oy + ya, c10);
-                na_fetch(a, W, ox + xa, oy + yb, c01);
-                na_fetch(a, W, ox + xb, oy + yb, c11);
-#pragma unroll
-                for (int k = 0; k < 3; ++k) rgb[k] = (c00[k] * sx + c10[k] * tx) * sy + (c01[k] * sx + c11[k] * tx) * ty;
-            }
-        }
+        for (int k = 0; k < 3; ++k) rgb[k] = nmc_bilinear(c00[k], c10[k], c01[k], c11[k], sx, tx, sy, ty);
     }
-    if (a.d_rgb) a.d_rgb[3 * w] = rgb[0], a.d_rgb[3 * w + 1] = rgb[1], a.d_rgb[3 * w + 2] = rgb[2];
-    if (a.d_rgb_u8) a.d_rgb_u8[3 * w] = na_byte(rgb[0]), a.d_rgb_u8[3 * w + 1] = na_byte(rgb[1]), a.d_rgb_u8[3 * w + 2] = na_byte(rgb[2]);
-    if (a.d_depth) a.d_depth[w] = depth;
-    if (a.d_triangle) a.d_triangle[w] = winner;
+    nmc_shade_out(a, w, rgb, depth, winner);
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
@@ -204,15 +168,9 @@ static bool na_layout_ok(int32_t C, int32_t cols, int32_t rows, i64 T, i64* texe
 
 static bool na_range_ok(i64 first, i64 n, i64 texels) { return first >= 0 && n >= 0 && first <= texels && n <= texels - first; }
 
-static bool na_mesh_ok(const float* ver, const int32_t* tri, i64 V, i64 T) {
-    if (!nm_sizes_ok(V, T)) return false;
-    if (V && (!ver || reinterpret_cast<uintptr_t>(ver) % 4)) return false;
-    return !(T && (!tri || reinterpret_cast<uintptr_t>(tri) % 4));
-}
-
 extern "C" int nfl_atlas_points(const nfl_atlas_points_args* a, void* stream) {
     i64 texels = 0;
-    if (!a || !na_mesh_ok(a->d_vertices, a->d_triangles, a->n_vertices, a->n_triangles)) return NFL_EINVAL;
+    if (!a || !nmc_mesh_ok(a->d_vertices, a->d_triangles, a->n_vertices, a->n_triangles)) return NFL_EINVAL;
     if (a->n_vertices && (!a->d_vertex_normals || reinterpret_cast<uintptr_t>(a->d_vertex_normals) % 4)) return NFL_EINVAL;
     if (!na_layout_ok(a->cell, a->cols, a->rows, a->n_triangles, &texels)) return NFL_EINVAL;
     if (!na_range_ok(a->first_texel, a->n_texels, texels)) return NFL_EINVAL;
@@ -239,14 +197,13 @@ extern "C" int nfl_atlas_resolve(const nfl_atlas_resolve_args* a, void* stream) 
 extern "C" int nfl_mesh_shade_atlas(const nfl_mesh_shade_atlas_args* a, void* stream) {
     i64 texels = 0;
     if (!a || !nmc_run_ok(a->d_table, a->n_images, a->first, a->count)) return NFL_EINVAL;
-    if (a->n_vis < 0 || a->n_vis > NMC_MAX_WORDS) return NFL_EINVAL;
-    if (!na_mesh_ok(a->d_vertices, a->d_triangles, a->n_vertices, a->n_triangles)) return NFL_EINVAL;
+    if (!nmc_words_ok(a->d_vis, a->n_vis, 8)) return NFL_EINVAL;
+    if (!nmc_mesh_ok(a->d_vertices, a->d_triangles, a->n_vertices, a->n_triangles)) return NFL_EINVAL;
     if (!na_layout_ok(a->cell, a->cols, a->rows, a->n_triangles, &texels)) return NFL_EINVAL;
     if ((a->d_atlas != nullptr) == (a->d_atlas_u8 != nullptr)) return NFL_EINVAL;      // exactly one of the two
     if (reinterpret_cast<uintptr_t>(a->d_atlas) % 4 || reinterpret_cast<uintptr_t>(a->d_rgb) % 4 ||
         reinterpret_cast<uintptr_t>(a->d_depth) % 4 || reinterpret_cast<uintptr_t>(a->d_triangle) % 4) return NFL_EINVAL;
     if (a->n_vis == 0) return NFL_OK;
-    if (!a->d_vis || reinterpret_cast<uintptr_t>(a->d_vis) % 8) return NFL_EINVAL;
     hipLaunchKernelGGL(nfl_mesh_shade_atlas_kernel, dim3(nm_grid(a->n_vis)), dim3(NM_THREADS), 0, static_cast<hipStream_t>(stream), *a);
     return ng_launched() ? NFL_OK : NFL_ELAUNCH;
 }

@@ -2,15 +2,10 @@
 // mesh per camera (fill + raster) and a blend of the bank's pixels into per-vertex accumulators.  DESIGN.md section 25.
 //
 // Fill.    A thread per depth word of the run: +inf.
-// Raster.  A thread per (triangle, image) of the run.  It transforms the three vertices once, culls (all behind the camera
-//          plane, a non-finite coordinate, an index out of range) and takes a pixel box: the projections' bounding box
-//          widened by one pixel and clamped to the frame, or the whole frame when the triangle straddles the camera plane.
-//          A box of at most NMC_SMALL_BOX pixels is walked by its own lane.  A larger one is NOT: one lane walking
-//          thousands of pixels holds its 63 neighbours for as long, so after the small boxes the wave ballots its large
-//          ones and takes them in turn, all 64 lanes striding the box (the triangle goes round by __shfl, 14 words).  One
-//          launch, no list, no second kernel.  A hit is an atomicMin on the depth word as uint32: the depths are
-//          non-negative floats, which order as their bits, and +inf is the largest.  The transform and the ray test are
-//          nfl_meshray.h's, shared with the visibility buffer of nfl_meshrender.hip, which has a walk of its own.
+// Raster.  The walk of nfl_meshray.h, shared with the visibility buffer of nfl_meshrender.hip: a thread per (triangle, image)
+//          of the run, small boxes by their own lane, larger ones by the whole wave.  A hit is an atomicMin on the depth word
+//          as uint32: the depths are non-negative floats, which order as their bits, and +inf is the largest.  The triangle
+//          number that the walk carries is not used here.
 // Blend.   A thread per vertex, the image loop inside: the records are read by every thread in the same order and stay in
 //          cache; per contributing image 4 pixels through nfl_pixel_rgb and one depth word.  The thread owns its row of the
 //          accumulators: no atomics, the same bits every time.
@@ -21,100 +16,23 @@
 #include "nfl_pixel.h"
 
 __global__ __launch_bounds__(NM_THREADS) void nfl_mesh_depth_fill_kernel(float* depth, i64 n) {
-    const i64 w = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
-    if (w < n) depth[w] = __builtin_huge_valf();
+    nmc_fill(depth, n, __builtin_huge_valf());
 }
 
-NFL_DEV void nmc_pixel(const NmcTri& t, const nfl_image_rec& im, int i, int j, float* depth, i64 base, i64 n_depth) {
-    float d;
-    if (!nmc_test(t, im, i, j, d)) return;
-    const i64 w = base + (i64)j * im.width + i;
-    if (w >= 0 && w < n_depth) atomicMin(reinterpret_cast<unsigned int*>(depth) + w, __float_as_uint(d));
-}
+struct NmcDepthSink {
+    unsigned int* depth;
+    NFL_DEV void hit(float d, int, i64 w) const { atomicMin(depth + w, __float_as_uint(d)); }
+};
 
 __global__ __launch_bounds__(NM_THREADS) void nfl_mesh_depth_raster_kernel(const nfl_mesh_depth_args a) {
-    const i64 item = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
-    const i64 T = a.n_triangles, V = a.n_vertices;
-    // every lane stays to the end: the wave's large boxes are walked by all of its lanes
-    int n = 0, x0 = 0, x1 = -1, y0 = 0, y1 = -1;
-    float q[3][3] = {};
-    if (item < T * a.count) {
-        n = (int)(item / T);
-        const i64 tr = item - (i64)n * T;
-        const int32_t ia = a.d_triangles[3 * tr], ib = a.d_triangles[3 * tr + 1], ic = a.d_triangles[3 * tr + 2];
-        const nfl_image_rec& im = a.d_table[a.first + n];
-        if (nm_in_range(ia, ib, ic, V) && im.width > 0 && im.height > 0) {
-            const int32_t idx[3] = {ia, ib, ic};
-            bool finite = true, all_front = true, any_front = false, boxed = true;
-            float bx0 = __builtin_huge_valf(), bx1 = -__builtin_huge_valf(), by0 = bx0, by1 = bx1;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float p[3] = {a.d_vertices[3 * (i64)idx[k]], a.d_vertices[3 * (i64)idx[k] + 1], a.d_vertices[3 * (i64)idx[k] + 2]};
-                nmc_to_camera(im, p, q[k]);
-                finite = finite && nmc_finite(q[k][0]) && nmc_finite(q[k][1]) && nmc_finite(q[k][2]);
-                const float s = -q[k][2];
-                if (s > 0.f) {
-                    any_front = true;
-                    const float u = im.cx + im.fx * (q[k][0] / s), v = im.cy - im.fy * (q[k][1] / s);
-                    boxed = boxed && nmc_finite(u) && nmc_finite(v);
-                    bx0 = fminf(bx0, u), bx1 = fmaxf(bx1, u), by0 = fminf(by0, v), by1 = fmaxf(by1, v);
-                } else all_front = false;
-            }
-            if (finite && any_front) {
-                const float wmax = (float)(im.width - 1), hmax = (float)(im.height - 1);
-                if (all_front && boxed) {                   // clamped as floats: a projection may lie far outside int range
-                    x0 = (int)fminf(fmaxf(floorf(bx0) - 1.f, 0.f), wmax + 1.f), x1 = (int)fmaxf(fminf(ceilf(bx1) + 1.f, wmax), -1.f);
-                    y0 = (int)fminf(fmaxf(floorf(by0) - 1.f, 0.f), hmax + 1.f), y1 = (int)fmaxf(fminf(ceilf(by1) + 1.f, hmax), -1.f);
-                } else {                                    // straddles the camera plane: no box to trust
-                    x0 = 0, x1 = im.width - 1, y0 = 0, y1 = im.height - 1;
-                }
-            }
-        }
-    }
-    const int bw = x1 - x0 + 1, bh = y1 - y0 + 1;
-    const i64 area = bw > 0 && bh > 0 ? (i64)bw * bh : 0;
-    const i64 pix_first = a.d_table[a.first].pix0;
-    if (area > 0 && area <= NMC_SMALL_BOX) {
-        const nfl_image_rec& im = a.d_table[a.first + n];
-        NmcTri t;
-        nmc_setup(q[0], q[1], q[2], t);
-        const i64 base = im.pix0 - pix_first;
-        for (int j = y0; j <= y1; ++j)
-            for (int i = x0; i <= x1; ++i) nmc_pixel(t, im, i, j, a.d_depth, base, a.n_depth);
-    }
-    unsigned long long big = __ballot(area > NMC_SMALL_BOX);
-    const int lane = threadIdx.x & 63;
-    while (big) {
-        const int src = __ffsll(big) - 1;
-        big &= big - 1;
-        float g[3][3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) g[k][c] = __shfl(q[k][c], src);
-        const int gn = __shfl(n, src), gx0 = __shfl(x0, src), gy0 = __shfl(y0, src), gw = __shfl(bw, src), gh = __shfl(bh, src);
-        const nfl_image_rec& im = a.d_table[a.first + gn];
-        NmcTri t;
-        nmc_setup(g[0], g[1], g[2], t);
-        const i64 base = im.pix0 - pix_first;
-        // pixels lane, lane + 64, ... of the box in row-major order, kept as (row, column) and advanced by
-        // (64 / gw, 64 % gw) with a carry: no division per pixel
-        const int dj = 64 / gw, di = 64 - dj * gw;
-        for (int j = lane / gw, i = lane - j * gw; j < gh; j += dj) {
-            nmc_pixel(t, im, gx0 + i, gy0 + j, a.d_depth, base, a.n_depth);
-            i += di;
-            if (i >= gw) i -= gw, ++j;
-        }
-    }
+    nmc_raster(a.d_vertices, a.d_triangles, a.n_vertices, a.n_triangles, a.d_table, a.first, a.count, a.n_depth,
+               NmcDepthSink{reinterpret_cast<unsigned int*>(a.d_depth)});
 }
 
 extern "C" int nfl_mesh_depth(const nfl_mesh_depth_args* a, void* stream) {
-    if (!a || !nm_sizes_ok(a->n_vertices, a->n_triangles)) return NFL_EINVAL;
+    if (!a || !nmc_mesh_ok(a->d_vertices, a->d_triangles, a->n_vertices, a->n_triangles)) return NFL_EINVAL;
     if (!nmc_run_ok(a->d_table, a->n_images, a->first, a->count)) return NFL_EINVAL;
-    if (a->n_depth < 0 || a->n_depth > NMC_MAX_WORDS) return NFL_EINVAL;
-    if (a->n_depth && (!a->d_depth || reinterpret_cast<uintptr_t>(a->d_depth) % 4)) return NFL_EINVAL;
-    if (a->n_vertices && (!a->d_vertices || reinterpret_cast<uintptr_t>(a->d_vertices) % 4)) return NFL_EINVAL;
-    if (a->n_triangles && (!a->d_triangles || reinterpret_cast<uintptr_t>(a->d_triangles) % 4)) return NFL_EINVAL;
+    if (!nmc_words_ok(a->d_depth, a->n_depth, 4)) return NFL_EINVAL;
     const i64 items = a->n_triangles * a->count;
     if (ng_cdiv(items, NM_THREADS) > INT32_MAX) return NFL_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -169,7 +87,7 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_mesh_blend_kernel(const nfl_me
         float off = 0.f;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            c[k] = (c00[k] * sx + c10[k] * tx) * sy + (c01[k] * sx + c11[k] * tx) * ty;
+            c[k] = nmc_bilinear(c00[k], c10[k], c01[k], c11[k], sx, tx, sy, ty);
             off = fmaxf(off, fabsf(c[k] - centre[k]));
         }
         if (a.d_center && !(off <= a.reject)) continue;                                 // 6

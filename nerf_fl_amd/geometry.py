@@ -495,13 +495,26 @@ def simplify_mesh(mesh, cell, origin=(0.0, 0.0, 0.0), placement="mean", return_m
     return (out, cluster) if return_map else out
 
 
-def _run_depth(lib, stream, ver, tri, table, n_images, first, count, depth):
-    """nfl_mesh_depth of images first .. first + count - 1 of `table` into `depth` (the run's pixels, fp32)."""
-    a = _lib.MeshDepthArgs()
+def _run_raster(name, a, fields, lib, stream, ver, tri, table, n_images, first, count, words):
+    """The raster `name` (its argument struct `a`) of images first .. first + count - 1 of `table` into `words`, one per
+    pixel of the run; `fields` names the struct's pointer to them and their number."""
     a.d_vertices, a.d_triangles, a.n_vertices, a.n_triangles = _ptr(ver), _ptr(tri), ver.shape[0], tri.shape[0]
     a.d_table, a.n_images, a.first, a.count = _ptr(table), n_images, first, count
-    a.d_depth, a.n_depth = _ptr(depth), depth.numel()
-    _lib.check(lib.nfl_mesh_depth(C.byref(a), stream), "nfl_mesh_depth")
+    setattr(a, fields[0], _ptr(words))
+    setattr(a, fields[1], words.numel())
+    _lib.check(getattr(lib, name)(C.byref(a), stream), name)
+
+
+def _run_depth(lib, stream, ver, tri, table, n_images, first, count, depth):
+    """nfl_mesh_depth of images first .. first + count - 1 of `table` into `depth` (the run's pixels, fp32)."""
+    _run_raster("nfl_mesh_depth", _lib.MeshDepthArgs(), ("d_depth", "n_depth"), lib, stream, ver, tri, table, n_images,
+                first, count, depth)
+
+
+def _run_visibility(lib, stream, ver, tri, table, n_images, first, count, vis):
+    """nfl_mesh_visibility of images first .. first + count - 1 of `table` into `vis` (the run's pixels, int64 words)."""
+    _run_raster("nfl_mesh_visibility", _lib.MeshVisibilityArgs(), ("d_vis", "n_vis"), lib, stream, ver, tri, table, n_images,
+                first, count, vis)
 
 
 def _camera_record(what, dev, c2w, K, H, W, bank, image):
@@ -536,6 +549,18 @@ def _camera_record(what, dev, c2w, K, H, W, bank, image):
     return words, 1, 0, H, W
 
 
+def _raster_one(what, run, dtype, mesh, c2w, K, H, W, bank, image):
+    """The body of mesh_depth and mesh_visibility: `run` of one camera into (H, W) words of `dtype`."""
+    ver, _, _, tri = _mesh_tensors(mesh)
+    dev = ver.device
+    lib = _lib.lib()
+    table, n_images, image, H, W = _camera_record(what, dev, c2w, K, H, W, bank, image)
+    words = torch.empty(H, W, dtype=dtype, device=dev)
+    with torch.cuda.device(dev):
+        run(lib, rendering._stream(), ver, tri, table, n_images, image, 1, words)
+    return words
+
+
 def mesh_depth(mesh, c2w=None, K=None, H=None, W=None, *, bank=None, image=None):
     """The depth map of `mesh` seen by one camera: (H, W) fp32, per pixel the distance from the camera centre to the
     nearest triangle its ray hits (the quantity rays[:, 6:8] and depth_fine are measured in when |rays_d| = 1), +inf
@@ -549,23 +574,7 @@ def mesh_depth(mesh, c2w=None, K=None, H=None, W=None, *, bank=None, image=None)
     occupancy grid's.  The bank form never synchronises with the host.  The free-camera form does not either when `c2w`
     and `K` are tensors on the mesh's device (its record is then written by device-side fills and copies); an array, a
     list or a CPU tensor is uploaded first, and that copy waits for the stream."""
-    ver, _, _, tri = _mesh_tensors(mesh)
-    dev = ver.device
-    lib = _lib.lib()
-    table, n_images, image, H, W = _camera_record("mesh_depth", dev, c2w, K, H, W, bank, image)
-    depth = torch.empty(H, W, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _run_depth(lib, rendering._stream(), ver, tri, table, n_images, image, 1, depth)
-    return depth
-
-
-def _run_visibility(lib, stream, ver, tri, table, n_images, first, count, vis):
-    """nfl_mesh_visibility of images first .. first + count - 1 of `table` into `vis` (the run's pixels, int64 words)."""
-    a = _lib.MeshVisibilityArgs()
-    a.d_vertices, a.d_triangles, a.n_vertices, a.n_triangles = _ptr(ver), _ptr(tri), ver.shape[0], tri.shape[0]
-    a.d_table, a.n_images, a.first, a.count = _ptr(table), n_images, first, count
-    a.d_vis, a.n_vis = _ptr(vis), vis.numel()
-    _lib.check(lib.nfl_mesh_visibility(C.byref(a), stream), "nfl_mesh_visibility")
+    return _raster_one("mesh_depth", _run_depth, torch.float32, mesh, c2w, K, H, W, bank, image)
 
 
 def mesh_visibility(mesh, c2w=None, K=None, H=None, W=None, *, bank=None, image=None):
@@ -574,14 +583,7 @@ def mesh_visibility(mesh, c2w=None, K=None, H=None, W=None, *, bank=None, image=
     ones, and -1 (all 64 bits set) where it hits none: `word & 0xFFFFFFFF` is the triangle, `(word >> 32)` viewed as fp32
     the value mesh_depth gives.  The camera forms, and what they synchronise, are mesh_depth's; the definition is written
     out in include/nerf_fl_amd.h, "mesh render"."""
-    ver, _, _, tri = _mesh_tensors(mesh)
-    dev = ver.device
-    lib = _lib.lib()
-    table, n_images, image, H, W = _camera_record("mesh_visibility", dev, c2w, K, H, W, bank, image)
-    vis = torch.empty(H, W, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _run_visibility(lib, rendering._stream(), ver, tri, table, n_images, image, 1, vis)
-    return vis
+    return _raster_one("mesh_visibility", _run_visibility, torch.int64, mesh, c2w, K, H, W, bank, image)
 
 
 def _atlas_of(texture, T, dev):

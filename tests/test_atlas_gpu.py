@@ -242,6 +242,43 @@ def test_forged_words_are_uncovered_or_sampled_inside_the_atlas(soup):
         assert (got["triangle"] >= 0).mean() > 0.4 and np.isfinite(got["rgb"][got["triangle"] >= 0]).all()
 
 
+def test_both_shades_give_the_same_depth_and_triangle(soup):
+    """One front for both shading passes: over ONE visibility buffer, written by the raster for two 65 x 33 images of the
+    65-triangle soup with a triangle across the frame that straddles the camera plane, and with two words forged,
+    nfl_mesh_shade and nfl_mesh_shade_atlas write the same depth bits and the same triangle index at every word."""
+    ver = np.concatenate([soup["ver"][:3 * 65], np.array([[-40, 2, -12], [40, 2, -12], [0, -3, 1.5]], dtype=F)])
+    tri = np.concatenate([soup["tri"][:65], [[195, 196, 197]]])
+    cams = [SOUP_CAM, mref.camera(65, 33, 40, 40, 32, 16)]
+    lib, n = _lib.lib(), 2 * 65 * 33
+    d_ver, d_tri = _dev(ver, F), _dev(tri, np.int32)
+    d_table = torch.from_numpy(mref.table_of(cams).view(np.uint8).reshape(-1).copy()).to(DEV)
+    vis = torch.empty(n, dtype=torch.int64, device=DEV)
+    geometry._run_visibility(lib, _stream(), d_ver, d_tri, d_table, 2, 0, 2, vis)
+    vis[5] = (0x40400000 << 32) | 66                                 # no such triangle: uncovered
+    vis[n - 7] = (0x40400000 << 32) | 3                              # a triangle the raster did not write there: covered
+    lay = aref.layout(66, 6)
+    atlas = torch.zeros(lay["height"], lay["width"], 3, dtype=torch.float32, device=DEV)
+    out = []
+    for name, s in (("nfl_mesh_shade", _lib.MeshShadeArgs()), ("nfl_mesh_shade_atlas", _lib.MeshShadeAtlasArgs())):
+        depth = torch.full((n,), S_F, dtype=torch.float32, device=DEV)
+        winner = torch.full((n,), S_I, dtype=torch.int32, device=DEV)
+        s.d_vertices, s.d_triangles, s.n_vertices, s.n_triangles = d_ver.data_ptr(), d_tri.data_ptr(), 198, 66
+        s.d_table, s.n_images, s.first, s.count = d_table.data_ptr(), 2, 0, 2
+        s.d_vis, s.n_vis, s.d_depth, s.d_triangle = vis.data_ptr(), n, depth.data_ptr(), winner.data_ptr()
+        if name == "nfl_mesh_shade":
+            s.mode = _lib.SHADE_MODES["facing"]
+        else:
+            s.d_atlas, s.cell, s.cols, s.rows = atlas.data_ptr(), lay["cell"], lay["cols"], lay["rows"]
+        _lib.check(getattr(lib, name)(C.byref(s), _stream()), name)
+        out.append((depth.view(torch.int32), winner))
+    (depth_a, winner_a), (depth_b, winner_b) = out
+    assert torch.equal(depth_a, depth_b) and torch.equal(winner_a, winner_b)
+    assert winner_a[5] == -1 and winner_a[n - 7] == 3
+    for k in (-1, 65):                                               # uncovered words, the straddling triangle, the soup
+        assert 0.1 < (winner_a == k).float().mean() < 0.8
+    assert ((winner_a >= 0) & (winner_a < 65)).sum() > 100
+
+
 def test_a_split_range_and_a_second_run_give_the_same_bits(soup):
     ver, nrm, tri = soup["ver"], soup["nrm"], _salted(soup["tri"], 257)
     lay = aref.layout(257, 7)

@@ -224,6 +224,27 @@ def test_shade_depth_is_bit_equal_to_mesh_depth():
     assert np.array_equal((got["words"] >> np.uint64(32)).astype(np.uint32)[np.isfinite(d)], d.view(np.uint32)[np.isfinite(d)])
 
 
+def test_the_two_rasters_agree_word_for_word():
+    """One walk for both rasters: on a run of two 65 x 33 images of the 65-triangle soup with a triangle across the frame
+    that straddles the camera plane (the whole frame is its box: the wave path), nfl_mesh_depth gives +inf exactly where
+    the visibility word is -1, and everywhere else the bits of the word's high half."""
+    ver, tri = mref.soup(400, 7)
+    ver = np.concatenate([ver[:3 * 65], np.array([[-40, 2, -12], [40, 2, -12], [0, -3, 1.5]], dtype=F)])
+    tri = np.concatenate([tri[:65], [[195, 196, 197]]])
+    cams = [_frame(65, 33), mref.camera(65, 33, 40, 40, 32, 16)]
+    d_table = torch.from_numpy(mref.table_of(cams).view(np.uint8).reshape(-1).copy()).to(DEV)
+    n = 2 * 65 * 33
+    vis = torch.empty(n, dtype=torch.int64, device=DEV)
+    depth = torch.empty(n, dtype=torch.float32, device=DEV)
+    geometry._run_visibility(_lib.lib(), _stream(), _dev(ver, F), _dev(tri, np.int32), d_table, 2, 0, 2, vis)
+    geometry._run_depth(_lib.lib(), _stream(), _dev(ver, F), _dev(tri, np.int32), d_table, 2, 0, 2, depth)
+    empty = vis == -1
+    assert torch.equal(depth[empty], torch.full_like(depth[empty], float("inf")))
+    assert torch.equal((vis[~empty] >> 32).to(torch.int32), depth[~empty].view(torch.int32))
+    winner = vis[~empty] & 0xFFFFFFFF
+    assert 0.1 < empty.float().mean() < 0.5 and 0.5 < (winner == 65).float().mean() < 0.9 and winner.unique().numel() > 40
+
+
 def test_null_outputs_are_skipped_and_untrusted_words_are_uncovered():
     ver, tri = mref.soup(400, 7)
     cam = _frame(65, 33)
