@@ -886,6 +886,120 @@ size_t nfl_mesh_simplify_bytes(int64_t n_vertices, int64_t n_triangles);
 int nfl_mesh_simplify_count(const nfl_mesh_simplify_args* args, void* stream);
 int nfl_mesh_simplify_emit(const nfl_mesh_simplify_args* args, void* stream);
 
+/* ---- mesh smoothing: vertex adjacency, Laplacian / Taubin steps and vertex normals from the triangles of an indexed triangle
+ * mesh (the reference has no counterpart) -------------------------------------------------------------------------------------
+ * Inputs: d_vertices (V, 3) fp32, d_triangles (T, 3) int32; V <= INT32_MAX, 3 T <= INT32_MAX.  Definitions:
+ *   IN-RANGE TRIANGLE.  Its three indices lie in [0, V).  Other triangles are counted (d_totals[2]) and take part in nothing.
+ *   INCIDENT ENTRIES of a vertex v.  The numbers e = 3 t + c of every in-range triangle t and corner c in {0, 1, 2} with
+ *     tri[t][c] == v, in ascending e; a triangle that names v twice is listed twice.  I = the number of all entries
+ *     = 3 x the in-range triangles.
+ *   CANDIDATES of v (a multiset).  For every incident entry of v the other two indices of that triangle, leaving out any
+ *     that equal v.  The NEIGHBOUR ROW of v: the distinct candidates, each once, in ascending index.  N = the total length
+ *     of all rows.
+ *   BOUNDARY FLAG.  boundary[v] = 1 when some candidate of v has multiplicity exactly 1 (an edge with a single triangle on
+ *     it), else 0.  On a closed manifold every multiplicity is 2; an edge shared by three triangles is not a boundary edge;
+ *     a vertex that no triangle names has an empty row and boundary = 0.
+ *   A SMOOTHING STEP with factor f.  Positions P are fp32; a step is Jacobi: it reads the buffer of the step before only.
+ *     FINITE(v): the three coordinates of v are finite.  pinned(v): the byte of d_pinned is non-zero, or fix_boundary is set
+ *     and boundary[v] is.  If !FINITE(v) or pinned(v): P'(v) = P(v) bit for bit.  Otherwise s = (0, 0, 0) in fp64, d = 0; for
+ *     each w of the row of v in ascending order with FINITE(w): s += (double)P(w) per component (a sequential sum), d += 1.
+ *     d == 0: P'(v) = P(v) bit for bit.  Otherwise m = s / (double)d and P'(v) = fl32(p + f * (m - p)), p = (double)P(v): the
+ *     subtraction, the product and the sum each rounded in fp64, no contraction, then ONE rounding to fp32.
+ *     A call takes a list of factors, one per step: plain Laplacian with n iterations is lambda n times, Taubin with n
+ *     iterations is lambda, mu, lambda, mu, ... over 2 n steps.
+ *   VERTEX NORMAL from the triangles.  For each incident entry 3 t + c of v in ascending order: p0, p1, p2 = the corners of t
+ *     in the triangle's own order, n_t = (p1 - p0) x (p2 - p0) in fp64 from the fp32 positions, each component the difference
+ *     of two separately rounded products (the vector of "mesh simplification"; with the winding of "surface" it points from
+ *     inside to outside).  An n_t with a non-finite component or with all components zero contributes nothing.
+ *     NFL_NORMALS_AREA adds n_t; NFL_NORMALS_UNIFORM adds n_t / |n_t|, |x| = sqrt((x_x x_x + x_y x_y) + x_z x_z).  The sum s
+ *     is sequential fp64 in entry order; the result is fl32(s / |s|).  When |s| = 0 or is not finite the result is the row of
+ *     d_fallback_normals bit for bit when that pointer is given, zeros otherwise.
+ *   nfl_mesh_adjacency_bytes(V, T)   scratch size of count and emit: per vertex two counters, a degree, two int64 offsets
+ *                    and a flag (4 + 4 + 4 + 8 + 8 + 1 B), per triangle the incident entries, the neighbour rows and a sorting
+ *                    area (12 + 24 + 24 B), and the tile sums of the scan.  0 for sizes the calls refuse.
+ *   nfl_mesh_adjacency_count   writes d_totals = {I, N, out-of-range triangles, boundary vertices} and leaves in the scratch
+ *                    what emit needs.  The counters are zeroed by a kernel; a thread per triangle checks the range and
+ *                    counts its corners (integer atomic adds); the counts are scanned (the scan of "mesh"); the rows are
+ *                    filled through per-vertex cursors in the order of arrival and then SORTED, which is what makes every
+ *                    output the same from run to run; the candidates of a vertex are sorted, made distinct and counted, and
+ *                    the degrees are scanned.  A row of up to NFL_ADJ_SHORT_ROW incident entries is sorted by one thread;
+ *                    a longer one by the whole workgroup (a bitonic sort in LDS up to 8192 words, a rank sort through LDS
+ *                    tiles beyond), in the same launch.
+ *   nfl_mesh_adjacency_emit    with the SAME arguments and scratch plus n_incident = I and n_neighbors = N: writes
+ *                    d_tri_offsets (V + 1) int64 and d_incident (I) int32, d_offsets (V + 1) int64 and d_neighbors (N) int32,
+ *                    d_boundary (V) uint8.  Nothing past I / N / V is written, and what is read from the scratch is checked
+ *                    against the sizes first.
+ *   nfl_mesh_smooth_bytes(V)   one (V, 3) fp32 buffer.  0 for sizes the call refuses.
+ *   nfl_mesh_smooth  n_steps in [0, NFL_SMOOTH_MAX_STEPS] steps with the factors[] of the host array, read when the call is
+ *                    made; a launch per step between d_scratch and d_out_vertices, so that the LAST step writes
+ *                    d_out_vertices whatever the parity; n_steps == 0 copies the input by a kernel.  d_vertices is never
+ *                    written (d_out_vertices must be another buffer).  d_boundary may be NULL without fix_boundary, d_pinned
+ *                    may be NULL.  Everything read from the CSR is bounded: an offset pair that is not
+ *                    0 <= a <= b <= n_neighbors gives an empty row, a neighbour outside [0, V) is skipped like a non-finite
+ *                    one, so a CSR that is not this mesh's gives wrong positions and never an access out of range.
+ *   nfl_mesh_normals the vertex normals above into d_out_normals (V, 3); incident entries outside [0, 3 T), triangles with
+ *                    an index outside [0, V) and offset pairs outside [0, n_incident] are skipped in the same way.
+ * No memset, no copy, no allocation, no synchronisation; integer atomics only: every output of the four calls is the same
+ * from run to run.  d_scratch: 8-byte aligned.
+ * NFL_EINVAL: args NULL, a negative size, V > INT32_MAX or 3 T > INT32_MAX, a NULL pointer the sizes need (d_triangles with
+ * T > 0; with V > 0 d_scratch, d_totals (count), the five outputs (emit; d_incident and d_neighbors with I, N > 0), d_vertices,
+ * d_offsets, d_out_vertices, d_neighbors with N > 0, d_boundary with fix_boundary, factors with n_steps > 0 (smooth),
+ * d_vertices, d_tri_offsets, d_out_normals, d_incident with I > 0 (normals)), a misaligned scratch, d_out_vertices ==
+ * d_vertices, an unknown weighting, a factor that is not finite, n_steps outside its range, n_incident outside [0, 3 T],
+ * n_neighbors outside [0, 2 n_incident] (emit; smooth and normals: a negative total).
+ * NFL_ESMALL: scratch_bytes below the query.  V == 0: NFL_OK, nothing launched, nothing written. */
+#define NFL_SMOOTH_MAX_STEPS 1024
+#define NFL_ADJ_SHORT_ROW 24
+#define NFL_NORMALS_AREA 0
+#define NFL_NORMALS_UNIFORM 1
+typedef struct nfl_mesh_adjacency_args {
+    const int32_t* d_triangles;       /* (T, 3) */
+    int64_t  n_vertices, n_triangles;
+    void*    d_scratch;
+    size_t   scratch_bytes;
+    int64_t* d_totals;                /* out (4): I, N, out-of-range triangles, boundary vertices (count) */
+    int64_t  n_incident, n_neighbors; /* emit: I and N, read back by the caller */
+    int64_t* d_tri_offsets;           /* out (V + 1) */
+    int32_t* d_incident;              /* out (I) */
+    int64_t* d_offsets;               /* out (V + 1) */
+    int32_t* d_neighbors;             /* out (N) */
+    uint8_t* d_boundary;              /* out (V) */
+} nfl_mesh_adjacency_args;
+size_t nfl_mesh_adjacency_bytes(int64_t n_vertices, int64_t n_triangles);
+int nfl_mesh_adjacency_count(const nfl_mesh_adjacency_args* args, void* stream);
+int nfl_mesh_adjacency_emit(const nfl_mesh_adjacency_args* args, void* stream);
+
+typedef struct nfl_mesh_smooth_args {
+    const float* d_vertices;          /* (V, 3) */
+    const int64_t* d_offsets;         /* (V + 1) */
+    const int32_t* d_neighbors;       /* (N) */
+    int64_t  n_vertices, n_neighbors;
+    const uint8_t* d_boundary;        /* (V) or NULL */
+    const uint8_t* d_pinned;          /* (V) or NULL */
+    int32_t  fix_boundary;            /* non-zero: boundary vertices stay */
+    int32_t  n_steps;
+    const double* factors;            /* HOST, n_steps of them */
+    void*    d_scratch;
+    size_t   scratch_bytes;
+    float*   d_out_vertices;          /* out (V, 3) */
+} nfl_mesh_smooth_args;
+size_t nfl_mesh_smooth_bytes(int64_t n_vertices);
+int nfl_mesh_smooth(const nfl_mesh_smooth_args* args, void* stream);
+
+typedef struct nfl_mesh_normals_args {
+    const float* d_vertices;          /* (V, 3) */
+    const int32_t* d_triangles;       /* (T, 3) */
+    int64_t  n_vertices, n_triangles;
+    const int64_t* d_tri_offsets;     /* (V + 1) */
+    const int32_t* d_incident;        /* (I) */
+    int64_t  n_incident;
+    int32_t  weighting;               /* NFL_NORMALS_AREA / NFL_NORMALS_UNIFORM */
+    int32_t  reserved;
+    const float* d_fallback_normals;  /* (V, 3) or NULL */
+    float*   d_out_normals;           /* out (V, 3) */
+} nfl_mesh_normals_args;
+int nfl_mesh_normals(const nfl_mesh_normals_args* args, void* stream);
+
 /* ---- occupancy: empty-space skipping at render time (a bit grid from a lattice, rays clipped to it; the reference has no
  * counterpart: it samples all of [near, far] on every ray) -------------------------------------------------------------------
  * The GRID.  A lattice (nz, ny, nx) as in "surface" has cx = nx - 1, cy = ny - 1, cz = nz - 1 cells; cell (i, j, k) spans the

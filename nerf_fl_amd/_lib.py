@@ -242,6 +242,36 @@ class MeshSimplifyArgs(C.Structure):
                 ("d_out_colors", C.c_void_p), ("d_out_triangles", C.c_void_p)]
 
 
+# nfl_mesh_adjacency_* / nfl_mesh_smooth / nfl_mesh_normals (nerf_fl_amd.geometry: smoothing) likewise: six new symbols and
+# three new structs
+SMOOTH_MAX_STEPS = 1024
+ADJ_SHORT_ROW = 24
+NORMAL_WEIGHTINGS = {"area": 0, "uniform": 1}
+
+
+class MeshAdjacencyArgs(C.Structure):
+    _fields_ = [("d_triangles", C.c_void_p), ("n_vertices", C.c_int64), ("n_triangles", C.c_int64),
+                ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_size_t), ("d_totals", C.c_void_p),
+                ("n_incident", C.c_int64), ("n_neighbors", C.c_int64), ("d_tri_offsets", C.c_void_p),
+                ("d_incident", C.c_void_p), ("d_offsets", C.c_void_p), ("d_neighbors", C.c_void_p),
+                ("d_boundary", C.c_void_p)]
+
+
+class MeshSmoothArgs(C.Structure):
+    _fields_ = [("d_vertices", C.c_void_p), ("d_offsets", C.c_void_p), ("d_neighbors", C.c_void_p),
+                ("n_vertices", C.c_int64), ("n_neighbors", C.c_int64), ("d_boundary", C.c_void_p),
+                ("d_pinned", C.c_void_p), ("fix_boundary", C.c_int32), ("n_steps", C.c_int32),
+                ("factors", C.POINTER(C.c_double)), ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_size_t),
+                ("d_out_vertices", C.c_void_p)]
+
+
+class MeshNormalsArgs(C.Structure):
+    _fields_ = [("d_vertices", C.c_void_p), ("d_triangles", C.c_void_p), ("n_vertices", C.c_int64),
+                ("n_triangles", C.c_int64), ("d_tri_offsets", C.c_void_p), ("d_incident", C.c_void_p),
+                ("n_incident", C.c_int64), ("weighting", C.c_int32), ("reserved", C.c_int32),
+                ("d_fallback_normals", C.c_void_p), ("d_out_normals", C.c_void_p)]
+
+
 # nfl_occ_* (nerf_fl_amd.geometry: occupancy grid, ray clipping) likewise: four new symbols and two new structs
 class OccBuildArgs(C.Structure):
     _fields_ = [("d_lattice", C.c_void_p), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
@@ -385,6 +415,12 @@ SYMBOLS = [
     ("nfl_mesh_simplify_bytes", C.c_size_t, [C.c_int64, C.c_int64]),
     ("nfl_mesh_simplify_count", C.c_int, [C.POINTER(MeshSimplifyArgs), C.c_void_p]),
     ("nfl_mesh_simplify_emit", C.c_int, [C.POINTER(MeshSimplifyArgs), C.c_void_p]),
+    ("nfl_mesh_adjacency_bytes", C.c_size_t, [C.c_int64, C.c_int64]),
+    ("nfl_mesh_adjacency_count", C.c_int, [C.POINTER(MeshAdjacencyArgs), C.c_void_p]),
+    ("nfl_mesh_adjacency_emit", C.c_int, [C.POINTER(MeshAdjacencyArgs), C.c_void_p]),
+    ("nfl_mesh_smooth_bytes", C.c_size_t, [C.c_int64]),
+    ("nfl_mesh_smooth", C.c_int, [C.POINTER(MeshSmoothArgs), C.c_void_p]),
+    ("nfl_mesh_normals", C.c_int, [C.POINTER(MeshNormalsArgs), C.c_void_p]),
     ("nfl_occ_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     ("nfl_occ_build_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     ("nfl_occ_build", C.c_int, [C.POINTER(OccBuildArgs), C.c_void_p]),

@@ -1,4 +1,4 @@
-// nfl_geom.h -- what the geometry translation units (nfl_surface, nfl_mesh, nfl_occupancy, nfl_simplify, nfl_mesh_scan)
+// nfl_geom.h -- what the geometry translation units (nfl_surface, nfl_mesh, nfl_occupancy, nfl_simplify, nfl_meshsmooth, nfl_mesh_scan)
 // share on the device side: launch sizes, the workgroup prefix sum, the library's tiled scan and the small pieces of the
 // mesh kernels.  The scratch layouts and the size checks are host arithmetic and live in nfl_geom_layout.h.
 #pragma once

@@ -1,4 +1,4 @@
-// nfl_geom_layout.h -- the scratch of the geometry entry points (surface, mesh, occupancy, simplify): every layout is
+// nfl_geom_layout.h -- the scratch of the geometry entry points (surface, mesh, occupancy, simplify, smoothing): every layout is
 // written ONCE, as an ordered list of regions, and one routine walks it.  Without a base the walk gives the size (what
 // the nfl_*_bytes functions return); with the caller's buffer it gives the pointers (what the entry points launch on),
 // so the two cannot disagree.  Plain C++ with no HIP in it: tests/geom_layout_sweep.cpp builds it with g++ under the
@@ -139,4 +139,28 @@ static inline NgLayout<NC_REGIONS> nc_layout(i64 V, i64 T) {
              {4, v},                                        // int32 members of cluster c -- emit; the first V' are used
              {72, v},                                       // int64 x 9 position, normal, colour sums
              {72, v}}, {}};                                 // double x 9 A (xx xy xz yy yz zz), b
+}
+
+// ---- mesh smoothing: nfl_mesh_adjacency_count / nfl_mesh_adjacency_emit
+enum { NA_CNT, NA_CUR, NA_DEG, NA_TOFF, NA_OFF, NA_INC, NA_CAND, NA_TMP, NA_FLAG, NA_SUMS, NA_REGIONS };
+static inline NgLayout<NA_REGIONS> na_layout(i64 V, i64 T) {
+    const size_t v = (size_t)V, t = (size_t)T;
+    return {{{4, v},                                        // int32 incident entries of v
+             {4, v},                                        // int32 cursor of v while its row is filled
+             {4, v},                                        // int32 length of the neighbour row of v
+             {8, v},                                        // int64 incident entries before v
+             {8, v},                                        // int64 neighbours before v
+             {4, 3 * t},                                    // int32 incident entries 3 t + c, the row of v at its offset
+             {4, 6 * t},                                    // int32 neighbour rows, the row of v at twice its incident offset
+             {4, 6 * t},                                    // int32 where a long row is sorted from
+             {1, v},                                        // uint8 boundary flag
+             {1, nm_scan_bytes(V)}}, {}};                   // tile sums of the two scans, one after the other
+}
+// the bounds of the totals emit takes: I <= 3 T, N <= 2 I
+static inline bool na_totals_ok(i64 T, i64 I, i64 N) { return I >= 0 && N >= 0 && I <= 3 * T && N <= 2 * I; }
+
+// ---- mesh smoothing: nfl_mesh_smooth
+enum { NA_S_PING, NA_S_REGIONS };
+static inline NgLayout<NA_S_REGIONS> na_smooth_layout(i64 V) {
+    return {{{12, (size_t)V}}, {}};                         // fp32 x 3 the positions of every other step
 }

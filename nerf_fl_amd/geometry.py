@@ -8,6 +8,9 @@
     filter_mesh       the mesh of the components a keep flag names: vertices, normals, colours, re-indexed triangles
     clean_mesh        keep by size, rank or bounding box (the floaters of an in-the-wild field go here)
     simplify_mesh     the same surface with fewer triangles: uniform vertex clustering on the device (csrc/nfl_simplify.hip)
+    mesh_adjacency    the neighbours and the incident triangle corners of every vertex, sorted, and the boundary flags (csrc/nfl_meshsmooth.hip)
+    smooth_mesh       Laplacian / Taubin smoothing over that adjacency, normals recomputed from the triangles
+    vertex_normals    vertex normals from the triangles alone, area- or uniformly weighted
     extract_mesh      all of it in a row
     occupancy_grid    one bit per cell of a lattice: occupied where a corner reaches a threshold, dilated (csrc/nfl_occupancy.hip)
     clip_rays         rays walked through such a grid: a tightened [near, far] per ray and a flag for rays that hit nothing
@@ -35,7 +38,8 @@ import torch
 from . import _lib, rendering
 
 __all__ = ["density_lattice", "extract_surface", "surface_colors", "write_ply", "extract_mesh", "lattice_points",
-           "mesh_components", "filter_mesh", "clean_mesh", "simplify_mesh", "OccupancyGrid", "occupancy_grid", "clip_rays",
+           "mesh_components", "filter_mesh", "clean_mesh", "simplify_mesh", "mesh_adjacency", "smooth_mesh",
+           "vertex_normals", "OccupancyGrid", "occupancy_grid", "clip_rays",
            "mesh_depth", "color_mesh_from_images", "mesh_visibility", "render_mesh", "atlas_layout", "atlas_uv",
            "bake_texture", "write_obj"]
 
@@ -493,6 +497,162 @@ def simplify_mesh(mesh, cell, origin=(0.0, 0.0, 0.0), placement="mean", return_m
             a.d_out_colors, a.d_out_triangles = _ptr(out.get("colors")), _ptr(out["triangles"])
             _lib.check(lib.nfl_mesh_simplify_emit(C.byref(a), stream), "nfl_mesh_simplify_emit")
     return (out, cluster) if return_map else out
+
+
+def mesh_adjacency(mesh):
+    """The vertex adjacency of `mesh` as two sorted CSR structures (include/nerf_fl_amd.h, "mesh smoothing"), a dict:
+
+        tri_offsets (V + 1,) int64, incident (I,) int32    the entries 3 t + c of the triangle corners that name vertex v,
+                                                           ascending, at incident[tri_offsets[v]:tri_offsets[v + 1]];
+        offsets (V + 1,) int64, neighbors (N,) int32       the distinct vertices that share a triangle with v, ascending;
+        boundary (V,) bool, n_boundary                     v lies on an edge that has a single triangle on it.
+
+    Integer work, and every row is sorted: two calls give the same bits.  ValueError when a triangle has an index outside
+    [0, V).
+
+    ONE host synchronisation: the four totals are read from the device to size the outputs and to raise."""
+    ver, _, _, tri = _mesh_tensors(mesh)
+    dev, V, T = ver.device, ver.shape[0], tri.shape[0]
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        a = _lib.MeshAdjacencyArgs()
+        if V:
+            stream = rendering._stream()
+            scratch = _scratch(lib.nfl_mesh_adjacency_bytes(V, T), dev)
+            totals = torch.empty(4, dtype=torch.int64, device=dev)
+            a.d_triangles, a.n_vertices, a.n_triangles = _ptr(tri), V, T
+            a.d_scratch, a.scratch_bytes, a.d_totals = _ptr(scratch), scratch.numel() * 8, _ptr(totals)
+            _lib.check(lib.nfl_mesh_adjacency_count(C.byref(a), stream), "nfl_mesh_adjacency_count")
+            I, N, outside, n_boundary = (int(v) for v in totals.tolist())  # the host synchronisation
+        else:
+            I, N, outside, n_boundary = 0, 0, T, 0
+        if outside:
+            raise ValueError(f"mesh: {outside} of {T} triangles have an index outside [0, {V})")
+        new = lambda n, dtype: torch.empty(n, dtype=dtype, device=dev)
+        out = {"offsets": new(V + 1, torch.int64), "neighbors": new(N, torch.int32), "boundary": new(V, torch.bool),
+               "tri_offsets": new(V + 1, torch.int64), "incident": new(I, torch.int32), "n_boundary": n_boundary}
+        if V:
+            a.n_incident, a.n_neighbors = I, N
+            a.d_tri_offsets, a.d_incident = _ptr(out["tri_offsets"]), _ptr(out["incident"])
+            a.d_offsets, a.d_neighbors, a.d_boundary = _ptr(out["offsets"]), _ptr(out["neighbors"]), _ptr(out["boundary"])
+            _lib.check(lib.nfl_mesh_adjacency_emit(C.byref(a), stream), "nfl_mesh_adjacency_emit")
+        else:
+            out["offsets"].zero_()
+            out["tri_offsets"].zero_()
+    return out
+
+
+def _adjacency_of(adjacency, mesh, V, dev):
+    """`adjacency` (what mesh_adjacency returned) checked against V vertices on `dev`; built from `mesh` when None."""
+    if adjacency is None:
+        return mesh_adjacency(mesh)
+    try:
+        rows = [adjacency[k] for k in ("offsets", "neighbors", "boundary", "tri_offsets", "incident")]
+    except (TypeError, KeyError):
+        raise ValueError("adjacency: the dict mesh_adjacency returns") from None
+    _on_device(*rows)
+    off, nbr, bnd, toff, inc = rows
+    if not (_is(off, torch.int64, 1, (V + 1,), dev) and _is(toff, torch.int64, 1, (V + 1,), dev)
+            and _is(bnd, torch.bool, 1, (V,), dev) and _is(nbr, torch.int32, 1, device=dev)
+            and _is(inc, torch.int32, 1, device=dev)):
+        raise ValueError(f"adjacency: not the adjacency of a mesh of {V} vertices on the mesh's device")
+    return adjacency
+
+
+def _smooth_arguments(iterations, lam, mu, boundary, normals):
+    """(the factors of the steps, fix_boundary, weighting name or None) of smooth_mesh, checked."""
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or not 0 <= iterations <= 512:
+        raise ValueError(f"iterations: an int in [0, 512], got {iterations!r}")
+    try:
+        lam = float(lam)
+    except (TypeError, ValueError):
+        raise ValueError("lam: a finite number with 0 < lam <= 1") from None
+    if not (np.isfinite(lam) and 0.0 < lam <= 1.0):
+        raise ValueError(f"lam: a finite number with 0 < lam <= 1, got {lam}")
+    if mu is not None:
+        try:
+            mu = float(mu)
+        except (TypeError, ValueError):
+            raise ValueError("mu: None, or a finite number < 0") from None
+        if not (np.isfinite(mu) and mu < 0.0):
+            raise ValueError(f"mu: None, or a finite number < 0, got {mu}")
+    if boundary not in ("fixed", "free"):
+        raise ValueError(f"boundary: 'fixed' or 'free', got {boundary!r}")
+    if normals is not None and normals not in _lib.NORMAL_WEIGHTINGS:
+        raise ValueError(f"normals: None or one of {sorted(_lib.NORMAL_WEIGHTINGS)}, got {normals!r}")
+    factors = [lam] * int(iterations) if mu is None else [lam, mu] * int(iterations)
+    return factors, boundary == "fixed", normals
+
+
+def vertex_normals(mesh, weighting="area", adjacency=None, fallback=None):
+    """(V, 3) fp32 vertex normals of `mesh` from its triangles (its own `normals` are not read): the normalised sum, over
+    the triangle corners that name the vertex, of the triangle vector (p1 - p0) x (p2 - p0) (`weighting` "area": larger
+    triangles count for more) or of that vector normalised ("uniform").  With the winding of extract_surface they point
+    outwards.  A vertex whose sum is zero or not finite (no triangle, degenerate ones only) gets its row of `fallback`
+    ((V, 3) fp32) bit for bit, or zeros.  The sums are fp64 in a fixed order: two calls give the same bits.
+    `adjacency` is what mesh_adjacency(mesh) returned; without it that call is made here (its synchronisation too)."""
+    if weighting not in _lib.NORMAL_WEIGHTINGS:
+        raise ValueError(f"weighting: one of {sorted(_lib.NORMAL_WEIGHTINGS)}, got {weighting!r}")
+    ver, _, _, tri = _mesh_tensors(mesh)
+    dev, V, T = ver.device, ver.shape[0], tri.shape[0]
+    if fallback is not None:
+        _on_device(fallback)
+        if not _is(fallback, torch.float32, 2, (V, 3), dev):
+            raise ValueError(f"fallback: expected a contiguous fp32 ({V}, 3) tensor on the mesh's device")
+    adj = _adjacency_of(adjacency, mesh, V, dev)
+    out = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    if V:
+        a = _lib.MeshNormalsArgs()
+        a.d_vertices, a.d_triangles, a.n_vertices, a.n_triangles = _ptr(ver), _ptr(tri), V, T
+        a.d_tri_offsets, a.d_incident, a.n_incident = _ptr(adj["tri_offsets"]), _ptr(adj["incident"]), adj["incident"].shape[0]
+        a.weighting, a.d_fallback_normals, a.d_out_normals = _lib.NORMAL_WEIGHTINGS[weighting], _ptr(fallback), _ptr(out)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().nfl_mesh_normals(C.byref(a), rendering._stream()), "nfl_mesh_normals")
+    return out
+
+
+def smooth_mesh(mesh, iterations=10, lam=0.5, mu=-0.53, boundary="fixed", pinned=None, adjacency=None, normals="area"):
+    """`mesh` smoothed over its vertex adjacency (include/nerf_fl_amd.h, "mesh smoothing"): a new dict whose `vertices`
+    are smoothed and whose `normals` are recomputed from the triangles (vertex_normals with weighting `normals`, the input
+    normals as the fallback; `normals=None` passes the input normals through); `triangles` and `colors` are the input's.
+
+    A step moves every vertex by a factor f towards the mean of its neighbours, all at once (Jacobi).  With `mu` an
+    iteration is Taubin's pair of steps, f = lam then f = mu < 0, which smooths without the shrinkage of the plain
+    Laplacian; `mu=None` is the plain Laplacian, one step of f = lam an iteration.  lam = 0.5, mu = -0.53 is the pair of
+    Taubin's paper: a convention, not a measurement made here.
+
+    boundary   "fixed": vertices on an edge with a single triangle stay where they are; "free": they move like the rest;
+    pinned     (V,) bool or uint8: vertices that stay;
+    adjacency  what mesh_adjacency(mesh) returned; without it that call is made here (its synchronisation too).
+
+    A vertex with a non-finite coordinate stays and is left out of its neighbours' means.  The sums are fp64 in the order
+    of the sorted rows: two calls give the same bits.  No host synchronisation of its own."""
+    factors, fix, weighting = _smooth_arguments(iterations, lam, mu, boundary, normals)
+    ver, nrm, col, tri = _mesh_tensors(mesh)
+    dev, V = ver.device, ver.shape[0]
+    if pinned is not None:
+        _on_device(pinned)
+        if not (_is(pinned, torch.bool, 1, (V,), dev) or _is(pinned, torch.uint8, 1, (V,), dev)):
+            raise ValueError(f"pinned: expected a contiguous bool or uint8 ({V},) tensor on the mesh's device")
+    adj = _adjacency_of(adjacency, mesh, V, dev)
+    out = {"vertices": torch.empty_like(ver), "normals": nrm, "triangles": tri}
+    if col is not None:
+        out["colors"] = col
+    if V:
+        lib = _lib.lib()
+        scratch = _scratch(lib.nfl_mesh_smooth_bytes(V), dev)
+        host = (C.c_double * max(len(factors), 1))(*factors)
+        a = _lib.MeshSmoothArgs()
+        a.d_vertices, a.d_offsets, a.d_neighbors = _ptr(ver), _ptr(adj["offsets"]), _ptr(adj["neighbors"])
+        a.n_vertices, a.n_neighbors = V, adj["neighbors"].shape[0]
+        a.d_boundary, a.d_pinned, a.fix_boundary = _ptr(adj["boundary"]), _ptr(pinned), int(fix)
+        a.n_steps, a.factors = len(factors), host
+        a.d_scratch, a.scratch_bytes, a.d_out_vertices = _ptr(scratch), scratch.numel() * 8, _ptr(out["vertices"])
+        with torch.cuda.device(dev):
+            _lib.check(lib.nfl_mesh_smooth(C.byref(a), rendering._stream()), "nfl_mesh_smooth")
+    if weighting is not None:
+        out["normals"] = vertex_normals(out, weighting=weighting, adjacency=adj, fallback=nrm)
+    return out
 
 
 def _run_raster(name, a, fields, lib, stream, ver, tri, table, n_images, first, count, words):
@@ -1003,7 +1163,7 @@ def write_obj(path, mesh, atlas):
 
 def extract_mesh(models, embeddings, lo, hi, res, iso, chunk=1 << 20, a_embedded=None, path=None, largest=None,
                  min_triangles=None, simplify=None, placement="mean", color_from=None, depth_tol=None, color_kwargs=None,
-                 texture=None):
+                 texture=None, smooth=None, smooth_kwargs=None):
     """density_lattice -> extract_surface -> surface_colors (-> write_ply when `path` is given) for the fine model of
     `models` (the coarse one when there is no fine one).  Returns the mesh dict with `colors` (V, 3) added.
 
@@ -1020,6 +1180,10 @@ def extract_mesh(models, embeddings, lo, hi, res, iso, chunk=1 << 20, a_embedded
     With `simplify` = a cell size the cleaned mesh goes through simplify_mesh (origin = `lo`, `placement` as there), also
     before the colour pass: the field is evaluated at the simplified vertices only, seen along their new normals.
 
+    With `smooth` = a number of iterations the cleaned mesh goes through smooth_mesh (`smooth_kwargs`: its lam, mu,
+    boundary and normals) BEFORE it is simplified and coloured, so that the quadric placement and the colour pass see the
+    smoothed surface and its recomputed normals.
+
     With `texture` = a cell size (and `color_from`) a texture atlas is baked from the same bank after the vertex colours
     exist (bake_texture with the `color_kwargs` that apply to it; the vertex colours are its fallback); the mesh gets
     `atlas`, and `path` is then written as an OBJ set (write_obj) instead of a PLY."""
@@ -1029,10 +1193,18 @@ def extract_mesh(models, embeddings, lo, hi, res, iso, chunk=1 << 20, a_embedded
         atlas_layout(0, texture)                                          # refused before anything is evaluated
     if simplify is not None:
         _simplify_arguments(simplify, lo, placement)                      # refused before anything is evaluated
+    if smooth is not None:                                                # refused before anything is evaluated
+        smooth_kwargs = dict(smooth_kwargs or {})
+        if set(smooth_kwargs) - {"lam", "mu", "boundary", "normals"}:
+            raise ValueError(f"smooth_kwargs: lam, mu, boundary and normals, got {sorted(smooth_kwargs)}")
+        _smooth_arguments(smooth, *(smooth_kwargs.get(k, d) for k, d in (("lam", 0.5), ("mu", -0.53), ("boundary", "fixed"),
+                                                                         ("normals", "area"))))
     model = models["fine"] if "fine" in models else models["coarse"]
     lattice = density_lattice(model, embeddings, lo, hi, res, chunk=chunk)
     mesh = extract_surface(lattice, iso, lo, hi)
     mesh = clean_mesh(mesh, largest=largest, min_triangles=min_triangles)
+    if smooth is not None:
+        mesh = smooth_mesh(mesh, smooth, **smooth_kwargs)
     if simplify is not None:
         mesh = simplify_mesh(mesh, simplify, origin=lo, placement=placement)
     if mesh["vertices"].shape[0] == 0 and not (largest is None and min_triangles is None and simplify is None):
