@@ -141,7 +141,7 @@ def ball_lattice(cells, radius, half):
 
 
 def spacing_of(lo, hi, shape):
-    """fp32 spacing of a (nz, ny, nx) lattice over [lo, hi], as geometry._box computes it (in double, rounded once)."""
+    """fp32 spacing of a (nz, ny, nx) lattice over [lo, hi], as geometry.lattice._box computes it (in double, rounded once)."""
     nz, ny, nx = shape
     return np.array([F((h - l) / (n - 1)) for l, h, n in zip(lo, hi, (nx, ny, nz))], dtype=F)
 

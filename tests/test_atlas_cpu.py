@@ -509,4 +509,4 @@ def test_extract_mesh_and_bake_texture_refuse_bad_arguments():
         geometry.render_mesh(cpu, bank=None, image=0, texture={"texture": cpu["vertices"], "cell": 6, "cols": 1})
     for bad in (dict(), dict(cell=6, cols=1), dict(texture=None, texture_u8=None, cell=6, cols=1), 7):
         with pytest.raises(ValueError, match="texture"):
-            geometry._atlas_of(bad, 4, torch.device("cpu"))
+            geometry.images._atlas_of(bad, 4, torch.device("cpu"))

@@ -19,51 +19,17 @@ import torch
 import atlas_ref as aref
 import meshcolor_ref as mref
 import meshrender_ref as rref
+from geom_gpu_util import (dev as _dev, F, field_bits as _bits, framed as _framed, PAD, ptr as _ptr,
+                           same_fields as _same, stream as _stream, unframe as _unframe)
 from gpu_util import DEV
 from nerf_fl_amd import _lib, eval as nfl_eval, geometry, metrics
 from nerf_fl_amd.data import ImageBank
 
 pytestmark = pytest.mark.gpu
 
-F = np.float32
-PAD = 64
 S_WORD, S_F, S_I, S_B = 0x0123456789ABCDEF, -7.0, -7, 0xAB
 BG = (0.25, 0.5, 0.75)
 KEYS = ("rgb", "rgb_u8", "depth", "triangle")
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _dev(a, dtype):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(DEV)
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None and t.numel() else None
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def _same(got, exp, what):
-    for k in exp:
-        if k in got:
-            bad = _bits(got[k]) != _bits(exp[k])
-            assert not bad.any(), (what, k, int(bad.sum()), "differ", got[k][bad][:4], exp[k][bad][:4])
-
-
-def _framed(n, tail, fill, dtype):
-    return torch.full((n + 2 * PAD,) + tail, fill, dtype=dtype, device=DEV)
-
-
-def _unframe(buf, n, sentinel, what):
-    h = buf.cpu().numpy()
-    assert (h[:PAD] == sentinel).all() and (h[PAD + n:] == sentinel).all(), what
-    return h[PAD:PAD + n]
 
 
 def _abi_points(ver, nrm, tri, lay, first=0, count=None):
@@ -253,7 +219,7 @@ def test_both_shades_give_the_same_depth_and_triangle(soup):
     d_ver, d_tri = _dev(ver, F), _dev(tri, np.int32)
     d_table = torch.from_numpy(mref.table_of(cams).view(np.uint8).reshape(-1).copy()).to(DEV)
     vis = torch.empty(n, dtype=torch.int64, device=DEV)
-    geometry._run_visibility(lib, _stream(), d_ver, d_tri, d_table, 2, 0, 2, vis)
+    geometry.images._run_visibility(d_ver, d_tri, d_table, 2, 0, 2, vis)
     vis[5] = (0x40400000 << 32) | 66                                 # no such triangle: uncovered
     vis[n - 7] = (0x40400000 << 32) | 3                              # a triangle the raster did not write there: covered
     lay = aref.layout(66, 6)

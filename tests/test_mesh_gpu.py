@@ -16,6 +16,7 @@ import torch
 import geometry_ref as gr
 import mesh_ref as mr
 import nerf_fl_amd
+from geom_gpu_util import bits as _bits, same as _same, to_dev as _to_dev
 from gpu_util import DEV, make_embeddings
 from nerf_fl_amd import NeRF, _lib, geometry, rendering, synth
 
@@ -39,17 +40,7 @@ def _device_mesh(tri, pos, colors=True):
     mesh = {"vertices": pos, "normals": (pos * np.float32(0.5)), "triangles": tri}
     if colors:
         mesh["colors"] = np.abs(pos) + np.float32(1)
-    return mesh, {k: torch.from_numpy(np.ascontiguousarray(v)).to(DEV) for k, v in mesh.items()}
-
-
-def _bits(a):
-    a = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-    return a.view(np.int32) if a.dtype == np.float32 else a
-
-
-def _same(got, exp, what):
-    g, e = _bits(got), _bits(exp)
-    assert g.dtype == e.dtype and g.shape == e.shape and np.array_equal(g, e), what
+    return mesh, _to_dev(mesh)
 
 
 def _check(tri, V, what, seed=0, colors=True):
@@ -369,6 +360,70 @@ def test_three_balls_by_size_and_by_box(balls):
         exp = mr.compact(comp, np.array(kept), host)
         for k in exp:
             _same(got[k], exp[k].reshape(-1, 3), (kw, k))
+
+
+def test_sized_calls_read_the_device_once(balls, monkeypatch):
+    """The host synchronisations of the sized calls, counted: one each, as their docstrings say, two for clean_mesh, and
+    none for the empty mesh, which launches no counting half either.  Reads of device values (tolist, item, cpu) are
+    counted and let through; torch's synchronisation check raises on any other.  The entry points called are recorded from
+    the status check every launch goes through."""
+    lat, lo, hi, sp, xx, mesh = balls
+    reads, calls = [], []
+    for name in ("tolist", "item", "cpu"):
+        def counted(self, *args, _real=getattr(torch.Tensor, name), _name=name, **kwargs):
+            if not self.is_cuda:
+                return _real(self, *args, **kwargs)
+            reads.append(_name)
+            torch.cuda.set_sync_debug_mode("default")
+            try:
+                return _real(self, *args, **kwargs)
+            finally:
+                torch.cuda.set_sync_debug_mode("error")
+        monkeypatch.setattr(torch.Tensor, name, counted)
+    real_check = _lib.check
+    monkeypatch.setattr(_lib, "check", lambda code, what: (calls.append(what), real_check(code, what))[1])
+
+    def counts(fn):
+        del reads[:], calls[:]
+        torch.cuda.synchronize()
+        torch.cuda.set_sync_debug_mode("error")
+        try:
+            out = fn()
+        finally:
+            torch.cuda.set_sync_debug_mode("default")
+        return out, len(reads), list(calls)
+
+    d_lat = torch.from_numpy(lat).to(DEV)
+    comps = geometry.mesh_components(mesh)
+    keep = torch.arange(comps["n_components"], device=DEV) != 1
+    _, empty = _device_mesh(np.zeros((0, 3)), _positions(0, 0))
+    none = {"component": torch.empty(0, dtype=torch.int32, device=DEV), "n_components": 0}
+    no_keep = torch.ones(0, dtype=torch.bool, device=DEV)
+    try:
+        for what, fn, n_reads, entries in (
+                ("extract_surface", lambda: geometry.extract_surface(d_lat, 0.0, lo, hi), 1, ["nfl_surface_count", "nfl_surface_emit"]),
+                ("extract_surface, no crossing", lambda: geometry.extract_surface(d_lat, 1e9, lo, hi), 1,
+                 ["nfl_surface_count", "nfl_surface_emit"]),
+                ("mesh_components", lambda: geometry.mesh_components(mesh), 1, ["nfl_mesh_label", "nfl_mesh_stats"]),
+                ("filter_mesh", lambda: geometry.filter_mesh(mesh, keep, components=comps), 1,
+                 ["nfl_mesh_compact_count", "nfl_mesh_compact_emit"]),
+                ("simplify_mesh", lambda: geometry.simplify_mesh(mesh, 0.1), 1, ["nfl_mesh_simplify_count", "nfl_mesh_simplify_emit"]),
+                ("mesh_adjacency", lambda: geometry.mesh_adjacency(mesh), 1, ["nfl_mesh_adjacency_count", "nfl_mesh_adjacency_emit"]),
+                ("clean_mesh", lambda: geometry.clean_mesh(mesh, min_triangles=1), 2,
+                 ["nfl_mesh_label", "nfl_mesh_stats", "nfl_mesh_compact_count", "nfl_mesh_compact_emit"]),
+                # the empty mesh: nothing is read back, no counting half runs (nfl_mesh_stats of no component sizes nothing)
+                ("empty mesh_components", lambda: geometry.mesh_components(empty), 0, ["nfl_mesh_stats"]),
+                ("empty filter_mesh", lambda: geometry.filter_mesh(empty, no_keep, components=none), 0, []),
+                ("empty simplify_mesh", lambda: geometry.simplify_mesh(empty, 0.1), 0, []),
+                ("empty mesh_adjacency", lambda: geometry.mesh_adjacency(empty), 0, []),
+                ("empty clean_mesh", lambda: geometry.clean_mesh(empty, min_triangles=1), 0, ["nfl_mesh_stats"])):
+            out, got_reads, got_entries = counts(fn)
+            print(f"{what}: {got_reads} host reads, entry points {got_entries}")
+            assert (got_reads, got_entries) == (n_reads, entries), what
+    finally:
+        monkeypatch.undo()
+    assert geometry.extract_surface(d_lat, 1e9, lo, hi)["vertices"].shape == (0, 3)
+    assert geometry.mesh_adjacency(empty)["offsets"].tolist() == [0]
 
 
 def test_extract_mesh_filters_before_colouring():

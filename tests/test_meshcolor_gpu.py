@@ -16,23 +16,15 @@ import pytest
 import torch
 
 import meshcolor_ref as mref
+from geom_gpu_util import (ball_mesh as _ball_mesh, dev as _dev, EYES, F, frame as _frame, framed as _framed,
+                           intrinsics as _intrinsics, PAD, pose as _pose, stream as _stream, unframe as _unframe)
 from gpu_util import DEV
 from nerf_fl_amd import NeRF, PosEmbedding, _lib, geometry, synth
 from nerf_fl_amd.data import ImageBank
 
 pytestmark = pytest.mark.gpu
 
-F = np.float32
-PAD = 64
 SENTINEL = -7.0
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _dev(a, dtype):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(DEV)
 
 
 def _depth_abi(ver, tri, cams, first=0, count=None):
@@ -44,7 +36,7 @@ def _depth_abi(ver, tri, cams, first=0, count=None):
     d_table = torch.from_numpy(table.view(np.uint8).reshape(-1).copy()).to(DEV)
     outs = []
     for _ in range(2):
-        buf = torch.full((n + 2 * PAD,), SENTINEL, dtype=torch.float32, device=DEV)
+        buf = _framed(n, (), SENTINEL, torch.float32)
         a = _lib.MeshDepthArgs()
         a.d_vertices = d_ver.data_ptr() if d_ver.numel() else None
         a.d_triangles = d_tri.data_ptr() if d_tri.numel() else None
@@ -52,9 +44,7 @@ def _depth_abi(ver, tri, cams, first=0, count=None):
         a.d_table, a.n_images, a.first, a.count = d_table.data_ptr(), len(cams), first, count
         a.d_depth, a.n_depth = buf[PAD:].data_ptr(), n
         _lib.check(_lib.lib().nfl_mesh_depth(C.byref(a), _stream()), "nfl_mesh_depth")
-        got = buf.cpu().numpy()
-        assert (got[:PAD] == SENTINEL).all() and (got[PAD + n:] == SENTINEL).all()
-        outs.append(got[PAD:PAD + n])
+        outs.append(_unframe(buf, n, SENTINEL, "depth"))
     assert np.array_equal(outs[0].view(np.uint32), outs[1].view(np.uint32))
     return outs[0]
 
@@ -65,12 +55,6 @@ def _check_depth(ver, tri, cams, what):
     bad = got.view(np.uint32) != exp.view(np.uint32)
     assert not bad.any(), (what, int(bad.sum()), "words differ", got[bad][:4], exp[bad][:4])
     return got
-
-
-def _frame(W, H):
-    if (W, H) == (65, 33):
-        return mref.camera(**mref.SOUP_CAMERA)
-    return mref.camera(W, H, 0.6 * W + 3.0, 0.6 * W + 3.0, W / 2 - 0.25, H / 2 - 0.2)
 
 
 # ---- depth -----------------------------------------------------------------------------------------------------------------
@@ -145,21 +129,8 @@ def test_depth_of_nothing():
         assert (_depth_abi(v, t, [cam]) == np.inf).all()
 
 
-def _ball_mesh(radius=0.8, n=17):
-    c = torch.linspace(-1.0, 1.0, n, device=DEV, dtype=torch.float64)
-    lat = (radius - torch.sqrt(c[:, None, None] ** 2 + c[None, :, None] ** 2 + c[None, None, :] ** 2)).float().contiguous()
-    return geometry.extract_surface(lat, 0.0, (-1.0,) * 3, (1.0,) * 3)
-
-
 def _np_mesh(mesh):
     return tuple(mesh[k].cpu().numpy() for k in ("vertices", "normals", "triangles"))
-
-
-EYES = [(3, 0, 0), (0, 3, 0), (0, 0, 3), (-3, 0, 0), (0, -3, 0), (0, 0, -3)]
-
-
-def _pose(eye):
-    return mref.look_at(eye, up=(0.0, 0.0, 1.0) if eye[2] == 0 else (0.0, 1.0, 0.0))
 
 
 def _bank(channels, sizes=None, eyes=EYES, images=None, seed=5):
@@ -168,7 +139,7 @@ def _bank(channels, sizes=None, eyes=EYES, images=None, seed=5):
     sizes = sizes or [(48, 40) if k % 2 == 0 else (40, 48) for k in range(len(eyes))]
     if images is None:
         images = [rng.integers(0, 256, size=(h, w, channels), dtype=np.uint8) for w, h in sizes]
-    K = np.stack([np.array([[50.0, 0, w / 2 - 0.25], [0, 50.0, h / 2 - 0.5], [0, 0, 1]]) for w, h in sizes])
+    K = np.stack([_intrinsics(w, h) for w, h in sizes])
     return ImageBank(images, np.stack([_pose(e) for e in eyes]), K, 2.0, 6.0, device=DEV), images
 
 
@@ -251,7 +222,7 @@ def _blend_abi(b, V, runs, ball):
     for k, (first, count) in enumerate(runs):
         n = int(sum(c["width"] * c["height"] for c in b["cams"][first:first + count]))
         depth = torch.empty(n, dtype=torch.float32, device=DEV)
-        geometry._run_depth(lib, _stream(), ball["vertices"], ball["triangles"], bank.table, bank.n_images, first, count, depth)
+        geometry.images._run_depth(ball["vertices"], ball["triangles"], bank.table, bank.n_images, first, count, depth)
         a = _lib.MeshBlendArgs()
         a.d_vertices, a.d_normals, a.n_vertices, a.d_pixels = d_ver.data_ptr(), d_nrm.data_ptr(), V, bank.pixels.data_ptr()
         a.d_table, a.n_images, a.first, a.count, a.weighting = bank.table.data_ptr(), bank.n_images, first, count, 0

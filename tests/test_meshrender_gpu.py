@@ -19,34 +19,18 @@ import torch
 
 import meshcolor_ref as mref
 import meshrender_ref as rref
+from geom_gpu_util import (ball_mesh as _ball_mesh, dev as _dev, EYES, F, field_bits as _bits, frame as _frame,
+                           framed as _framed, intrinsics as _intrinsics, PAD, pose as _pose, ptr as _ptr,
+                           same_fields as _same, stream as _stream, unframe as _unframe)
 from gpu_util import DEV
 from nerf_fl_amd import _lib, eval as nfl_eval, geometry, metrics
 from nerf_fl_amd.data import ImageBank
 
 pytestmark = pytest.mark.gpu
 
-F = np.float32
-PAD = 64
 S_WORD, S_F, S_I, S_B = 0x0123456789ABCDEF, -7.0, -7, 0xAB
 BG = (0.25, 0.5, 0.75)
 KEYS = ("rgb", "rgb_u8", "depth", "triangle")
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _dev(a, dtype):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(DEV)
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None and t.numel() else None
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
 
 
 def _abi(ver, tri, cams, mode="color", attr=None, first=0, count=None, outputs=KEYS, background=BG, words=None):
@@ -63,24 +47,20 @@ def _abi(ver, tri, cams, mode="color", attr=None, first=0, count=None, outputs=K
     if words is None:
         runs = []
         for _ in range(2):
-            vis = torch.full((n + 2 * PAD,), S_WORD, dtype=torch.int64, device=DEV)
+            vis = _framed(n, (), S_WORD, torch.int64)
             a = _lib.MeshVisibilityArgs()
             a.d_vertices, a.d_triangles, a.n_vertices, a.n_triangles = _ptr(d_ver), _ptr(d_tri), d_ver.shape[0], d_tri.shape[0]
             a.d_table, a.n_images, a.first, a.count = d_table.data_ptr(), len(cams), first, count
             a.d_vis, a.n_vis = vis[PAD:].data_ptr(), n
             _lib.check(lib.nfl_mesh_visibility(C.byref(a), _stream()), "nfl_mesh_visibility")
-            w = vis.cpu().numpy()
-            assert (w[:PAD] == S_WORD).all() and (w[PAD + n:] == S_WORD).all()
-            runs.append(w[PAD:PAD + n].view(np.uint64))
+            runs.append(_unframe(vis, n, S_WORD, "words").view(np.uint64))
         assert np.array_equal(runs[0], runs[1])
         got["words"] = runs[0]
     else:
-        vis = torch.full((n + 2 * PAD,), S_WORD, dtype=torch.int64, device=DEV)
+        vis = _framed(n, (), S_WORD, torch.int64)
         vis[PAD:PAD + n] = torch.from_numpy(np.asarray(words, dtype=np.uint64).view(np.int64).copy()).to(DEV)
-    bufs = {"rgb": torch.full((n + 2 * PAD, 3), S_F, dtype=torch.float32, device=DEV),
-            "rgb_u8": torch.full((n + 2 * PAD, 3), S_B, dtype=torch.uint8, device=DEV),
-            "depth": torch.full((n + 2 * PAD,), S_F, dtype=torch.float32, device=DEV),
-            "triangle": torch.full((n + 2 * PAD,), S_I, dtype=torch.int32, device=DEV)}
+    bufs = {"rgb": _framed(n, (3,), S_F, torch.float32), "rgb_u8": _framed(n, (3,), S_B, torch.uint8),
+            "depth": _framed(n, (), S_F, torch.float32), "triangle": _framed(n, (), S_I, torch.int32)}
     s = _lib.MeshShadeArgs()
     s.d_vertices, s.d_triangles, s.n_vertices, s.n_triangles = _ptr(d_ver), _ptr(d_tri), d_ver.shape[0], d_tri.shape[0]
     s.d_table, s.n_images, s.first, s.count, s.mode = d_table.data_ptr(), len(cams), first, count, _lib.SHADE_MODES[mode]
@@ -89,10 +69,9 @@ def _abi(ver, tri, cams, mode="color", attr=None, first=0, count=None, outputs=K
     s.d_rgb, s.d_rgb_u8, s.d_depth, s.d_triangle = (bufs[k][PAD:].data_ptr() if k in outputs else None for k in KEYS)
     _lib.check(lib.nfl_mesh_shade(C.byref(s), _stream()), "nfl_mesh_shade")
     for k, sentinel in zip(KEYS, (S_F, S_B, S_F, S_I)):
-        h = bufs[k].cpu().numpy()
-        assert (h[:PAD] == sentinel).all() and (h[PAD + n:] == sentinel).all(), k
+        h = _unframe(bufs[k], n, sentinel, k)
         if k in outputs:
-            got[k] = h[PAD:PAD + n]
+            got[k] = h
         else:
             assert (h == sentinel).all(), k                          # a NULL output is skipped, and nothing else lands there
     return got
@@ -104,13 +83,6 @@ def _attrs(ver, seed=11):
     return {"color": rng.uniform(-0.2, 1.2, size=(V, 3)).astype(F), "normal": rng.normal(size=(V, 3)).astype(F), "facing": None}
 
 
-def _same(got, exp, what):
-    for k in exp:
-        if k in got:
-            bad = _bits(got[k]) != _bits(exp[k])
-            assert not bad.any(), (what, k, int(bad.sum()), "differ", got[k][bad][:4], exp[k][bad][:4])
-
-
 def _check(ver, tri, cams, what, modes=rref.MODES):
     """All three modes against the restatement, bit for bit; returns the restatement of the last mode."""
     attrs = _attrs(ver)
@@ -118,12 +90,6 @@ def _check(ver, tri, cams, what, modes=rref.MODES):
         exp = rref.run_render(ver, tri, cams, mode, attrs[mode], BG)
         _same(_abi(ver, tri, cams, mode, attrs[mode]), exp, (what, mode))
     return exp
-
-
-def _frame(W, H):
-    if (W, H) == (65, 33):
-        return mref.camera(**mref.SOUP_CAMERA)
-    return mref.camera(W, H, 0.6 * W + 3.0, 0.6 * W + 3.0, W / 2 - 0.25, H / 2 - 0.2)
 
 
 # ---- the kernels against the restatement ---------------------------------------------------------------------------------
@@ -218,7 +184,7 @@ def test_shade_depth_is_bit_equal_to_mesh_depth():
     d_table = torch.from_numpy(table.view(np.uint8).reshape(-1).copy()).to(DEV)
     n = 65 * 33 + 64 * 64
     depth = torch.empty(n, dtype=torch.float32, device=DEV)
-    geometry._run_depth(_lib.lib(), _stream(), _dev(ver, F), _dev(tri[:257], np.int32), d_table, 2, 0, 2, depth)
+    geometry.images._run_depth(_dev(ver, F), _dev(tri[:257], np.int32), d_table, 2, 0, 2, depth)
     d = depth.cpu().numpy()
     assert np.array_equal(got["depth"].view(np.uint32), d.view(np.uint32))
     assert np.array_equal((got["words"] >> np.uint64(32)).astype(np.uint32)[np.isfinite(d)], d.view(np.uint32)[np.isfinite(d)])
@@ -236,8 +202,8 @@ def test_the_two_rasters_agree_word_for_word():
     n = 2 * 65 * 33
     vis = torch.empty(n, dtype=torch.int64, device=DEV)
     depth = torch.empty(n, dtype=torch.float32, device=DEV)
-    geometry._run_visibility(_lib.lib(), _stream(), _dev(ver, F), _dev(tri, np.int32), d_table, 2, 0, 2, vis)
-    geometry._run_depth(_lib.lib(), _stream(), _dev(ver, F), _dev(tri, np.int32), d_table, 2, 0, 2, depth)
+    geometry.images._run_visibility(_dev(ver, F), _dev(tri, np.int32), d_table, 2, 0, 2, vis)
+    geometry.images._run_depth(_dev(ver, F), _dev(tri, np.int32), d_table, 2, 0, 2, depth)
     empty = vis == -1
     assert torch.equal(depth[empty], torch.full_like(depth[empty], float("inf")))
     assert torch.equal((vis[~empty] >> 32).to(torch.int32), depth[~empty].view(torch.int32))
@@ -267,22 +233,7 @@ def test_null_outputs_are_skipped_and_untrusted_words_are_uncovered():
 
 # ---- the ball of test_meshcolor_gpu.py, its cameras and its banks -------------------------------------------------------
 
-def _ball_mesh(radius=0.8, n=17):
-    c = torch.linspace(-1.0, 1.0, n, device=DEV, dtype=torch.float64)
-    lat = (radius - torch.sqrt(c[:, None, None] ** 2 + c[None, :, None] ** 2 + c[None, None, :] ** 2)).float().contiguous()
-    return geometry.extract_surface(lat, 0.0, (-1.0,) * 3, (1.0,) * 3)
-
-
-EYES = [(3, 0, 0), (0, 3, 0), (0, 0, 3), (-3, 0, 0), (0, -3, 0), (0, 0, -3)]
 SIZES = [(48, 40) if k % 2 == 0 else (40, 48) for k in range(6)]
-
-
-def _pose(eye):
-    return mref.look_at(eye, up=(0.0, 0.0, 1.0) if eye[2] == 0 else (0.0, 1.0, 0.0))
-
-
-def _intrinsics(w, h):
-    return np.array([[50.0, 0, w / 2 - 0.25], [0, 50.0, h / 2 - 0.5], [0, 0, 1]])
 
 
 def _bank(images, sizes=SIZES):

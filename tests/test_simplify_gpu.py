@@ -21,24 +21,11 @@ import torch
 
 import simplify_ref as sr
 import nerf_fl_amd
+from geom_gpu_util import bits as _bits, same as _same, to_dev as _to_dev
 from gpu_util import DEV, make_embeddings
 from nerf_fl_amd import NeRF, _lib, geometry, rendering, synth
 
 pytestmark = pytest.mark.gpu
-
-
-def _to_dev(mesh):
-    return {k: torch.from_numpy(np.ascontiguousarray(v)).to(DEV) for k, v in mesh.items()}
-
-
-def _bits(a):
-    a = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-    return a.view(np.int32) if a.dtype == np.float32 else a
-
-
-def _same(got, exp, what):
-    g, e = _bits(got), _bits(exp)
-    assert g.dtype == e.dtype and g.shape == e.shape and np.array_equal(g, e), what
 
 
 def _ulps(a, b):

@@ -102,8 +102,8 @@ def main():
         ms, pairs = [], 0
         for first in range(0, a.images, run):
             count = min(run, a.images - first)
-            geometry._run_depth(lib, stream(), mesh["vertices"], mesh["triangles"], bank.table, bank.n_images, first, count,
-                                depths[:count * S * S])
+            geometry.images._run_depth(mesh["vertices"], mesh["triangles"], bank.table, bank.n_images, first, count,
+                                       depths[:count * S * S])
             b = _lib.MeshBlendArgs()
             b.d_vertices, b.d_normals, b.n_vertices, b.d_pixels = points.data_ptr(), normals.data_ptr(), n_pts, bank.pixels.data_ptr()
             b.d_table, b.n_images, b.first, b.count, b.weighting = bank.table.data_ptr(), bank.n_images, first, count, 0
@@ -133,7 +133,7 @@ def main():
 
     # ---- the shading pass: the atlas beside the vertex colours, one camera's words
     vis = torch.empty(S * S, dtype=torch.int64, device=dev)
-    geometry._run_visibility(lib, stream(), ver, tri, bank.table, bank.n_images, 0, 1, vis)
+    geometry.images._run_visibility(ver, tri, bank.table, bank.n_images, 0, 1, vis)
     out = {"rgb": torch.empty(S * S, 3, dtype=torch.float32, device=dev), "u8": torch.empty(S * S, 3, dtype=torch.uint8, device=dev),
            "depth": torch.empty(S * S, dtype=torch.float32, device=dev), "tri": torch.empty(S * S, dtype=torch.int32, device=dev)}
     row = {"covered": (vis != -1).float().mean().item()}

@@ -100,7 +100,7 @@ def main():
              "triangles": torch.cat([fine["triangles"], torch.tensor([[V0, V0 + 1, V0 + 2]], dtype=torch.int32, device=dev)])}
     for name, mesh in (("depth_fine_mesh", fine), ("depth_simplified", coarse), ("depth_fine_plus_frame_triangle", mixed)):
         ver, tri = mesh["vertices"], mesh["triangles"]
-        call = lambda: geometry._run_depth(lib, stream(), ver, tri, bank.table, bank.n_images, 0, 1, depth)
+        call = lambda: geometry.images._run_depth(ver, tri, bank.table, bank.n_images, 0, 1, depth)
         t = timed(call, a.warmup, a.iters)
         tests, hits, big = boxes(ver, tri, torch.from_numpy(c2w[0]).to(dev), K.double(), S)
         rec[name] = {"vertices": ver.shape[0], "triangles": tri.shape[0], "ms": t, "tests": tests,
@@ -132,7 +132,7 @@ def main():
     ms, pairs = [], 0
     for first in range(0, a.images, run):
         count = min(run, a.images - first)
-        geometry._run_depth(lib, stream(), ver, tri, bank.table, bank.n_images, first, count, depths[:count * S * S])
+        geometry.images._run_depth(ver, tri, bank.table, bank.n_images, first, count, depths[:count * S * S])
         b = _lib.MeshBlendArgs()
         b.d_vertices, b.d_normals, b.n_vertices, b.d_pixels = ver.data_ptr(), nrm.data_ptr(), V, bank.pixels.data_ptr()
         b.d_table, b.n_images, b.first, b.count, b.weighting = bank.table.data_ptr(), bank.n_images, first, count, 0

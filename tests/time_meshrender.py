@@ -69,9 +69,9 @@ def main():
     for name, mesh in (("fine", fine), ("simplified", coarse)):
         ver, nrm, col, tri = mesh["vertices"], mesh["normals"], mesh["colors"], mesh["triangles"]
         row = {"vertices": ver.shape[0], "triangles": tri.shape[0]}
-        row["visibility_ms"] = timed(lambda: geometry._run_visibility(lib, stream(), ver, tri, bank.table, bank.n_images, 0, 1, vis),
+        row["visibility_ms"] = timed(lambda: geometry.images._run_visibility(ver, tri, bank.table, bank.n_images, 0, 1, vis),
                                      a.warmup, a.iters)
-        row["depth_ms"] = timed(lambda: geometry._run_depth(lib, stream(), ver, tri, bank.table, bank.n_images, 0, 1, depth),
+        row["depth_ms"] = timed(lambda: geometry.images._run_depth(ver, tri, bank.table, bank.n_images, 0, 1, depth),
                                 a.warmup, a.iters)
         row["visibility_over_depth"] = row["visibility_ms"]["median"] / row["depth_ms"]["median"]
         row["covered"] = (vis != -1).float().mean().item()
