@@ -1303,6 +1303,84 @@ typedef struct nfl_mesh_shade_atlas_args {
 } nfl_mesh_shade_atlas_args;
 int nfl_mesh_shade_atlas(const nfl_mesh_shade_atlas_args* args, void* stream);
 
+/* ---- depth fusion: depth maps of a run of cameras fused into a truncated signed distance function (TSDF) on a lattice, the
+ * lattice points that were observed, and the vertices of a surface that stand on observed points only (the route NeRF
+ * exporters take to a mesh: render a depth map per training camera, fuse, take the zero set) -----------------------------------
+ * Every operation fp32 and rounded on its own, divisions and square roots correctly rounded; camera, run, q, dot and the
+ * numbering of a run's depth words are those of "mesh colour" above, word for word, so a projection here has the bits of
+ * nfl_mesh_blend's.  The lattice is nfl_surface's: (nz, ny, nx), x fastest, point (x, y, z) at p[k] = lo[k] + index[k] *
+ * spacing[k], the product and the sum rounded separately.  A depth word is a distance from the camera centre, the unit of
+ * nfl_mesh_depth and of depth_fine when |rays_d| = 1.  No memset, no copy, no allocation, no atomics, no scratch.
+ *
+ * nfl_tsdf_fuse   one launch, one thread per lattice point, the images of the run in increasing n inside.  For point p image
+ *   n contributes when all of these hold:
+ *     1  wi = d_image_weights[n] > 0 (NULL: 1 for every image; the array is indexed by the TABLE's n);
+ *     2  s = -q.z > 0;
+ *     3  u = cx + fx * (q.x / s), v = cy - fy * (q.y / s) with 0 <= u <= width - 1 and 0 <= v <= height - 1 (NaN fails);
+ *     4  D = the depth word of pixel (floorf(u + 0.5f), floorf(v + 0.5f)), wp = its word of d_pixel_weights (NULL: 1),
+ *        w = wi * wp, with w > 0 and D > 0 (NaN fails both; +inf passes: the ray hit nothing, so the point is free);
+ *     5  e = t - p, dist = sqrt(dot(e, e)), phi = (dist - D) / trunc, and NOT phi > 1: a point more than trunc behind the
+ *        surface is hidden, and nothing is known about it.  Then phi = fmaxf(phi, -1).
+ *   The image adds w * phi to d_acc[p][0], w to d_acc[p][1] and 1 to d_views[p].  phi is positive BEHIND the surface: the
+ *   inside of nfl_surface at iso = 0.  start != 0 begins the accumulators at zero, start == 0 continues what the caller's
+ *   arrays hold, so a bank may be walked in runs; the result does not depend on the split.  A word outside [0, n_depth) is
+ *   not read, and its image does not contribute.
+ *   NFL_EINVAL (nothing launched): args / d_table NULL or d_table not 8-byte aligned, n_images < 1, a run outside the table,
+ *   a size below 2 or above nfl_surface's limits (ny or nz above 65535, more than 2^30 points), trunc not positive or NaN,
+ *   n_depth negative or above 2^38, d_depth NULL with n_depth > 0, d_acc or d_views NULL, a misaligned pointer (d_acc 8 B, the
+ *   others 4 B).  count == 0 with start == 0: NFL_OK, no launch.
+ *
+ * nfl_tsdf_resolve   one launch, one thread per lattice point: where d_acc[p][1] >= min_weight and d_views[p] >= min_views,
+ *   d_lattice[p] = d_acc[p][0] / d_acc[p][1] and d_known[p] = 1; elsewhere d_lattice[p] = fill and d_known[p] = 0.
+ *   NFL_EINVAL: args or one of the four arrays NULL or misaligned, the sizes as above, min_weight not positive or NaN,
+ *   min_views < 1, a NaN fill.
+ *
+ * nfl_tsdf_support   one launch, one thread per vertex: g[k] = (p[k] - lo[k]) / spacing[k]; the vertex is unsupported when
+ *   any g[k] is not finite or lies outside [0, n[k] - 1]; otherwise a[k] = floorf(g[k]), b[k] = ceilf(g[k]) and d_support[v] = 1
+ *   when d_known holds at every lattice point of {a.x, b.x} x {a.y, b.y} x {a.z, b.z}, else 0.  A vertex of nfl_surface lies on
+ *   a lattice edge: on an axis edge the rule reads "both ends of the crossing edge were observed", on a diagonal its face or
+ *   its cell.  nfl_surface counts the fill value of an unobserved point as outside, so without this rule a fused lattice
+ *   grows a second wall where the observed band behind the surface ends.
+ *   NFL_EINVAL: args or d_known NULL, the sizes as above, V < 0 or above INT32_MAX, and for V > 0 a NULL d_vertices / d_support
+ *   or a misaligned d_vertices.  V == 0: NFL_OK, no launch. */
+typedef struct nfl_tsdf_fuse_args {
+    const nfl_image_rec* d_table;     /* (n_images) */
+    int32_t  n_images, first, count;
+    int32_t  start;                   /* != 0: the accumulators begin at zero */
+    const float* d_depth;             /* (n_depth): the run's depth words, nfl_mesh_depth's numbering */
+    int64_t  n_depth;
+    const float* d_pixel_weights;     /* (n_depth) or NULL */
+    const float* d_image_weights;     /* (n_images) or NULL */
+    int32_t  nx, ny, nz;
+    float    trunc;
+    float    lo[3];                   /* position of lattice point (0, 0, 0): x, y, z */
+    float    spacing[3];              /* x, y, z */
+    float*   d_acc;                   /* in/out (nz, ny, nx, 2): sum of w * phi, sum of w */
+    int32_t* d_views;                 /* in/out (nz, ny, nx) */
+} nfl_tsdf_fuse_args;
+int nfl_tsdf_fuse(const nfl_tsdf_fuse_args* args, void* stream);
+
+typedef struct nfl_tsdf_resolve_args {
+    const float*   d_acc;             /* (nz, ny, nx, 2) */
+    const int32_t* d_views;           /* (nz, ny, nx) */
+    int32_t  nx, ny, nz, min_views;
+    float    min_weight, fill;
+    float*   d_lattice;               /* out (nz, ny, nx) */
+    uint8_t* d_known;                 /* out (nz, ny, nx) */
+} nfl_tsdf_resolve_args;
+int nfl_tsdf_resolve(const nfl_tsdf_resolve_args* args, void* stream);
+
+typedef struct nfl_tsdf_support_args {
+    const float*   d_vertices;        /* (V, 3) */
+    int64_t  n_vertices;
+    const uint8_t* d_known;           /* (nz, ny, nx) */
+    int32_t  nx, ny, nz, reserved;
+    float    lo[3];
+    float    spacing[3];
+    uint8_t* d_support;               /* out (V) */
+} nfl_tsdf_support_args;
+int nfl_tsdf_support(const nfl_tsdf_support_args* args, void* stream);
+
 /* ---- hierarchical sampling (reference sample_pdf, rendering.py:7-46, plus the
  * concat + sort of rendering.py:267-272) -------------------------------------
  * d_z_coarse (R,S), d_weights_coarse (R,S); d_u (R,I) or NULL with d_u_row (I)

@@ -352,6 +352,28 @@ class MeshShadeAtlasArgs(C.Structure):
                 ("d_rgb", C.c_void_p), ("d_rgb_u8", C.c_void_p), ("d_depth", C.c_void_p), ("d_triangle", C.c_void_p)]
 
 
+# nfl_tsdf_fuse / nfl_tsdf_resolve / nfl_tsdf_support (nerf_fl_amd.fusion: depth maps fused into a TSDF lattice) likewise:
+# three new symbols and structs
+class TsdfFuseArgs(C.Structure):
+    _fields_ = [("d_table", C.c_void_p), ("n_images", C.c_int32), ("first", C.c_int32), ("count", C.c_int32),
+                ("start", C.c_int32), ("d_depth", C.c_void_p), ("n_depth", C.c_int64), ("d_pixel_weights", C.c_void_p),
+                ("d_image_weights", C.c_void_p), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
+                ("trunc", C.c_float), ("lo", C.c_float * 3), ("spacing", C.c_float * 3), ("d_acc", C.c_void_p),
+                ("d_views", C.c_void_p)]
+
+
+class TsdfResolveArgs(C.Structure):
+    _fields_ = [("d_acc", C.c_void_p), ("d_views", C.c_void_p), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
+                ("min_views", C.c_int32), ("min_weight", C.c_float), ("fill", C.c_float), ("d_lattice", C.c_void_p),
+                ("d_known", C.c_void_p)]
+
+
+class TsdfSupportArgs(C.Structure):
+    _fields_ = [("d_vertices", C.c_void_p), ("n_vertices", C.c_int64), ("d_known", C.c_void_p), ("nx", C.c_int32),
+                ("ny", C.c_int32), ("nz", C.c_int32), ("reserved", C.c_int32), ("lo", C.c_float * 3),
+                ("spacing", C.c_float * 3), ("d_support", C.c_void_p)]
+
+
 # every symbol include/nerf_fl_amd.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("nfl_plan_bytes", C.c_size_t, [C.POINTER(FieldDesc)]),
@@ -432,6 +454,9 @@ SYMBOLS = [
     ("nfl_atlas_points", C.c_int, [C.POINTER(AtlasPointsArgs), C.c_void_p]),
     ("nfl_atlas_resolve", C.c_int, [C.POINTER(AtlasResolveArgs), C.c_void_p]),
     ("nfl_mesh_shade_atlas", C.c_int, [C.POINTER(MeshShadeAtlasArgs), C.c_void_p]),
+    ("nfl_tsdf_fuse", C.c_int, [C.POINTER(TsdfFuseArgs), C.c_void_p]),
+    ("nfl_tsdf_resolve", C.c_int, [C.POINTER(TsdfResolveArgs), C.c_void_p]),
+    ("nfl_tsdf_support", C.c_int, [C.POINTER(TsdfSupportArgs), C.c_void_p]),
     ("nfl_abi_version", C.c_int, []),
     ("nfl_version", C.c_char_p, []),
     ("nfl_strerror", C.c_char_p, [C.c_int]),
