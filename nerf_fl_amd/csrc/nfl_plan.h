@@ -26,6 +26,32 @@
 //
 // Chunks (the unit of the LDS ring; every chunk starts a new barrier epoch):
 //   L1: 2 row tiles per chunk; T2..T4: 2 row tiles per chunk; otherwise 1.
+//
+// Dgrad stream order (nfl_plan_fill_bwd).  The backward chain delta_in = W^T delta_out walks the network from the heads
+// down, so its A operand is W TRANSPOSED: tile row i is INPUT column tcol0 + i of the source layer (i < tncols, the
+// other rows are zero), and the k-slots of a segment run over that layer's OUTPUT rows col0 + map(k-slot), valid
+// while map < ncols (element(i, m) = W[seg.layer][seg.col0 + m][tcol0 + i], see NflRowTile).  A tile may have up to
+// three segments of DIFFERENT layers whose products land on the same 32 gradients.  Every bias-table row of a
+// transposed tile is 0.  cx = 6 n_emb_xyz + 3, cd = 6 n_emb_dir + 3; "ACT" / "NAT" = the k-slot map of the segment:
+//   with the transient head (has_t):
+//     THEAD^T  4 tiles (columns 32 t ..), 3 ks: transient_sigma NAT 1 row | transient_rgb NAT 3 rows |
+//              transient_beta NAT 1 row                                               -> d(g4)
+//     T4..T2^T 4 tiles each, 8 ks ACT over the layer's 128 rows                       -> d(g3), d(g2), d(g1)
+//     T1 tau   1 tile: columns 256 .. 256 + n_tau of T1, 8 ks ACT over its 128 rows   -> d(tau)
+//   ---- the backward of a pass without the transient head starts here ----
+//   RGB^T    4 tiles, 1 ks NAT over static_rgb's 3 rows                               -> d(dirh)
+//   with appearance codes (has_a): 2 tiles of DIR's columns 256 + cd + 32 t .., of min(n_a, 32) and max(n_a - 32, 0)
+//            rows (the second may be partial or EMPTY: all padding), 8 ks ACT over DIR's 128 rows -> d(appearance)
+//   with the ray gradient: 1 tile of DIR's columns 256 .. 256 + cd, 8 ks ACT          -> d(encoded direction)
+//   H8       8 tiles (columns 32 t ..): DIR 8 ks ACT over 128 rows | has_t: T1 8 ks ACT over 128 rows |
+//            static_sigma 1 ks NAT over 1 row (DIR and T1 as folded through xyz_encoding_final)   -> d(h8)
+//   L8..L2^T 8 tiles each, 16 ks ACT over the layer's 256 rows; L5's tiles read its columns cx + 32 t .. (the h4 part)
+//            with the ray gradient, behind L5's 8 tiles: (nkp + 1) / 2 tiles of L5's columns 32 t .., of
+//            clamp(cx - 32 t, 0, 32) rows, 16 ks ACT (the last may be partial or empty)  -> d(encoded position)
+//   with the ray gradient, at the end: the same (nkp + 1) / 2 tiles of L1's columns   -> d(encoded position)
+// Without the ray gradient L1, the first cx columns of L5 and DIR's direction columns appear nowhere in the stream.
+// Chunks: one tile per chunk; in the hi-only stream (NFL_PREC_F16) the tiles of the 4- and 8-tile groups travel two
+// per chunk.  The hi + lo streams (NFL_PREC_F16W, NFL_PREC_F16X3) hold the same tiles at 2 KiB per k-step.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
