@@ -1381,6 +1381,179 @@ typedef struct nfl_tsdf_support_args {
 } nfl_tsdf_support_args;
 int nfl_tsdf_support(const nfl_tsdf_support_args* args, void* stream);
 
+/* ---- mesh distance: the closest point of a triangle mesh for many query points, a uniform grid of triangle lists that finds it
+ * without trying every triangle, area-weighted samples of a surface, and the reduction of a run of distances (what Chamfer
+ * distance, Hausdorff distance and the F-score of a reconstruction are made of) --------------------------------------------------
+ * Every operation fp32 and rounded on its own unless fp64 is named, divisions and square roots correctly rounded; dot and cross
+ * are those of "mesh colour" above.  Triangle indices are NOT trusted.  A triangle is USABLE when its three indices lie in
+ * [0, n_vertices) and its nine coordinates are finite; every other triangle is listed nowhere, is never an answer and gets
+ * no sample.  mix(x) is the finaliser of splitmix64 on uint64 (x ^= x >> 30, x *= 0xBF58476D1CE4E5B9, x ^= x >> 27,
+ * x *= 0x94D049BB133111EB, x ^= x >> 31), sums of uint64 wrap.
+ *
+ * THE GRID is lo[3], one cell size `cell` (cubic cells) and dims[3] = (nx, ny, nz) cells, 1 <= dims[k] <= 65535 and at most
+ * 2^30 cells; cell (x, y, z) is number (z * ny + y) * nx + x.  The cell of a coordinate on axis k is
+ *     cellf(x) = (int)fminf(fmaxf(floorf((x - lo[k]) / cell), 0), (float)(dims[k] - 1)),
+ * a monotone function of x (a NaN goes to cell 0).  A usable triangle is listed in every cell of the index box
+ * [cellf(min corner), cellf(max corner)] of its bounding box, so by monotonicity every point of it lies in a cell that lists
+ * it (after clamping, too: the cells on the grid's faces list what lies beyond them).
+ *
+ * nfl_trigrid_count   zero, one thread per triangle (an int32 atomicAdd per cell of its box), a scan of the counts to int64.
+ *   d_totals[0] = the entries of all rows, d_totals[1] = the triangles with an index outside [0, n_vertices).
+ * nfl_trigrid_emit    d_offsets (cells + 1) int64, row c being d_entries[d_offsets[c] .. d_offsets[c + 1]), and the rows,
+ *   filled through a per-cell cursor: the ORDER INSIDE A ROW IS NOT DEFINED, and nothing below depends on it.
+ *   n_entries = d_totals[0] of the count call on the same scratch; at most INT32_MAX.
+ *   NFL_EINVAL (nothing launched), both: args NULL, a negative size, V > INT32_MAX or 3 T > INT32_MAX, dims as above, cell not
+ *   positive or not finite, a non-finite lo, a NULL or misaligned (4 B) d_vertices / d_triangles that a non-zero size needs,
+ *   d_totals NULL (count), n_entries negative or above INT32_MAX or a NULL / misaligned d_offsets (8 B) / d_entries (emit).
+ *   The scratch as everywhere: NULL or misaligned NFL_EINVAL, short NFL_ESMALL.  T == 0 is served: empty rows.
+ *
+ * POINT AND TRIANGLE.  For a query p and a usable triangle (a, b, c), the seven regions of Ericson, Real-Time Collision
+ * Detection, 5.1.5.  THIS PARAGRAPH IS FP64, every operation rounded on its own, the fp32 inputs converted first (the 2 x 2
+ * determinants below cancel: in fp32 the slivers that marching tetrahedra leave put q some 3e-6 away from a point that lay
+ * on the triangle): ab = b - a, ac = c - a, ap = p - a, d1 = dot(ab, ap), d2 = dot(ac, ap); bp = p - b, d3 = dot(ab, bp),
+ * d4 = dot(ac, bp); cp = p - c, d5 = dot(ab, cp), d6 = dot(ac, cp); vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6,
+ * va = d3 * d6 - d5 * d4.  The first of these that holds gives the barycentrics (u, v, w) of a, b, c and the point q, each
+ * rounded to fp32 at the end:
+ *     1  d1 <= 0 and d2 <= 0                          (1, 0, 0), q = a
+ *     2  d3 >= 0 and d4 <= d3                         (0, 1, 0), q = b
+ *     3  vc <= 0 and d1 >= 0 and d3 <= 0              s = d1 / (d1 - d3): (1 - s, s, 0), q = a + s * ab
+ *     4  d6 >= 0 and d5 <= d6                         (0, 0, 1), q = c
+ *     5  vb <= 0 and d2 >= 0 and d6 <= 0              s = d2 / (d2 - d6): (1 - s, 0, s), q = a + s * ac
+ *     6  va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0    s = (d4 - d3) / ((d4 - d3) + (d5 - d6)): (0, 1 - s, s), q = b + s * (c - b)
+ *     7  otherwise                                    den = 1 / ((va + vb) + vc), s = vb * den, r = vc * den:
+ *                                                     ((1 - s) - r, s, r), q = (a + s * ab) + r * ac.
+ * Back in fp32, q is CLAMPED into the triangle's bounding box, q[k] = mn[k] when q[k] < mn[k], mx[k] when q[k] > mx[k], else
+ * q[k] (a NaN stays), mn and mx the least and the largest of the three corners -- rounding moves q out by an ulp at most,
+ * and the clamp is what the grid's stopping rule stands on -- and with e = p - q, dd = (e0 * e0 + e1 * e1) + e2 * e2.  A candidate is ACCEPTED when dd <= max_distance * max_distance and dd < +inf (a NaN,
+ * which a degenerate triangle can give through 0 / 0, fails).  The answer is the accepted candidate with the least
+ * (dd, triangle index): ties go to the lower index, so the answer depends neither on the order in which triangles are tried
+ * nor on how often.
+ *
+ * nfl_mesh_closest   one launch, one thread per query.  d_distance = sqrtf(dd), d_triangle, d_point = q, d_bary = (u, v, w)
+ *   of the answer; with d_normals (a vector per query) and d_dot, d_dot = dot(query vector, face normal), the face normal
+ *   cross(ab, ac) divided by its length sqrtf(dot(cr, cr)), three zeros when that length is zero.  A query with no accepted
+ *   candidate -- nothing within max_distance, an empty mesh, a non-finite query coordinate -- gets +inf, -1 and NaNs.
+ *   max_distance is positive; +inf means no limit.
+ *   BRUTE (d_offsets NULL): every query tries every triangle, which a workgroup stages through LDS 256 at a time.
+ *   GRID (d_offsets, d_entries, n_entries, lo, cell, dims of nfl_trigrid_emit for the SAME mesh): with C the query's own cell
+ *   (cellf per axis), shells r = 0, 1, 2, ...: shell r is the cells at Chebyshev distance r from C inside the grid, and every
+ *   triangle its rows list is tried.  After shell r the block [C - r, C + r], cut to the grid, has been walked; a usable
+ *   triangle NOT listed in it lies, on some axis k, wholly beyond a face of the block that is not a face of the grid.  The
+ *   walk ends when the block is the whole grid, or when best < bound or bound > max_distance^2, best being the least accepted
+ *   dd so far (+inf: none) and bound the minimum over the block's faces that are not faces of the grid of g * g, where
+ *   g = (float)(G * (1 - 2^-23)) and, in FP64, with F = lo[k] + i * cell the face at index i (i = the block's first index, or
+ *   its last + 1) and S = 2^-21 * (|lo[k]| + i * cell):  G = p[k] - (F + S) on the low side, (F - S) - p[k] on the high side,
+ *   0 when that is negative.  The slack S is explicit because cellf is computed in fp32: the smallest x with cellf(x) >= i
+ *   lies within S of F.  Every corner of an unlisted triangle beyond that face, hence (the clamp) its q[k], is then at least
+ *   G from p[k]; fp32 rounding is monotone, so |e[k]| >= g and dd >= g * g = bound > best: it can neither win nor tie.
+ *   THE CONTRACT: grid mode returns the bits of brute mode, for every cell size and every origin.
+ *   A grid that is not this mesh's (rows out of range, unknown triangles) is read inside its arrays and never faults.
+ *   NFL_EINVAL (nothing launched): args NULL, a negative size, the mesh sizes as above, max_distance not positive (NaN
+ *   included), and for N > 0 a NULL or misaligned (4 B) d_points or output, d_normals without d_dot or the reverse; in grid
+ *   mode dims / cell / lo as above, d_entries NULL with n_entries > 0, n_entries outside [0, INT32_MAX], d_offsets not 8-byte
+ *   aligned.  N == 0: NFL_OK, no launch.
+ *
+ * SURFACE SAMPLES.  For triangle t: cr = cross(b - a, c - a), len = sqrtf(dot(cr, cr)), area = 0.5f * len;
+ *   ht = mix(mix(seed) + t), ut = (float)(ht >> 40) * 2^-24 (24 bits, in [0, 1)), m_t = floorf(area * density + ut): the
+ *   rounding is stochastic, so the expected count is area * density exactly and small triangles are not starved.  A triangle
+ *   that is not usable, or whose len is zero or not finite, has m_t = 0.  Sample j of triangle t: hj = mix(ht + (j + 1)),
+ *   k1 = hj >> 40, k2 = (hj >> 16) & 0xFFFFFF, r = ((float)k + 0.5f) * 2^-24 each (in (0, 1]; the sum rounds to even above
+ *   2^23); when r1 + r2 > 1 both become 1 - r; p = (a + r1 * (b - a)) + r2 * (c - a); the normal is cr[k] / len.
+ *   Samples lie in triangle order, sample j of triangle t at row (the m of the triangles before t) + j.
+ * nfl_mesh_sample_count   d_totals[0] = the samples, [1] = triangles with an index out of range, [2] = triangles whose
+ *   area * density + ut is 2^24 or more (they count 0; the caller refuses).
+ * nfl_mesh_sample_emit    d_points (n_samples, 3), d_sample_triangles (n_samples) int32, d_normals (n_samples, 3).  A triangle
+ *   of more than 64 samples is written by its whole wave, in the same launch.  n_samples = d_totals[0], at most INT32_MAX.
+ *   NFL_EINVAL: args NULL, the mesh sizes and pointers as above, density negative or not finite, d_totals NULL (count),
+ *   n_samples outside [0, INT32_MAX] or a NULL / misaligned output with n_samples > 0 (emit); the scratch as everywhere.
+ *
+ * nfl_meshdist_reduce   two launches, no atomics: d_row (NFL_MESHDIST_COLUMNS fp64) of n distances.  An element COUNTS when
+ *   its distance d is below +inf (a NaN does not count; +inf is what max_distance leaves).  Columns: the count; the sum of d;
+ *   of d * d (in fp64); the maximum of d (0 when nothing counts); for k < n_tau the count of d <= tau[k] (fp32 comparison),
+ *   0 for k >= n_tau; the sum of |d_dot| over the counting elements (0 without d_dot).  G = min(ceil(n / 256), 1024) workgroups
+ *   of 256: thread t of workgroup g adds elements (g + j * G) * 256 + t, j = 0, 1, ... in that order in fp64, the 256 threads
+ *   are folded by halving (row t += row t + off for t < off, off = 128 .. 1), the G partial rows are dealt to the 256
+ *   threads of ONE workgroup (thread t adds rows t, t + 256, ... in order) and folded the same way; maxima by fmax.  The row
+ *   is bit-reproducible.
+ *   NFL_EINVAL: args, d_distance (n > 0) or d_row NULL, misaligned pointers (4 B; d_row and the scratch 8 B), n negative or
+ *   above INT32_MAX, n_tau outside [0, 8], a NaN tau below n_tau.  n == 0 writes the row of zeros. */
+#define NFL_MESHDIST_MAX_TAU 8
+enum { NFL_MESHDIST_COUNT = 0, NFL_MESHDIST_SUM = 1, NFL_MESHDIST_SUM_SQ = 2, NFL_MESHDIST_MAX = 3, NFL_MESHDIST_WITHIN = 4,
+       NFL_MESHDIST_SUM_DOT = 12, NFL_MESHDIST_COLUMNS = 13 };
+typedef struct nfl_trigrid_args {
+    const float*   d_vertices;        /* (V, 3) */
+    const int32_t* d_triangles;       /* (T, 3) */
+    int64_t  n_vertices, n_triangles;
+    float    lo[3];
+    float    cell;
+    int32_t  dims[3];                 /* cells along x, y, z */
+    int32_t  reserved;
+    void*    d_scratch;               /* nfl_trigrid_bytes(dims); the emit call reads what the count call left */
+    size_t   scratch_bytes;
+    int64_t* d_totals;                /* count: out (2) */
+    int64_t  n_entries;               /* emit: d_totals[0] */
+    int64_t* d_offsets;               /* emit: out (cells + 1) */
+    int32_t* d_entries;               /* emit: out (n_entries) */
+} nfl_trigrid_args;
+size_t nfl_trigrid_bytes(int32_t nx, int32_t ny, int32_t nz);
+int nfl_trigrid_count(const nfl_trigrid_args* args, void* stream);
+int nfl_trigrid_emit(const nfl_trigrid_args* args, void* stream);
+
+typedef struct nfl_mesh_closest_args {
+    const float*   d_points;          /* (N, 3) queries */
+    int64_t  n_points;
+    const float*   d_vertices;        /* (V, 3) */
+    const int32_t* d_triangles;       /* (T, 3) */
+    int64_t  n_vertices, n_triangles;
+    const int64_t* d_offsets;         /* (cells + 1) of nfl_trigrid_emit, or NULL: brute mode */
+    const int32_t* d_entries;         /* (n_entries) */
+    int64_t  n_entries;
+    float    lo[3];
+    float    cell;
+    int32_t  dims[3];
+    float    max_distance;            /* positive; +inf: no limit */
+    const float*   d_normals;         /* (N, 3) a vector per query, or NULL */
+    float*   d_distance;              /* out (N) */
+    int32_t* d_triangle;              /* out (N) */
+    float*   d_point;                 /* out (N, 3) */
+    float*   d_bary;                  /* out (N, 3) */
+    float*   d_dot;                   /* out (N), with d_normals; else NULL */
+} nfl_mesh_closest_args;
+int nfl_mesh_closest(const nfl_mesh_closest_args* args, void* stream);
+
+typedef struct nfl_mesh_sample_args {
+    const float*   d_vertices;        /* (V, 3) */
+    const int32_t* d_triangles;       /* (T, 3) */
+    int64_t  n_vertices, n_triangles;
+    uint64_t seed;
+    float    density;                 /* samples per unit area */
+    int32_t  reserved;
+    void*    d_scratch;               /* nfl_mesh_sample_bytes(T) */
+    size_t   scratch_bytes;
+    int64_t* d_totals;                /* count: out (3) */
+    int64_t  n_samples;               /* emit: d_totals[0] */
+    float*   d_points;                /* emit: out (n_samples, 3) */
+    int32_t* d_sample_triangles;      /* emit: out (n_samples) */
+    float*   d_normals;               /* emit: out (n_samples, 3) */
+} nfl_mesh_sample_args;
+size_t nfl_mesh_sample_bytes(int64_t n_triangles);
+int nfl_mesh_sample_count(const nfl_mesh_sample_args* args, void* stream);
+int nfl_mesh_sample_emit(const nfl_mesh_sample_args* args, void* stream);
+
+typedef struct nfl_meshdist_reduce_args {
+    const float* d_distance;          /* (n) */
+    const float* d_dot;               /* (n) or NULL */
+    int64_t  n;
+    int32_t  n_tau;
+    float    tau[NFL_MESHDIST_MAX_TAU];
+    int32_t  reserved;
+    void*    d_scratch;               /* nfl_meshdist_reduce_bytes(n) */
+    size_t   scratch_bytes;
+    double*  d_row;                   /* out (NFL_MESHDIST_COLUMNS) */
+} nfl_meshdist_reduce_args;
+size_t nfl_meshdist_reduce_bytes(int64_t n);
+int nfl_meshdist_reduce(const nfl_meshdist_reduce_args* args, void* stream);
+
 /* ---- hierarchical sampling (reference sample_pdf, rendering.py:7-46, plus the
  * concat + sort of rendering.py:267-272) -------------------------------------
  * d_z_coarse (R,S), d_weights_coarse (R,S); d_u (R,I) or NULL with d_u_row (I)

@@ -374,6 +374,42 @@ class TsdfSupportArgs(C.Structure):
                 ("spacing", C.c_float * 3), ("d_support", C.c_void_p)]
 
 
+# nfl_trigrid_* / nfl_mesh_closest / nfl_mesh_sample_* / nfl_meshdist_reduce (nerf_fl_amd.meshdist: the distance between two
+# meshes) likewise: nine new symbols and four new structs
+MESHDIST_MAX_TAU = 8
+MESHDIST_COLUMNS = 13                           # count, sum, sum of squares, max, 8 x within tau, sum of |dot|
+
+
+class TriGridArgs(C.Structure):
+    _fields_ = [("d_vertices", C.c_void_p), ("d_triangles", C.c_void_p), ("n_vertices", C.c_int64),
+                ("n_triangles", C.c_int64), ("lo", C.c_float * 3), ("cell", C.c_float), ("dims", C.c_int32 * 3),
+                ("reserved", C.c_int32), ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_size_t),
+                ("d_totals", C.c_void_p), ("n_entries", C.c_int64), ("d_offsets", C.c_void_p), ("d_entries", C.c_void_p)]
+
+
+class MeshClosestArgs(C.Structure):
+    _fields_ = [("d_points", C.c_void_p), ("n_points", C.c_int64), ("d_vertices", C.c_void_p),
+                ("d_triangles", C.c_void_p), ("n_vertices", C.c_int64), ("n_triangles", C.c_int64),
+                ("d_offsets", C.c_void_p), ("d_entries", C.c_void_p), ("n_entries", C.c_int64), ("lo", C.c_float * 3),
+                ("cell", C.c_float), ("dims", C.c_int32 * 3), ("max_distance", C.c_float), ("d_normals", C.c_void_p),
+                ("d_distance", C.c_void_p), ("d_triangle", C.c_void_p), ("d_point", C.c_void_p), ("d_bary", C.c_void_p),
+                ("d_dot", C.c_void_p)]
+
+
+class MeshSampleArgs(C.Structure):
+    _fields_ = [("d_vertices", C.c_void_p), ("d_triangles", C.c_void_p), ("n_vertices", C.c_int64),
+                ("n_triangles", C.c_int64), ("seed", C.c_uint64), ("density", C.c_float), ("reserved", C.c_int32),
+                ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_size_t), ("d_totals", C.c_void_p),
+                ("n_samples", C.c_int64), ("d_points", C.c_void_p), ("d_sample_triangles", C.c_void_p),
+                ("d_normals", C.c_void_p)]
+
+
+class MeshDistReduceArgs(C.Structure):
+    _fields_ = [("d_distance", C.c_void_p), ("d_dot", C.c_void_p), ("n", C.c_int64), ("n_tau", C.c_int32),
+                ("tau", C.c_float * MESHDIST_MAX_TAU), ("reserved", C.c_int32), ("d_scratch", C.c_void_p),
+                ("scratch_bytes", C.c_size_t), ("d_row", C.c_void_p)]
+
+
 # every symbol include/nerf_fl_amd.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("nfl_plan_bytes", C.c_size_t, [C.POINTER(FieldDesc)]),
@@ -457,6 +493,15 @@ SYMBOLS = [
     ("nfl_tsdf_fuse", C.c_int, [C.POINTER(TsdfFuseArgs), C.c_void_p]),
     ("nfl_tsdf_resolve", C.c_int, [C.POINTER(TsdfResolveArgs), C.c_void_p]),
     ("nfl_tsdf_support", C.c_int, [C.POINTER(TsdfSupportArgs), C.c_void_p]),
+    ("nfl_trigrid_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    ("nfl_trigrid_count", C.c_int, [C.POINTER(TriGridArgs), C.c_void_p]),
+    ("nfl_trigrid_emit", C.c_int, [C.POINTER(TriGridArgs), C.c_void_p]),
+    ("nfl_mesh_closest", C.c_int, [C.POINTER(MeshClosestArgs), C.c_void_p]),
+    ("nfl_mesh_sample_bytes", C.c_size_t, [C.c_int64]),
+    ("nfl_mesh_sample_count", C.c_int, [C.POINTER(MeshSampleArgs), C.c_void_p]),
+    ("nfl_mesh_sample_emit", C.c_int, [C.POINTER(MeshSampleArgs), C.c_void_p]),
+    ("nfl_meshdist_reduce_bytes", C.c_size_t, [C.c_int64]),
+    ("nfl_meshdist_reduce", C.c_int, [C.POINTER(MeshDistReduceArgs), C.c_void_p]),
     ("nfl_abi_version", C.c_int, []),
     ("nfl_version", C.c_char_p, []),
     ("nfl_strerror", C.c_char_p, [C.c_int]),

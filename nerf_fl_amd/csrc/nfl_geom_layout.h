@@ -164,3 +164,39 @@ enum { NA_S_PING, NA_S_REGIONS };
 static inline NgLayout<NA_S_REGIONS> na_smooth_layout(i64 V) {
     return {{{12, (size_t)V}}, {}};                         // fp32 x 3 the positions of every other step
 }
+
+// ---- mesh distance: nfl_trigrid_count / nfl_trigrid_emit
+#define ND_MAX_ENTRIES ((i64)INT32_MAX)                    // entries of a grid's rows, samples of a surface, distances of a run
+#define ND_MAX_SAMPLES_PER_TRIANGLE 16777216.0f             // 2^24
+#define ND_REDUCE_MAX_BLOCKS 1024
+static inline bool nd_dims_ok(const int32_t* dims) {
+    for (int k = 0; k < 3; ++k)
+        if (dims[k] < 1 || dims[k] > NG_MAX_DIM) return false;
+    return (i64)dims[0] * dims[1] * dims[2] <= NG_MAX_POINTS;
+}
+enum { ND_G_CNT, ND_G_OFF, ND_G_SUMS, ND_G_REGIONS };
+static inline NgLayout<ND_G_REGIONS> nd_grid_layout(i64 cells) {
+    const size_t c = (size_t)cells;
+    return {{{4, c},                                        // int32 triangles listed in cell c; the cursor of c while emit fills
+             {8, c},                                        // int64 entries before cell c
+             {1, nm_scan_bytes(cells)}}, {}};               // tile sums of the scan
+}
+
+// ---- mesh distance: nfl_mesh_sample_count / nfl_mesh_sample_emit
+enum { ND_S_CNT, ND_S_OFF, ND_S_SUMS, ND_S_REGIONS };
+static inline NgLayout<ND_S_REGIONS> nd_sample_layout(i64 T) {
+    const size_t t = (size_t)T;
+    return {{{4, t},                                        // int32 samples of triangle t
+             {8, t},                                        // int64 samples before triangle t
+             {1, nm_scan_bytes(T)}}, {}};
+}
+
+// ---- mesh distance: nfl_meshdist_reduce
+static inline i64 nd_reduce_blocks(i64 n) {
+    const i64 g = ng_cdiv(n, 256);
+    return g < ND_REDUCE_MAX_BLOCKS ? g : ND_REDUCE_MAX_BLOCKS;
+}
+enum { ND_R_PARTS, ND_R_REGIONS };
+static inline NgLayout<ND_R_REGIONS> nd_reduce_layout(i64 n) {
+    return {{{8 * NFL_MESHDIST_COLUMNS, (size_t)nd_reduce_blocks(n)}}, {}};    // one fp64 row per workgroup
+}

@@ -1,0 +1,672 @@
+// nfl_meshdist.hip -- the distance between triangle meshes on the device (include/nerf_fl_amd.h, "mesh distance"): a uniform
+// grid of triangle lists, the closest point of a mesh for many queries (through the grid, or trying every triangle), area-
+// weighted samples of a surface, and the reduction of a run of distances.  DESIGN.md section 33.
+//
+//   grid     count   zero; a thread per triangle adds 1 to every cell of its index box (int32 atomics); nm_scan: the rows' offsets
+//            emit    the offsets (cells + 1), the cursors = 0; a thread per triangle writes itself into its rows at the place
+//                    the cell's cursor hands out (the order of arrival: arbitrary, and nothing reads a row for its order)
+//   closest  a thread per query.  Brute: the workgroup stages 256 triangles' corners in LDS (nine planes of 256 floats and a
+//            flag, so the 64 lanes of a wave read ONE word each step: a broadcast) and every thread tries them all.  Grid: the
+//            thread walks the shells of cells round its own and stops on the bound of the header; neighbouring queries
+//            (samples lie in triangle order) walk neighbouring rows, which is what the caches are for.
+//   samples  count   a thread per triangle: m_t; nm_scan: the first row of every triangle
+//            emit    a thread per triangle writes up to 64 samples itself; the wave then takes the larger triangles of its
+//                    lanes one after the other, 64 samples a step (nfl_mesh_depth's treatment of large boxes)
+//   reduce   partial rows per workgroup in fp64 in a fixed order, one workgroup folds them (nfl_image_metrics' scheme)
+//
+// Only integer atomics, and nothing that depends on their order leaves a call except the order inside a grid row.  Nothing
+// here allocates, sets or copies memory through the runtime.
+#include <math.h>
+
+#include "nfl_geom.h"
+
+typedef unsigned long long u64;
+
+#define ND_TILE NM_THREADS                                  // triangles a workgroup stages in brute mode
+#define ND_WAVE_SAMPLES 64                                  // a triangle with more samples is emitted by the whole wave
+
+#ifdef NFL_MESHDIST_COUNT_TESTS
+// a diagnostic build (make variant VFLAGS=-DNFL_MESHDIST_COUNT_TESTS=1 VTU=nfl_meshdist) counts what the grid walk does:
+// [0] point-triangle tests, [1] cells read, [2] queries.  tests/time_meshdist.py reads them; the product never has them.
+__device__ u64 nd_debug_counts[3];
+extern "C" int nfl_meshdist_debug_counts(u64* out3, int reset) {
+    const u64 zero[3] = {0, 0, 0};
+    if (out3 && hipMemcpyFromSymbol(out3, HIP_SYMBOL(nd_debug_counts), sizeof zero) != hipSuccess) return NFL_ELAUNCH;
+    if (reset && hipMemcpyToSymbol(HIP_SYMBOL(nd_debug_counts), zero, sizeof zero) != hipSuccess) return NFL_ELAUNCH;
+    return NFL_OK;
+}
+#define ND_DEBUG_ADD(k, n) atomicAdd(&nd_debug_counts[k], (u64)(n))
+#else
+#define ND_DEBUG_ADD(k, n)
+#endif
+
+struct NdGrid {
+    float lo[3];
+    float cell;
+    int32_t dims[3];
+};
+
+static inline bool nd_misaligned(const void* p, int align) { return reinterpret_cast<uintptr_t>(p) % align != 0; }
+static inline bool nd_finite(float x) { return x - x == 0.f; }
+
+// the mesh a call takes: sizes, and the pointers a non-zero size needs
+static bool nd_mesh_ok(const float* ver, const int32_t* tri, i64 V, i64 T) {
+    if (!nm_sizes_ok(V, T)) return false;
+    if ((V && !ver) || (T && !tri)) return false;
+    return !nd_misaligned(ver, 4) && !nd_misaligned(tri, 4);
+}
+
+static bool nd_grid_ok(const float* lo, float cell, const int32_t* dims) {
+    if (!nd_dims_ok(dims) || !(cell > 0.f) || !nd_finite(cell)) return false;
+    return nd_finite(lo[0]) && nd_finite(lo[1]) && nd_finite(lo[2]);
+}
+
+// ---------------------------------------------------------------------------------------------------------- device pieces
+
+__device__ __forceinline__ bool nd_is_finite(float x) { return x - x == 0.f; }
+
+// the finaliser of splitmix64 (nfl_simplify.hip's)
+__device__ __forceinline__ u64 nd_mix(u64 x) {
+    x ^= x >> 30;
+    x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27;
+    x *= 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return x;
+}
+
+__device__ __forceinline__ int nd_cellf(float x, float lo, float cell, int n) {
+    return (int)fminf(fmaxf(floorf((x - lo) / cell), 0.f), (float)(n - 1));
+}
+
+__device__ __forceinline__ float nd_dot(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+
+__device__ __forceinline__ void nd_cross(const float* a, const float* b, float* c) {
+    c[0] = a[1] * b[2] - a[2] * b[1];
+    c[1] = a[2] * b[0] - a[0] * b[2];
+    c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// the corners of triangle t; false when it is not usable
+__device__ __forceinline__ bool nd_corners(const float* ver, const int32_t* tri, i64 V, i64 t, float* a, float* b, float* c) {
+    const int32_t ia = tri[3 * t], ib = tri[3 * t + 1], ic = tri[3 * t + 2];
+    if (!nm_in_range(ia, ib, ic, V)) return false;
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        a[k] = ver[3 * (i64)ia + k];
+        b[k] = ver[3 * (i64)ib + k];
+        c[k] = ver[3 * (i64)ic + k];
+        ok = ok && nd_is_finite(a[k]) && nd_is_finite(b[k]) && nd_is_finite(c[k]);
+    }
+    return ok;
+}
+
+// the index box of a usable triangle
+__device__ __forceinline__ void nd_box(const NdGrid& G, const float* a, const float* b, const float* c, int* i0, int* i1) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        i0[k] = nd_cellf(fminf(fminf(a[k], b[k]), c[k]), G.lo[k], G.cell, G.dims[k]);
+        i1[k] = nd_cellf(fmaxf(fmaxf(a[k], b[k]), c[k]), G.lo[k], G.cell, G.dims[k]);
+    }
+}
+
+// POINT AND TRIANGLE of the header: q, (u, v, w) and dd for the query p.  The regions and the parameters in fp64 -- the
+// 2 x 2 determinants cancel, and in fp32 a sliver of marching tetrahedra put q 3e-6 from a point that lay ON it -- q rounded
+// to fp32, clamped, and the distance in fp32
+__device__ __forceinline__ double nd_dot64(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+
+__device__ __forceinline__ float nd_point_triangle(const float* p, const float* a, const float* b, const float* c, float* q,
+                                                   float* uvw) {
+    double ab[3], ac[3], bc[3], ap[3], bp[3], cp[3], A[3], B[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        A[k] = (double)a[k], B[k] = (double)b[k];
+        ab[k] = B[k] - A[k];
+        ac[k] = (double)c[k] - A[k];
+        bc[k] = (double)c[k] - B[k];
+        ap[k] = (double)p[k] - A[k];
+        bp[k] = (double)p[k] - B[k];
+        cp[k] = (double)p[k] - (double)c[k];
+    }
+    const double d1 = nd_dot64(ab, ap), d2 = nd_dot64(ac, ap), d3 = nd_dot64(ab, bp), d4 = nd_dot64(ac, bp);
+    const double d5 = nd_dot64(ab, cp), d6 = nd_dot64(ac, cp);
+    const double vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    double u, v, w, Q[3];
+    if (d1 <= 0.0 && d2 <= 0.0) {
+        u = 1.0, v = 0.0, w = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) Q[k] = A[k];
+    } else if (d3 >= 0.0 && d4 <= d3) {
+        u = 0.0, v = 1.0, w = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) Q[k] = B[k];
+    } else if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {
+        const double s = d1 / (d1 - d3);
+        u = 1.0 - s, v = s, w = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) Q[k] = A[k] + s * ab[k];
+    } else if (d6 >= 0.0 && d5 <= d6) {
+        u = 0.0, v = 0.0, w = 1.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) Q[k] = (double)c[k];
+    } else if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {
+        const double s = d2 / (d2 - d6);
+        u = 1.0 - s, v = 0.0, w = s;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) Q[k] = A[k] + s * ac[k];
+    } else if (va <= 0.0 && d4 - d3 >= 0.0 && d5 - d6 >= 0.0) {
+        const double s = (d4 - d3) / ((d4 - d3) + (d5 - d6));
+        u = 0.0, v = 1.0 - s, w = s;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) Q[k] = B[k] + s * bc[k];
+    } else {
+        const double den = 1.0 / ((va + vb) + vc), s = vb * den, r = vc * den;
+        u = (1.0 - s) - r, v = s, w = r;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) Q[k] = (A[k] + s * ab[k]) + r * ac[k];
+    }
+    uvw[0] = (float)u, uvw[1] = (float)v, uvw[2] = (float)w;
+    float e[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float mn = fminf(fminf(a[k], b[k]), c[k]), mx = fmaxf(fmaxf(a[k], b[k]), c[k]);
+        q[k] = (float)Q[k];
+        q[k] = q[k] < mn ? mn : (q[k] > mx ? mx : q[k]);                // a NaN stays
+        e[k] = p[k] - q[k];
+    }
+    return (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+}
+
+// the best candidate of a query so far
+struct NdBest {
+    float dd;
+    int32_t t;
+    float q[3], uvw[3];
+};
+
+__device__ __forceinline__ void nd_try(NdBest& B, const float* p, int32_t t, const float* a, const float* b, const float* c,
+                                       float limit) {
+    float q[3], uvw[3];
+    const float dd = nd_point_triangle(p, a, b, c, q, uvw);
+    if (dd <= limit && dd < INFINITY && (dd < B.dd || (dd == B.dd && t < B.t))) {
+        B.dd = dd;
+        B.t = t;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) B.q[k] = q[k], B.uvw[k] = uvw[k];
+    }
+}
+
+// --------------------------------------------------------------------------------------------------------------- the grid
+
+extern "C" size_t nfl_trigrid_bytes(int32_t nx, int32_t ny, int32_t nz) {
+    const int32_t dims[3] = {nx, ny, nz};
+    if (!nd_dims_ok(dims)) return 0;
+    return ng_bytes(nd_grid_layout((i64)nx * ny * nz));
+}
+
+typedef NgLayout<ND_G_REGIONS> NdGridScratch;
+
+static int nd_grid_carve(const nfl_trigrid_args* a, NdGridScratch& S) {
+    if (!a || !nd_mesh_ok(a->d_vertices, a->d_triangles, a->n_vertices, a->n_triangles)) return NFL_EINVAL;
+    if (!nd_grid_ok(a->lo, a->cell, a->dims)) return NFL_EINVAL;
+    S = nd_grid_layout((i64)a->dims[0] * a->dims[1] * a->dims[2]);
+    return ng_carve(S, a->d_scratch, a->scratch_bytes);
+}
+
+static NdGrid nd_grid_of(const float* lo, float cell, const int32_t* dims) {
+    return {{lo[0], lo[1], lo[2]}, cell, {dims[0], dims[1], dims[2]}};
+}
+
+__global__ __launch_bounds__(NM_THREADS) void nfl_trigrid_zero_kernel(int32_t* cnt, i64 cells, i64* totals) {
+    const i64 c = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
+    if (c < cells) cnt[c] = 0;
+    if (c == 0 && totals) totals[1] = 0;
+}
+
+// FILL false: count the cells' triangles; true: write triangle t into its rows
+template <bool FILL>
+__global__ __launch_bounds__(NM_THREADS) void nfl_trigrid_walk_kernel(const float* ver, const int32_t* tri, i64 V, i64 T,
+                                                                      const NdGrid G, int32_t* cnt, const i64* off,
+                                                                      i64 n_entries, int32_t* entries, i64* n_outside) {
+    const i64 t = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
+    bool outside = false;
+    if (t < T) {
+        float a[3], b[3], c[3];
+        outside = !nm_in_range(tri[3 * t], tri[3 * t + 1], tri[3 * t + 2], V);
+        if (nd_corners(ver, tri, V, t, a, b, c)) {
+            int i0[3], i1[3];
+            nd_box(G, a, b, c, i0, i1);
+            for (int z = i0[2]; z <= i1[2]; ++z)
+                for (int y = i0[1]; y <= i1[1]; ++y)
+                    for (int x = i0[0]; x <= i1[0]; ++x) {
+                        const i64 cell = ((i64)z * G.dims[1] + y) * G.dims[0] + x;
+                        const int32_t k = atomicAdd(cnt + cell, 1);
+                        if (FILL) {
+                            const i64 at = off[cell] + k;
+                            if (k >= 0 && at >= 0 && at < n_entries) entries[at] = (int32_t)t;      // the counts of the count call put it there
+                        }
+                    }
+        }
+    }
+    if (!FILL) ng_count_bad(outside, n_outside);
+}
+
+extern "C" int nfl_trigrid_count(const nfl_trigrid_args* a, void* stream) {
+    NdGridScratch S;
+    const int rc = nd_grid_carve(a, S);
+    if (rc != NFL_OK) return rc;
+    if (!a->d_totals || nd_misaligned(a->d_totals, 8)) return NFL_EINVAL;
+    const i64 cells = (i64)a->dims[0] * a->dims[1] * a->dims[2], T = a->n_triangles;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int32_t* cnt = S.get<int32_t>(ND_G_CNT);
+    hipLaunchKernelGGL(nfl_trigrid_zero_kernel, dim3(nm_grid(cells)), dim3(NM_THREADS), 0, s, cnt, cells, a->d_totals);
+    if (T)
+        hipLaunchKernelGGL(nfl_trigrid_walk_kernel<false>, dim3(nm_grid(T)), dim3(NM_THREADS), 0, s, a->d_vertices, a->d_triangles,
+                           a->n_vertices, T, nd_grid_of(a->lo, a->cell, a->dims), cnt, nullptr, 0, nullptr, a->d_totals + 1);
+    nm_scan(cnt, S.get<i64>(ND_G_OFF), cells, S.get<i64>(ND_G_SUMS), a->d_totals, s);
+    return ng_launched() ? NFL_OK : NFL_ELAUNCH;
+}
+
+// thread c of cells + 1: the offset (the total at the end), and the cursor of cell c back to zero
+__global__ __launch_bounds__(NM_THREADS) void nfl_trigrid_offsets_kernel(const i64* off, i64 cells, i64 n_entries, i64* out,
+                                                                         int32_t* cnt) {
+    const i64 c = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
+    if (c > cells) return;
+    const i64 o = c < cells ? off[c] : n_entries;
+    out[c] = o < 0 ? 0 : o > n_entries ? n_entries : o;
+    if (c < cells) cnt[c] = 0;
+}
+
+extern "C" int nfl_trigrid_emit(const nfl_trigrid_args* a, void* stream) {
+    NdGridScratch S;
+    const int rc = nd_grid_carve(a, S);
+    if (rc != NFL_OK) return rc;
+    if (a->n_entries < 0 || a->n_entries > ND_MAX_ENTRIES) return NFL_EINVAL;
+    if (!a->d_offsets || nd_misaligned(a->d_offsets, 8)) return NFL_EINVAL;
+    if (a->n_entries && (!a->d_entries || nd_misaligned(a->d_entries, 4))) return NFL_EINVAL;
+    const i64 cells = (i64)a->dims[0] * a->dims[1] * a->dims[2], T = a->n_triangles;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int32_t* cnt = S.get<int32_t>(ND_G_CNT);
+    const i64* off = S.get<i64>(ND_G_OFF);
+    hipLaunchKernelGGL(nfl_trigrid_offsets_kernel, dim3(nm_grid(cells + 1)), dim3(NM_THREADS), 0, s, off, cells, a->n_entries,
+                       a->d_offsets, cnt);
+    if (T && a->n_entries)
+        hipLaunchKernelGGL(nfl_trigrid_walk_kernel<true>, dim3(nm_grid(T)), dim3(NM_THREADS), 0, s, a->d_vertices, a->d_triangles,
+                           a->n_vertices, T, nd_grid_of(a->lo, a->cell, a->dims), cnt, off, a->n_entries, a->d_entries, nullptr);
+    return ng_launched() ? NFL_OK : NFL_ELAUNCH;
+}
+
+// ---------------------------------------------------------------------------------------------------------- closest point
+
+// g * g of the header for one face: the face at index i of axis k, p beyond it by G in fp64
+__device__ __forceinline__ float nd_face_bound(const NdGrid& G, int k, int i, float p, bool low_side) {
+    const double lo = (double)G.lo[k], ic = (double)i * (double)G.cell;
+    const double F = lo + ic, S = 4.76837158203125e-07 * (fabs(lo) + ic);              // 2^-21
+    double gap = low_side ? (double)p - (F + S) : (F - S) - (double)p;
+    if (!(gap > 0.0)) gap = 0.0;
+    const float g = (float)(gap * (1.0 - 1.1920928955078125e-07));                      // 1 - 2^-23
+    return g * g;
+}
+
+// one row of the grid, read inside the arrays whatever it holds
+__device__ __forceinline__ void nd_try_row(NdBest& B, const float* p, const nfl_mesh_closest_args& a, i64 cell, float limit) {
+    i64 r0 = a.d_offsets[cell], r1 = a.d_offsets[cell + 1];
+    r0 = r0 < 0 ? 0 : r0;
+    r1 = r1 > a.n_entries ? a.n_entries : r1;
+    ND_DEBUG_ADD(1, 1);
+    for (i64 e = r0; e < r1; ++e) {
+        const int32_t t = a.d_entries[e];
+        if (t < 0 || t >= a.n_triangles) continue;
+        float ca[3], cb[3], cc[3];
+        if (!nd_corners(a.d_vertices, a.d_triangles, a.n_vertices, t, ca, cb, cc)) continue;
+        ND_DEBUG_ADD(0, 1);
+        nd_try(B, p, t, ca, cb, cc, limit);
+    }
+}
+
+__device__ __forceinline__ int nd_iabs(int x) { return x < 0 ? -x : x; }
+
+__device__ __forceinline__ void nd_walk_grid(NdBest& B, const float* p, const nfl_mesh_closest_args& a, float limit) {
+    const NdGrid G = {{a.lo[0], a.lo[1], a.lo[2]}, a.cell, {a.dims[0], a.dims[1], a.dims[2]}};
+    int c[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[k] = nd_cellf(p[k], G.lo[k], G.cell, G.dims[k]);
+    ND_DEBUG_ADD(2, 1);
+    const int r_max = max(max(G.dims[0], G.dims[1]), G.dims[2]);        // the block is the whole grid by then
+    for (int r = 0; r <= r_max; ++r) {
+        int b0[3], b1[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) b0[k] = max(c[k] - r, 0), b1[k] = min(c[k] + r, G.dims[k] - 1);
+        for (int z = b0[2]; z <= b1[2]; ++z)
+            for (int y = b0[1]; y <= b1[1]; ++y) {
+                const i64 row = ((i64)z * G.dims[1] + y) * G.dims[0];
+                if (nd_iabs(z - c[2]) == r || nd_iabs(y - c[1]) == r) {
+                    for (int x = b0[0]; x <= b1[0]; ++x) nd_try_row(B, p, a, row + x, limit);
+                } else {
+                    if (c[0] - r >= 0) nd_try_row(B, p, a, row + (c[0] - r), limit);
+                    if (r > 0 && c[0] + r < G.dims[0]) nd_try_row(B, p, a, row + (c[0] + r), limit);
+                }
+            }
+        float bound = INFINITY;
+        bool whole = true;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (b0[k] > 0) bound = fminf(bound, nd_face_bound(G, k, b0[k], p[k], true)), whole = false;
+            if (b1[k] < G.dims[k] - 1) bound = fminf(bound, nd_face_bound(G, k, b1[k] + 1, p[k], false)), whole = false;
+        }
+        if (whole || B.dd < bound || bound > limit) return;
+    }
+}
+
+template <bool GRID>
+__global__ __launch_bounds__(NM_THREADS) void nfl_mesh_closest_kernel(const nfl_mesh_closest_args a) {
+    const i64 n = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
+    const bool mine = n < a.n_points;
+    float p[3] = {0.f, 0.f, 0.f};
+    if (mine) p[0] = a.d_points[3 * n], p[1] = a.d_points[3 * n + 1], p[2] = a.d_points[3 * n + 2];
+    const bool asks = mine && nd_is_finite(p[0]) && nd_is_finite(p[1]) && nd_is_finite(p[2]);
+    const float limit = a.max_distance * a.max_distance;
+    NdBest B;
+    B.dd = INFINITY, B.t = -1;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) B.q[k] = B.uvw[k] = NAN;
+    if (GRID) {
+        if (asks) nd_walk_grid(B, p, a, limit);
+    } else {
+        __shared__ float corner[9][ND_TILE];
+        __shared__ int32_t usable[ND_TILE];
+        for (i64 base = 0; base < a.n_triangles; base += ND_TILE) {     // the same trips for every thread: barriers inside
+            const i64 t = base + threadIdx.x;
+            float ca[3] = {0.f, 0.f, 0.f}, cb[3] = {0.f, 0.f, 0.f}, cc[3] = {0.f, 0.f, 0.f};
+            const bool ok = t < a.n_triangles && nd_corners(a.d_vertices, a.d_triangles, a.n_vertices, t, ca, cb, cc);
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                corner[k][threadIdx.x] = ca[k];
+                corner[3 + k][threadIdx.x] = cb[k];
+                corner[6 + k][threadIdx.x] = cc[k];
+            }
+            usable[threadIdx.x] = ok ? 1 : 0;
+            __syncthreads();
+            if (asks) {
+                const int len = (int)(a.n_triangles - base < ND_TILE ? a.n_triangles - base : ND_TILE);
+                for (int j = 0; j < len; ++j) {
+                    if (!usable[j]) continue;
+                    const float ta[3] = {corner[0][j], corner[1][j], corner[2][j]};
+                    const float tb[3] = {corner[3][j], corner[4][j], corner[5][j]};
+                    const float tc[3] = {corner[6][j], corner[7][j], corner[8][j]};
+                    nd_try(B, p, (int32_t)(base + j), ta, tb, tc, limit);
+                }
+            }
+        }
+    }
+    if (!mine) return;
+    a.d_distance[n] = B.t >= 0 ? sqrtf(B.dd) : INFINITY;
+    a.d_triangle[n] = B.t;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) a.d_point[3 * n + k] = B.q[k], a.d_bary[3 * n + k] = B.uvw[k];
+    if (a.d_dot) {
+        float dot = NAN;
+        float ca[3], cb[3], cc[3];
+        if (B.t >= 0 && nd_corners(a.d_vertices, a.d_triangles, a.n_vertices, B.t, ca, cb, cc)) {
+            const float ab[3] = {cb[0] - ca[0], cb[1] - ca[1], cb[2] - ca[2]}, ac[3] = {cc[0] - ca[0], cc[1] - ca[1], cc[2] - ca[2]};
+            float cr[3];
+            nd_cross(ab, ac, cr);
+            const float len = sqrtf(nd_dot(cr, cr));
+            float nf[3] = {0.f, 0.f, 0.f};
+            if (len > 0.f) nf[0] = cr[0] / len, nf[1] = cr[1] / len, nf[2] = cr[2] / len;
+            const float nq[3] = {a.d_normals[3 * n], a.d_normals[3 * n + 1], a.d_normals[3 * n + 2]};
+            dot = nd_dot(nq, nf);
+        }
+        a.d_dot[n] = dot;
+    }
+}
+
+extern "C" int nfl_mesh_closest(const nfl_mesh_closest_args* a, void* stream) {
+    if (!a || a->n_points < 0 || a->n_points > ND_MAX_ENTRIES) return NFL_EINVAL;
+    if (!nd_mesh_ok(a->d_vertices, a->d_triangles, a->n_vertices, a->n_triangles)) return NFL_EINVAL;
+    if (!(a->max_distance > 0.f)) return NFL_EINVAL;                                    // NaN included
+    if ((a->d_normals == nullptr) != (a->d_dot == nullptr)) return NFL_EINVAL;
+    const bool grid = a->d_offsets != nullptr;
+    if (grid) {
+        if (!nd_grid_ok(a->lo, a->cell, a->dims) || nd_misaligned(a->d_offsets, 8)) return NFL_EINVAL;
+        if (a->n_entries < 0 || a->n_entries > ND_MAX_ENTRIES) return NFL_EINVAL;
+        if (a->n_entries && (!a->d_entries || nd_misaligned(a->d_entries, 4))) return NFL_EINVAL;
+    }
+    if (a->n_points == 0) return NFL_OK;
+    const void* need[] = {a->d_points, a->d_distance, a->d_triangle, a->d_point, a->d_bary};
+    for (const void* p : need)
+        if (!p || nd_misaligned(p, 4)) return NFL_EINVAL;
+    if (nd_misaligned(a->d_normals, 4) || nd_misaligned(a->d_dot, 4)) return NFL_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (grid)
+        hipLaunchKernelGGL(nfl_mesh_closest_kernel<true>, dim3(nm_grid(a->n_points)), dim3(NM_THREADS), 0, s, *a);
+    else
+        hipLaunchKernelGGL(nfl_mesh_closest_kernel<false>, dim3(nm_grid(a->n_points)), dim3(NM_THREADS), 0, s, *a);
+    return ng_launched() ? NFL_OK : NFL_ELAUNCH;
+}
+
+// -------------------------------------------------------------------------------------------------------- surface samples
+
+extern "C" size_t nfl_mesh_sample_bytes(int64_t T) {
+    if (!nm_sizes_ok(0, T)) return 0;
+    return ng_bytes(nd_sample_layout(T));
+}
+
+typedef NgLayout<ND_S_REGIONS> NdSampleScratch;
+
+// Checks shared by count and emit.  NFL_OK with T == 0 means: nothing to carve.
+static int nd_sample_carve(const nfl_mesh_sample_args* a, NdSampleScratch& S) {
+    if (!a || !nd_mesh_ok(a->d_vertices, a->d_triangles, a->n_vertices, a->n_triangles)) return NFL_EINVAL;
+    if (!(a->density >= 0.f) || !nd_finite(a->density)) return NFL_EINVAL;
+    S = nd_sample_layout(a->n_triangles);
+    if (a->n_triangles == 0) return NFL_OK;
+    return ng_carve(S, a->d_scratch, a->scratch_bytes);
+}
+
+// cr and len of triangle t from its corners; the hash of the triangle
+struct NdFace {
+    float a[3], e1[3], e2[3], cr[3], len;
+};
+
+__device__ __forceinline__ bool nd_face(const float* ver, const int32_t* tri, i64 V, i64 t, NdFace& f) {
+    float b[3], c[3];
+    if (!nd_corners(ver, tri, V, t, f.a, b, c)) return false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) f.e1[k] = b[k] - f.a[k], f.e2[k] = c[k] - f.a[k];
+    nd_cross(f.e1, f.e2, f.cr);
+    f.len = sqrtf(nd_dot(f.cr, f.cr));
+    return f.len > 0.f && nd_is_finite(f.len);
+}
+
+#define ND_2M24 5.9604644775390625e-08f                     // 2^-24
+
+__global__ __launch_bounds__(NM_THREADS) void nfl_mesh_sample_count_kernel(const float* ver, const int32_t* tri, i64 V, i64 T,
+                                                                           float density, u64 seed, int32_t* cnt, i64* totals) {
+    const i64 t = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
+    bool outside = false, dense = false;
+    if (t < T) {
+        outside = !nm_in_range(tri[3 * t], tri[3 * t + 1], tri[3 * t + 2], V);
+        NdFace f;
+        int32_t m = 0;
+        if (nd_face(ver, tri, V, t, f)) {
+            const u64 ht = nd_mix(nd_mix(seed) + (u64)t);
+            const float ut = (float)(ht >> 40) * ND_2M24;
+            const float x = (0.5f * f.len) * density + ut;
+            dense = !(x < ND_MAX_SAMPLES_PER_TRIANGLE);
+            m = dense ? 0 : (int32_t)floorf(x);
+        }
+        cnt[t] = m;
+    }
+    ng_count_bad(outside, totals + 1);
+    ng_count_bad(dense, totals + 2);
+}
+
+__global__ __launch_bounds__(64) void nfl_mesh_sample_zero_kernel(i64* totals) {
+    if (threadIdx.x < 3) totals[threadIdx.x] = 0;
+}
+
+extern "C" int nfl_mesh_sample_count(const nfl_mesh_sample_args* a, void* stream) {
+    NdSampleScratch S;
+    const int rc = nd_sample_carve(a, S);
+    if (rc != NFL_OK) return rc;
+    if (!a->d_totals || nd_misaligned(a->d_totals, 8)) return NFL_EINVAL;
+    const i64 T = a->n_triangles;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(nfl_mesh_sample_zero_kernel, dim3(1), dim3(64), 0, s, a->d_totals);
+    if (T) {
+        int32_t* cnt = S.get<int32_t>(ND_S_CNT);
+        hipLaunchKernelGGL(nfl_mesh_sample_count_kernel, dim3(nm_grid(T)), dim3(NM_THREADS), 0, s, a->d_vertices, a->d_triangles,
+                           a->n_vertices, T, a->density, a->seed, cnt, a->d_totals);
+        nm_scan(cnt, S.get<i64>(ND_S_OFF), T, S.get<i64>(ND_S_SUMS), a->d_totals, s);
+    }
+    return ng_launched() ? NFL_OK : NFL_ELAUNCH;
+}
+
+// sample j of triangle t to row `at`
+__device__ __forceinline__ void nd_emit_sample(const nfl_mesh_sample_args& a, const NdFace& f, u64 ht, i64 t, int32_t j, i64 at) {
+    if (at < 0 || at >= a.n_samples) return;
+    const u64 hj = nd_mix(ht + (u64)(j + 1));
+    float r1 = ((float)(hj >> 40) + 0.5f) * ND_2M24, r2 = ((float)((hj >> 16) & 0xFFFFFFull) + 0.5f) * ND_2M24;
+    if (r1 + r2 > 1.f) r1 = 1.f - r1, r2 = 1.f - r2;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        a.d_points[3 * at + k] = (f.a[k] + r1 * f.e1[k]) + r2 * f.e2[k];
+        a.d_normals[3 * at + k] = f.cr[k] / f.len;
+    }
+    a.d_sample_triangles[at] = (int32_t)t;
+}
+
+__global__ __launch_bounds__(NM_THREADS) void nfl_mesh_sample_emit_kernel(const nfl_mesh_sample_args a, const int32_t* cnt,
+                                                                          const i64* off) {
+    const i64 t = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    int32_t m = 0;
+    i64 o = 0;
+    NdFace f;
+    u64 ht = 0;
+    if (t < a.n_triangles) {
+        m = cnt[t];
+        o = off[t];
+        if (m < 0 || m > (int32_t)ND_MAX_SAMPLES_PER_TRIANGLE || !nd_face(a.d_vertices, a.d_triangles, a.n_vertices, t, f)) m = 0;
+        ht = nd_mix(nd_mix(a.seed) + (u64)t);
+    }
+    if (m <= ND_WAVE_SAMPLES)
+        for (int32_t j = 0; j < m; ++j) nd_emit_sample(a, f, ht, t, j, o + j);
+    // the larger triangles of the wave's lanes, one after the other, every lane 1 / 64 of the samples
+    u64 todo = __ballot(m > ND_WAVE_SAMPLES);
+    while (todo) {
+        const int src = __ffsll(todo) - 1;
+        todo &= todo - 1;
+        const i64 wt = t - lane + src;                                  // that lane's triangle
+        const int32_t wm = __shfl(m, src);
+        const i64 wo = __shfl(o, src);
+        NdFace wf;
+        if (!nd_face(a.d_vertices, a.d_triangles, a.n_vertices, wt, wf)) continue;     // the same for every lane
+        const u64 wh = nd_mix(nd_mix(a.seed) + (u64)wt);
+        for (int32_t j = lane; j < wm; j += 64) nd_emit_sample(a, wf, wh, wt, j, wo + j);
+    }
+}
+
+extern "C" int nfl_mesh_sample_emit(const nfl_mesh_sample_args* a, void* stream) {
+    NdSampleScratch S;
+    const int rc = nd_sample_carve(a, S);
+    if (rc != NFL_OK) return rc;
+    if (a->n_samples < 0 || a->n_samples > ND_MAX_ENTRIES) return NFL_EINVAL;
+    if (a->n_samples == 0 || a->n_triangles == 0) return NFL_OK;
+    const void* need[] = {a->d_points, a->d_sample_triangles, a->d_normals};
+    for (const void* p : need)
+        if (!p || nd_misaligned(p, 4)) return NFL_EINVAL;
+    hipLaunchKernelGGL(nfl_mesh_sample_emit_kernel, dim3(nm_grid(a->n_triangles)), dim3(NM_THREADS), 0,
+                       static_cast<hipStream_t>(stream), *a, S.get<int32_t>(ND_S_CNT), S.get<i64>(ND_S_OFF));
+    return ng_launched() ? NFL_OK : NFL_ELAUNCH;
+}
+
+// ------------------------------------------------------------------------------------------------------------- reduction
+
+extern "C" size_t nfl_meshdist_reduce_bytes(int64_t n) {
+    if (n < 0 || n > ND_MAX_ENTRIES) return 0;
+    return ng_bytes(nd_reduce_layout(n));
+}
+
+#define ND_COLS NFL_MESHDIST_COLUMNS
+
+// the 256 rows of red folded by halving into red[..][0]; column NFL_MESHDIST_MAX by fmax, the others by +
+__device__ __forceinline__ void nd_fold(double (*red)[256]) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (tid < off) {
+#pragma unroll
+            for (int k = 0; k < ND_COLS; ++k)
+                red[k][tid] = k == NFL_MESHDIST_MAX ? fmax(red[k][tid], red[k][tid + off]) : red[k][tid] + red[k][tid + off];
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void nfl_meshdist_parts_kernel(const nfl_meshdist_reduce_args a, double* parts) {
+    __shared__ double red[ND_COLS][256];
+    const int tid = threadIdx.x;
+    double acc[ND_COLS];
+#pragma unroll
+    for (int k = 0; k < ND_COLS; ++k) acc[k] = 0.0;
+    for (i64 i = (i64)blockIdx.x * 256 + tid; i < a.n; i += (i64)gridDim.x * 256) {
+        const float d = a.d_distance[i];
+        if (!(d < INFINITY)) continue;                                  // +inf and NaN: missing
+        const double x = (double)d;
+        acc[NFL_MESHDIST_COUNT] += 1.0;
+        acc[NFL_MESHDIST_SUM] += x;
+        acc[NFL_MESHDIST_SUM_SQ] += x * x;
+        acc[NFL_MESHDIST_MAX] = fmax(acc[NFL_MESHDIST_MAX], x);
+#pragma unroll
+        for (int k = 0; k < NFL_MESHDIST_MAX_TAU; ++k)
+            if (k < a.n_tau && d <= a.tau[k]) acc[NFL_MESHDIST_WITHIN + k] += 1.0;
+        if (a.d_dot) acc[NFL_MESHDIST_SUM_DOT] += fabs((double)a.d_dot[i]);
+    }
+#pragma unroll
+    for (int k = 0; k < ND_COLS; ++k) red[k][tid] = acc[k];
+    nd_fold(red);
+    if (tid < ND_COLS) parts[(size_t)blockIdx.x * ND_COLS + tid] = red[tid][0];
+}
+
+__global__ __launch_bounds__(256) void nfl_meshdist_finish_kernel(const double* parts, int n_parts, double* row) {
+    __shared__ double red[ND_COLS][256];
+    const int tid = threadIdx.x;
+    double acc[ND_COLS];
+#pragma unroll
+    for (int k = 0; k < ND_COLS; ++k) acc[k] = 0.0;
+    for (int i = tid; i < n_parts; i += 256) {
+#pragma unroll
+        for (int k = 0; k < ND_COLS; ++k) {
+            const double v = parts[(size_t)i * ND_COLS + k];
+            acc[k] = k == NFL_MESHDIST_MAX ? fmax(acc[k], v) : acc[k] + v;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < ND_COLS; ++k) red[k][tid] = acc[k];
+    nd_fold(red);
+    if (tid < ND_COLS) row[tid] = red[tid][0];
+}
+
+extern "C" int nfl_meshdist_reduce(const nfl_meshdist_reduce_args* a, void* stream) {
+    if (!a || a->n < 0 || a->n > ND_MAX_ENTRIES || !a->d_row || nd_misaligned(a->d_row, 8)) return NFL_EINVAL;
+    if (a->n_tau < 0 || a->n_tau > NFL_MESHDIST_MAX_TAU) return NFL_EINVAL;
+    for (int k = 0; k < a->n_tau; ++k)
+        if (a->tau[k] != a->tau[k]) return NFL_EINVAL;
+    if (a->n && (!a->d_distance || nd_misaligned(a->d_distance, 4))) return NFL_EINVAL;
+    if (nd_misaligned(a->d_dot, 4)) return NFL_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const double* parts = nullptr;
+    const i64 blocks = nd_reduce_blocks(a->n);
+    if (blocks) {
+        NgLayout<ND_R_REGIONS> S = nd_reduce_layout(a->n);
+        const int rc = ng_carve(S, a->d_scratch, a->scratch_bytes);
+        if (rc != NFL_OK) return rc;
+        hipLaunchKernelGGL(nfl_meshdist_parts_kernel, dim3((unsigned)blocks), dim3(256), 0, s, *a, S.get<double>(ND_R_PARTS));
+        parts = S.get<double>(ND_R_PARTS);
+    }
+    hipLaunchKernelGGL(nfl_meshdist_finish_kernel, dim3(1), dim3(256), 0, s, parts, (int)blocks, a->d_row);
+    return ng_launched() ? NFL_OK : NFL_ELAUNCH;
+}
