@@ -2,6 +2,11 @@
 
 There is no fallback: if the shared library is missing or does not export the
 ABI this package was written against, importing a renderer entry point raises.
+
+The mirror is written by hand and names itself: STRUCTS, SYMBOLS and CONSTANTS below list every struct, entry point and
+constant repeated here, and tests/test_abi_cpu.py holds each of them to the header.  NFL_ABI_VERSION moves when an
+existing struct or signature changes; a new symbol or struct alone does not move it (a library that lacks a symbol
+already fails in lib(), which looks every SYMBOLS entry up).
 """
 import ctypes as C
 import os
@@ -154,8 +159,6 @@ class AppFitArgs(C.Structure):
                 ("d_partials", C.c_void_p), ("d_grad", C.c_void_p), ("d_loss", C.c_void_p), ("d_rgb", C.c_void_p)]
 
 
-# nfl_gather_batch (data.ImageBank) was added without moving NFL_ABI_VERSION: no existing struct or signature changed, and
-# a library that lacks the symbol already fails in lib() below (every SYMBOLS entry is looked up)
 NFL_LAYOUT_WORLD, NFL_LAYOUT_CAMERA = 0, 1
 
 
@@ -171,7 +174,6 @@ class GatherArgs(C.Structure):
                 ("reserved", C.c_int32), ("d_rays", C.c_void_p), ("d_ts", C.c_void_p), ("d_rgb", C.c_void_p)]
 
 
-# nfl_image_metrics / nfl_depth_image (nerf_fl_amd.metrics) were added the same way: new symbols, no struct changed
 NFL_METRIC_COLUMNS = 8
 
 
@@ -190,14 +192,11 @@ class DepthArgs(C.Structure):
                 ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
 
 
-# nfl_depth_bounds (data.depth_bounds) likewise: a new symbol and a new struct, nothing existing moved, so NFL_ABI_VERSION
-# stays where the header has it
 class BoundsArgs(C.Structure):
     _fields_ = [("d_xyz", C.c_void_p), ("d_row", C.c_void_p), ("n_points", C.c_int32), ("n_images", C.c_int32),
                 ("q_lo", C.c_double), ("q_hi", C.c_double), ("d_bounds", C.c_void_p), ("d_count", C.c_void_p)]
 
 
-# nfl_surface_* (nerf_fl_amd.geometry) likewise: three new symbols and a new struct
 class SurfaceArgs(C.Structure):
     _fields_ = [("d_lattice", C.c_void_p), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("iso", C.c_float),
                 ("lo", C.c_float * 3), ("spacing", C.c_float * 3), ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_size_t),
@@ -205,7 +204,6 @@ class SurfaceArgs(C.Structure):
                 ("d_vertices", C.c_void_p), ("d_normals", C.c_void_p), ("d_triangles", C.c_void_p)]
 
 
-# nfl_mesh_* (nerf_fl_amd.geometry: components, table, compaction) likewise: six new symbols and three new structs
 class MeshLabelArgs(C.Structure):
     _fields_ = [("d_triangles", C.c_void_p), ("n_vertices", C.c_int64), ("n_triangles", C.c_int64),
                 ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_size_t), ("d_component", C.c_void_p),
@@ -228,7 +226,6 @@ class MeshCompactArgs(C.Structure):
                 ("d_out_triangles", C.c_void_p)]
 
 
-# nfl_mesh_simplify_* (nerf_fl_amd.geometry: vertex clustering) likewise: three new symbols and a new struct
 SIMPLIFY_LAMBDA = 1e-3
 SIMPLIFY_PLACEMENTS = {"mean": 0, "quadric": 1}
 
@@ -242,8 +239,6 @@ class MeshSimplifyArgs(C.Structure):
                 ("d_out_colors", C.c_void_p), ("d_out_triangles", C.c_void_p)]
 
 
-# nfl_mesh_adjacency_* / nfl_mesh_smooth / nfl_mesh_normals (nerf_fl_amd.geometry: smoothing) likewise: six new symbols and
-# three new structs
 SMOOTH_MAX_STEPS = 1024
 ADJ_SHORT_ROW = 24
 NORMAL_WEIGHTINGS = {"area": 0, "uniform": 1}
@@ -272,7 +267,6 @@ class MeshNormalsArgs(C.Structure):
                 ("d_fallback_normals", C.c_void_p), ("d_out_normals", C.c_void_p)]
 
 
-# nfl_occ_* (nerf_fl_amd.geometry: occupancy grid, ray clipping) likewise: four new symbols and two new structs
 class OccBuildArgs(C.Structure):
     _fields_ = [("d_lattice", C.c_void_p), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
                 ("threshold", C.c_float), ("dilate", C.c_int32), ("reserved", C.c_int32), ("d_scratch", C.c_void_p),
@@ -285,7 +279,6 @@ class OccClipArgs(C.Structure):
                 ("reserved", C.c_int32), ("d_near_far", C.c_void_p), ("d_hit", C.c_void_p)]
 
 
-# nfl_mesh_depth / nfl_mesh_blend (nerf_fl_amd.geometry: mesh colour from the images) likewise: two new symbols and structs
 BLEND_WEIGHTINGS = {"cos": 0, "uniform": 1}
 
 
@@ -303,8 +296,6 @@ class MeshBlendArgs(C.Structure):
                 ("start", C.c_int32), ("d_sum", C.c_void_p), ("d_views", C.c_void_p)]
 
 
-# nfl_mesh_visibility / nfl_mesh_shade (nerf_fl_amd.geometry: a coloured mesh rendered to images) likewise: two new symbols
-# and structs
 SHADE_MODES = {"color": 0, "normal": 1, "facing": 2}
 VIS_EMPTY = -1                                  # 2^64 - 1 as the int64 that torch holds the words in
 
@@ -323,8 +314,6 @@ class MeshShadeArgs(C.Structure):
                 ("d_rgb_u8", C.c_void_p), ("d_depth", C.c_void_p), ("d_triangle", C.c_void_p)]
 
 
-# nfl_atlas_points / nfl_atlas_resolve / nfl_mesh_shade_atlas (nerf_fl_amd.geometry: a texture atlas baked from the images and
-# sampled by the shading pass) likewise: three new symbols and structs
 ATLAS_MIN_CELL, ATLAS_MAX_CELL = 6, 1024
 
 
@@ -352,8 +341,6 @@ class MeshShadeAtlasArgs(C.Structure):
                 ("d_rgb", C.c_void_p), ("d_rgb_u8", C.c_void_p), ("d_depth", C.c_void_p), ("d_triangle", C.c_void_p)]
 
 
-# nfl_tsdf_fuse / nfl_tsdf_resolve / nfl_tsdf_support (nerf_fl_amd.fusion: depth maps fused into a TSDF lattice) likewise:
-# three new symbols and structs
 class TsdfFuseArgs(C.Structure):
     _fields_ = [("d_table", C.c_void_p), ("n_images", C.c_int32), ("first", C.c_int32), ("count", C.c_int32),
                 ("start", C.c_int32), ("d_depth", C.c_void_p), ("n_depth", C.c_int64), ("d_pixel_weights", C.c_void_p),
@@ -374,8 +361,6 @@ class TsdfSupportArgs(C.Structure):
                 ("spacing", C.c_float * 3), ("d_support", C.c_void_p)]
 
 
-# nfl_trigrid_* / nfl_mesh_closest / nfl_mesh_sample_* / nfl_meshdist_reduce (nerf_fl_amd.meshdist: the distance between two
-# meshes) likewise: nine new symbols and four new structs
 MESHDIST_MAX_TAU = 8
 MESHDIST_COLUMNS = 13                           # count, sum, sum of squares, max, 8 x within tau, sum of |dot|
 
@@ -410,7 +395,49 @@ class MeshDistReduceArgs(C.Structure):
                 ("scratch_bytes", C.c_size_t), ("d_row", C.c_void_p)]
 
 
-# every symbol include/nerf_fl_amd.h declares: (name, restype, argtypes)
+# every struct include/nerf_fl_amd.h declares: C name -> its mirror
+STRUCTS = {
+    "nfl_field_desc": FieldDesc, "nfl_field_params": FieldParams, "nfl_pack_job": PackJob, "nfl_camera": Camera,
+    "nfl_pass_args": PassArgs, "nfl_compbwd_args": CompBwdArgs, "nfl_dgrad_args": DgradArgs,
+    "nfl_field_grads": FieldGrads, "nfl_adam_tensors": AdamTensors, "nfl_optim_tensors": OptimTensors,
+    "nfl_loss_args": LossArgs, "nfl_pose_args": PoseArgs, "nfl_appfit_args": AppFitArgs, "nfl_image_rec": ImageRec,
+    "nfl_gather_args": GatherArgs, "nfl_metrics_args": MetricsArgs, "nfl_depth_args": DepthArgs,
+    "nfl_bounds_args": BoundsArgs, "nfl_surface_args": SurfaceArgs, "nfl_mesh_label_args": MeshLabelArgs,
+    "nfl_mesh_stats_args": MeshStatsArgs, "nfl_mesh_compact_args": MeshCompactArgs,
+    "nfl_mesh_simplify_args": MeshSimplifyArgs, "nfl_mesh_adjacency_args": MeshAdjacencyArgs,
+    "nfl_mesh_smooth_args": MeshSmoothArgs, "nfl_mesh_normals_args": MeshNormalsArgs,
+    "nfl_occ_build_args": OccBuildArgs, "nfl_occ_clip_args": OccClipArgs, "nfl_mesh_depth_args": MeshDepthArgs,
+    "nfl_mesh_blend_args": MeshBlendArgs, "nfl_mesh_visibility_args": MeshVisibilityArgs,
+    "nfl_mesh_shade_args": MeshShadeArgs, "nfl_atlas_points_args": AtlasPointsArgs,
+    "nfl_atlas_resolve_args": AtlasResolveArgs, "nfl_mesh_shade_atlas_args": MeshShadeAtlasArgs,
+    "nfl_tsdf_fuse_args": TsdfFuseArgs, "nfl_tsdf_resolve_args": TsdfResolveArgs,
+    "nfl_tsdf_support_args": TsdfSupportArgs, "nfl_trigrid_args": TriGridArgs,
+    "nfl_mesh_closest_args": MeshClosestArgs, "nfl_mesh_sample_args": MeshSampleArgs,
+    "nfl_meshdist_reduce_args": MeshDistReduceArgs,
+}
+
+# every constant of the header (#define or enum) that this module repeats: C name -> the value held here
+CONSTANTS = {
+    "NFL_ABI_VERSION": NFL_ABI_VERSION, "NFL_GMAX_SLOTS": NFL_GMAX_SLOTS,
+    "NFL_PREC_F16X3": NFL_PREC_F16X3, "NFL_PREC_F16": NFL_PREC_F16, "NFL_PREC_F16W": NFL_PREC_F16W,
+    "NFL_STATUS_NONFINITE": NFL_STATUS_NONFINITE, "NFL_STATUS_RANGE": NFL_STATUS_RANGE,
+    "NFL_STATUS_POSE_ID": NFL_STATUS_POSE_ID, "NFL_NUM_LAYERS": NFL_NUM_LAYERS,
+    "NFL_PACK_MAX_JOBS": NFL_PACK_MAX_JOBS, "NFL_ADAM_MAX_TENSORS": NFL_ADAM_MAX_TENSORS,
+    "NFL_OPT_SGD": NFL_OPT_SGD, "NFL_OPT_ADAM": NFL_OPT_ADAM, "NFL_OPT_RADAM": NFL_OPT_RADAM,
+    "NFL_OPT_RANGER": NFL_OPT_RANGER, "NFL_OPT_HYPER": NFL_OPT_HYPER,
+    "NFL_LAYOUT_WORLD": NFL_LAYOUT_WORLD, "NFL_LAYOUT_CAMERA": NFL_LAYOUT_CAMERA,
+    "NFL_METRIC_COLUMNS": NFL_METRIC_COLUMNS,
+    "NFL_SIMPLIFY_LAMBDA": SIMPLIFY_LAMBDA,
+    "NFL_SIMPLIFY_MEAN": SIMPLIFY_PLACEMENTS["mean"], "NFL_SIMPLIFY_QUADRIC": SIMPLIFY_PLACEMENTS["quadric"],
+    "NFL_SMOOTH_MAX_STEPS": SMOOTH_MAX_STEPS, "NFL_ADJ_SHORT_ROW": ADJ_SHORT_ROW,
+    "NFL_NORMALS_AREA": NORMAL_WEIGHTINGS["area"], "NFL_NORMALS_UNIFORM": NORMAL_WEIGHTINGS["uniform"],
+    "NFL_BLEND_COS": BLEND_WEIGHTINGS["cos"], "NFL_BLEND_UNIFORM": BLEND_WEIGHTINGS["uniform"],
+    "NFL_SHADE_COLOR": SHADE_MODES["color"], "NFL_SHADE_NORMAL": SHADE_MODES["normal"],
+    "NFL_SHADE_FACING": SHADE_MODES["facing"],
+    "NFL_MESHDIST_MAX_TAU": MESHDIST_MAX_TAU, "NFL_MESHDIST_COLUMNS": MESHDIST_COLUMNS,
+}
+
+# every function include/nerf_fl_amd.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("nfl_plan_bytes", C.c_size_t, [C.POINTER(FieldDesc)]),
     ("nfl_plan_build", C.c_int, [C.POINTER(FieldDesc), C.c_int, C.c_void_p, C.c_size_t]),

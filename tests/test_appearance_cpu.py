@@ -1,41 +1,13 @@
 """Appearance fitting (nerf_fl_amd.appearance, C ABI nfl_appearance_cache / nfl_appearance_fit): what can be checked
-without a device -- the exported symbols, the ctypes mirror of nfl_appfit_args, argument validation."""
+without a device -- argument validation (nfl_appfit_args and the signatures are held to the header in
+tests/test_abi_cpu.py)."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import pytest
 import torch
 
 from nerf_fl_amd import NeRF, PosEmbedding, _lib
 from nerf_fl_amd.appearance import AppearanceFit
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("nfl_appearance_cache", "nfl_appfit_partials_floats", "nfl_appearance_fit")
-
-
-def test_new_symbols_are_exported():
-    names = [s[0] for s in _lib.SYMBOLS]
-    L = _lib.lib()
-    for n in NEW:
-        assert n in names
-        getattr(L, n)
-    assert L.nfl_abi_version() == _lib.NFL_ABI_VERSION == 10
-
-
-def test_appfit_args_layout_matches_the_header():
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "nerf_fl_amd.h"\nint main(void) {\n'
-           '  printf("%zu %zu %zu\\n", sizeof(nfl_appfit_args), offsetof(nfl_appfit_args, n_rays), '
-           'offsetof(nfl_appfit_args, d_partials));\n  return 0;\n}\n')
-    with tempfile.TemporaryDirectory() as td:
-        c, exe = os.path.join(td, "sz.c"), os.path.join(td, "sz")
-        with open(c, "w") as f:
-            f.write(src)
-        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe], check=True)
-        size, off_n, off_p = map(int, subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split())
-    assert size == C.sizeof(_lib.AppFitArgs)
-    assert off_n == _lib.AppFitArgs.n_rays.offset and off_p == _lib.AppFitArgs.d_partials.offset
 
 
 def test_c_argument_validation():

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import data_util as du
+from abi_probe import probe
 from nerf_fl_amd import _lib, data
 
 
@@ -168,18 +169,9 @@ def test_gather_entry_point_validates_arguments():
     assert L.nfl_gather_batch(C.byref(a), None) == 0                        # every output NULL: nothing to launch
 
 
-def test_struct_layouts_match_the_header(tmp_path):
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    names = {"nfl_image_rec": _lib.ImageRec, "nfl_gather_args": _lib.GatherArgs}
-    src = '#include <stdio.h>\n#include "nerf_fl_amd.h"\nint main(void) {\n' + "".join(
-        f'  printf("{n} %zu\\n", sizeof({n}));\n' for n in names) + "  return 0;\n}\n"
-    (tmp_path / "sz.c").write_text(src)
-    subprocess.run(["gcc", "-I", os.path.join(root, "include"), str(tmp_path / "sz.c"), "-o", str(tmp_path / "sz")], check=True)
-    out = subprocess.run([str(tmp_path / "sz")], check=True, capture_output=True, text=True).stdout
-    sizes = dict(line.split() for line in out.strip().splitlines())
-    for n, cls in names.items():
-        assert int(sizes[n]) == C.sizeof(cls), n
-    assert data.RECORD.itemsize == C.sizeof(_lib.ImageRec)
+def test_struct_layouts_match_the_header():
+    """data.RECORD against the compiled nfl_image_rec (every struct's ctypes mirror: tests/test_abi_cpu.py)."""
+    rec = probe()["structs"]["nfl_image_rec"]
+    assert data.RECORD.itemsize == rec["size"] == C.sizeof(_lib.ImageRec)
     for name, _ in _lib.ImageRec._fields_:
-        assert data.RECORD.fields[name][1] == getattr(_lib.ImageRec, name).offset, name
+        assert data.RECORD.fields[name][1] == rec["fields"][name][0] == getattr(_lib.ImageRec, name).offset, name

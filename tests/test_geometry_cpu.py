@@ -1,6 +1,6 @@
 """CPU-side checks of the geometry feature (nerf_fl_amd.geometry, csrc/nfl_surface.hip): the numpy restatement of the
 extraction (tests/geometry_ref.py), which the GPU tests hold the kernels to, is itself checked on an analytic volume;
-write_ply round-trips; the three C entry points exist and refuse bad arguments.  No kernel is launched."""
+write_ply round-trips; the three C entry points size their scratch and refuse bad arguments.  No kernel is launched."""
 import ctypes as C
 import os
 
@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import geometry_ref as gr
+from abi_probe import L  # noqa: F401  (a fixture)
 
 R0, N = 0.6, 24
 
@@ -196,16 +197,7 @@ def test_geometry_rejects_host_inputs():
     assert p[0, 0, 0].tolist() == [-1, 0, 1] and p[2, 3, 4].tolist() == [1, 3, 2]
 
 
-# ---- the C ABI, without a GPU (in the manner of test_capi_cpu.py)
-
-@pytest.fixture(scope="module")
-def L():
-    from nerf_fl_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return _lib.lib()
-
+# ---- the C entry points, without a GPU (structs and signatures: tests/test_abi_cpu.py)
 
 def test_surface_symbols_exported(L):
     for name in ("nfl_surface_bytes", "nfl_surface_count", "nfl_surface_emit"):

@@ -1,18 +1,16 @@
 """CPU-side checks of the mesh cleaning (nerf_fl_amd.geometry.mesh_components / filter_mesh / clean_mesh,
 csrc/nfl_mesh.hip): the numpy restatement (tests/mesh_ref.py), which the GPU tests hold the kernels to, on hand-written
-cases and on the three-ball lattice; the new argument structs against the header; everything the C entry points refuse
-before a launch.  No kernel is launched."""
+cases and on the three-ball lattice; everything the C entry points refuse before a launch (their structs and signatures
+are held to the header in tests/test_abi_cpu.py).  No kernel is launched."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import geometry_ref as gr
 import mesh_ref as mr
+from abi_probe import L  # noqa: F401  (a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, ESMALL = -1, -4
 
 
@@ -115,47 +113,11 @@ def test_three_balls_on_the_restatements():
 
 # ---- the C ABI, without a GPU
 
-@pytest.fixture(scope="module")
-def L():
-    from nerf_fl_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return _lib.lib()
-
-
-MESH_SYMBOLS = ("nfl_mesh_label_bytes", "nfl_mesh_label", "nfl_mesh_stats", "nfl_mesh_compact_bytes",
-                "nfl_mesh_compact_count", "nfl_mesh_compact_emit")
-
-
-def test_mesh_symbols_bound_and_exported(L):
-    from nerf_fl_amd import _lib, geometry
-    bound = {name for name, _, _ in _lib.SYMBOLS}
-    for name in MESH_SYMBOLS:
-        assert name in bound and hasattr(L, name)
-    assert _lib.NFL_ABI_VERSION == 10 == L.nfl_abi_version()               # new symbols only: the number stays
+def test_mesh_symbols_bound_and_exported():
+    """The stages are exported by the geometry package (the C symbols under them: tests/test_abi_cpu.py)."""
+    from nerf_fl_amd import geometry
     for name in ("mesh_components", "filter_mesh", "clean_mesh"):
         assert name in geometry.__all__ and callable(getattr(geometry, name))
-
-
-def test_mesh_arg_structs_match_the_header(tmp_path):
-    from nerf_fl_amd import _lib
-    structs = {"nfl_mesh_label_args": _lib.MeshLabelArgs, "nfl_mesh_stats_args": _lib.MeshStatsArgs,
-               "nfl_mesh_compact_args": _lib.MeshCompactArgs}
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "nerf_fl_amd.h"\nint main(void) {\n'
-    for name, cls in structs.items():
-        src += f'  printf("%zu\\n", sizeof({name}));\n'
-        src += "".join(f'  printf("%zu\\n", offsetof({name}, {f}));\n' for f, _ in cls._fields_)
-    src += "  return 0;\n}\n"
-    (tmp_path / "sz.c").write_text(src)
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(tmp_path / "sz.c"), "-o", str(tmp_path / "sz")], check=True)
-    out = [int(x) for x in subprocess.run([str(tmp_path / "sz")], check=True, capture_output=True, text=True).stdout.split()]
-    for name, cls in structs.items():
-        n = len(cls._fields_)
-        assert out[0] == C.sizeof(cls), name
-        assert out[1:1 + n] == [getattr(cls, f).offset for f, _ in cls._fields_], name
-        out = out[1 + n:]
-    assert C.sizeof(_lib.MeshLabelArgs) == 56 and C.sizeof(_lib.MeshStatsArgs) == 72 and C.sizeof(_lib.MeshCompactArgs) == 144
 
 
 def _tiles(n, tile=2048):

@@ -1,62 +1,28 @@
 """CPU-side checks of mesh colour (nerf_fl_amd.geometry.mesh_depth / color_mesh_from_images, csrc/nfl_meshcolor.hip): the
-C entry points exist, mirror the header and refuse bad arguments before any launch; the numpy restatement
+C entry points refuse bad arguments before any launch (their structs and signatures are held to the header in
+tests/test_abi_cpu.py); the numpy restatement
 (tests/meshcolor_ref.py), which the GPU tests hold the kernels to bit for bit, is itself checked on hand cases whose
 expected numbers are written out and, independent of its own fp32 arithmetic, against the same algorithm in fp64 on a
 seeded triangle soup.  No kernel is launched."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import meshcolor_ref as mref
+from abi_probe import L, probe  # noqa: F401  (L is a fixture)
 from nerf_fl_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 EINVAL = -1
 INF = np.inf
 
 
-@pytest.fixture(scope="module")
-def L():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return _lib.lib()
+# ---- the image record and validation ------------------------------------------------------------------------------------------------
 
-
-# ---- ABI and validation ------------------------------------------------------------------------------------------------
-
-@pytest.mark.parametrize("struct,name,size", [(_lib.MeshDepthArgs, "nfl_mesh_depth_args", 72),
-                                              (_lib.MeshBlendArgs, "nfl_mesh_blend_args", 120)])
-def test_structs_mirror_the_header(tmp_path, struct, name, size):
-    fields = [n for n, _ in struct._fields_]
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "nerf_fl_amd.h"\nint main(void) {\n'
-           f'  printf("%zu %d %zu\\n", sizeof({name}), NFL_ABI_VERSION, sizeof(nfl_image_rec));\n'
-           + "".join(f'  printf("%zu\\n", offsetof({name}, {n}));\n' for n in fields) + "  return 0;\n}\n")
-    (tmp_path / "sz.c").write_text(src)
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(tmp_path / "sz.c"), "-o", str(tmp_path / "sz")], check=True)
-    out = subprocess.run([str(tmp_path / "sz")], check=True, capture_output=True, text=True).stdout.split()
-    assert int(out[0]) == C.sizeof(struct) == size
-    assert int(out[1]) == 10
-    assert int(out[2]) == mref.RECORD.itemsize == C.sizeof(_lib.ImageRec) == 104
-    assert [int(x) for x in out[3:]] == [getattr(struct, n).offset for n in fields]
-
-
-def test_symbols_exported_and_abi_unchanged(L):
-    names = [s[0] for s in _lib.SYMBOLS]
-    for n in ("nfl_mesh_depth", "nfl_mesh_blend"):
-        assert n in names
-        getattr(L, n)
-    assert _lib.NFL_ABI_VERSION == L.nfl_abi_version() == 10
-    header = open(os.path.join(ROOT, "include", "nerf_fl_amd.h")).read()
-    assert re.search(r"int nfl_mesh_depth\(const nfl_mesh_depth_args\* args, void\* stream\);", header)
-    assert re.search(r"int nfl_mesh_blend\(const nfl_mesh_blend_args\* args, void\* stream\);", header)
-    assert _lib.BLEND_WEIGHTINGS == {"cos": 0, "uniform": 1}
-    assert re.search(r"enum \{ NFL_BLEND_COS = 0, NFL_BLEND_UNIFORM = 1 \};", header)
+def test_the_restatement_reads_the_image_record_of_the_header():
+    assert probe()["structs"]["nfl_image_rec"]["size"] == mref.RECORD.itemsize == C.sizeof(_lib.ImageRec) == 104
+    assert _lib.BLEND_WEIGHTINGS == {"cos": 0, "uniform": 1}               # held to the header's enum in test_abi_cpu.py
 
 
 def _depth_args():

@@ -1,17 +1,17 @@
-"""CPU-side checks of the mesh distance (nerf_fl_amd.meshdist, csrc/nfl_meshdist.hip): the nine C entry points exist, mirror
-the header and refuse bad arguments before any launch; the module stands beside the geometry package without growing it; the
-numpy restatement (tests/meshdist_ref.py), which the GPU tests hold the kernels to bit for bit, is checked on hand cases whose
-expected numbers are written out, and on two squares whose distances are known in closed form; read_ply reads back what
-write_ply writes.  No kernel is launched."""
+"""CPU-side checks of the mesh distance (nerf_fl_amd.meshdist, csrc/nfl_meshdist.hip): the nine C entry points refuse bad
+arguments before any launch (their structs and signatures are held to the header in tests/test_abi_cpu.py); the module stands
+beside the geometry package without growing it; the numpy restatement (tests/meshdist_ref.py), which the GPU tests hold the
+kernels to bit for bit, is checked on hand cases whose expected numbers are written out, and on two squares whose distances
+are known in closed form; read_ply reads back what write_ply writes.  No kernel is launched."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import meshdist_ref as dref
+from abi_probe import L, probe  # noqa: F401  (L is a fixture)
 from nerf_fl_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,47 +20,16 @@ EINVAL, ESMALL = -1, -4
 INF, NAN = np.inf, np.nan
 
 
-@pytest.fixture(scope="module")
-def L():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return _lib.lib()
+# ---- sources and validation ------------------------------------------------------------------------------------------------
+
+def test_the_restatement_has_the_columns_of_the_header():
+    constants = probe()["constants"]
+    assert ((constants["NFL_MESHDIST_COLUMNS"], constants["NFL_MESHDIST_MAX_TAU"]) == (_lib.MESHDIST_COLUMNS, _lib.MESHDIST_MAX_TAU)
+            == (dref.COLUMNS, dref.MAX_TAU))
 
 
-# ---- ABI and validation ------------------------------------------------------------------------------------------------
-
-@pytest.mark.parametrize("struct,name,size", [(_lib.TriGridArgs, "nfl_trigrid_args", 112),
-                                              (_lib.MeshClosestArgs, "nfl_mesh_closest_args", 152),
-                                              (_lib.MeshSampleArgs, "nfl_mesh_sample_args", 104),
-                                              (_lib.MeshDistReduceArgs, "nfl_meshdist_reduce_args", 88)])
-def test_structs_mirror_the_header(tmp_path, struct, name, size):
-    fields = [n for n, _ in struct._fields_]
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "nerf_fl_amd.h"\nint main(void) {\n'
-           f'  printf("%zu %d %d %d\\n", sizeof({name}), NFL_ABI_VERSION, NFL_MESHDIST_COLUMNS, NFL_MESHDIST_MAX_TAU);\n'
-           + "".join(f'  printf("%zu\\n", offsetof({name}, {n}));\n' for n in fields) + "  return 0;\n}\n")
-    (tmp_path / "sz.c").write_text(src)
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(tmp_path / "sz.c"), "-o", str(tmp_path / "sz")], check=True)
-    out = subprocess.run([str(tmp_path / "sz")], check=True, capture_output=True, text=True).stdout.split()
-    assert int(out[0]) == C.sizeof(struct) == size
-    assert int(out[1]) == 10
-    assert (int(out[2]), int(out[3])) == (_lib.MESHDIST_COLUMNS, _lib.MESHDIST_MAX_TAU) == (dref.COLUMNS, dref.MAX_TAU)
-    assert [int(x) for x in out[4:]] == [getattr(struct, n).offset for n in fields]
-
-
-NAMES = ("nfl_trigrid_bytes", "nfl_trigrid_count", "nfl_trigrid_emit", "nfl_mesh_closest", "nfl_mesh_sample_bytes",
-         "nfl_mesh_sample_count", "nfl_mesh_sample_emit", "nfl_meshdist_reduce_bytes", "nfl_meshdist_reduce")
-
-
-def test_symbols_exported_and_abi_unchanged(L):
-    names = [s[0] for s in _lib.SYMBOLS]
-    header = open(os.path.join(ROOT, "include", "nerf_fl_amd.h")).read()
-    for n in NAMES:
-        assert n in names
-        getattr(L, n)
-        assert re.search(rf"\b{n}\(", header)
-    assert _lib.NFL_ABI_VERSION == L.nfl_abi_version() == 10
-    assert "#define NFL_ABI_VERSION 10" in header and "---- mesh distance:" in header
+def test_the_unit_is_built_and_has_its_section():
+    assert "---- mesh distance:" in open(os.path.join(ROOT, "include", "nerf_fl_amd.h")).read()
     make = open(os.path.join(ROOT, "nerf_fl_amd", "csrc", "Makefile")).read()
     assert "nfl_meshdist.o" in make.split("all:")[0]                       # in OBJS
     assert re.search(r"^nfl_meshdist\.o:.*nfl_geom\.h.*nfl_geom_layout\.h", make, flags=re.M)

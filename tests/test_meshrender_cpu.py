@@ -1,5 +1,6 @@
 """CPU-side checks of mesh render (nerf_fl_amd.geometry.mesh_visibility / render_mesh, csrc/nfl_meshrender.hip): the C entry
-points exist, mirror the header and refuse bad arguments before any launch; the numpy restatement (tests/meshrender_ref.py),
+points refuse bad arguments before any launch (their structs and signatures are held to the header in
+tests/test_abi_cpu.py); the numpy restatement (tests/meshrender_ref.py),
 which the GPU tests hold the kernels to bit for bit, is itself checked on hand cases whose expected numbers are written out
 and, independent of its own fp32 arithmetic, against the same algorithm in fp64 on the seeded triangle soup.  No kernel is
 launched."""
@@ -13,6 +14,7 @@ import pytest
 
 import meshcolor_ref as mref
 import meshrender_ref as rref
+from abi_probe import L  # noqa: F401  (a fixture)
 from nerf_fl_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,42 +23,11 @@ EINVAL = -1
 INF = np.inf
 
 
-@pytest.fixture(scope="module")
-def L():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return _lib.lib()
+# ---- sources and validation ------------------------------------------------------------------------------------------------
 
-
-# ---- ABI and validation ------------------------------------------------------------------------------------------------
-
-@pytest.mark.parametrize("struct,name,size", [(_lib.MeshVisibilityArgs, "nfl_mesh_visibility_args", 72),
-                                              (_lib.MeshShadeArgs, "nfl_mesh_shade_args", 128)])
-def test_structs_mirror_the_header(tmp_path, struct, name, size):
-    fields = [n for n, _ in struct._fields_]
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "nerf_fl_amd.h"\nint main(void) {\n'
-           f'  printf("%zu %d\\n", sizeof({name}), NFL_ABI_VERSION);\n'
-           + "".join(f'  printf("%zu\\n", offsetof({name}, {n}));\n' for n in fields) + "  return 0;\n}\n")
-    (tmp_path / "sz.c").write_text(src)
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(tmp_path / "sz.c"), "-o", str(tmp_path / "sz")], check=True)
-    out = subprocess.run([str(tmp_path / "sz")], check=True, capture_output=True, text=True).stdout.split()
-    assert int(out[0]) == C.sizeof(struct) == size
-    assert int(out[1]) == 10
-    assert [int(x) for x in out[2:]] == [getattr(struct, n).offset for n in fields]
-
-
-def test_symbols_exported_and_abi_unchanged(L):
-    names = [s[0] for s in _lib.SYMBOLS]
-    for n in ("nfl_mesh_visibility", "nfl_mesh_shade"):
-        assert n in names
-        getattr(L, n)
-    assert _lib.NFL_ABI_VERSION == L.nfl_abi_version() == 10
+def test_shade_modes_and_the_header_s_sections():
+    assert _lib.SHADE_MODES == {"color": 0, "normal": 1, "facing": 2}      # held to the header's enum in test_abi_cpu.py
     header = open(os.path.join(ROOT, "include", "nerf_fl_amd.h")).read()
-    assert re.search(r"int nfl_mesh_visibility\(const nfl_mesh_visibility_args\* args, void\* stream\);", header)
-    assert re.search(r"int nfl_mesh_shade\(const nfl_mesh_shade_args\* args, void\* stream\);", header)
-    assert _lib.SHADE_MODES == {"color": 0, "normal": 1, "facing": 2}
-    assert re.search(r"enum \{ NFL_SHADE_COLOR = 0, NFL_SHADE_NORMAL = 1, NFL_SHADE_FACING = 2 \};", header)
     assert header.index("---- mesh colour") < header.index("---- mesh render") < header.index("---- hierarchical sampling")
 
 

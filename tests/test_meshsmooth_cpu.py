@@ -2,17 +2,17 @@
 csrc/nfl_meshsmooth.hip): the numpy restatement (tests/meshsmooth_ref.py), which the GPU tests hold the kernels to, on
 hand-written cases with the expected rows and flags written out; the condition under which the GPU test may compare
 positions on the bits (the order of the triangles and the rotation of their corners change nothing); what smoothing is
-for, on a noisy ball; the new argument structs against the header; everything refused before a launch.  No kernel is
-launched."""
+for, on a noisy ball; everything refused before a launch (the argument structs and the signatures are held to the header
+in tests/test_abi_cpu.py).  No kernel is launched."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import meshsmooth_ref as mr
+from abi_probe import L  # noqa: F401  (a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, ESMALL = -1, -4
@@ -235,50 +235,13 @@ def test_recomputed_normals_agree_with_the_extractor():
 
 # ---- the C ABI, without a GPU
 
-@pytest.fixture(scope="module")
-def L():
-    from nerf_fl_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return _lib.lib()
-
-
-SYMBOLS = ("nfl_mesh_adjacency_bytes", "nfl_mesh_adjacency_count", "nfl_mesh_adjacency_emit", "nfl_mesh_smooth_bytes",
-           "nfl_mesh_smooth", "nfl_mesh_normals")
-
-
-def test_smoothing_symbols_bound_and_exported(L):
+def test_smoothing_symbols_bound_and_exported():
+    """The stages are exported by the geometry package with the constants pinned (the C symbols under them: tests/test_abi_cpu.py)."""
     from nerf_fl_amd import _lib, geometry
-    bound = {name for name, _, _ in _lib.SYMBOLS}
-    for name in SYMBOLS:
-        assert name in bound and hasattr(L, name)
-    assert _lib.NFL_ABI_VERSION == 10 == L.nfl_abi_version()               # new symbols only: the number stays
     for name in ("mesh_adjacency", "smooth_mesh", "vertex_normals"):
         assert name in geometry.__all__ and callable(getattr(geometry, name))
-
-
-def test_arg_structs_and_constants_match_the_header(tmp_path):
-    from nerf_fl_amd import _lib
-    structs = ((_lib.MeshAdjacencyArgs, "nfl_mesh_adjacency_args", 104), (_lib.MeshSmoothArgs, "nfl_mesh_smooth_args", 96),
-               (_lib.MeshNormalsArgs, "nfl_mesh_normals_args", 80))
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "nerf_fl_amd.h"\nint main(void) {\n'
-    for cls, name, _ in structs:
-        src += f'  printf("%zu\\n", sizeof({name}));\n'
-        src += "".join(f'  printf("%zu\\n", offsetof({name}, {f}));\n' for f, _ in cls._fields_)
-    src += ('  printf("%d %d %d %d %d\\n", NFL_SMOOTH_MAX_STEPS, NFL_ADJ_SHORT_ROW, NFL_NORMALS_AREA, NFL_NORMALS_UNIFORM, '
-            'NFL_ABI_VERSION);\n  return 0;\n}\n')
-    (tmp_path / "sz.c").write_text(src)
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(tmp_path / "sz.c"), "-o", str(tmp_path / "sz")], check=True)
-    out = subprocess.run([str(tmp_path / "sz")], check=True, capture_output=True, text=True).stdout.split()
-    at = 0
-    for cls, name, size in structs:
-        n = len(cls._fields_)
-        assert int(out[at]) == C.sizeof(cls) == size, name
-        assert [int(x) for x in out[at + 1:at + 1 + n]] == [getattr(cls, f).offset for f, _ in cls._fields_], name
-        at += 1 + n
-    assert [int(x) for x in out[at:]] == [_lib.SMOOTH_MAX_STEPS, _lib.ADJ_SHORT_ROW, _lib.NORMAL_WEIGHTINGS["area"],
-                                          _lib.NORMAL_WEIGHTINGS["uniform"], 10] == [1024, 24, 0, 1, 10]
+    assert [_lib.SMOOTH_MAX_STEPS, _lib.ADJ_SHORT_ROW, _lib.NORMAL_WEIGHTINGS["area"],
+            _lib.NORMAL_WEIGHTINGS["uniform"]] == [1024, 24, 0, 1]         # held to the header in test_abi_cpu.py
 
 
 def test_unit_stands_on_the_geometry_headers_alone():

@@ -1,59 +1,23 @@
 """CPU-side checks of the occupancy feature (nerf_fl_amd.geometry.occupancy_grid / clip_rays, csrc/nfl_occupancy.hip):
-the C entry points exist, mirror the header and refuse bad arguments before any launch; the numpy restatement
+the C entry points size their buffers and refuse bad arguments before any launch (their structs and signatures are held to
+the header in tests/test_abi_cpu.py); the numpy restatement
 (tests/occupancy_ref.py), which the GPU tests hold the kernels to, is itself checked on hand cases whose expected values
 are plane distances written out, against a brute-force dilation, and -- independent of the walk -- for conservativeness
 and tightness against points sampled densely along random rays.  No kernel is launched."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import occupancy_ref as oref
+from abi_probe import L  # noqa: F401  (a fixture)
 from nerf_fl_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 EINVAL, ESMALL = -1, -4
 
 
-@pytest.fixture(scope="module")
-def L():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return _lib.lib()
-
-
-# ---- ABI and validation ------------------------------------------------------------------------------------------------
-
-@pytest.mark.parametrize("struct,name,size", [(_lib.OccBuildArgs, "nfl_occ_build_args", 56),
-                                              (_lib.OccClipArgs, "nfl_occ_clip_args", 80)])
-def test_structs_mirror_the_header(tmp_path, struct, name, size):
-    fields = [n for n, _ in struct._fields_]
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "nerf_fl_amd.h"\nint main(void) {\n'
-           f'  printf("%zu %d\\n", sizeof({name}), NFL_ABI_VERSION);\n'
-           + "".join(f'  printf("%zu\\n", offsetof({name}, {n}));\n' for n in fields) + "  return 0;\n}\n")
-    (tmp_path / "sz.c").write_text(src)
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(tmp_path / "sz.c"), "-o", str(tmp_path / "sz")], check=True)
-    out = subprocess.run([str(tmp_path / "sz")], check=True, capture_output=True, text=True).stdout.split()
-    assert int(out[0]) == C.sizeof(struct) == size
-    assert int(out[1]) == 10
-    assert [int(x) for x in out[2:]] == [getattr(struct, n).offset for n in fields]
-
-
-def test_symbols_exported_and_abi_unchanged(L):
-    names = [s[0] for s in _lib.SYMBOLS]
-    for n in ("nfl_occ_bytes", "nfl_occ_build_bytes", "nfl_occ_build", "nfl_occ_clip_rays"):
-        assert n in names
-        getattr(L, n)
-    assert _lib.NFL_ABI_VERSION == L.nfl_abi_version() == 10
-    header = open(os.path.join(ROOT, "include", "nerf_fl_amd.h")).read()
-    assert re.search(r"int nfl_occ_build\(const nfl_occ_build_args\* args, void\* stream\);", header)
-    assert re.search(r"int nfl_occ_clip_rays\(const nfl_occ_clip_args\* args, void\* stream\);", header)
-
+# ---- sizes and validation ------------------------------------------------------------------------------------------------
 
 def test_size_queries(L):
     for nx, ny, nz in [(2, 2, 2), (33, 3, 2), (34, 5, 4), (66, 9, 7), (300, 6, 5)]:

@@ -1,30 +1,22 @@
 """CPU checks of the one-launch optimisers and the schedules: argument validation of nfl_optim_step / nfl_optim_step_dev
-(no kernel is launched), the ctypes mirror of nfl_optim_tensors, and make_scheduler against learning-rate sequences
-recorded from the reference's own warm-up scheduler (tests/golden/make_sched_golden.py)."""
+(no kernel is launched; nfl_optim_tensors and the NFL_OPT_* constants are held to the header in tests/test_abi_cpu.py), and
+make_scheduler against learning-rate sequences recorded from the reference's own warm-up scheduler
+(tests/golden/make_sched_golden.py)."""
 import ctypes as C
 import json
 import os
-import subprocess
-import tempfile
 import warnings
 
 import numpy as np
 import pytest
 import torch
 
+from abi_probe import L  # noqa: F401  (a fixture)
 from nerf_fl_amd import _lib
 from nerf_fl_amd.train import SGD, Adam, GradualWarmupLR, RAdam, Ranger, make_optimizer, make_scheduler
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "g21_lr_schedules.npz")
-
-
-@pytest.fixture(scope="module")
-def L():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return _lib.lib()
 
 
 def _hyper(lr=1e-3, b1=0.9, b2=0.999, eps=1e-8, wd=0.0, alpha=0.5, k=6.0, thr=5.0):
@@ -86,22 +78,6 @@ def test_optim_step_dev_validates_arguments(L):
         assert L.nfl_optim_step_dev(C.byref(t), _lib.NFL_ADAM_MAX_TENSORS + 1, kind, d, d, 1, None) == -1
         assert L.nfl_optim_step_dev(C.byref(_lib.OptimTensors()), 0, kind, d, d, 1, None) == 0
     assert L.nfl_optim_step_dev(C.byref(t), 1, 4, d, d, 1, None) == -1
-
-
-def test_optim_tensors_layout_matches_the_header():
-    src = ('#include <stddef.h>\n#include <stdio.h>\n#include "nerf_fl_amd.h"\nint main(void) {\n'
-           '  printf("%zu %zu %zu %d %d %d %d %d\\n", sizeof(nfl_optim_tensors), offsetof(nfl_optim_tensors, state2),\n'
-           '         offsetof(nfl_optim_tensors, numel), NFL_OPT_SGD, NFL_OPT_ADAM, NFL_OPT_RADAM, NFL_OPT_RANGER,\n'
-           '         NFL_OPT_HYPER);\n  return 0;\n}\n')
-    with tempfile.TemporaryDirectory() as td:
-        c, exe = os.path.join(td, "sz.c"), os.path.join(td, "sz")
-        with open(c, "w") as f:
-            f.write(src)
-        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe], check=True)
-        got = [int(x) for x in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
-    O = _lib.OptimTensors
-    assert got == [C.sizeof(O), O.state2.offset, O.numel.offset, _lib.NFL_OPT_SGD, _lib.NFL_OPT_ADAM, _lib.NFL_OPT_RADAM,
-                   _lib.NFL_OPT_RANGER, _lib.NFL_OPT_HYPER]
 
 
 def test_version_string_names_the_abi(L):

@@ -1,12 +1,10 @@
 """nerf_fl_amd.colmap.read_phototourism on the fixture scene (tests/golden/make_photo_golden.py: written by its own COLMAP
 writer, read back by the REAL reference's PhototourismDataset), and what of nfl_depth_bounds can be checked without a
-device: the exported symbol, the ctypes mirror of nfl_bounds_args, the ABI number, argument validation."""
+device: argument validation (nfl_bounds_args and the signature are held to the header in tests/test_abi_cpu.py)."""
 import ctypes as C
 import os
-import re
 import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,7 +12,6 @@ import pytest
 from nerf_fl_amd import _lib, colmap, data
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 SCENE = os.path.join(HERE, "golden", "data_photo")
 
 
@@ -99,28 +96,6 @@ def test_a_file_name_missing_from_images_bin_raises_key_error(tmp_path):
 def test_downscale_below_one_is_refused():
     with pytest.raises(ValueError):
         colmap.read_phototourism(SCENE, 0)
-
-
-def test_bounds_args_layout_symbol_and_abi_agree(tmp_path):
-    """Header, ctypes struct and ABI number, as test_struct_layouts_match_the_header does for the other structs."""
-    names = [s[0] for s in _lib.SYMBOLS]
-    L = _lib.lib()
-    assert "nfl_depth_bounds" in names
-    getattr(L, "nfl_depth_bounds")
-    fields = [n for n, _ in _lib.BoundsArgs._fields_]
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "nerf_fl_amd.h"\nint main(void) {\n'
-           '  printf("%zu %d\\n", sizeof(nfl_bounds_args), NFL_ABI_VERSION);\n'
-           + "".join(f'  printf("%zu\\n", offsetof(nfl_bounds_args, {n}));\n' for n in fields) + "  return 0;\n}\n")
-    (tmp_path / "sz.c").write_text(src)
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(tmp_path / "sz.c"), "-o", str(tmp_path / "sz")], check=True)
-    out = subprocess.run([str(tmp_path / "sz")], check=True, capture_output=True, text=True).stdout.split()
-    assert int(out[0]) == C.sizeof(_lib.BoundsArgs) == 56
-    assert [int(x) for x in out[2:]] == [getattr(_lib.BoundsArgs, n).offset for n in fields]
-    # one ABI number in the header, the binding, the library and its version string
-    assert int(out[1]) == _lib.NFL_ABI_VERSION == L.nfl_abi_version()
-    assert f"abi {_lib.NFL_ABI_VERSION})".encode() in L.nfl_version()
-    header = open(os.path.join(ROOT, "include", "nerf_fl_amd.h")).read()
-    assert re.search(r"int nfl_depth_bounds\(const nfl_bounds_args\* args, void\* stream\);", header)
 
 
 def test_c_argument_validation():

@@ -1,10 +1,7 @@
-"""CPU side of --refine_pose: the pose kernels' C ABI (struct layout, symbols, status bit), the id -> row table, the BARF
-buffer helper and RayTrainer's refine_pose argument checks (which run before it asks for a device)."""
+"""CPU side of --refine_pose: the pose kernels' status bit and argument checks (nfl_pose_args and the signatures are held to
+the header in tests/test_abi_cpu.py), the id -> row table, the BARF buffer helper and RayTrainer's refine_pose argument
+checks (which run before it asks for a device)."""
 import ctypes as C
-import os
-import re
-import subprocess
-import tempfile
 
 import pytest
 import torch
@@ -14,29 +11,9 @@ from nerf_fl_amd.poses import row_table
 from nerf_fl_amd.rendering import fill_barf_weights
 from nerf_fl_amd.train import RayTrainer
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-
-def test_pose_args_layout_matches_the_header():
-    src = ('#include <stdio.h>\n#include "nerf_fl_amd.h"\nint main(void) {\n'
-           '  printf("%zu %d\\n", sizeof(nfl_pose_args), NFL_STATUS_POSE_ID);\n  return 0;\n}\n')
-    with tempfile.TemporaryDirectory() as td:
-        c, exe = os.path.join(td, "sz.c"), os.path.join(td, "sz")
-        with open(c, "w") as f:
-            f.write(src)
-        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe], check=True)
-        size, bit = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()
-    assert int(size) == C.sizeof(_lib.PoseArgs)
-    assert int(bit) == _lib.NFL_STATUS_POSE_ID
+def test_pose_status_bit_is_its_own():
     assert not _lib.NFL_STATUS_POSE_ID & (_lib.NFL_STATUS_RANGE | _lib.NFL_STATUS_NONFINITE)
-
-
-def test_pose_symbols_declared_bound_and_exported():
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "nerf_fl_amd.h")).read(), flags=re.S)
-    bound = {name for name, _, _ in _lib.SYMBOLS}
-    L = _lib.lib()
-    for name in ("nfl_pose_rays", "nfl_pose_rays_backward"):
-        assert re.search(rf"\b{name}\s*\(", hdr) and name in bound and hasattr(L, name)
 
 
 def test_pose_entry_points_reject_bad_arguments_without_a_device():

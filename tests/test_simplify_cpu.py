@@ -1,18 +1,16 @@
 """CPU-side checks of the mesh simplification (nerf_fl_amd.geometry.simplify_mesh, csrc/nfl_simplify.hip): the numpy
 restatement (tests/simplify_ref.py), which the GPU tests hold the kernels to, on hand-written cases with the expected values
 written out, its invariants on random soups, the quadric placement on a cube, and the condition under which the GPU test
-may compare quadric positions to within 2 ulps; the new argument struct against the header; everything refused before a
-launch.  No kernel is launched."""
+may compare quadric positions to within 2 ulps; everything refused before a launch (the argument struct and the
+signatures are held to the header in tests/test_abi_cpu.py).  No kernel is launched."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import simplify_ref as sr
+from abi_probe import L, probe  # noqa: F401  (L is a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, ESMALL = -1, -4
 
 
@@ -231,39 +229,15 @@ def test_ball_mesh_shrinks():
 
 # ---- the C ABI, without a GPU
 
-@pytest.fixture(scope="module")
-def L():
-    from nerf_fl_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return _lib.lib()
-
-
-def test_simplify_symbols_bound_and_exported(L):
-    from nerf_fl_amd import _lib, geometry
-    bound = {name for name, _, _ in _lib.SYMBOLS}
-    for name in ("nfl_mesh_simplify_bytes", "nfl_mesh_simplify_count", "nfl_mesh_simplify_emit"):
-        assert name in bound and hasattr(L, name)
-    assert _lib.NFL_ABI_VERSION == 10 == L.nfl_abi_version()               # new symbols only: the number stays
+def test_simplify_symbols_bound_and_exported():
+    """The stage is exported by the geometry package (the C symbols under it: tests/test_abi_cpu.py)."""
+    from nerf_fl_amd import geometry
     assert "simplify_mesh" in geometry.__all__ and callable(geometry.simplify_mesh)
 
 
-def test_simplify_arg_struct_and_constants_match_the_header(tmp_path):
+def test_the_restatement_regularises_as_the_header_says():
     from nerf_fl_amd import _lib
-    cls, name = _lib.MeshSimplifyArgs, "nfl_mesh_simplify_args"
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "nerf_fl_amd.h"\nint main(void) {\n'
-    src += f'  printf("%zu\\n", sizeof({name}));\n'
-    src += "".join(f'  printf("%zu\\n", offsetof({name}, {f}));\n' for f, _ in cls._fields_)
-    src += '  printf("%d %d %.17g\\n", NFL_SIMPLIFY_MEAN, NFL_SIMPLIFY_QUADRIC, NFL_SIMPLIFY_LAMBDA);\n  return 0;\n}\n'
-    (tmp_path / "sz.c").write_text(src)
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(tmp_path / "sz.c"), "-o", str(tmp_path / "sz")], check=True)
-    out = subprocess.run([str(tmp_path / "sz")], check=True, capture_output=True, text=True).stdout.split()
-    n = len(cls._fields_)
-    assert int(out[0]) == C.sizeof(cls) == 168
-    assert [int(x) for x in out[1:1 + n]] == [getattr(cls, f).offset for f, _ in cls._fields_]
-    assert (int(out[1 + n]), int(out[2 + n])) == (_lib.SIMPLIFY_PLACEMENTS["mean"], _lib.SIMPLIFY_PLACEMENTS["quadric"])
-    assert float(out[3 + n]) == _lib.SIMPLIFY_LAMBDA == sr.LAMBDA == 1e-3
+    assert probe()["constants"]["NFL_SIMPLIFY_LAMBDA"] == _lib.SIMPLIFY_LAMBDA == sr.LAMBDA == 1e-3
 
 
 def _tiles(n, tile=2048):

@@ -1,12 +1,11 @@
-"""CPU-side checks of depth fusion (nerf_fl_amd.fusion, csrc/nfl_tsdf.hip): the three C entry points exist, mirror the header
-and refuse bad arguments before any launch; the module stands beside the geometry package without growing it; the numpy
+"""CPU-side checks of depth fusion (nerf_fl_amd.fusion, csrc/nfl_tsdf.hip): the three C entry points refuse bad arguments before
+any launch (their structs and signatures are held to the header in tests/test_abi_cpu.py); the module stands beside the geometry package without growing it; the numpy
 restatement (tests/tsdf_ref.py), which the GPU tests hold the kernels to bit for bit, is checked on hand cases whose expected
 numbers are written out; and what the issue's prototype claimed of a fused sphere -- a second wall without the support rule,
 a closed surface within one spacing of the sphere with it -- holds on the fp32 restatement.  No kernel is launched."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,6 +14,7 @@ import geometry_ref as gref
 import mesh_ref
 import meshcolor_ref as mref
 import tsdf_ref as tref
+from abi_probe import L  # noqa: F401  (a fixture)
 from nerf_fl_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,41 +23,10 @@ EINVAL = -1
 INF, NAN = np.inf, np.nan
 
 
-@pytest.fixture(scope="module")
-def L():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return _lib.lib()
+# ---- sources and validation ------------------------------------------------------------------------------------------------
 
-
-# ---- ABI and validation ------------------------------------------------------------------------------------------------
-
-@pytest.mark.parametrize("struct,name,size", [(_lib.TsdfFuseArgs, "nfl_tsdf_fuse_args", 112),
-                                              (_lib.TsdfResolveArgs, "nfl_tsdf_resolve_args", 56),
-                                              (_lib.TsdfSupportArgs, "nfl_tsdf_support_args", 72)])
-def test_structs_mirror_the_header(tmp_path, struct, name, size):
-    fields = [n for n, _ in struct._fields_]
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "nerf_fl_amd.h"\nint main(void) {\n'
-           f'  printf("%zu %d\\n", sizeof({name}), NFL_ABI_VERSION);\n'
-           + "".join(f'  printf("%zu\\n", offsetof({name}, {n}));\n' for n in fields) + "  return 0;\n}\n")
-    (tmp_path / "sz.c").write_text(src)
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(tmp_path / "sz.c"), "-o", str(tmp_path / "sz")], check=True)
-    out = subprocess.run([str(tmp_path / "sz")], check=True, capture_output=True, text=True).stdout.split()
-    assert int(out[0]) == C.sizeof(struct) == size
-    assert int(out[1]) == 10
-    assert [int(x) for x in out[2:]] == [getattr(struct, n).offset for n in fields]
-
-
-def test_symbols_exported_and_abi_unchanged(L):
-    names = [s[0] for s in _lib.SYMBOLS]
-    header = open(os.path.join(ROOT, "include", "nerf_fl_amd.h")).read()
-    for n in ("nfl_tsdf_fuse", "nfl_tsdf_resolve", "nfl_tsdf_support"):
-        assert n in names
-        getattr(L, n)
-        assert re.search(rf"int {n}\(const {n}_args\* args, void\* stream\);", header)
-    assert _lib.NFL_ABI_VERSION == L.nfl_abi_version() == 10
-    assert "#define NFL_ABI_VERSION 10" in header and "---- depth fusion:" in header
+def test_the_unit_is_built_and_has_its_section():
+    assert "---- depth fusion:" in open(os.path.join(ROOT, "include", "nerf_fl_amd.h")).read()
     make = open(os.path.join(ROOT, "nerf_fl_amd", "csrc", "Makefile")).read()
     assert "nfl_tsdf.o" in make.split("all:")[0]                           # in OBJS
     assert re.search(r"^nfl_tsdf\.o:.*nfl_meshray\.h", make, flags=re.M)
