@@ -1554,6 +1554,86 @@ typedef struct nfl_meshdist_reduce_args {
 size_t nfl_meshdist_reduce_bytes(int64_t n);
 int nfl_meshdist_reduce(const nfl_meshdist_reduce_args* args, void* stream);
 
+/* ---- registration: the similarity transform x' = s R x + t that brings points onto a mesh (point-to-plane or point-to-point
+ * ICP around nfl_mesh_closest) or onto given partners (the closed form) -------------------------------------------------------
+ * Entry points take pointers and scalars; there is no argument struct.  EVERYTHING HERE IS FP64 unless fp32 is named, every
+ * operation rounded on its own, divisions and square roots correctly rounded, sums of three written (x + y) + z, the fp32
+ * inputs converted first.  A TRANSFORM is NFL_REGISTER_TRANSFORM = 13 doubles in device memory: s, R row-major (9), t (3).
+ *
+ * nfl_register_apply   one thread per row of d_in (n, 3) fp32: y_i = (R_i0 x_0 + R_i1 x_1) + R_i2 x_2, and
+ *   d_out_i = (float)(s * y_i + t_i), with vectors = 1 (float)y_i (normals: rotated only).  The transform is read from device
+ *   memory by the kernel; d_in == d_out is allowed.
+ *
+ * nfl_register_moments   the row d_row (NFL_REGISTER_COLUMNS) of n pairs: P = d_points (the transformed points), Q = d_closest,
+ *   and d_triangle, d_distance as nfl_mesh_closest left them for P.  A pair COUNTS when the six coordinates of P and Q are
+ *   finite, its distance d is below +inf and d <= max_distance (fp32 comparison; +inf: no limit), and its triangle index t lies
+ *   in [0, n_triangles), is USABLE in the sense of "mesh distance" and has a face normal: with ab, ac, cr = cross(ab, ac) and
+ *   len = sqrtf(dot(cr, cr)) IN FP32 as nfl_mesh_closest computes them for d_dot, 0 < len < +inf, and nf = cr / len.  In point
+ *   mode d_distance and d_triangle may each be NULL: that test is then not made (given partners).
+ *   With c = (cx, cy, cz), p = P - c, q = Q - c, e = P - Q:
+ *     NFL_REGISTER_COUNT   1 per counting pair          NFL_REGISTER_SUM_DD   d * d; without d_distance (e0 e0 + e1 e1) + e2 e2
+ *   NFL_REGISTER_POINT:  SUM_P + k = p_k, SUM_Q + k = q_k, SUM_PP = (p0 p0 + p1 p1) + p2 p2, SUM_QQ likewise,
+ *     SUM_PQ + 3 i + j = p_i q_j.
+ *   NFL_REGISTER_PLANE:  N = nf; a = (p x N, N, N . p), a 7-vector: a0 = p1 N2 - p2 N1, a1 = p2 N0 - p0 N2,
+ *     a2 = p0 N1 - p1 N0, a6 = (p0 N0 + p1 N1) + p2 N2; r = (N0 e0 + N1 e1) + N2 e2.  ATA + (the place of (i, j), i <= j, in
+ *     the upper triangle read row by row: 7 i - i (i - 1) / 2 + j - i) = a_i a_j; ATB + i = a_i r; SUM_RR = r r.
+ *   The columns of the other mode are zeros.  The order of the additions is nfl_meshdist_reduce's: G = min(ceil(n / 256), 1024)
+ *   workgroups of 256, thread t of workgroup g adds elements (g + j G) * 256 + t, j = 0, 1, ... in order (a pair that does not
+ *   count adds nothing), the 256 threads are folded by halving, the G partial rows are dealt to the 256 threads of ONE
+ *   workgroup (thread t adds rows t, t + 256, ...) and folded the same way.  No float atomics: the row is bit-reproducible.
+ *   The scratch is nfl_register_bytes(n): a partial row per workgroup.  n == 0 writes the row of zeros.
+ *
+ * nfl_register_solve   one working thread.  From the row an increment (ds, dR, dt), composed IN PLACE into d_transform:
+ *   s <- ds s;  R <- dR R (R_ij = (dR_i0 R_0j + dR_i1 R_1j) + dR_i2 R_2j);  t <- ds (dR t) + dt, dR t as y above.
+ *   d_history[4 iteration ..] = (count, sqrt(SUM_DD / count), status, the s that is left).  Status: NFL_REGISTER_OK;
+ *   NFL_REGISTER_FEW when count < min_pairs; NFL_REGISTER_SINGULAR when a pivot below is not > 0 (a NaN is not) or one of the
+ *   13 new doubles is not finite.  On either failure the transform is left as it was, bit for bit.
+ *   rot(w, x, y, z) of a unit quaternion, by products: R00 = 1 - 2 (yy + zz), R01 = 2 (xy - wz), R02 = 2 (xz + wy),
+ *   R10 = 2 (xy + wz), R11 = 1 - 2 (xx + zz), R12 = 2 (yz - wx), R20 = 2 (xz - wy), R21 = 2 (yz + wx), R22 = 1 - 2 (xx + yy).
+ *   POINT (Horn 1987; Umeyama's problem): n = count, mp = SUM_P / n, mq = SUM_Q / n, M_ij = SUM_PQ_ij - SUM_P_i * mq_j;
+ *     N = the symmetric 4 x 4 matrix  [ (M00 + M11) + M22,  M12 - M21,          M20 - M02,          M01 - M10
+ *                                                         (M00 - M11) - M22,  M01 + M10,          M20 + M02
+ *                                                                             (M11 - M00) - M22,  M12 + M21
+ *                                                                                                 (M22 - M00) - M11 ];
+ *     V = I; 12 sweeps of cyclic Jacobi over (p, q) = (0,1), (0,2), (0,3), (1,2), (1,3), (2,3); a rotation whose A_pq is
+ *     exactly 0 is skipped; g = A_pq, theta = (A_qq - A_pp) / (2 g), t = sgn / (|theta| + sqrt(theta theta + 1)) with
+ *     sgn = 1 for theta >= 0, else -1; c = 1 / sqrt(t t + 1), s = t c; A_pp -= t g, A_qq += t g, A_pq = A_qp = 0; for the
+ *     two other r:  (A_rp, A_rq) <- (c A_rp - s A_rq, s A_rp + c A_rq), mirrored; for all r the same of (V_rp, V_rq).
+ *     The column of V under the largest diagonal entry (the lowest index on a tie) is (w, x, y, z) after scaling by
+ *     1 / sqrt(((v0 v0 + v1 v1) + v2 v2) + v3 v3) and negating all four when w < 0.  dR = rot(w, x, y, z).
+ *     With scale, the pivot is den = SUM_PP - ((SUM_P0 mp0 + SUM_P1 mp1) + SUM_P2 mp2) and ds = (sum over i = 0..2, then
+ *     j = 0..2, added one after the other to 0, of dR_ij M_ji) / den; a ds that is not > 0 is SINGULAR; without, ds = 1.
+ *     dt_i = (mq_i + c_i) - ds * y_i, y = dR (mp + c).
+ *   PLANE: the leading m x m system, m = 7 with scale and 6 without, A x = -b by Cholesky A = L L^T: for j = 0 .. m - 1:
+ *     d = A_jj, then d -= L_jk L_jk for k = 0 .. j - 1, the pivot d, L_jj = sqrt(d); for i > j: v = A_ji, v -= L_ik L_jk
+ *     for k < j, L_ij = v / L_jj.  Forward: y_i = (-b_i - L_i0 y_0 - ... - L_i,i-1 y_i-1) / L_ii in that order; backward from
+ *     i = m - 1: x_i = (y_i - L_i+1,i x_i+1 - ... - L_m-1,i x_m-1) / L_ii, k ascending.
+ *     (h0, h1, h2) = 0.5 * x[0..2], k = 1 / sqrt(((1 + h0 h0) + h1 h1) + h2 h2), dR = rot(k, h0 k, h1 k, h2 k) -- a
+ *     rotation about x[0..2] by 2 atan(|x[0..2]| / 2), rational but for one square root; ds = 1 + x[6] with scale (not > 0:
+ *     SINGULAR), else 1; dt_i = (c_i + x[3 + i]) - ds * y_i, y = dR c.
+ *
+ *   NFL_EINVAL (nothing launched): n negative or above INT32_MAX, the mesh sizes as in "mesh distance", a mode outside the
+ *   enum, vectors / with_scale outside {0, 1}, max_distance not positive (NaN included), a non-finite cx, cy or cz,
+ *   min_pairs < 1, iteration negative or above INT32_MAX / 4; d_transform, d_row or d_history NULL or not 8-byte aligned; for
+ *   n > 0 a NULL or misaligned (4 B) d_in, d_out, d_points or d_closest, in plane mode also d_triangle and d_distance, and
+ *   wherever d_triangle is given the mesh pointers a non-zero size needs.  The scratch as everywhere: NULL or misaligned
+ *   NFL_EINVAL, short NFL_ESMALL.  nfl_register_apply with n == 0: NFL_OK, no launch.  nfl_register_bytes: 0 for such an n. */
+enum { NFL_REGISTER_POINT = 0, NFL_REGISTER_PLANE = 1 };
+enum { NFL_REGISTER_OK = 0, NFL_REGISTER_FEW = 1, NFL_REGISTER_SINGULAR = 2 };
+#define NFL_REGISTER_TRANSFORM 13
+#define NFL_REGISTER_HISTORY 4
+enum { NFL_REGISTER_COUNT = 0, NFL_REGISTER_SUM_DD = 1, NFL_REGISTER_SUM_P = 2, NFL_REGISTER_SUM_Q = 5, NFL_REGISTER_SUM_PP = 8,
+       NFL_REGISTER_SUM_QQ = 9, NFL_REGISTER_SUM_PQ = 10, NFL_REGISTER_ATA = 19, NFL_REGISTER_ATB = 47, NFL_REGISTER_SUM_RR = 54,
+       NFL_REGISTER_COLUMNS = 55 };
+size_t nfl_register_bytes(int64_t n);
+int nfl_register_apply(const float* d_in, float* d_out, int64_t n, const double* d_transform, int32_t vectors, void* stream);
+int nfl_register_moments(const float* d_points, const float* d_closest, const int32_t* d_triangle, const float* d_distance,
+                         const float* d_vertices, const int32_t* d_triangles, int64_t n, int64_t n_vertices, int64_t n_triangles,
+                         int32_t mode, float max_distance, double cx, double cy, double cz,
+                         void* d_scratch, size_t scratch_bytes, double* d_row, void* stream);
+int nfl_register_solve(const double* d_row, int32_t mode, int32_t with_scale, int64_t min_pairs, double cx, double cy, double cz,
+                       double* d_transform, double* d_history, int32_t iteration, void* stream);
+
 /* ---- hierarchical sampling (reference sample_pdf, rendering.py:7-46, plus the
  * concat + sort of rendering.py:267-272) -------------------------------------
  * d_z_coarse (R,S), d_weights_coarse (R,S); d_u (R,I) or NULL with d_u_row (I)

@@ -395,6 +395,16 @@ class MeshDistReduceArgs(C.Structure):
                 ("scratch_bytes", C.c_size_t), ("d_row", C.c_void_p)]
 
 
+# registration (nerf_fl_amd/registration.py): plain arguments, no struct
+REGISTER_MODES = {"point": 0, "plane": 1}
+REGISTER_STATUS = {"ok": 0, "few": 1, "singular": 2}
+REGISTER_TRANSFORM = 13                         # s, R row-major, t
+REGISTER_HISTORY = 4                            # count, rms, status, s per iteration
+# the columns of the moments row: where each run starts
+REGISTER_ROW = {"COUNT": 0, "SUM_DD": 1, "SUM_P": 2, "SUM_Q": 5, "SUM_PP": 8, "SUM_QQ": 9, "SUM_PQ": 10, "ATA": 19, "ATB": 47,
+                "SUM_RR": 54, "COLUMNS": 55}
+
+
 # every struct include/nerf_fl_amd.h declares: C name -> its mirror
 STRUCTS = {
     "nfl_field_desc": FieldDesc, "nfl_field_params": FieldParams, "nfl_pack_job": PackJob, "nfl_camera": Camera,
@@ -435,6 +445,11 @@ CONSTANTS = {
     "NFL_SHADE_COLOR": SHADE_MODES["color"], "NFL_SHADE_NORMAL": SHADE_MODES["normal"],
     "NFL_SHADE_FACING": SHADE_MODES["facing"],
     "NFL_MESHDIST_MAX_TAU": MESHDIST_MAX_TAU, "NFL_MESHDIST_COLUMNS": MESHDIST_COLUMNS,
+    "NFL_REGISTER_POINT": REGISTER_MODES["point"], "NFL_REGISTER_PLANE": REGISTER_MODES["plane"],
+    "NFL_REGISTER_OK": REGISTER_STATUS["ok"], "NFL_REGISTER_FEW": REGISTER_STATUS["few"],
+    "NFL_REGISTER_SINGULAR": REGISTER_STATUS["singular"],
+    "NFL_REGISTER_TRANSFORM": REGISTER_TRANSFORM, "NFL_REGISTER_HISTORY": REGISTER_HISTORY,
+    **{"NFL_REGISTER_" + k: v for k, v in REGISTER_ROW.items()},
 }
 
 # every function include/nerf_fl_amd.h declares: (name, restype, argtypes)
@@ -529,6 +544,13 @@ SYMBOLS = [
     ("nfl_mesh_sample_emit", C.c_int, [C.POINTER(MeshSampleArgs), C.c_void_p]),
     ("nfl_meshdist_reduce_bytes", C.c_size_t, [C.c_int64]),
     ("nfl_meshdist_reduce", C.c_int, [C.POINTER(MeshDistReduceArgs), C.c_void_p]),
+    ("nfl_register_bytes", C.c_size_t, [C.c_int64]),
+    ("nfl_register_apply", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("nfl_register_moments", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.c_int64, C.c_int64, C.c_int32, C.c_float, C.c_double, C.c_double, C.c_double,
+                                       C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    ("nfl_register_solve", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_double, C.c_double, C.c_double,
+                                     C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     ("nfl_abi_version", C.c_int, []),
     ("nfl_version", C.c_char_p, []),
     ("nfl_strerror", C.c_char_p, [C.c_int]),

@@ -200,3 +200,9 @@ enum { ND_R_PARTS, ND_R_REGIONS };
 static inline NgLayout<ND_R_REGIONS> nd_reduce_layout(i64 n) {
     return {{{8 * NFL_MESHDIST_COLUMNS, (size_t)nd_reduce_blocks(n)}}, {}};    // one fp64 row per workgroup
 }
+
+// ---- registration: nfl_register_moments.  The workgroups are the reduction's: nd_reduce_blocks
+enum { NR_M_PARTS, NR_M_REGIONS };
+static inline NgLayout<NR_M_REGIONS> nr_moments_layout(i64 n) {
+    return {{{8 * NFL_REGISTER_COLUMNS, (size_t)nd_reduce_blocks(n)}}, {}};    // one fp64 row per workgroup
+}
