@@ -171,12 +171,11 @@ static bool na_range_ok(i64 first, i64 n, i64 texels) { return first >= 0 && n >
 extern "C" int nfl_atlas_points(const nfl_atlas_points_args* a, void* stream) {
     i64 texels = 0;
     if (!a || !nmc_mesh_ok(a->d_vertices, a->d_triangles, a->n_vertices, a->n_triangles)) return NFL_EINVAL;
-    if (a->n_vertices && (!a->d_vertex_normals || reinterpret_cast<uintptr_t>(a->d_vertex_normals) % 4)) return NFL_EINVAL;
+    if (a->n_vertices && ng_bad(a->d_vertex_normals, 4)) return NFL_EINVAL;
     if (!na_layout_ok(a->cell, a->cols, a->rows, a->n_triangles, &texels)) return NFL_EINVAL;
     if (!na_range_ok(a->first_texel, a->n_texels, texels)) return NFL_EINVAL;
     if (a->n_texels == 0) return NFL_OK;
-    if (!a->d_points || !a->d_normals || reinterpret_cast<uintptr_t>(a->d_points) % 4 || reinterpret_cast<uintptr_t>(a->d_normals) % 4)
-        return NFL_EINVAL;
+    if (ng_bad(a->d_points, 4) || ng_bad(a->d_normals, 4)) return NFL_EINVAL;
     hipLaunchKernelGGL(nfl_atlas_points_kernel, dim3(nm_grid(a->n_texels)), dim3(NM_THREADS), 0, static_cast<hipStream_t>(stream), *a);
     return ng_launched() ? NFL_OK : NFL_ELAUNCH;
 }
@@ -184,12 +183,12 @@ extern "C" int nfl_atlas_points(const nfl_atlas_points_args* a, void* stream) {
 extern "C" int nfl_atlas_resolve(const nfl_atlas_resolve_args* a, void* stream) {
     i64 texels = 0;
     if (!a || !nm_sizes_ok(a->n_vertices, a->n_triangles)) return NFL_EINVAL;
-    if (a->n_triangles && (!a->d_triangles || reinterpret_cast<uintptr_t>(a->d_triangles) % 4)) return NFL_EINVAL;
+    if (a->n_triangles && ng_bad(a->d_triangles, 4)) return NFL_EINVAL;
     if (!na_layout_ok(a->cell, a->cols, a->rows, a->n_triangles, &texels)) return NFL_EINVAL;
     if (!na_range_ok(a->first_texel, a->n_texels, texels)) return NFL_EINVAL;
-    if (reinterpret_cast<uintptr_t>(a->d_vertex_colors) % 4 || reinterpret_cast<uintptr_t>(a->d_texture) % 4) return NFL_EINVAL;
+    if (ng_misaligned(a->d_vertex_colors, 4) || ng_misaligned(a->d_texture, 4)) return NFL_EINVAL;
     if (a->n_texels == 0) return NFL_OK;
-    if (!a->d_sum || !a->d_views || reinterpret_cast<uintptr_t>(a->d_sum) % 16 || reinterpret_cast<uintptr_t>(a->d_views) % 4) return NFL_EINVAL;
+    if (ng_bad(a->d_sum, 16) || ng_bad(a->d_views, 4)) return NFL_EINVAL;
     hipLaunchKernelGGL(nfl_atlas_resolve_kernel, dim3(nm_grid(a->n_texels)), dim3(NM_THREADS), 0, static_cast<hipStream_t>(stream), *a);
     return ng_launched() ? NFL_OK : NFL_ELAUNCH;
 }
@@ -201,8 +200,8 @@ extern "C" int nfl_mesh_shade_atlas(const nfl_mesh_shade_atlas_args* a, void* st
     if (!nmc_mesh_ok(a->d_vertices, a->d_triangles, a->n_vertices, a->n_triangles)) return NFL_EINVAL;
     if (!na_layout_ok(a->cell, a->cols, a->rows, a->n_triangles, &texels)) return NFL_EINVAL;
     if ((a->d_atlas != nullptr) == (a->d_atlas_u8 != nullptr)) return NFL_EINVAL;      // exactly one of the two
-    if (reinterpret_cast<uintptr_t>(a->d_atlas) % 4 || reinterpret_cast<uintptr_t>(a->d_rgb) % 4 ||
-        reinterpret_cast<uintptr_t>(a->d_depth) % 4 || reinterpret_cast<uintptr_t>(a->d_triangle) % 4) return NFL_EINVAL;
+    if (ng_misaligned(a->d_atlas, 4) || ng_misaligned(a->d_rgb, 4) || ng_misaligned(a->d_depth, 4) ||
+        ng_misaligned(a->d_triangle, 4)) return NFL_EINVAL;
     if (a->n_vis == 0) return NFL_OK;
     hipLaunchKernelGGL(nfl_mesh_shade_atlas_kernel, dim3(nm_grid(a->n_vis)), dim3(NM_THREADS), 0, static_cast<hipStream_t>(stream), *a);
     return ng_launched() ? NFL_OK : NFL_ELAUNCH;

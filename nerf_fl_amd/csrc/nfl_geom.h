@@ -1,6 +1,10 @@
-// nfl_geom.h -- what the geometry translation units (nfl_surface, nfl_mesh, nfl_occupancy, nfl_simplify, nfl_meshsmooth, nfl_mesh_scan)
-// share on the device side: launch sizes, the workgroup prefix sum, the library's tiled scan and the small pieces of the
-// mesh kernels.  The scratch layouts and the size checks are host arithmetic and live in nfl_geom_layout.h.
+// nfl_geom.h -- what the geometry translation units share on the device side (every unit that makes, cleans, simplifies,
+// smooths, colours, renders, fuses, measures or registers a lattice or a mesh: nfl_surface, nfl_mesh, nfl_mesh_scan,
+// nfl_occupancy, nfl_simplify, nfl_meshsmooth, nfl_tsdf, nfl_meshdist, nfl_register, and through nfl_meshray.h nfl_meshcolor,
+// nfl_meshrender and nfl_atlas): launch sizes, the finite test, the splitmix64 hash, the fetch of an fp32 triangle and its
+// face normal, the workgroup prefix sum, the library's tiled scan and the small pieces of the mesh kernels.  The scratch
+// layouts, the size checks and the pointer checks are host arithmetic and live in nfl_geom_layout.h; the fixed-order fp64
+// reduction is nfl_reduce.h.  DESIGN.md sections 22 and 35.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,6 +20,46 @@ static inline bool ng_launched() { return hipGetLastError() == hipSuccess; }
 
 __device__ __forceinline__ bool nm_in_range(int32_t a, int32_t b, int32_t c, i64 V) {
     return a >= 0 && b >= 0 && c >= 0 && a < V && b < V && c < V;
+}
+
+// neither an infinity nor a NaN.  The same answer as isfinite on every input: nothing here is built with fast-math
+__device__ __forceinline__ bool ng_is_finite(float x) { return x - x == 0.f; }
+__device__ __forceinline__ bool ng_is_finite(double x) { return x - x == 0.0; }
+
+// the finaliser of splitmix64, every input bit reaches every output bit: the hash of the simplify tables and of the surface
+// sampler's draws
+__device__ __forceinline__ uint64_t ng_mix(uint64_t x) {
+    x ^= x >> 30;
+    x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27;
+    x *= 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return x;
+}
+
+// the corners of triangle t of an fp32 mesh; false when an index is out of range or a coordinate is not finite
+__device__ __forceinline__ bool nm_corners(const float* ver, const int32_t* tri, i64 V, i64 t, float* a, float* b, float* c) {
+    const int32_t ia = tri[3 * t], ib = tri[3 * t + 1], ic = tri[3 * t + 2];
+    if (!nm_in_range(ia, ib, ic, V)) return false;
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        a[k] = ver[3 * (i64)ia + k];
+        b[k] = ver[3 * (i64)ib + k];
+        c[k] = ver[3 * (i64)ic + k];
+        ok = ok && ng_is_finite(a[k]) && ng_is_finite(b[k]) && ng_is_finite(c[k]);
+    }
+    return ok;
+}
+
+// cr = (b - a) x (c - a) and its length, every operation rounded on its own; cr / len is the unit face normal.  What len
+// must be for the triangle to count is the caller's: the sampler, nfl_mesh_closest's d_dot and the registration differ.
+__device__ __forceinline__ void nm_face_cross(const float* a, const float* b, const float* c, float* cr, float* len) {
+    const float ab[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+    cr[0] = ab[1] * ac[2] - ab[2] * ac[1];
+    cr[1] = ab[2] * ac[0] - ab[0] * ac[2];
+    cr[2] = ab[0] * ac[1] - ab[1] * ac[0];
+    *len = sqrtf((cr[0] * cr[0] + cr[1] * cr[1]) + cr[2] * cr[2]);
 }
 
 // adds the wave's number of `bad` lanes to *counter: one atomic per wave that has any.  Every lane must call it.

@@ -1,8 +1,10 @@
-// nfl_geom_layout.h -- the scratch of the geometry entry points (surface, mesh, occupancy, simplify, smoothing): every layout is
-// written ONCE, as an ordered list of regions, and one routine walks it.  Without a base the walk gives the size (what
-// the nfl_*_bytes functions return); with the caller's buffer it gives the pointers (what the entry points launch on),
-// so the two cannot disagree.  Plain C++ with no HIP in it: tests/geom_layout_sweep.cpp builds it with g++ under the
-// sanitizers.  DESIGN.md section 22.
+// nfl_geom_layout.h -- the host arithmetic of the geometry entry points.  The scratch of every one of them (surface, mesh,
+// occupancy, simplify, smoothing, mesh distance, registration) is written ONCE, as an ordered list of regions, and one
+// routine walks it.  Without a base the walk gives the size (what the nfl_*_bytes functions return); with the caller's
+// buffer it gives the pointers (what the entry points launch on), so the two cannot disagree.  Beside the layouts: the size
+// limits, and the pointer and finite checks every entry point makes of its arguments (ng_misaligned, ng_bad, ng_finite).
+// Plain C++ with no HIP in it: the tests/*_layout_sweep.cpp programs build it with g++ under the sanitizers.  DESIGN.md
+// sections 22 and 35.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -23,6 +25,14 @@ static inline size_t ng_pad(size_t bytes) { return (bytes + 15) / 16 * 16; }
 static inline i64 ng_cdiv(i64 a, i64 b) { return (a + b - 1) / b; }
 static inline size_t ng_max(size_t a, size_t b) { return a > b ? a : b; }
 
+// The pointer checks of every geometry entry point; the only uintptr_t casts of the geometry sources are these.  A null
+// pointer is aligned: an optional argument is checked with ng_misaligned alone, a required one with ng_bad.
+static inline bool ng_misaligned(const void* p, int align) { return reinterpret_cast<uintptr_t>(p) % align != 0; }
+static inline bool ng_bad(const void* p, int align) { return !p || ng_misaligned(p, align); }      // absent or misaligned
+// neither an infinity nor a NaN (host arguments; the kernels' is ng_is_finite of nfl_geom.h)
+static inline bool ng_finite(float x) { return x - x == 0.f; }
+static inline bool ng_finite(double x) { return x - x == 0.0; }
+
 // a lattice the surface and occupancy kernels take
 static inline bool ng_dims_ok(int nx, int ny, int nz) {
     if (nx < 2 || ny < 2 || nz < 2 || ny > NG_MAX_DIM || nz > NG_MAX_DIM) return false;
@@ -30,6 +40,12 @@ static inline bool ng_dims_ok(int nx, int ny, int nz) {
 }
 // a mesh the mesh and simplify kernels take: int32 indices
 static inline bool nm_sizes_ok(i64 V, i64 T) { return V >= 0 && T >= 0 && V <= INT32_MAX && T <= INT32_MAX / 3; }
+// the mesh of a mesh distance or registration call: sizes, the pointers a non-zero size needs, and BOTH pointers aligned
+// even where the mesh is empty (nmc_mesh_ok of nfl_meshray.h does not look at the pointer of an empty side)
+static inline bool nd_mesh_ok(const float* ver, const int32_t* tri, i64 V, i64 T) {
+    if (!nm_sizes_ok(V, T) || (V && !ver) || (T && !tri)) return false;
+    return !ng_misaligned(ver, 4) && !ng_misaligned(tri, 4);
+}
 
 // what nm_scan (nfl_mesh_scan.hip) needs for n elements: the tile sums of all levels above the elements, 8 B each
 static inline size_t nm_scan_bytes(i64 n) {
@@ -76,7 +92,7 @@ static inline size_t ng_bytes(const NgLayout<N>& L) { return ng_walk(L.r, N, nul
 template <int N>
 static inline int ng_carve(NgLayout<N>& L, void* scratch, size_t scratch_bytes, bool size_first = false) {
     if (!scratch) return NFL_EINVAL;
-    const bool misaligned = reinterpret_cast<uintptr_t>(scratch) % 8 != 0, small = scratch_bytes < ng_bytes(L);
+    const bool misaligned = ng_misaligned(scratch, 8), small = scratch_bytes < ng_bytes(L);
     if (small && (size_first || !misaligned)) return NFL_ESMALL;
     if (misaligned) return NFL_EINVAL;
     ng_walk(L.r, N, scratch, L.at);

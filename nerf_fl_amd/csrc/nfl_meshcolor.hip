@@ -109,10 +109,9 @@ extern "C" int nfl_mesh_blend(const nfl_mesh_blend_args* a, void* stream) {
     if (a->n_depth < 0 || a->n_depth > NMC_MAX_WORDS) return NFL_EINVAL;
     if (a->n_vertices == 0) return NFL_OK;
     if (!a->d_vertices || !a->d_normals || !a->d_sum || !a->d_views) return NFL_EINVAL;
-    if (reinterpret_cast<uintptr_t>(a->d_vertices) % 4 || reinterpret_cast<uintptr_t>(a->d_normals) % 4 ||
-        reinterpret_cast<uintptr_t>(a->d_sum) % 16 || reinterpret_cast<uintptr_t>(a->d_views) % 4 ||
-        reinterpret_cast<uintptr_t>(a->d_center) % 4 || reinterpret_cast<uintptr_t>(a->d_image_weights) % 4) return NFL_EINVAL;
-    if (a->count && (!a->d_pixels || !a->d_depth || reinterpret_cast<uintptr_t>(a->d_depth) % 4)) return NFL_EINVAL;
+    if (ng_misaligned(a->d_vertices, 4) || ng_misaligned(a->d_normals, 4) || ng_misaligned(a->d_sum, 16) ||
+        ng_misaligned(a->d_views, 4) || ng_misaligned(a->d_center, 4) || ng_misaligned(a->d_image_weights, 4)) return NFL_EINVAL;
+    if (a->count && (!a->d_pixels || ng_bad(a->d_depth, 4))) return NFL_EINVAL;
     if (a->count == 0 && !a->start) return NFL_OK;
     hipLaunchKernelGGL(nfl_mesh_blend_kernel, dim3(nm_grid(a->n_vertices)), dim3(NM_THREADS), 0, static_cast<hipStream_t>(stream), *a);
     return ng_launched() ? NFL_OK : NFL_ELAUNCH;

@@ -12,13 +12,17 @@
 //   samples  count   a thread per triangle: m_t; nm_scan: the first row of every triangle
 //            emit    a thread per triangle writes up to 64 samples itself; the wave then takes the larger triangles of its
 //                    lanes one after the other, 64 samples a step (nfl_mesh_depth's treatment of large boxes)
-//   reduce   partial rows per workgroup in fp64 in a fixed order, one workgroup folds them (nfl_image_metrics' scheme)
+//   reduce   the library's fixed-order fp64 reduction (nfl_reduce.h); here only its policy: what a distance adds to the columns
+//
+// The triangle fetch (nm_corners), the face normal (nm_face_cross), the hash (ng_mix) and the finite test are nfl_geom.h's,
+// the pointer checks nfl_geom_layout.h's: registration and the sampler read a triangle exactly as nfl_mesh_closest does.
 //
 // Only integer atomics, and nothing that depends on their order leaves a call except the order inside a grid row.  Nothing
 // here allocates, sets or copies memory through the runtime.
 #include <math.h>
 
 #include "nfl_geom.h"
+#include "nfl_reduce.h"
 
 typedef unsigned long long u64;
 
@@ -46,61 +50,18 @@ struct NdGrid {
     int32_t dims[3];
 };
 
-static inline bool nd_misaligned(const void* p, int align) { return reinterpret_cast<uintptr_t>(p) % align != 0; }
-static inline bool nd_finite(float x) { return x - x == 0.f; }
-
-// the mesh a call takes: sizes, and the pointers a non-zero size needs
-static bool nd_mesh_ok(const float* ver, const int32_t* tri, i64 V, i64 T) {
-    if (!nm_sizes_ok(V, T)) return false;
-    if ((V && !ver) || (T && !tri)) return false;
-    return !nd_misaligned(ver, 4) && !nd_misaligned(tri, 4);
-}
-
 static bool nd_grid_ok(const float* lo, float cell, const int32_t* dims) {
-    if (!nd_dims_ok(dims) || !(cell > 0.f) || !nd_finite(cell)) return false;
-    return nd_finite(lo[0]) && nd_finite(lo[1]) && nd_finite(lo[2]);
+    if (!nd_dims_ok(dims) || !(cell > 0.f) || !ng_finite(cell)) return false;
+    return ng_finite(lo[0]) && ng_finite(lo[1]) && ng_finite(lo[2]);
 }
 
 // ---------------------------------------------------------------------------------------------------------- device pieces
-
-__device__ __forceinline__ bool nd_is_finite(float x) { return x - x == 0.f; }
-
-// the finaliser of splitmix64 (nfl_simplify.hip's)
-__device__ __forceinline__ u64 nd_mix(u64 x) {
-    x ^= x >> 30;
-    x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27;
-    x *= 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    return x;
-}
 
 __device__ __forceinline__ int nd_cellf(float x, float lo, float cell, int n) {
     return (int)fminf(fmaxf(floorf((x - lo) / cell), 0.f), (float)(n - 1));
 }
 
 __device__ __forceinline__ float nd_dot(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-
-__device__ __forceinline__ void nd_cross(const float* a, const float* b, float* c) {
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// the corners of triangle t; false when it is not usable
-__device__ __forceinline__ bool nd_corners(const float* ver, const int32_t* tri, i64 V, i64 t, float* a, float* b, float* c) {
-    const int32_t ia = tri[3 * t], ib = tri[3 * t + 1], ic = tri[3 * t + 2];
-    if (!nm_in_range(ia, ib, ic, V)) return false;
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        a[k] = ver[3 * (i64)ia + k];
-        b[k] = ver[3 * (i64)ib + k];
-        c[k] = ver[3 * (i64)ic + k];
-        ok = ok && nd_is_finite(a[k]) && nd_is_finite(b[k]) && nd_is_finite(c[k]);
-    }
-    return ok;
-}
 
 // the index box of a usable triangle
 __device__ __forceinline__ void nd_box(const NdGrid& G, const float* a, const float* b, const float* c, int* i0, int* i1) {
@@ -234,7 +195,7 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_trigrid_walk_kernel(const floa
     if (t < T) {
         float a[3], b[3], c[3];
         outside = !nm_in_range(tri[3 * t], tri[3 * t + 1], tri[3 * t + 2], V);
-        if (nd_corners(ver, tri, V, t, a, b, c)) {
+        if (nm_corners(ver, tri, V, t, a, b, c)) {
             int i0[3], i1[3];
             nd_box(G, a, b, c, i0, i1);
             for (int z = i0[2]; z <= i1[2]; ++z)
@@ -256,7 +217,7 @@ extern "C" int nfl_trigrid_count(const nfl_trigrid_args* a, void* stream) {
     NdGridScratch S;
     const int rc = nd_grid_carve(a, S);
     if (rc != NFL_OK) return rc;
-    if (!a->d_totals || nd_misaligned(a->d_totals, 8)) return NFL_EINVAL;
+    if (ng_bad(a->d_totals, 8)) return NFL_EINVAL;
     const i64 cells = (i64)a->dims[0] * a->dims[1] * a->dims[2], T = a->n_triangles;
     hipStream_t s = static_cast<hipStream_t>(stream);
     int32_t* cnt = S.get<int32_t>(ND_G_CNT);
@@ -283,8 +244,8 @@ extern "C" int nfl_trigrid_emit(const nfl_trigrid_args* a, void* stream) {
     const int rc = nd_grid_carve(a, S);
     if (rc != NFL_OK) return rc;
     if (a->n_entries < 0 || a->n_entries > ND_MAX_ENTRIES) return NFL_EINVAL;
-    if (!a->d_offsets || nd_misaligned(a->d_offsets, 8)) return NFL_EINVAL;
-    if (a->n_entries && (!a->d_entries || nd_misaligned(a->d_entries, 4))) return NFL_EINVAL;
+    if (ng_bad(a->d_offsets, 8)) return NFL_EINVAL;
+    if (a->n_entries && ng_bad(a->d_entries, 4)) return NFL_EINVAL;
     const i64 cells = (i64)a->dims[0] * a->dims[1] * a->dims[2], T = a->n_triangles;
     hipStream_t s = static_cast<hipStream_t>(stream);
     int32_t* cnt = S.get<int32_t>(ND_G_CNT);
@@ -319,7 +280,7 @@ __device__ __forceinline__ void nd_try_row(NdBest& B, const float* p, const nfl_
         const int32_t t = a.d_entries[e];
         if (t < 0 || t >= a.n_triangles) continue;
         float ca[3], cb[3], cc[3];
-        if (!nd_corners(a.d_vertices, a.d_triangles, a.n_vertices, t, ca, cb, cc)) continue;
+        if (!nm_corners(a.d_vertices, a.d_triangles, a.n_vertices, t, ca, cb, cc)) continue;
         ND_DEBUG_ADD(0, 1);
         nd_try(B, p, t, ca, cb, cc, limit);
     }
@@ -365,7 +326,7 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_mesh_closest_kernel(const nfl_
     const bool mine = n < a.n_points;
     float p[3] = {0.f, 0.f, 0.f};
     if (mine) p[0] = a.d_points[3 * n], p[1] = a.d_points[3 * n + 1], p[2] = a.d_points[3 * n + 2];
-    const bool asks = mine && nd_is_finite(p[0]) && nd_is_finite(p[1]) && nd_is_finite(p[2]);
+    const bool asks = mine && ng_is_finite(p[0]) && ng_is_finite(p[1]) && ng_is_finite(p[2]);
     const float limit = a.max_distance * a.max_distance;
     NdBest B;
     B.dd = INFINITY, B.t = -1;
@@ -379,7 +340,7 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_mesh_closest_kernel(const nfl_
         for (i64 base = 0; base < a.n_triangles; base += ND_TILE) {     // the same trips for every thread: barriers inside
             const i64 t = base + threadIdx.x;
             float ca[3] = {0.f, 0.f, 0.f}, cb[3] = {0.f, 0.f, 0.f}, cc[3] = {0.f, 0.f, 0.f};
-            const bool ok = t < a.n_triangles && nd_corners(a.d_vertices, a.d_triangles, a.n_vertices, t, ca, cb, cc);
+            const bool ok = t < a.n_triangles && nm_corners(a.d_vertices, a.d_triangles, a.n_vertices, t, ca, cb, cc);
             __syncthreads();
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
@@ -409,12 +370,10 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_mesh_closest_kernel(const nfl_
     if (a.d_dot) {
         float dot = NAN;
         float ca[3], cb[3], cc[3];
-        if (B.t >= 0 && nd_corners(a.d_vertices, a.d_triangles, a.n_vertices, B.t, ca, cb, cc)) {
-            const float ab[3] = {cb[0] - ca[0], cb[1] - ca[1], cb[2] - ca[2]}, ac[3] = {cc[0] - ca[0], cc[1] - ca[1], cc[2] - ca[2]};
-            float cr[3];
-            nd_cross(ab, ac, cr);
-            const float len = sqrtf(nd_dot(cr, cr));
-            float nf[3] = {0.f, 0.f, 0.f};
+        if (B.t >= 0 && nm_corners(a.d_vertices, a.d_triangles, a.n_vertices, B.t, ca, cb, cc)) {
+            float cr[3], len;
+            nm_face_cross(ca, cb, cc, cr, &len);
+            float nf[3] = {0.f, 0.f, 0.f};                              // a face without a normal: dot = 0
             if (len > 0.f) nf[0] = cr[0] / len, nf[1] = cr[1] / len, nf[2] = cr[2] / len;
             const float nq[3] = {a.d_normals[3 * n], a.d_normals[3 * n + 1], a.d_normals[3 * n + 2]};
             dot = nd_dot(nq, nf);
@@ -430,15 +389,15 @@ extern "C" int nfl_mesh_closest(const nfl_mesh_closest_args* a, void* stream) {
     if ((a->d_normals == nullptr) != (a->d_dot == nullptr)) return NFL_EINVAL;
     const bool grid = a->d_offsets != nullptr;
     if (grid) {
-        if (!nd_grid_ok(a->lo, a->cell, a->dims) || nd_misaligned(a->d_offsets, 8)) return NFL_EINVAL;
+        if (!nd_grid_ok(a->lo, a->cell, a->dims) || ng_misaligned(a->d_offsets, 8)) return NFL_EINVAL;
         if (a->n_entries < 0 || a->n_entries > ND_MAX_ENTRIES) return NFL_EINVAL;
-        if (a->n_entries && (!a->d_entries || nd_misaligned(a->d_entries, 4))) return NFL_EINVAL;
+        if (a->n_entries && ng_bad(a->d_entries, 4)) return NFL_EINVAL;
     }
     if (a->n_points == 0) return NFL_OK;
     const void* need[] = {a->d_points, a->d_distance, a->d_triangle, a->d_point, a->d_bary};
     for (const void* p : need)
-        if (!p || nd_misaligned(p, 4)) return NFL_EINVAL;
-    if (nd_misaligned(a->d_normals, 4) || nd_misaligned(a->d_dot, 4)) return NFL_EINVAL;
+        if (ng_bad(p, 4)) return NFL_EINVAL;
+    if (ng_misaligned(a->d_normals, 4) || ng_misaligned(a->d_dot, 4)) return NFL_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (grid)
         hipLaunchKernelGGL(nfl_mesh_closest_kernel<true>, dim3(nm_grid(a->n_points)), dim3(NM_THREADS), 0, s, *a);
@@ -459,7 +418,7 @@ typedef NgLayout<ND_S_REGIONS> NdSampleScratch;
 // Checks shared by count and emit.  NFL_OK with T == 0 means: nothing to carve.
 static int nd_sample_carve(const nfl_mesh_sample_args* a, NdSampleScratch& S) {
     if (!a || !nd_mesh_ok(a->d_vertices, a->d_triangles, a->n_vertices, a->n_triangles)) return NFL_EINVAL;
-    if (!(a->density >= 0.f) || !nd_finite(a->density)) return NFL_EINVAL;
+    if (!(a->density >= 0.f) || !ng_finite(a->density)) return NFL_EINVAL;
     S = nd_sample_layout(a->n_triangles);
     if (a->n_triangles == 0) return NFL_OK;
     return ng_carve(S, a->d_scratch, a->scratch_bytes);
@@ -472,12 +431,11 @@ struct NdFace {
 
 __device__ __forceinline__ bool nd_face(const float* ver, const int32_t* tri, i64 V, i64 t, NdFace& f) {
     float b[3], c[3];
-    if (!nd_corners(ver, tri, V, t, f.a, b, c)) return false;
+    if (!nm_corners(ver, tri, V, t, f.a, b, c)) return false;
 #pragma unroll
     for (int k = 0; k < 3; ++k) f.e1[k] = b[k] - f.a[k], f.e2[k] = c[k] - f.a[k];
-    nd_cross(f.e1, f.e2, f.cr);
-    f.len = sqrtf(nd_dot(f.cr, f.cr));
-    return f.len > 0.f && nd_is_finite(f.len);
+    nm_face_cross(f.a, b, c, f.cr, &f.len);
+    return f.len > 0.f && ng_is_finite(f.len);
 }
 
 #define ND_2M24 5.9604644775390625e-08f                     // 2^-24
@@ -491,7 +449,7 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_mesh_sample_count_kernel(const
         NdFace f;
         int32_t m = 0;
         if (nd_face(ver, tri, V, t, f)) {
-            const u64 ht = nd_mix(nd_mix(seed) + (u64)t);
+            const u64 ht = ng_mix(ng_mix(seed) + (u64)t);
             const float ut = (float)(ht >> 40) * ND_2M24;
             const float x = (0.5f * f.len) * density + ut;
             dense = !(x < ND_MAX_SAMPLES_PER_TRIANGLE);
@@ -511,7 +469,7 @@ extern "C" int nfl_mesh_sample_count(const nfl_mesh_sample_args* a, void* stream
     NdSampleScratch S;
     const int rc = nd_sample_carve(a, S);
     if (rc != NFL_OK) return rc;
-    if (!a->d_totals || nd_misaligned(a->d_totals, 8)) return NFL_EINVAL;
+    if (ng_bad(a->d_totals, 8)) return NFL_EINVAL;
     const i64 T = a->n_triangles;
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(nfl_mesh_sample_zero_kernel, dim3(1), dim3(64), 0, s, a->d_totals);
@@ -527,7 +485,7 @@ extern "C" int nfl_mesh_sample_count(const nfl_mesh_sample_args* a, void* stream
 // sample j of triangle t to row `at`
 __device__ __forceinline__ void nd_emit_sample(const nfl_mesh_sample_args& a, const NdFace& f, u64 ht, i64 t, int32_t j, i64 at) {
     if (at < 0 || at >= a.n_samples) return;
-    const u64 hj = nd_mix(ht + (u64)(j + 1));
+    const u64 hj = ng_mix(ht + (u64)(j + 1));
     float r1 = ((float)(hj >> 40) + 0.5f) * ND_2M24, r2 = ((float)((hj >> 16) & 0xFFFFFFull) + 0.5f) * ND_2M24;
     if (r1 + r2 > 1.f) r1 = 1.f - r1, r2 = 1.f - r2;
 #pragma unroll
@@ -550,7 +508,7 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_mesh_sample_emit_kernel(const 
         m = cnt[t];
         o = off[t];
         if (m < 0 || m > (int32_t)ND_MAX_SAMPLES_PER_TRIANGLE || !nd_face(a.d_vertices, a.d_triangles, a.n_vertices, t, f)) m = 0;
-        ht = nd_mix(nd_mix(a.seed) + (u64)t);
+        ht = ng_mix(ng_mix(a.seed) + (u64)t);
     }
     if (m <= ND_WAVE_SAMPLES)
         for (int32_t j = 0; j < m; ++j) nd_emit_sample(a, f, ht, t, j, o + j);
@@ -564,7 +522,7 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_mesh_sample_emit_kernel(const 
         const i64 wo = __shfl(o, src);
         NdFace wf;
         if (!nd_face(a.d_vertices, a.d_triangles, a.n_vertices, wt, wf)) continue;     // the same for every lane
-        const u64 wh = nd_mix(nd_mix(a.seed) + (u64)wt);
+        const u64 wh = ng_mix(ng_mix(a.seed) + (u64)wt);
         for (int32_t j = lane; j < wm; j += 64) nd_emit_sample(a, wf, wh, wt, j, wo + j);
     }
 }
@@ -577,7 +535,7 @@ extern "C" int nfl_mesh_sample_emit(const nfl_mesh_sample_args* a, void* stream)
     if (a->n_samples == 0 || a->n_triangles == 0) return NFL_OK;
     const void* need[] = {a->d_points, a->d_sample_triangles, a->d_normals};
     for (const void* p : need)
-        if (!p || nd_misaligned(p, 4)) return NFL_EINVAL;
+        if (ng_bad(p, 4)) return NFL_EINVAL;
     hipLaunchKernelGGL(nfl_mesh_sample_emit_kernel, dim3(nm_grid(a->n_triangles)), dim3(NM_THREADS), 0,
                        static_cast<hipStream_t>(stream), *a, S.get<int32_t>(ND_S_CNT), S.get<i64>(ND_S_OFF));
     return ng_launched() ? NFL_OK : NFL_ELAUNCH;
@@ -590,31 +548,19 @@ extern "C" size_t nfl_meshdist_reduce_bytes(int64_t n) {
     return ng_bytes(nd_reduce_layout(n));
 }
 
-#define ND_COLS NFL_MESHDIST_COLUMNS
-
-// the 256 rows of red folded by halving into red[..][0]; column NFL_MESHDIST_MAX by fmax, the others by +
-__device__ __forceinline__ void nd_fold(double (*red)[256]) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (tid < off) {
-#pragma unroll
-            for (int k = 0; k < ND_COLS; ++k)
-                red[k][tid] = k == NFL_MESHDIST_MAX ? fmax(red[k][tid], red[k][tid + off]) : red[k][tid] + red[k][tid + off];
+// the reduction's policy (nfl_reduce.h): every column of the row is a thread's, NFL_MESHDIST_MAX combines by fmax
+struct NdReduce {
+    nfl_meshdist_reduce_args a;
+    static constexpr int cols = NFL_MESHDIST_COLUMNS, width = NFL_MESHDIST_COLUMNS;
+    __host__ __device__ static constexpr int column(int k) { return k; }
+    struct Combine {
+        __device__ __forceinline__ double operator()(int k, double x, double y) const {
+            return k == NFL_MESHDIST_MAX ? fmax(x, y) : x + y;
         }
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(256) void nfl_meshdist_parts_kernel(const nfl_meshdist_reduce_args a, double* parts) {
-    __shared__ double red[ND_COLS][256];
-    const int tid = threadIdx.x;
-    double acc[ND_COLS];
-#pragma unroll
-    for (int k = 0; k < ND_COLS; ++k) acc[k] = 0.0;
-    for (i64 i = (i64)blockIdx.x * 256 + tid; i < a.n; i += (i64)gridDim.x * 256) {
+    };
+    __device__ __forceinline__ void add(i64 i, double* acc) const {
         const float d = a.d_distance[i];
-        if (!(d < INFINITY)) continue;                                  // +inf and NaN: missing
+        if (!(d < INFINITY)) return;                                    // +inf and NaN: missing
         const double x = (double)d;
         acc[NFL_MESHDIST_COUNT] += 1.0;
         acc[NFL_MESHDIST_SUM] += x;
@@ -625,48 +571,23 @@ __global__ __launch_bounds__(256) void nfl_meshdist_parts_kernel(const nfl_meshd
             if (k < a.n_tau && d <= a.tau[k]) acc[NFL_MESHDIST_WITHIN + k] += 1.0;
         if (a.d_dot) acc[NFL_MESHDIST_SUM_DOT] += fabs((double)a.d_dot[i]);
     }
-#pragma unroll
-    for (int k = 0; k < ND_COLS; ++k) red[k][tid] = acc[k];
-    nd_fold(red);
-    if (tid < ND_COLS) parts[(size_t)blockIdx.x * ND_COLS + tid] = red[tid][0];
-}
-
-__global__ __launch_bounds__(256) void nfl_meshdist_finish_kernel(const double* parts, int n_parts, double* row) {
-    __shared__ double red[ND_COLS][256];
-    const int tid = threadIdx.x;
-    double acc[ND_COLS];
-#pragma unroll
-    for (int k = 0; k < ND_COLS; ++k) acc[k] = 0.0;
-    for (int i = tid; i < n_parts; i += 256) {
-#pragma unroll
-        for (int k = 0; k < ND_COLS; ++k) {
-            const double v = parts[(size_t)i * ND_COLS + k];
-            acc[k] = k == NFL_MESHDIST_MAX ? fmax(acc[k], v) : acc[k] + v;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < ND_COLS; ++k) red[k][tid] = acc[k];
-    nd_fold(red);
-    if (tid < ND_COLS) row[tid] = red[tid][0];
-}
+};
 
 extern "C" int nfl_meshdist_reduce(const nfl_meshdist_reduce_args* a, void* stream) {
-    if (!a || a->n < 0 || a->n > ND_MAX_ENTRIES || !a->d_row || nd_misaligned(a->d_row, 8)) return NFL_EINVAL;
+    if (!a || a->n < 0 || a->n > ND_MAX_ENTRIES || ng_bad(a->d_row, 8)) return NFL_EINVAL;
     if (a->n_tau < 0 || a->n_tau > NFL_MESHDIST_MAX_TAU) return NFL_EINVAL;
     for (int k = 0; k < a->n_tau; ++k)
         if (a->tau[k] != a->tau[k]) return NFL_EINVAL;
-    if (a->n && (!a->d_distance || nd_misaligned(a->d_distance, 4))) return NFL_EINVAL;
-    if (nd_misaligned(a->d_dot, 4)) return NFL_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const double* parts = nullptr;
+    if (a->n && ng_bad(a->d_distance, 4)) return NFL_EINVAL;
+    if (ng_misaligned(a->d_dot, 4)) return NFL_EINVAL;
+    double* parts = nullptr;
     const i64 blocks = nd_reduce_blocks(a->n);
     if (blocks) {
         NgLayout<ND_R_REGIONS> S = nd_reduce_layout(a->n);
         const int rc = ng_carve(S, a->d_scratch, a->scratch_bytes);
         if (rc != NFL_OK) return rc;
-        hipLaunchKernelGGL(nfl_meshdist_parts_kernel, dim3((unsigned)blocks), dim3(256), 0, s, *a, S.get<double>(ND_R_PARTS));
         parts = S.get<double>(ND_R_PARTS);
     }
-    hipLaunchKernelGGL(nfl_meshdist_finish_kernel, dim3(1), dim3(256), 0, s, parts, (int)blocks, a->d_row);
+    ng_reduce_launch(NdReduce{*a}, a->n, blocks, parts, a->d_row, static_cast<hipStream_t>(stream));
     return ng_launched() ? NFL_OK : NFL_ELAUNCH;
 }

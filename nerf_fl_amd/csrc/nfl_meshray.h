@@ -26,8 +26,6 @@ NFL_DEV void nmc_to_camera(const nfl_image_rec& im, const float p[3], float q[3]
     for (int c = 0; c < 3; ++c) q[c] = nmc_dot(im.c2w[c], im.c2w[4 + c], im.c2w[8 + c], wx, wy, wz);
 }
 
-NFL_DEV bool nmc_finite(float v) { return v - v == 0.f; }
-
 // what a triangle's pixel tests share: the Moeller-Trumbore terms that do not depend on the ray (origin 0: tvec = -a)
 struct NmcTri {
     float tv[3], e1[3], e2[3], qv[3], tnum;
@@ -106,12 +104,12 @@ NFL_DEV void nmc_raster(const float* ver, const int32_t* tris, i64 V, i64 T, con
             for (int k = 0; k < 3; ++k) {
                 const float p[3] = {ver[3 * (i64)idx[k]], ver[3 * (i64)idx[k] + 1], ver[3 * (i64)idx[k] + 2]};
                 nmc_to_camera(im, p, q[k]);
-                finite = finite && nmc_finite(q[k][0]) && nmc_finite(q[k][1]) && nmc_finite(q[k][2]);
+                finite = finite && ng_is_finite(q[k][0]) && ng_is_finite(q[k][1]) && ng_is_finite(q[k][2]);
                 const float s = -q[k][2];
                 if (s > 0.f) {
                     any_front = true;
                     const float u = im.cx + im.fx * (q[k][0] / s), v = im.cy - im.fy * (q[k][1] / s);
-                    boxed = boxed && nmc_finite(u) && nmc_finite(v);
+                    boxed = boxed && ng_is_finite(u) && ng_is_finite(v);
                     bx0 = fminf(bx0, u), bx1 = fmaxf(bx1, u), by0 = fminf(by0, v), by1 = fmaxf(by1, v);
                 } else all_front = false;
             }
@@ -243,19 +241,19 @@ NFL_DEV void nmc_shade_out(const Args& a, i64 w, const float rgb[3], float depth
 
 // a run of images of the table
 static inline bool nmc_run_ok(const void* table, int32_t n_images, int32_t first, int32_t count) {
-    if (!table || reinterpret_cast<uintptr_t>(table) % 8) return false;
+    if (ng_bad(table, 8)) return false;
     return n_images >= 1 && first >= 0 && count >= 0 && (long long)first + count <= n_images;
 }
 
-// a mesh: sizes in range, and each of the two arrays, where it has any element, present and aligned
+// a mesh: sizes in range, and each of the two arrays, where it has any element, present and aligned.  The array of an
+// empty side is not looked at; nd_mesh_ok (nfl_geom_layout.h) is the stricter check of the mesh distance and registration calls.
 static inline bool nmc_mesh_ok(const float* ver, const int32_t* tri, i64 V, i64 T) {
     if (!nm_sizes_ok(V, T)) return false;
-    if (V && (!ver || reinterpret_cast<uintptr_t>(ver) % 4)) return false;
-    return !(T && (!tri || reinterpret_cast<uintptr_t>(tri) % 4));
+    return !(V && ng_bad(ver, 4)) && !(T && ng_bad(tri, 4));
 }
 
 // the n words of a run (depths or visibility): n in range and the buffer, where it has any word, present and aligned
 static inline bool nmc_words_ok(const void* words, i64 n, int align) {
     if (n < 0 || n > NMC_MAX_WORDS) return false;
-    return !(n && (!words || reinterpret_cast<uintptr_t>(words) % align));
+    return !(n && ng_bad(words, align));
 }

@@ -86,8 +86,8 @@ extern "C" int nfl_mesh_shade(const nfl_mesh_shade_args* a, void* stream) {
     if (!nmc_words_ok(a->d_vis, a->n_vis, 8)) return NFL_EINVAL;
     if (!nmc_mesh_ok(a->d_vertices, a->d_triangles, a->n_vertices, a->n_triangles)) return NFL_EINVAL;
     if (a->mode != NFL_SHADE_FACING && a->n_vertices && !a->d_attr) return NFL_EINVAL;
-    if (reinterpret_cast<uintptr_t>(a->d_attr) % 4 || reinterpret_cast<uintptr_t>(a->d_rgb) % 4 ||
-        reinterpret_cast<uintptr_t>(a->d_depth) % 4 || reinterpret_cast<uintptr_t>(a->d_triangle) % 4) return NFL_EINVAL;
+    if (ng_misaligned(a->d_attr, 4) || ng_misaligned(a->d_rgb, 4) || ng_misaligned(a->d_depth, 4) ||
+        ng_misaligned(a->d_triangle, 4)) return NFL_EINVAL;
     if (a->n_vis == 0) return NFL_OK;
     hipLaunchKernelGGL(nfl_mesh_shade_kernel, dim3(nm_grid(a->n_vis)), dim3(NM_THREADS), 0, static_cast<hipStream_t>(stream), *a);
     return ng_launched() ? NFL_OK : NFL_ELAUNCH;

@@ -380,7 +380,7 @@ extern "C" int nfl_mesh_adjacency_emit(const nfl_mesh_adjacency_args* a, void* s
 
 // -------------------------------------------------------------------------------------------------------------- smooth
 
-__device__ __forceinline__ bool na_finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+__device__ __forceinline__ bool na_finite3(float x, float y, float z) { return ng_is_finite(x) && ng_is_finite(y) && ng_is_finite(z); }
 
 __global__ __launch_bounds__(NM_THREADS) void nfl_smooth_copy_kernel(const float* in, i64 n, float* out) {
     for (i64 i = (i64)blockIdx.x * NM_THREADS + threadIdx.x; i < n; i += (i64)gridDim.x * NM_THREADS) out[i] = in[i];

@@ -9,12 +9,13 @@
 // owns 64 columns x 4 rows: every lane filters its column's 6 halo rows horizontally for the 5 moments of each channel
 // (p, t, pp, tt, pt) and combines three of them vertically per output pixel -- the 3 x 3 window is an outer product.
 // Sums are kept per lane in fp64 (12 elements each), reduced across the wavefront by shuffles and across the 4 wavefronts
-// in a fixed order; the workgroup writes ONE partial.  nfl_metrics_finish_kernel (one workgroup) adds the partials in a
-// fixed order and writes the slot.  Nothing is atomic, memset or copied: two runs give the same bits and the pair of
+// in a fixed order; the workgroup writes ONE partial.  nfl_metrics_finish_kernel (one workgroup) adds the partials in the
+// fixed order of nfl_reduce.h and writes the slot.  Nothing is atomic, memset or copied: two runs give the same bits and the pair of
 // launches can be captured in a HIP graph.  The work is launch-bound (10 MB at 800 x 800), as nfl_gather_batch is.
 #include <math.h>
 
 #include "nfl_pixel.h"
+#include "nfl_reduce.h"
 
 #define NFL_MT_W 64
 #define NFL_MT_H 16
@@ -154,28 +155,19 @@ __global__ __launch_bounds__(256) void nfl_metrics_tiles_kernel(const nfl_metric
     }
 }
 
-// one workgroup: thread t adds partials t, t + 256, ... in index order, then a fixed tree over the 256 threads
+// one workgroup: thread t adds partials t, t + 256, ... in index order, then the library's fold of the 256 threads (nfl_reduce.h)
 __global__ __launch_bounds__(256) void nfl_metrics_finish_kernel(const double* __restrict__ parts, int n_parts,
                                                                  double* __restrict__ row) {
-    __shared__ double red[NFL_MT_PART][256];
+    __shared__ double lds[NFL_MT_PART * 128];
     const int tid = threadIdx.x;
     double acc[NFL_MT_PART] = {0.0, 0.0, 0.0, 0.0, 0.0};
     for (int i = tid; i < n_parts; i += 256) {
 #pragma unroll
         for (int k = 0; k < NFL_MT_PART; ++k) acc[k] += parts[(size_t)i * NFL_MT_PART + k];
     }
-#pragma unroll
-    for (int k = 0; k < NFL_MT_PART; ++k) red[k][tid] = acc[k];
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (tid < off) {
-#pragma unroll
-            for (int k = 0; k < NFL_MT_PART; ++k) red[k][tid] += red[k][tid + off];
-        }
-        __syncthreads();
-    }
+    ng_fold<NFL_MT_PART>(acc, lds, NgAdd());
     if (tid == 0) {
-        const double sse = red[0][0], count = red[1][0], sse_valid = red[2][0], count_valid = red[3][0], ssim_sum = red[4][0];
+        const double sse = acc[0], count = acc[1], sse_valid = acc[2], count_valid = acc[3], ssim_sum = acc[4];
         row[NFL_METRIC_SSE] = sse;
         row[NFL_METRIC_COUNT] = count;
         row[NFL_METRIC_SSE_VALID] = sse_valid;

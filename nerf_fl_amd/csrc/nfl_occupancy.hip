@@ -92,7 +92,7 @@ extern "C" size_t nfl_occ_build_bytes(int32_t nx, int32_t ny, int32_t nz, int32_
 extern "C" int nfl_occ_build(const nfl_occ_build_args* a, void* stream) {
     if (!a || !a->d_lattice || !a->d_scratch || !a->d_bits) return NFL_EINVAL;
     if (!ng_dims_ok(a->nx, a->ny, a->nz) || a->dilate < 0 || a->dilate > NO_MAX_DILATE) return NFL_EINVAL;
-    if (reinterpret_cast<uintptr_t>(a->d_lattice) % 4 || reinterpret_cast<uintptr_t>(a->d_bits) % 4) return NFL_EINVAL;
+    if (ng_misaligned(a->d_lattice, 4) || ng_misaligned(a->d_bits, 4)) return NFL_EINVAL;
     auto L = no_layout(a->nx, a->ny, a->nz);
     const int rc = ng_carve(L, a->d_scratch, a->scratch_bytes);
     if (rc != NFL_OK) return rc;
@@ -207,11 +207,9 @@ extern "C" int nfl_occ_clip_rays(const nfl_occ_clip_args* a, void* stream) {
     if (!a || a->n_rays < 0 || a->n_rays > INT32_MAX) return NFL_EINVAL;
     if (!ng_dims_ok(a->nx, a->ny, a->nz)) return NFL_EINVAL;
     for (int k = 0; k < 3; ++k)
-        if (!(a->spacing[k] > 0.f) || !(a->spacing[k] < __builtin_huge_valf()) || !(a->lo[k] - a->lo[k] == 0.f)) return NFL_EINVAL;
+        if (!(a->spacing[k] > 0.f) || !(a->spacing[k] < __builtin_huge_valf()) || !ng_finite(a->lo[k])) return NFL_EINVAL;
     if (a->n_rays == 0) return NFL_OK;
-    if (!a->d_rays || !a->d_bits || !a->d_near_far || !a->d_hit) return NFL_EINVAL;
-    if (reinterpret_cast<uintptr_t>(a->d_rays) % 16 || reinterpret_cast<uintptr_t>(a->d_bits) % 4 ||
-        reinterpret_cast<uintptr_t>(a->d_near_far) % 8) return NFL_EINVAL;
+    if (ng_bad(a->d_rays, 16) || ng_bad(a->d_bits, 4) || ng_bad(a->d_near_far, 8) || !a->d_hit) return NFL_EINVAL;
     const unsigned blocks = (unsigned)((a->n_rays + NO_TILE - 1) / NO_TILE);
     hipLaunchKernelGGL(nfl_occ_clip_kernel, dim3(blocks), dim3(NO_TILE), 0, static_cast<hipStream_t>(stream), *a);
     return ng_launched() ? NFL_OK : NFL_ELAUNCH;

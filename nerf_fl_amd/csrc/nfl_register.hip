@@ -4,11 +4,10 @@
 // transform lives in device memory and every kernel reads it there.  DESIGN.md section 34.
 //
 //   apply    a thread per row, fp64 inside, one fp32 rounding at the end
-//   moments  nfl_meshdist_reduce's order of additions.  A thread keeps its columns in registers (19 in point mode, 38 in plane
-//            mode: the kernels are instantiated per mode and the other mode's columns are written as zeros).  The halving fold
-//            of 256 threads: the two steps that cross waves go through LDS, 128 then 64 rows of it (38 x 128 doubles = 38 KiB;
-//            all 256 rows would be 76 KiB, half of the CU's 160 KiB for one workgroup), the six steps inside wave 0 are
-//            cross-lane moves.  Lane t adds what lane t + off holds, which is what row t += row t + off says.
+//   moments  the library's fixed-order fp64 reduction (nfl_reduce.h: the kernels, the fold and so the order of additions are
+//            nfl_meshdist_reduce's).  Here only its policy: what a pair adds to a thread's columns, 19 of them in point mode
+//            and 38 in plane mode (the kernels are instantiated per mode and the other mode's columns are written as zeros).
+//            The face normal of a pair's triangle is nm_corners + nm_face_cross of nfl_geom.h, what nfl_mesh_closest runs.
 //   solve    one thread: 4 x 4 Jacobi (point mode) or a 7 x 7 Cholesky (plane mode), unrolled so that the matrices stay in
 //            registers
 //
@@ -16,18 +15,13 @@
 #include <math.h>
 
 #include "nfl_geom.h"
+#include "nfl_reduce.h"
 
 #define NR_COLS NFL_REGISTER_COLUMNS
 #define NR_POINT_COLS 19                                    // count, sum dd, and the 17 point-mode sums: columns 0 .. 18
 #define NR_PLANE_COLS 38                                    // count, sum dd, and columns NFL_REGISTER_ATA .. NR_COLS - 1
 
-static inline bool nr_misaligned(const void* p, int align) { return reinterpret_cast<uintptr_t>(p) % align != 0; }
-static inline bool nr_bad(const void* p, int align) { return !p || nr_misaligned(p, align); }
-static inline bool nr_finite(double x) { return x - x == 0.0; }
 static inline bool nr_size_ok(i64 n) { return n >= 0 && n <= ND_MAX_ENTRIES; }
-
-__device__ __forceinline__ bool nr_is_finite(float x) { return x - x == 0.f; }
-__device__ __forceinline__ bool nr_is_finite(double x) { return x - x == 0.0; }
 
 // ------------------------------------------------------------------------------------------------------------------ apply
 
@@ -46,9 +40,9 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_register_apply_kernel(const fl
 
 extern "C" int nfl_register_apply(const float* d_in, float* d_out, int64_t n, const double* d_transform, int32_t vectors,
                                   void* stream) {
-    if (!nr_size_ok(n) || (vectors != 0 && vectors != 1) || nr_bad(d_transform, 8)) return NFL_EINVAL;
+    if (!nr_size_ok(n) || (vectors != 0 && vectors != 1) || ng_bad(d_transform, 8)) return NFL_EINVAL;
     if (n == 0) return NFL_OK;
-    if (nr_bad(d_in, 4) || nr_bad(d_out, 4)) return NFL_EINVAL;
+    if (ng_bad(d_in, 4) || ng_bad(d_out, 4)) return NFL_EINVAL;
     hipLaunchKernelGGL(nfl_register_apply_kernel, dim3(nm_grid(n)), dim3(NM_THREADS), 0, static_cast<hipStream_t>(stream), d_in,
                        d_out, (i64)n, d_transform, (int)vectors);
     return ng_launched() ? NFL_OK : NFL_ELAUNCH;
@@ -66,177 +60,87 @@ struct NrPairs {
     const int32_t* triangle;
     const float *distance, *vertices;
     const int32_t* triangles;
-    i64 n, V, T;
+    i64 V, T;
     float max_distance;
     double c[3];
 };
 
+// The reduction's policy (nfl_reduce.h), one per mode: a thread keeps only its mode's columns (19 in point mode, 38 in
+// plane mode: 38 x 128 doubles of LDS = 38 KiB), and the finish writes the other mode's columns of the row as zeros.
 template <int MODE>
-struct NrMode;
-template <>
-struct NrMode<NFL_REGISTER_POINT> {
-    static constexpr int cols = NR_POINT_COLS;
-    __host__ __device__ static constexpr int column(int k) { return k; }
-};
-template <>
-struct NrMode<NFL_REGISTER_PLANE> {
-    static constexpr int cols = NR_PLANE_COLS;
-    __host__ __device__ static constexpr int column(int k) { return k < 2 ? k : k + (NFL_REGISTER_ATA - 2); }
-};
+struct NrMoments {
+    NrPairs a;
+    static constexpr int cols = MODE == NFL_REGISTER_POINT ? NR_POINT_COLS : NR_PLANE_COLS, width = NR_COLS;
+    __host__ __device__ static constexpr int column(int k) {
+        return MODE == NFL_REGISTER_POINT || k < 2 ? k : k + (NFL_REGISTER_ATA - 2);
+    }
+    typedef NgAdd Combine;
 
-// the unit face normal of triangle t as nfl_mesh_closest computes it for d_dot; false when t is not usable or has none
-__device__ __forceinline__ bool nr_face_normal(const NrPairs& a, int32_t t, float* nf) {
-    if (t < 0 || t >= a.T) return false;
-    const int32_t ia = a.triangles[3 * (i64)t], ib = a.triangles[3 * (i64)t + 1], ic = a.triangles[3 * (i64)t + 2];
-    if (!nm_in_range(ia, ib, ic, a.V)) return false;
-    float ab[3], ac[3];
-    bool ok = true;
+    // the unit face normal of triangle t, from the corners and the cross product nfl_mesh_closest's d_dot takes; false when
+    // t is not usable or has none
+    __device__ __forceinline__ bool face_normal(int32_t t, float* nf) const {
+        float ca[3], cb[3], cc[3], cr[3], len;
+        if (t < 0 || t >= a.T || !nm_corners(a.vertices, a.triangles, a.V, t, ca, cb, cc)) return false;
+        nm_face_cross(ca, cb, cc, cr, &len);
+        if (!(len > 0.f && len < INFINITY)) return false;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float va = a.vertices[3 * (i64)ia + k], vb = a.vertices[3 * (i64)ib + k], vc = a.vertices[3 * (i64)ic + k];
-        ok = ok && nr_is_finite(va) && nr_is_finite(vb) && nr_is_finite(vc);
-        ab[k] = vb - va, ac[k] = vc - va;
+        for (int k = 0; k < 3; ++k) nf[k] = cr[k] / len;
+        return true;
     }
-    if (!ok) return false;
-    const float cr[3] = {ab[1] * ac[2] - ab[2] * ac[1], ab[2] * ac[0] - ab[0] * ac[2], ab[0] * ac[1] - ab[1] * ac[0]};
-    const float len = sqrtf((cr[0] * cr[0] + cr[1] * cr[1]) + cr[2] * cr[2]);
-    if (!(len > 0.f && len < INFINITY)) return false;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) nf[k] = cr[k] / len;
-    return true;
-}
 
-// adds pair i to the thread's columns when it counts
-template <int MODE>
-__device__ __forceinline__ void nr_add_pair(const NrPairs& a, i64 i, double* acc) {
-    const float P[3] = {a.points[3 * i], a.points[3 * i + 1], a.points[3 * i + 2]};
-    const float Q[3] = {a.closest[3 * i], a.closest[3 * i + 1], a.closest[3 * i + 2]};
-    bool ok = true;
+    // adds pair i to the thread's columns when it counts
+    __device__ __forceinline__ void add(i64 i, double* acc) const {
+        const float P[3] = {a.points[3 * i], a.points[3 * i + 1], a.points[3 * i + 2]};
+        const float Q[3] = {a.closest[3 * i], a.closest[3 * i + 1], a.closest[3 * i + 2]};
+        bool ok = true;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) ok = ok && nr_is_finite(P[k]) && nr_is_finite(Q[k]);
-    if (!ok) return;
-    double p[3], q[3], e[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        p[k] = (double)P[k] - a.c[k];
-        q[k] = (double)Q[k] - a.c[k];
-        e[k] = (double)P[k] - (double)Q[k];
-    }
-    double dd = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
-    if (a.distance) {
-        const float d = a.distance[i];
-        if (!(d < INFINITY) || !(d <= a.max_distance)) return;
-        dd = (double)d * (double)d;
-    }
-    float nf[3] = {0.f, 0.f, 0.f};
-    if (a.triangle && !nr_face_normal(a, a.triangle[i], nf)) return;
-    acc[0] += 1.0;
-    acc[1] += dd;
-    if (MODE == NFL_REGISTER_POINT) {
+        for (int k = 0; k < 3; ++k) ok = ok && ng_is_finite(P[k]) && ng_is_finite(Q[k]);
+        if (!ok) return;
+        double p[3], q[3], e[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            acc[NFL_REGISTER_SUM_P + k] += p[k];
-            acc[NFL_REGISTER_SUM_Q + k] += q[k];
+            p[k] = (double)P[k] - a.c[k];
+            q[k] = (double)Q[k] - a.c[k];
+            e[k] = (double)P[k] - (double)Q[k];
         }
-        acc[NFL_REGISTER_SUM_PP] += (p[0] * p[0] + p[1] * p[1]) + p[2] * p[2];
-        acc[NFL_REGISTER_SUM_QQ] += (q[0] * q[0] + q[1] * q[1]) + q[2] * q[2];
+        double dd = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+        if (a.distance) {
+            const float d = a.distance[i];
+            if (!(d < INFINITY) || !(d <= a.max_distance)) return;
+            dd = (double)d * (double)d;
+        }
+        float nf[3] = {0.f, 0.f, 0.f};
+        if (a.triangle && !face_normal(a.triangle[i], nf)) return;
+        acc[0] += 1.0;
+        acc[1] += dd;
+        if (MODE == NFL_REGISTER_POINT) {
 #pragma unroll
-        for (int i3 = 0; i3 < 3; ++i3)
+            for (int k = 0; k < 3; ++k) {
+                acc[NFL_REGISTER_SUM_P + k] += p[k];
+                acc[NFL_REGISTER_SUM_Q + k] += q[k];
+            }
+            acc[NFL_REGISTER_SUM_PP] += (p[0] * p[0] + p[1] * p[1]) + p[2] * p[2];
+            acc[NFL_REGISTER_SUM_QQ] += (q[0] * q[0] + q[1] * q[1]) + q[2] * q[2];
 #pragma unroll
-            for (int j = 0; j < 3; ++j) acc[NFL_REGISTER_SUM_PQ + 3 * i3 + j] += p[i3] * q[j];
-    } else {
-        const double N[3] = {(double)nf[0], (double)nf[1], (double)nf[2]};
-        const double v[7] = {p[1] * N[2] - p[2] * N[1], p[2] * N[0] - p[0] * N[2], p[0] * N[1] - p[1] * N[0], N[0], N[1], N[2],
-                             (p[0] * N[0] + p[1] * N[1]) + p[2] * N[2]};
-        const double r = (N[0] * e[0] + N[1] * e[1]) + N[2] * e[2];
-        int at = 2;                                                     // the thread's columns: count, dd, then ATA .. SUM_RR
+            for (int i3 = 0; i3 < 3; ++i3)
 #pragma unroll
-        for (int i7 = 0; i7 < 7; ++i7)
+                for (int j = 0; j < 3; ++j) acc[NFL_REGISTER_SUM_PQ + 3 * i3 + j] += p[i3] * q[j];
+        } else {
+            const double N[3] = {(double)nf[0], (double)nf[1], (double)nf[2]};
+            const double v[7] = {p[1] * N[2] - p[2] * N[1], p[2] * N[0] - p[0] * N[2], p[0] * N[1] - p[1] * N[0], N[0], N[1], N[2],
+                                 (p[0] * N[0] + p[1] * N[1]) + p[2] * N[2]};
+            const double r = (N[0] * e[0] + N[1] * e[1]) + N[2] * e[2];
+            int at = 2;                                                 // the thread's columns: count, dd, then ATA .. SUM_RR
 #pragma unroll
-            for (int j = i7; j < 7; ++j) acc[at++] += v[i7] * v[j];
+            for (int i7 = 0; i7 < 7; ++i7)
 #pragma unroll
-        for (int i7 = 0; i7 < 7; ++i7) acc[at++] += v[i7] * r;
-        acc[at] += r * r;
-    }
-}
-
-// The 256 threads' columns folded by halving into thread 0's: row t += row t + off for t < off, off = 128 .. 1.  `lds` is
-// NC x 128 doubles.  Every thread calls.
-template <int NC>
-__device__ __forceinline__ void nr_fold(double* acc, double* lds) {
-    const int tid = threadIdx.x;
-    __syncthreads();                                                    // whoever used lds before has finished with it
-    if (tid >= 128) {
+                for (int j = i7; j < 7; ++j) acc[at++] += v[i7] * v[j];
 #pragma unroll
-        for (int k = 0; k < NC; ++k) lds[k * 128 + (tid - 128)] = acc[k];
-    }
-    __syncthreads();
-    if (tid < 128) {
-#pragma unroll
-        for (int k = 0; k < NC; ++k) acc[k] = acc[k] + lds[k * 128 + tid];
-    }
-    __syncthreads();
-    if (tid >= 64 && tid < 128) {
-#pragma unroll
-        for (int k = 0; k < NC; ++k) lds[k * 128 + (tid - 64)] = acc[k];
-    }
-    __syncthreads();
-    if (tid < 64) {                                                     // wave 0, all of its lanes
-#pragma unroll
-        for (int k = 0; k < NC; ++k) {
-            double v = acc[k] + lds[k * 128 + tid];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v = v + __shfl_down(v, off);     // lanes >= off hold what nobody reads
-            acc[k] = v;
+            for (int i7 = 0; i7 < 7; ++i7) acc[at++] += v[i7] * r;
+            acc[at] += r * r;
         }
     }
-}
-
-template <int MODE>
-__global__ __launch_bounds__(256) void nfl_register_parts_kernel(const NrPairs a, double* parts) {
-    constexpr int NC = NrMode<MODE>::cols;
-    __shared__ double lds[NC * 128];
-    double acc[NC];
-#pragma unroll
-    for (int k = 0; k < NC; ++k) acc[k] = 0.0;
-    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (i64)gridDim.x * 256) nr_add_pair<MODE>(a, i, acc);
-    nr_fold<NC>(acc, lds);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < NC; ++k) parts[(size_t)blockIdx.x * NR_COLS + NrMode<MODE>::column(k)] = acc[k];
-    }
-}
-
-template <int MODE>
-__global__ __launch_bounds__(256) void nfl_register_finish_kernel(const double* parts, int n_parts, double* row) {
-    constexpr int NC = NrMode<MODE>::cols;
-    __shared__ double lds[NC * 128];
-    const int tid = threadIdx.x;
-    double acc[NC];
-#pragma unroll
-    for (int k = 0; k < NC; ++k) acc[k] = 0.0;
-    for (int i = tid; i < n_parts; i += 256) {
-#pragma unroll
-        for (int k = 0; k < NC; ++k) acc[k] += parts[(size_t)i * NR_COLS + NrMode<MODE>::column(k)];
-    }
-    nr_fold<NC>(acc, lds);
-    // the other mode's columns: zeros, written by the threads that own nothing else
-    if (tid >= 64 && tid < 64 + NR_COLS) {
-        const int col = tid - 64;
-        const bool mine = MODE == NFL_REGISTER_POINT ? col < NR_POINT_COLS : (col < 2 || col >= NFL_REGISTER_ATA);
-        if (!mine) row[col] = 0.0;
-    }
-    if (tid == 0) {
-#pragma unroll
-        for (int k = 0; k < NC; ++k) row[NrMode<MODE>::column(k)] = acc[k];
-    }
-}
-
-template <int MODE>
-static void nr_launch_moments(const NrPairs& a, i64 blocks, double* parts, double* row, hipStream_t s) {
-    if (blocks) hipLaunchKernelGGL(nfl_register_parts_kernel<MODE>, dim3((unsigned)blocks), dim3(256), 0, s, a, parts);
-    hipLaunchKernelGGL(nfl_register_finish_kernel<MODE>, dim3(1), dim3(256), 0, s, parts, (int)blocks, row);
-}
+};
 
 extern "C" int nfl_register_moments(const float* d_points, const float* d_closest, const int32_t* d_triangle,
                                     const float* d_distance, const float* d_vertices, const int32_t* d_triangles, int64_t n,
@@ -245,15 +149,12 @@ extern "C" int nfl_register_moments(const float* d_points, const float* d_closes
     if (!nr_size_ok(n) || !nm_sizes_ok(n_vertices, n_triangles)) return NFL_EINVAL;
     if (mode != NFL_REGISTER_POINT && mode != NFL_REGISTER_PLANE) return NFL_EINVAL;
     if (!(max_distance > 0.f)) return NFL_EINVAL;                                       // NaN included
-    if (!nr_finite(cx) || !nr_finite(cy) || !nr_finite(cz) || nr_bad(d_row, 8)) return NFL_EINVAL;
+    if (!ng_finite(cx) || !ng_finite(cy) || !ng_finite(cz) || ng_bad(d_row, 8)) return NFL_EINVAL;
     if (n) {
-        if (nr_bad(d_points, 4) || nr_bad(d_closest, 4)) return NFL_EINVAL;
+        if (ng_bad(d_points, 4) || ng_bad(d_closest, 4)) return NFL_EINVAL;
         if (mode == NFL_REGISTER_PLANE && (!d_triangle || !d_distance)) return NFL_EINVAL;
-        if (nr_misaligned(d_triangle, 4) || nr_misaligned(d_distance, 4)) return NFL_EINVAL;
-        if (d_triangle) {
-            if ((n_vertices && !d_vertices) || (n_triangles && !d_triangles)) return NFL_EINVAL;
-            if (nr_misaligned(d_vertices, 4) || nr_misaligned(d_triangles, 4)) return NFL_EINVAL;
-        }
+        if (ng_misaligned(d_triangle, 4) || ng_misaligned(d_distance, 4)) return NFL_EINVAL;
+        if (d_triangle && !nd_mesh_ok(d_vertices, d_triangles, n_vertices, n_triangles)) return NFL_EINVAL;
     }
     double* parts = nullptr;
     const i64 blocks = nd_reduce_blocks(n);
@@ -263,13 +164,13 @@ extern "C" int nfl_register_moments(const float* d_points, const float* d_closes
         if (rc != NFL_OK) return rc;
         parts = S.get<double>(NR_M_PARTS);
     }
-    const NrPairs a = {d_points, d_closest, d_triangle, d_distance, d_vertices, d_triangles, n, n_vertices, n_triangles,
+    const NrPairs a = {d_points, d_closest, d_triangle, d_distance, d_vertices, d_triangles, n_vertices, n_triangles,
                        max_distance, {cx, cy, cz}};
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (mode == NFL_REGISTER_POINT)
-        nr_launch_moments<NFL_REGISTER_POINT>(a, blocks, parts, d_row, s);
+        ng_reduce_launch(NrMoments<NFL_REGISTER_POINT>{a}, n, blocks, parts, d_row, s);
     else
-        nr_launch_moments<NFL_REGISTER_PLANE>(a, blocks, parts, d_row, s);
+        ng_reduce_launch(NrMoments<NFL_REGISTER_PLANE>{a}, n, blocks, parts, d_row, s);
     return ng_launched() ? NFL_OK : NFL_ELAUNCH;
 }
 
@@ -473,7 +374,7 @@ __global__ __launch_bounds__(64) void nfl_register_solve_kernel(const double* ro
 #pragma unroll
             for (int i = 0; i < 3; ++i) N[10 + i] = S.ds * y[i] + S.dt[i];
 #pragma unroll
-            for (int k = 0; k < NFL_REGISTER_TRANSFORM; ++k) ok = ok && nr_is_finite(N[k]);
+            for (int k = 0; k < NFL_REGISTER_TRANSFORM; ++k) ok = ok && ng_is_finite(N[k]);
         }
         if (ok) {
 #pragma unroll
@@ -491,8 +392,8 @@ extern "C" int nfl_register_solve(const double* d_row, int32_t mode, int32_t wit
     if (mode != NFL_REGISTER_POINT && mode != NFL_REGISTER_PLANE) return NFL_EINVAL;
     if ((with_scale != 0 && with_scale != 1) || min_pairs < 1 || iteration < 0 || iteration > INT32_MAX / NFL_REGISTER_HISTORY)
         return NFL_EINVAL;
-    if (!nr_finite(cx) || !nr_finite(cy) || !nr_finite(cz)) return NFL_EINVAL;
-    if (nr_bad(d_row, 8) || nr_bad(d_transform, 8) || nr_bad(d_history, 8)) return NFL_EINVAL;
+    if (!ng_finite(cx) || !ng_finite(cy) || !ng_finite(cz)) return NFL_EINVAL;
+    if (ng_bad(d_row, 8) || ng_bad(d_transform, 8) || ng_bad(d_history, 8)) return NFL_EINVAL;
     const NrCentre C = {{cx, cy, cz}};
     hipLaunchKernelGGL(nfl_register_solve_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), d_row, (int)mode,
                        (int)with_scale, (i64)min_pairs, C, d_transform, d_history, (int)iteration);

@@ -81,16 +81,6 @@ __device__ __forceinline__ double nc_centre(const NcGrid& G, int k, i64 i) {
     return G.origin[k] + ((double)i + 0.5) * G.cell;
 }
 
-// the finaliser of splitmix64: every input bit reaches every output bit
-__device__ __forceinline__ u64 nc_mix(u64 x) {
-    x ^= x >> 30;
-    x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27;
-    x *= 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    return x;
-}
-
 // --------------------------------------------------------------------------------------------------------------- count
 
 __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_init_kernel(u64* vkey, int32_t* vmin, u64 cap_v, int32_t* towner,
@@ -120,7 +110,7 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_vertices_kernel(const
         if (nc_cell(pos, v, G, pd, ijk)) {
             const u64 key = (u64)(ijk[0] + NC_HALF) | (u64)(ijk[1] + NC_HALF) << 21 | (u64)(ijk[2] + NC_HALF) << 42;
             const u64 mask = cap_v - 1;
-            s = nc_mix(key) & mask;
+            s = ng_mix(key) & mask;
             for (u64 n = 0; n < cap_v; ++n) {
                 u64 cur = NM_LOAD(vkey + s);
                 if (cur == NC_EMPTY_KEY) {                  // free when read: claim it, or learn who did
@@ -188,7 +178,7 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_simplify_triangles_kernel(cons
     u64 s = 0;
     if (m0 >= 0) {
         const u64 mask = cap_t - 1;
-        s = nc_mix(nc_mix((u64)(uint32_t)m0 | (u64)(uint32_t)m1 << 32) + (u64)(uint32_t)m2) & mask;
+        s = ng_mix(ng_mix((u64)(uint32_t)m0 | (u64)(uint32_t)m1 << 32) + (u64)(uint32_t)m2) & mask;
         for (u64 n = 0; n < cap_t; ++n) {
             int32_t cur = NM_LOAD(towner + s);
             if (cur == -1) {

@@ -76,15 +76,13 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_tsdf_fuse_kernel(const nfl_tsd
     a.d_views[at] = views;
 }
 
-static inline bool nts_misaligned(const void* p, int align) { return reinterpret_cast<uintptr_t>(p) % align != 0; }
-
 extern "C" int nfl_tsdf_fuse(const nfl_tsdf_fuse_args* a, void* stream) {
     if (!a || !nmc_run_ok(a->d_table, a->n_images, a->first, a->count)) return NFL_EINVAL;
     if (!ng_dims_ok(a->nx, a->ny, a->nz)) return NFL_EINVAL;
     if (!(a->trunc > 0.f)) return NFL_EINVAL;                                           // NaN included
     if (!nmc_words_ok(a->d_depth, a->n_depth, 4)) return NFL_EINVAL;
-    if (nts_misaligned(a->d_pixel_weights, 4) || nts_misaligned(a->d_image_weights, 4)) return NFL_EINVAL;
-    if (!a->d_acc || !a->d_views || nts_misaligned(a->d_acc, 8) || nts_misaligned(a->d_views, 4)) return NFL_EINVAL;
+    if (ng_misaligned(a->d_pixel_weights, 4) || ng_misaligned(a->d_image_weights, 4)) return NFL_EINVAL;
+    if (ng_bad(a->d_acc, 8) || ng_bad(a->d_views, 4)) return NFL_EINVAL;
     if (a->count == 0 && !a->start) return NFL_OK;
     const i64 tiles = nts_tiles(a->nx, a->ny, a->nz);                                   // 2^30 points: far below 2^31 tiles
     if (tiles > INT32_MAX) return NFL_EINVAL;
@@ -108,7 +106,7 @@ extern "C" int nfl_tsdf_resolve(const nfl_tsdf_resolve_args* a, void* stream) {
     if (!a || !ng_dims_ok(a->nx, a->ny, a->nz)) return NFL_EINVAL;
     if (!(a->min_weight > 0.f) || a->min_views < 1 || !(a->fill == a->fill)) return NFL_EINVAL;
     if (!a->d_acc || !a->d_views || !a->d_lattice || !a->d_known) return NFL_EINVAL;
-    if (nts_misaligned(a->d_acc, 8) || nts_misaligned(a->d_views, 4) || nts_misaligned(a->d_lattice, 4)) return NFL_EINVAL;
+    if (ng_misaligned(a->d_acc, 8) || ng_misaligned(a->d_views, 4) || ng_misaligned(a->d_lattice, 4)) return NFL_EINVAL;
     const i64 n_points = (i64)a->nx * a->ny * a->nz;
     hipLaunchKernelGGL(nfl_tsdf_resolve_kernel, dim3(nm_grid(n_points)), dim3(NM_THREADS), 0, static_cast<hipStream_t>(stream), *a);
     return ng_launched() ? NFL_OK : NFL_ELAUNCH;
@@ -125,7 +123,7 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_tsdf_support_kernel(const nfl_
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const float g = (a.d_vertices[3 * v + k] - a.lo[k]) / a.spacing[k];
-        inside = inside && nmc_finite(g) && g >= 0.f && g <= (float)(dims[k] - 1);
+        inside = inside && ng_is_finite(g) && g >= 0.f && g <= (float)(dims[k] - 1);
         lo[k] = inside ? (int)floorf(g) : 0, hi[k] = inside ? (int)ceilf(g) : 0;
     }
     bool all = inside;
@@ -144,7 +142,7 @@ extern "C" int nfl_tsdf_support(const nfl_tsdf_support_args* a, void* stream) {
     if (a->n_vertices < 0 || a->n_vertices > INT32_MAX) return NFL_EINVAL;
     if (!a->d_known) return NFL_EINVAL;
     if (a->n_vertices == 0) return NFL_OK;
-    if (!a->d_vertices || !a->d_support || nts_misaligned(a->d_vertices, 4)) return NFL_EINVAL;
+    if (!a->d_vertices || !a->d_support || ng_misaligned(a->d_vertices, 4)) return NFL_EINVAL;
     hipLaunchKernelGGL(nfl_tsdf_support_kernel, dim3(nm_grid(a->n_vertices)), dim3(NM_THREADS), 0, static_cast<hipStream_t>(stream), *a);
     return ng_launched() ? NFL_OK : NFL_ELAUNCH;
 }

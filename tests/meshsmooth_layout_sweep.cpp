@@ -1,52 +1,8 @@
 // Host-side sweep of the two scratch layouts of the mesh smoothing (na_layout, na_smooth_layout of csrc/nfl_geom_layout.h),
-// built with -fsanitize=address,undefined by tests/test_meshsmooth_layout_sanitizer_cpu.py: the same checks
-// tests/geom_layout_sweep.cpp makes of the older layouts.  For every size: the walk without a base and the walk over a
-// buffer agree; every region starts 16-byte aligned, regions follow each other without overlap and the last one ends inside
-// the buffer; one byte less is NFL_ESMALL and a misaligned buffer NFL_EINVAL.  The buffer has exactly the size the first
-// walk gave and the first and last byte of every region are written.  Also the bounds emit puts on the totals.
+// built with -fsanitize=address,undefined by tests/test_meshsmooth_layout_sanitizer_cpu.py.  Every size goes through the
+// check of tests/layout_sweep.h, which says what it asserts.  Also the bounds emit puts on the totals.
 // Prints "layouts ok <n>".
-#include <cstdio>
-#include <cstdlib>
-
-#include "../nerf_fl_amd/csrc/nfl_geom_layout.h"
-
-static long g_checked = 0;
-
-#define NG_CHECK(cond)                                                                  \
-    do {                                                                                \
-        if (!(cond)) {                                                                  \
-            printf("layout invariant broken: %s (%s %lld %lld)\n", #cond, what, a, b);  \
-            return false;                                                               \
-        }                                                                               \
-    } while (0)
-
-template <int N>
-static bool check(NgLayout<N> L, const char* what, long long a, long long b) {
-    const size_t total = ng_bytes(L);
-    NG_CHECK(total % 16 == 0);
-    if (total == 0) {
-        for (int i = 0; i < N; ++i) NG_CHECK(L.r[i].elem * L.r[i].count == 0);
-        ++g_checked;
-        return true;
-    }
-    char* buf = static_cast<char*>(aligned_alloc(16, total));
-    NG_CHECK(buf != nullptr);
-    NG_CHECK(ng_carve(L, buf, total - 1) == NFL_ESMALL && ng_carve(L, buf + 4, total) == NFL_EINVAL);
-    NG_CHECK(ng_carve(L, nullptr, total) == NFL_EINVAL && ng_carve(L, buf + 4, total - 1) == NFL_EINVAL);
-    NG_CHECK(ng_carve(L, buf, total) == NFL_OK);
-    const char* end = buf;
-    for (int i = 0; i < N; ++i) {
-        const size_t bytes = L.r[i].elem * L.r[i].count;
-        NG_CHECK(L.at[i] >= end && (L.at[i] - buf) % 16 == 0 && L.at[i] - end < 16);
-        NG_CHECK((size_t)(L.at[i] - buf) + bytes <= total);
-        if (bytes) L.at[i][0] = L.at[i][bytes - 1] = (char)i;
-        end = L.at[i] + bytes;
-    }
-    NG_CHECK((size_t)(end - buf) <= total && total - (size_t)(end - buf) < 16);
-    free(buf);
-    ++g_checked;
-    return true;
-}
+#include "layout_sweep.h"
 
 int main() {
     const long long mesh[] = {0, 1, 2, 3, 63, 64, 65, 2047, 2048, 2049, 5000, 100003};

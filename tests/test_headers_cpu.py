@@ -24,7 +24,7 @@ def includes(name):
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 @pytest.mark.parametrize("header", ["nfl_math.h", "nfl_dev.h", "nfl_pixel.h", "nfl_mlp.h", "nfl_render_impl.h",
-                                    "nfl_geom_layout.h", "nfl_geom.h", "nfl_launch.h", "nfl_compose.h"])
+                                    "nfl_geom_layout.h", "nfl_geom.h", "nfl_reduce.h", "nfl_launch.h", "nfl_compose.h"])
 def test_header_compiles_on_its_own(header, tmp_path):
     src = tmp_path / "includer.hip"
     src.write_text('#include "%s"\n' % header)

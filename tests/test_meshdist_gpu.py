@@ -296,7 +296,7 @@ def test_samples_of_a_ball_lie_on_their_triangles():
 
 # ---- the reduction
 
-@pytest.mark.parametrize("N", [1, 255, 256, 257, 70001])
+@pytest.mark.parametrize("N", [1, 255, 256, 257, 70001, 262145])          # 256 * 1024 + 1: the grid-stride loop's second trip
 def test_reduction_equals_the_fixed_order_sum_on_the_bits(N):
     rng = np.random.default_rng(N)
     d = rng.random(N).astype(F) * F(3.0)

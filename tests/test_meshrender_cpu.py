@@ -37,9 +37,15 @@ def test_the_ray_test_exists_once(tmp_path):
     csrc = os.path.join(ROOT, "nerf_fl_amd", "csrc")
     hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     text = {n: open(os.path.join(csrc, n)).read() for n in ("nfl_meshray.h", "nfl_meshcolor.hip", "nfl_meshrender.hip")}
-    for fn in ("nmc_dot", "nmc_to_camera", "nmc_finite", "nmc_setup", "nmc_test", "nmc_ray"):
+    for fn in ("nmc_dot", "nmc_to_camera", "nmc_setup", "nmc_test", "nmc_ray"):
         defined = [n for n, t in text.items() if re.search(r"NFL_DEV \w+ %s\(" % fn, t)]
         assert defined == ["nfl_meshray.h"], (fn, defined)
+    # the finite test of the cull is the geometry layer's, defined there once for float and used by the raster
+    text["nfl_geom.h"] = open(os.path.join(csrc, "nfl_geom.h")).read()
+    defined = [n for n, t in text.items() if re.search(r"bool ng_is_finite\(float", t)]
+    assert defined == ["nfl_geom.h"] and "ng_is_finite(q[k][0])" in text["nfl_meshray.h"], defined
+    assert not any(re.search(r"bool \w*finite\w*\(", text[n]) for n in ("nfl_meshray.h", "nfl_meshcolor.hip", "nfl_meshrender.hip"))
+    del text["nfl_geom.h"]
     assert [n for n, t in text.items() if "struct NmcTri" in t] == ["nfl_meshray.h"]
     for unit in ("nfl_meshcolor.hip", "nfl_meshrender.hip"):
         assert '#include "nfl_meshray.h"' in text[unit] and '#include "nfl_geom.h"' in text[unit]

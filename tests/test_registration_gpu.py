@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 F = np.float32
 INF, NAN = np.inf, np.nan
 SENTINEL = -7.0
-SIZES = (1, 255, 256, 257, 70001)
+SIZES = (1, 255, 256, 257, 70001, 262145)                                   # 256 * 1024 + 1: the second trip of the reduction's loop
 MODES = {"point": rref.POINT, "plane": rref.PLANE}
 LIMIT = 0.05                                                                 # max_distance of the moments cases
 

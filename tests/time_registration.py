@@ -26,15 +26,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path[:0] = [ROOT, HERE]
 from geom_timing import host_timed, timed  # noqa: E402
+from time_meshdist import ball  # noqa: E402
 
 BYTES_PER_PAIR = 12 + 12 + 4 + 4 + 12 + 36
-
-
-def ball(n, dev, radius=0.6):
-    from nerf_fl_amd import geometry
-    c = torch.linspace(-1, 1, n, device=dev, dtype=torch.float64)
-    lat = (radius - torch.sqrt(c[:, None, None] ** 2 + c[None, :, None] ** 2 + c[None, None, :] ** 2)).float().contiguous()
-    return geometry.extract_surface(lat, 0.0, (-1.0,) * 3, (1.0,) * 3)
 
 
 def step(samples, a):
