@@ -1634,6 +1634,76 @@ int nfl_register_moments(const float* d_points, const float* d_closest, const in
 int nfl_register_solve(const double* d_row, int32_t mode, int32_t with_scale, int64_t min_pairs, double cx, double cy, double cz,
                        double* d_transform, double* d_history, int32_t iteration, void* stream);
 
+/* ---- mesh cast: where an arbitrary ray first hits a triangle mesh, whether it hits it at all, and the share of a point's
+ * hemisphere that the mesh leaves open (ambient occlusion); through THE GRID of "mesh distance", or trying every triangle --------
+ * Entry points take pointers and scalars; there is no argument struct.  Triangles are USABLE in the sense of "mesh distance",
+ * every other triangle is never hit; mix() is that section's.  A RAY is 8 floats [o (3), d (3), near, far]; d need not be
+ * normalised, t is the ray's own parameter.  A ray with a non-finite o or d, a NaN near or far, d == 0 or near > far hits
+ * nothing; near = -inf and far = +inf are allowed.
+ *
+ * THE RAY TEST of a ray and a usable triangle (a, b, c).  THIS PARAGRAPH IS FP64, every operation rounded on its own, the fp32
+ * inputs converted first, dot(x, y) = (x0 y0 + x1 y1) + x2 y2, cross(x, y) = (x1 y2 - x2 y1, x2 y0 - x0 y2, x0 y1 - x1 y0):
+ *   e1 = b - a, e2 = c - a, p = cross(d, e2), det = dot(e1, p); a det that is 0 or NaN is a miss (both faces hit: no culling);
+ *   s = o - a, u = dot(s, p) / det, q = cross(s, e1), v = dot(d, q) / det, t = dot(e2, q) / det.
+ *   The hit needs u >= 0, v >= 0, u + v <= 1, and tf = (float)t finite with near <= tf <= far (fp32 comparisons).
+ *   Q = (a + u * e1) + v * e2; qf[k] = (float)Q[k] CLAMPED into the triangle's fp32 bounding box as "mesh distance" clamps q.
+ *   THE CONSISTENCY CONDITION: with td[k] = t * d[k], on every axis |(o[k] + td[k]) - qf[k]| <= tol, where
+ *   tol = 2^-20 * max over k of (|o[k]| + |td[k]|).  It fails only where the conditioning of the test is beyond about 1e10
+ *   (triangles seen edge-on), and it is what the grid walk stands on: an accepted hit lies within tol of the ray, and (the
+ *   clamp, cellf being monotone) in a cell that lists its triangle.
+ *   THE BOX RULE, wherever a grid is given (lo, cell, dims; with or without its rows): on every axis
+ *   lo[k] <= qf[k] <= lo[k] + dims[k] * cell, the right side in fp64.  Space outside the grid's box is empty, as in "occupancy".
+ *   The hit carries tf, the corner weights ((float)((1 - u) - v), (float)u, (float)v) of a, b, c, and qf.
+ * THE ANSWER of a ray is the accepted hit with the least (tf, triangle index): ties go to the lower index, so the answer
+ * depends neither on the order in which triangles are tried nor on how often.
+ *
+ * THE WALK (grid mode), in fp64.  m = the axis of the largest |d[k]|, the lowest on a tie.  E = 2^-19 * (2 * max|o[k]| + bmax),
+ * bmax the largest absolute coordinate of the box's two corners: inside the box tol <= E / 2 for every accepted hit, whatever
+ * its t.  tn = near - (|near| * 2^-23 + 2^-148), tf' = far + (|far| * 2^-23 + 2^-148): every t with near <= (float)t <= far
+ * lies in [tn, tf'].  Slab i of axis m is the cells with index i there; with F, S the faces and slacks of "mesh distance", a hit
+ * whose qf[m] has cellf = i has o[m] + t * d[m] in [(F_i - S_i) - E, (F_i+1 + S_i+1) + E]; dividing the ends by d[m] gives
+ * [te_i, tx_i], and te_i does not decrease along the walk.  The slabs are taken in the ray's direction from two slabs before
+ * the one that floor() puts o[m] + tn * d[m] - (E + S) in; a slab with tx_i < tn is passed over; the walk ends at te_i > tf',
+ * at the grid's last slab, or BEFORE slab i when a hit is held whose tf is STRICTLY below (te_i - |te_i| * 2^-40) rounded down
+ * to fp32.  In a slab, on each other axis k the coordinates o[k] + t * d[k] at the two ends of [max(te, tn), min(tx, tf')],
+ * the lesser minus E rounded down to fp32, the greater plus E rounded up, go through cellf: every triangle of every row of
+ * that block of cells (at most 3 x 3 when E is small beside a cell, |d[k]| <= |d[m]|) is tried with THE RAY TEST.  Any-hit
+ * mode ends at the first accepted hit.  THE CONTRACT: grid mode returns the bits of brute mode given the same box, for every
+ * cell size and every origin.  A grid that is not this mesh's is read inside its arrays and never faults.
+ *
+ * nfl_mesh_cast   one launch, one thread per ray of d_rays (n_rays, 8).  BRUTE (d_offsets NULL): every ray tries every triangle,
+ *   staged through LDS 256 at a time; with nx = ny = nz = 0 there is no box rule, otherwise lo, cell and dims give the box.
+ *   GRID: d_offsets, d_entries, n_entries, lo, cell, dims of nfl_trigrid_emit for the SAME mesh.  NFL_CAST_FIRST writes d_t = tf
+ *   (+inf on a miss) and, where given, d_triangle (-1), d_bary (n_rays, 3) and d_point (n_rays, 3) = qf (NaN on a miss);
+ *   NFL_CAST_ANY writes d_t alone: 0 for a ray that hits anything, +inf for one that does not.
+ * nfl_mesh_occlusion   one launch, a wave per point i of d_points with normal n = d_normals[i] (unit length is the caller's):
+ *   the origin is o[k] = p[k] + bias * n[k] (fp32).  DIRECTION j < n_directions, fp32 throughout, no trigonometry:
+ *   h = mix(mix(mix(seed) + i) + j); attempt a = 0 .. 7: ha = mix(h + (a + 1)), x = (float)(ha >> 40) * 2^-23 - 1,
+ *   y = (float)((ha >> 16) & 0xFFFFFF) * 2^-23 - 1 (both exact, in [-1, 1)), s = x * x + y * y; the first attempt with s < 1
+ *   is taken, (x, y, s) = (0, 0, 0) if there is none; z = sqrtf(1 - s).  The frame (Duff et al. 2017): sg = copysignf(1, n2),
+ *   A = -1 / (sg + n2), B = (n0 * n1) * A, t1 = (1 + ((sg * n0) * n0) * A, sg * B, -(sg * n0)), t2 = (B, sg + (n1 * n1) * A, -n1);
+ *   d[k] = (x * t1[k] + y * t2[k]) + z * n[k]: cosine-weighted about n.  The ray [0, radius] is walked in any-hit mode;
+ *   d_hits[i] = the rays that hit (counted by ballot: no order enters), d_open[i] = (float)(n_directions - hits) / (float)
+ *   n_directions.  A point or normal with a non-finite coordinate, or a zero normal: d_hits = -1, d_open = NaN.  The grid is
+ *   required.  radius = +inf means no limit inside the box.
+ *
+ *   NFL_EINVAL (nothing launched): n_rays / n negative or above INT32_MAX, the mesh sizes and pointers as in "mesh distance",
+ *   a mode outside the enum, n_directions outside [1, 4096], radius not positive (NaN included), bias negative or not finite;
+ *   with d_offsets: dims / cell / lo as in "mesh distance", d_entries NULL or misaligned with n_entries > 0, n_entries outside
+ *   [0, INT32_MAX], d_offsets not 8-byte aligned; without (nfl_mesh_cast only; nfl_mesh_occlusion refuses): dims neither all
+ *   zero nor a grid's; for n > 0 a NULL or misaligned (4 B) d_rays, d_t, d_points, d_normals, d_hits or d_open, a misaligned
+ *   optional output.  n == 0: NFL_OK, no launch. */
+enum { NFL_CAST_FIRST = 0, NFL_CAST_ANY = 1 };
+int nfl_mesh_cast(const float* d_rays, int64_t n_rays, const float* d_vertices, const int32_t* d_triangles, int64_t n_vertices,
+                  int64_t n_triangles, const int64_t* d_offsets, const int32_t* d_entries, int64_t n_entries,
+                  float lo_x, float lo_y, float lo_z, float cell, int32_t nx, int32_t ny, int32_t nz, int32_t mode,
+                  float* d_t, int32_t* d_triangle, float* d_bary, float* d_point, void* stream);
+int nfl_mesh_occlusion(const float* d_points, const float* d_normals, int64_t n, const float* d_vertices,
+                       const int32_t* d_triangles, int64_t n_vertices, int64_t n_triangles, const int64_t* d_offsets,
+                       const int32_t* d_entries, int64_t n_entries, float lo_x, float lo_y, float lo_z, float cell,
+                       int32_t nx, int32_t ny, int32_t nz, int32_t n_directions, float radius, float bias, uint64_t seed,
+                       int32_t* d_hits, float* d_open, void* stream);
+
 /* ---- hierarchical sampling (reference sample_pdf, rendering.py:7-46, plus the
  * concat + sort of rendering.py:267-272) -------------------------------------
  * d_z_coarse (R,S), d_weights_coarse (R,S); d_u (R,I) or NULL with d_u_row (I)

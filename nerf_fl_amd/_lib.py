@@ -404,6 +404,8 @@ REGISTER_HISTORY = 4                            # count, rms, status, s per iter
 REGISTER_ROW = {"COUNT": 0, "SUM_DD": 1, "SUM_P": 2, "SUM_Q": 5, "SUM_PP": 8, "SUM_QQ": 9, "SUM_PQ": 10, "ATA": 19, "ATB": 47,
                 "SUM_RR": 54, "COLUMNS": 55}
 
+# mesh cast (nerf_fl_amd/raycast.py): plain arguments, no struct
+CAST_MODES = {"first": 0, "any": 1}
 
 # every struct include/nerf_fl_amd.h declares: C name -> its mirror
 STRUCTS = {
@@ -450,6 +452,7 @@ CONSTANTS = {
     "NFL_REGISTER_SINGULAR": REGISTER_STATUS["singular"],
     "NFL_REGISTER_TRANSFORM": REGISTER_TRANSFORM, "NFL_REGISTER_HISTORY": REGISTER_HISTORY,
     **{"NFL_REGISTER_" + k: v for k, v in REGISTER_ROW.items()},
+    "NFL_CAST_FIRST": CAST_MODES["first"], "NFL_CAST_ANY": CAST_MODES["any"],
 }
 
 # every function include/nerf_fl_amd.h declares: (name, restype, argtypes)
@@ -551,6 +554,13 @@ SYMBOLS = [
                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     ("nfl_register_solve", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_double, C.c_double, C.c_double,
                                      C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("nfl_mesh_cast", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32,
+                                C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nfl_mesh_occlusion", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                     C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32,
+                                     C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
     ("nfl_abi_version", C.c_int, []),
     ("nfl_version", C.c_char_p, []),
     ("nfl_strerror", C.c_char_p, [C.c_int]),

@@ -1,10 +1,10 @@
 // nfl_geom.h -- what the geometry translation units share on the device side (every unit that makes, cleans, simplifies,
-// smooths, colours, renders, fuses, measures or registers a lattice or a mesh: nfl_surface, nfl_mesh, nfl_mesh_scan,
-// nfl_occupancy, nfl_simplify, nfl_meshsmooth, nfl_tsdf, nfl_meshdist, nfl_register, and through nfl_meshray.h nfl_meshcolor,
-// nfl_meshrender and nfl_atlas): launch sizes, the finite test, the splitmix64 hash, the fetch of an fp32 triangle and its
-// face normal, the workgroup prefix sum, the library's tiled scan and the small pieces of the mesh kernels.  The scratch
-// layouts, the size checks and the pointer checks are host arithmetic and live in nfl_geom_layout.h; the fixed-order fp64
-// reduction is nfl_reduce.h.  DESIGN.md sections 22 and 35.
+// smooths, colours, renders, fuses, measures, registers or casts rays against a lattice or a mesh: nfl_surface, nfl_mesh,
+// nfl_mesh_scan, nfl_occupancy, nfl_simplify, nfl_meshsmooth, nfl_tsdf, nfl_meshdist, nfl_register, nfl_meshcast, and through
+// nfl_meshray.h nfl_meshcolor, nfl_meshrender and nfl_atlas): launch sizes, the finite test, the splitmix64 hash, the fetch of
+// an fp32 triangle and its face normal, the triangle grid's cell function and faces, the workgroup prefix sum, the library's
+// tiled scan and the small pieces of the mesh kernels.  The scratch layouts, the size checks and the pointer checks are host
+// arithmetic and live in nfl_geom_layout.h; the fixed-order fp64 reduction is nfl_reduce.h.  DESIGN.md sections 22 and 35.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -60,6 +60,35 @@ __device__ __forceinline__ void nm_face_cross(const float* a, const float* b, co
     cr[1] = ab[2] * ac[0] - ab[0] * ac[2];
     cr[2] = ab[0] * ac[1] - ab[1] * ac[0];
     *len = sqrtf((cr[0] * cr[0] + cr[1] * cr[1]) + cr[2] * cr[2]);
+}
+
+// THE GRID of "mesh distance": what nfl_meshdist (which builds it and finds closest points in it) and nfl_meshcast (which
+// walks rays through it) share, so that both mean the same cells
+struct NdGrid {
+    float lo[3];
+    float cell;
+    int32_t dims[3];
+};
+
+static inline bool nd_grid_ok(const float* lo, float cell, const int32_t* dims) {
+    if (!nd_dims_ok(dims) || !(cell > 0.f) || !ng_finite(cell)) return false;
+    return ng_finite(lo[0]) && ng_finite(lo[1]) && ng_finite(lo[2]);
+}
+
+static inline NdGrid nd_grid_of(const float* lo, float cell, const int32_t* dims) {
+    return {{lo[0], lo[1], lo[2]}, cell, {dims[0], dims[1], dims[2]}};
+}
+
+__device__ __forceinline__ int nd_cellf(float x, float lo, float cell, int n) {
+    return (int)fminf(fmaxf(floorf((x - lo) / cell), 0.f), (float)(n - 1));
+}
+
+// the face at index i of an axis that starts at lo, in fp64: F = lo + i * cell, and its explicit slack S = 2^-21 * (|lo| + i * cell).
+// cellf is computed in fp32, and the smallest x with cellf(x) >= i lies within S of F
+__device__ __forceinline__ void nd_face(float lo32, float cell, int i, double* F, double* S) {
+    const double lo = (double)lo32, ic = (double)i * (double)cell;
+    *F = lo + ic;
+    *S = 4.76837158203125e-07 * (fabs(lo) + ic);                                        // 2^-21
 }
 
 // adds the wave's number of `bad` lanes to *counter: one atomic per wave that has any.  Every lane must call it.

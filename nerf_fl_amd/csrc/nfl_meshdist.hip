@@ -44,22 +44,8 @@ extern "C" int nfl_meshdist_debug_counts(u64* out3, int reset) {
 #define ND_DEBUG_ADD(k, n)
 #endif
 
-struct NdGrid {
-    float lo[3];
-    float cell;
-    int32_t dims[3];
-};
-
-static bool nd_grid_ok(const float* lo, float cell, const int32_t* dims) {
-    if (!nd_dims_ok(dims) || !(cell > 0.f) || !ng_finite(cell)) return false;
-    return ng_finite(lo[0]) && ng_finite(lo[1]) && ng_finite(lo[2]);
-}
-
 // ---------------------------------------------------------------------------------------------------------- device pieces
-
-__device__ __forceinline__ int nd_cellf(float x, float lo, float cell, int n) {
-    return (int)fminf(fmaxf(floorf((x - lo) / cell), 0.f), (float)(n - 1));
-}
+// (the grid itself -- NdGrid, nd_grid_ok, nd_grid_of, nd_cellf, nd_face -- is nfl_geom.h's: nfl_meshcast walks the same cells)
 
 __device__ __forceinline__ float nd_dot(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 
@@ -175,10 +161,6 @@ static int nd_grid_carve(const nfl_trigrid_args* a, NdGridScratch& S) {
     return ng_carve(S, a->d_scratch, a->scratch_bytes);
 }
 
-static NdGrid nd_grid_of(const float* lo, float cell, const int32_t* dims) {
-    return {{lo[0], lo[1], lo[2]}, cell, {dims[0], dims[1], dims[2]}};
-}
-
 __global__ __launch_bounds__(NM_THREADS) void nfl_trigrid_zero_kernel(int32_t* cnt, i64 cells, i64* totals) {
     const i64 c = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
     if (c < cells) cnt[c] = 0;
@@ -262,8 +244,8 @@ extern "C" int nfl_trigrid_emit(const nfl_trigrid_args* a, void* stream) {
 
 // g * g of the header for one face: the face at index i of axis k, p beyond it by G in fp64
 __device__ __forceinline__ float nd_face_bound(const NdGrid& G, int k, int i, float p, bool low_side) {
-    const double lo = (double)G.lo[k], ic = (double)i * (double)G.cell;
-    const double F = lo + ic, S = 4.76837158203125e-07 * (fabs(lo) + ic);              // 2^-21
+    double F, S;
+    nd_face(G.lo[k], G.cell, i, &F, &S);
     double gap = low_side ? (double)p - (F + S) : (F - S) - (double)p;
     if (!(gap > 0.0)) gap = 0.0;
     const float g = (float)(gap * (1.0 - 1.1920928955078125e-07));                      // 1 - 2^-23

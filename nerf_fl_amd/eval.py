@@ -169,7 +169,8 @@ def batched_inference(models, embeddings, rays, ts, N_samples, N_importance, use
 def clipped_inference(models, embeddings, rays, ts, grid, N_samples, N_importance, use_disp=False, chunk=1024 * 128,
                       white_back=False, **kwargs):
     """batched_inference with empty space skipped: `rays` ((B, 8) matrix) are clipped to the geometry.OccupancyGrid
-    `grid` (geometry.clip_rays), the rays that meet an occupied cell are rendered between their tightened bounds with
+    `grid` (geometry.clip_rays) -- or to the band round a surface of a raycast.MeshBand (its clip: the first hit of every
+    ray against a mesh, -+ the band) -- the rays that meet an occupied cell are rendered between their tightened bounds with
     the same N_samples + N_importance, and the rows of the others are filled with what the compositing gives when every
     weight is zero: 1 (white_back) or 0 for every key containing `rgb`, the fine model's beta_min for `beta`, 0 for the
     rest.  `ts` and the per-ray kwargs (GraphedChunk.PER_RAY) with B rows follow their rays; a (1, C) one stays
@@ -179,8 +180,9 @@ def clipped_inference(models, embeddings, rays, ts, grid, N_samples, N_importanc
     ONE host synchronisation per call: the hit rays are compacted, in their original order, with torch.nonzero.
     Space outside the grid's box renders as empty."""
     from . import geometry
+    from .raycast import MeshBand
     B = rays.shape[0]
-    clipped, hit = geometry.clip_rays(grid, rays)
+    clipped, hit = grid.clip(rays) if isinstance(grid, MeshBand) else geometry.clip_rays(grid, rays)
     idx = torch.nonzero(hit).squeeze(1)                             # the host synchronisation
     n = idx.shape[0]
     kw = dict(kwargs)
@@ -428,7 +430,7 @@ def render_frame(models, embeddings, c2w, K, H, W, near, far, N_samples, N_impor
     """One H x W frame from (pose, intrinsics): the rays are generated in the render kernel's prologue (CameraRays), the
     image is converted on the device.  Returns (uint8 (H, W, 3), dict of the float outputs).  `ts`: image id for the
     latent tables -- an int, a (H*W,) tensor, or None when `a_embedded` is given / the model has no latent inputs.
-    `occupancy`: a geometry.OccupancyGrid; the frame's rays are then a matrix (frame_rays: the bounds are per ray) and go
+    `occupancy`: a geometry.OccupancyGrid, or a raycast.MeshBand (a surface and a band round it); the frame's rays are then a matrix (frame_rays: the bounds are per ray) and go
     through clipped_inference, which skips the pixels that see no occupied cell (one host synchronisation per frame)."""
     if occupancy is not None:
         rays = frame_rays(c2w, K, H, W, near, far, device)
