@@ -6,20 +6,20 @@
 //   walk    THE WALK of the header, written once (nc_walk): the slabs of grid cells along the ray's major axis, in each the
 //           cells the ray can touch on the other two axes, until no later slab can hold an earlier hit.  Every bound is
 //           widened by E, a per-ray constant above every tolerance the consistency condition can grant inside the grid's box.
-//   cast    a thread per ray.  Brute: the workgroup stages 256 triangles' corners in LDS as nfl_mesh_closest does and every
-//           thread tries them all.  Grid: the thread walks.  Rays of a frame arrive in pixel order, so neighbouring lanes
+//   cast    a thread per ray.  Brute: the workgroup stages 256 triangles' corners in LDS (nt_tiles, as nfl_mesh_closest does) and
+//           every thread tries them all.  Grid: the thread walks.  Rays of a frame arrive in pixel order, so neighbouring lanes
 //           walk neighbouring rows.  First-hit mode keeps (t, triangle) only and tests the answer once more for its point.
 //   occlusion   a wave per point: lane l casts directions l, l + 64, ... in any-hit mode, the hits are counted by ballot.
 //
 // No atomics, no scratch buffer, nothing that depends on an order.  The grid (NdGrid, nd_cellf, nd_face), the triangle fetch and
-// the hash are nfl_geom.h's, the pointer checks nfl_geom_layout.h's: a ray meets the cells nfl_trigrid_emit filled.
+// the hash are nfl_geom.h's, the pointer checks nfl_geom_layout.h's: a ray meets the cells nfl_trigrid_emit filled.  The view
+// of the mesh with its grid (NtMesh), the read of a row and the staged tiles are nfl_trigrid.h's, shared with nfl_meshdist.
 #include <math.h>
 
-#include "nfl_geom.h"
+#include "nfl_trigrid.h"
 
 typedef unsigned long long u64;
 
-#define NC_TILE NM_THREADS                                  // triangles a workgroup stages in brute mode
 #define NC_MAX_DIRECTIONS 4096
 #define NC_ATTEMPTS 8
 #define NC_2M19 1.9073486328125e-06                         // 2^-19
@@ -42,18 +42,6 @@ extern "C" int nfl_meshcast_debug_counts(u64* out3, int reset) {
 #else
 #define NC_DEBUG_ADD(k, n)
 #endif
-
-// the mesh, its grid (off == nullptr: none) and whether the box rule holds
-struct NcMesh {
-    const float* ver;
-    const int32_t* tri;
-    i64 V, T;
-    const i64* off;
-    const int32_t* ent;
-    i64 E;
-    NdGrid G;
-    int boxed;
-};
 
 struct NcRay {
     double o[3], d[3];
@@ -160,23 +148,6 @@ __device__ __forceinline__ void nc_try(NcBest& best, const NcRay& R, const NcBox
 
 // --------------------------------------------------------------------------------------------------------------- the walk
 
-// one row of the grid, read inside the arrays whatever it holds
-template <bool ANY>
-__device__ __forceinline__ void nc_try_row(NcBest& best, const NcRay& R, const NcBox& B, const NcMesh& M, i64 cell) {
-    i64 r0 = M.off[cell], r1 = M.off[cell + 1];
-    r0 = r0 < 0 ? 0 : r0;
-    r1 = r1 > M.E ? M.E : r1;
-    NC_DEBUG_ADD(1, 1);
-    for (i64 e = r0; e < r1; ++e) {
-        const int32_t t = M.ent[e];
-        if (t < 0 || t >= M.T) continue;
-        float ca[3], cb[3], cc[3];
-        if (!nm_corners(M.ver, M.tri, M.V, t, ca, cb, cc)) continue;
-        nc_try(best, R, B, true, t, ca, cb, cc);
-        if (ANY && best.t >= 0) return;
-    }
-}
-
 template <typename T>
 __device__ __forceinline__ T nc_pick(const T* v, int k) { return k == 0 ? v[0] : (k == 1 ? v[1] : v[2]); }
 
@@ -211,8 +182,12 @@ __device__ __forceinline__ void nc_span(float lo, float cell, int n, double o, d
 
 // THE WALK of the header.  ANY: stops at the first accepted hit.
 template <bool ANY>
-__device__ __forceinline__ void nc_walk(NcBest& best, const NcRay& R, const NcBox& B, const NcMesh& M) {
+__device__ __forceinline__ void nc_walk(NcBest& best, const NcRay& R, const NcBox& B, const NtMesh& M) {
     const NdGrid& G = M.G;
+    const auto attempt = [&](int32_t t, const float* ca, const float* cb, const float* cc) NT_INLINE {
+        nc_try(best, R, B, true, t, ca, cb, cc);                        // where rows are walked the box rule holds
+        return ANY && best.t >= 0;
+    };
     int m = 0;
     double am = fabs(R.d[0]);
     if (fabs(R.d[1]) > am) m = 1, am = fabs(R.d[1]);
@@ -254,7 +229,8 @@ __device__ __forceinline__ void nc_walk(NcBest& best, const NcRay& R, const NcBo
             for (int j1 = a0; j1 <= a1; ++j1) {
                 const int x = m == 0 ? i : (m == 1 ? j2 : j1), y = m == 0 ? j1 : (m == 1 ? i : j2);
                 const int z = m == 0 ? j2 : (m == 1 ? j1 : i);
-                nc_try_row<ANY>(best, R, B, M, ((i64)z * G.dims[1] + y) * G.dims[0] + x);
+                NC_DEBUG_ADD(1, 1);
+                nt_row(M, ((i64)z * G.dims[1] + y) * G.dims[0] + x, attempt);
                 if (ANY && best.t >= 0) return;
             }
     }
@@ -265,7 +241,8 @@ __device__ __forceinline__ void nc_walk(NcBest& best, const NcRay& R, const NcBo
 struct NcCast {
     const float* rays;
     i64 n;
-    NcMesh M;
+    NtMesh M;
+    int boxed;                                              // the box rule holds: always with rows, in brute mode with a box
     float* t;
     int32_t* triangle;
     float *bary, *point;
@@ -282,39 +259,18 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_mesh_cast_kernel(const NcCast 
     }
     NcRay R;
     const bool asks = nc_ray(w, w + 3, w[6], w[7], R) && mine;
-    const bool boxed = a.M.boxed != 0;
+    const bool boxed = a.boxed != 0;
     NcBox B = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
     if (boxed) B = nc_box(a.M.G);
     NcBest best = {INFINITY, -1};
     if (GRID) {
         if (asks) nc_walk<ANY>(best, R, B, a.M);
     } else {
-        __shared__ float corner[9][NC_TILE];
-        __shared__ int32_t usable[NC_TILE];
-        for (i64 base = 0; base < a.M.T; base += NC_TILE) {         // the same trips for every thread: barriers inside
-            const i64 t = base + threadIdx.x;
-            float ca[3] = {0.f, 0.f, 0.f}, cb[3] = {0.f, 0.f, 0.f}, cc[3] = {0.f, 0.f, 0.f};
-            const bool ok = t < a.M.T && nm_corners(a.M.ver, a.M.tri, a.M.V, t, ca, cb, cc);
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                corner[k][threadIdx.x] = ca[k];
-                corner[3 + k][threadIdx.x] = cb[k];
-                corner[6 + k][threadIdx.x] = cc[k];
-            }
-            usable[threadIdx.x] = ok ? 1 : 0;
-            __syncthreads();
-            if (asks && !(ANY && best.t >= 0)) {
-                const int len = (int)(a.M.T - base < NC_TILE ? a.M.T - base : NC_TILE);
-                for (int j = 0; j < len; ++j) {
-                    if (!usable[j]) continue;
-                    const float ta[3] = {corner[0][j], corner[1][j], corner[2][j]};
-                    const float tb[3] = {corner[3][j], corner[4][j], corner[5][j]};
-                    const float tc[3] = {corner[6][j], corner[7][j], corner[8][j]};
-                    nc_try(best, R, B, boxed, (int32_t)(base + j), ta, tb, tc);
-                }
-            }
-        }
+        const auto still = [&]() NT_INLINE { return asks && !(ANY && best.t >= 0); };
+        const auto attempt = [&](int32_t t, const float* ta, const float* tb, const float* tc) NT_INLINE {
+            nc_try(best, R, B, boxed, t, ta, tb, tc);
+        };
+        nt_tiles(a.M, still, attempt);
     }
     if (!mine) return;
     if (ANY) {
@@ -334,14 +290,13 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_mesh_cast_kernel(const NcCast 
     }
 }
 
-// the grid part of a call: what nfl_mesh_closest asks of its grid.  `need`: the call cannot do without one
+// the grid part of a call: with rows what nfl_mesh_closest asks of them; without, all zeros or the box of a grid.  `need`: the
+// call cannot do without rows
 static bool nc_grid_args_ok(const int64_t* d_offsets, const int32_t* d_entries, int64_t n_entries, const float* lo, float cell,
                             const int32_t* dims, bool need) {
     const bool none = dims[0] == 0 && dims[1] == 0 && dims[2] == 0;
     if (!d_offsets) return !need && (none || nd_grid_ok(lo, cell, dims));              // brute mode, with or without the box
-    if (!nd_grid_ok(lo, cell, dims) || ng_misaligned(d_offsets, 8)) return false;
-    if (n_entries < 0 || n_entries > ND_MAX_ENTRIES) return false;
-    return !(n_entries && ng_bad(d_entries, 4));
+    return nt_rows_ok(d_offsets, d_entries, n_entries, lo, cell, dims);
 }
 
 extern "C" int nfl_mesh_cast(const float* d_rays, int64_t n_rays, const float* d_vertices, const int32_t* d_triangles,
@@ -359,8 +314,8 @@ extern "C" int nfl_mesh_cast(const float* d_rays, int64_t n_rays, const float* d
     if (ng_misaligned(d_triangle, 4) || ng_misaligned(d_bary, 4) || ng_misaligned(d_point, 4)) return NFL_EINVAL;
     const bool grid = d_offsets != nullptr, boxed = nx != 0;
     NcCast a = {d_rays, n_rays, {d_vertices, d_triangles, n_vertices, n_triangles, d_offsets, d_entries, grid ? n_entries : 0,
-                                 boxed ? nd_grid_of(lo, cell, dims) : NdGrid{{0.f, 0.f, 0.f}, 1.f, {1, 1, 1}}, boxed ? 1 : 0},
-                d_t, d_triangle, d_bary, d_point};
+                                 boxed ? nd_grid_of(lo, cell, dims) : NdGrid{{0.f, 0.f, 0.f}, 1.f, {1, 1, 1}}},
+                boxed ? 1 : 0, d_t, d_triangle, d_bary, d_point};
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 blocks(nm_grid(n_rays)), threads(NM_THREADS);
     if (grid && mode == NFL_CAST_FIRST) hipLaunchKernelGGL((nfl_mesh_cast_kernel<true, false>), blocks, threads, 0, s, a);
@@ -375,7 +330,7 @@ extern "C" int nfl_mesh_cast(const float* d_rays, int64_t n_rays, const float* d
 struct NcOcc {
     const float *points, *normals;
     i64 n;
-    NcMesh M;
+    NtMesh M;
     int32_t K;
     float radius, bias;
     u64 seed;
@@ -457,7 +412,7 @@ extern "C" int nfl_mesh_occlusion(const float* d_points, const float* d_normals,
     if (n == 0) return NFL_OK;
     if (ng_bad(d_points, 4) || ng_bad(d_normals, 4) || ng_bad(d_hits, 4) || ng_bad(d_open, 4)) return NFL_EINVAL;
     NcOcc a = {d_points, d_normals, n, {d_vertices, d_triangles, n_vertices, n_triangles, d_offsets, d_entries, n_entries,
-                                        nd_grid_of(lo, cell, dims), 1},
+                                        nd_grid_of(lo, cell, dims)},
                n_directions, radius, bias, seed, d_hits, d_open};
     hipLaunchKernelGGL(nfl_mesh_occlusion_kernel, dim3((unsigned)ng_cdiv(n, NM_THREADS / 64)), dim3(NM_THREADS), 0,
                        static_cast<hipStream_t>(stream), a);

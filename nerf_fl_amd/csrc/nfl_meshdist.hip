@@ -16,17 +16,17 @@
 //
 // The triangle fetch (nm_corners), the face normal (nm_face_cross), the hash (ng_mix) and the finite test are nfl_geom.h's,
 // the pointer checks nfl_geom_layout.h's: registration and the sampler read a triangle exactly as nfl_mesh_closest does.
+// The view of a mesh with its grid, the read of a row and brute mode's staged tiles are nfl_trigrid.h's, shared with nfl_meshcast.
 //
 // Only integer atomics, and nothing that depends on their order leaves a call except the order inside a grid row.  Nothing
 // here allocates, sets or copies memory through the runtime.
 #include <math.h>
 
-#include "nfl_geom.h"
 #include "nfl_reduce.h"
+#include "nfl_trigrid.h"
 
 typedef unsigned long long u64;
 
-#define ND_TILE NM_THREADS                                  // triangles a workgroup stages in brute mode
 #define ND_WAVE_SAMPLES 64                                  // a triangle with more samples is emitted by the whole wave
 
 #ifdef NFL_MESHDIST_COUNT_TESTS
@@ -252,26 +252,19 @@ __device__ __forceinline__ float nd_face_bound(const NdGrid& G, int k, int i, fl
     return g * g;
 }
 
-// one row of the grid, read inside the arrays whatever it holds
-__device__ __forceinline__ void nd_try_row(NdBest& B, const float* p, const nfl_mesh_closest_args& a, i64 cell, float limit) {
-    i64 r0 = a.d_offsets[cell], r1 = a.d_offsets[cell + 1];
-    r0 = r0 < 0 ? 0 : r0;
-    r1 = r1 > a.n_entries ? a.n_entries : r1;
-    ND_DEBUG_ADD(1, 1);
-    for (i64 e = r0; e < r1; ++e) {
-        const int32_t t = a.d_entries[e];
-        if (t < 0 || t >= a.n_triangles) continue;
-        float ca[3], cb[3], cc[3];
-        if (!nm_corners(a.d_vertices, a.d_triangles, a.n_vertices, t, ca, cb, cc)) continue;
-        ND_DEBUG_ADD(0, 1);
-        nd_try(B, p, t, ca, cb, cc, limit);
-    }
-}
-
 __device__ __forceinline__ int nd_iabs(int x) { return x < 0 ? -x : x; }
 
-__device__ __forceinline__ void nd_walk_grid(NdBest& B, const float* p, const nfl_mesh_closest_args& a, float limit) {
-    const NdGrid G = {{a.lo[0], a.lo[1], a.lo[2]}, a.cell, {a.dims[0], a.dims[1], a.dims[2]}};
+__device__ __forceinline__ void nd_walk_grid(NdBest& B, const float* p, const NtMesh& M, float limit) {
+    const NdGrid& G = M.G;
+    const auto attempt = [&](int32_t t, const float* ca, const float* cb, const float* cc) NT_INLINE {
+        ND_DEBUG_ADD(0, 1);
+        nd_try(B, p, t, ca, cb, cc, limit);
+        return false;                                                   // a closer triangle can stand anywhere in a row
+    };
+    const auto row = [&](i64 cell) NT_INLINE {
+        ND_DEBUG_ADD(1, 1);
+        nt_row(M, cell, attempt);
+    };
     int c[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) c[k] = nd_cellf(p[k], G.lo[k], G.cell, G.dims[k]);
@@ -283,12 +276,12 @@ __device__ __forceinline__ void nd_walk_grid(NdBest& B, const float* p, const nf
         for (int k = 0; k < 3; ++k) b0[k] = max(c[k] - r, 0), b1[k] = min(c[k] + r, G.dims[k] - 1);
         for (int z = b0[2]; z <= b1[2]; ++z)
             for (int y = b0[1]; y <= b1[1]; ++y) {
-                const i64 row = ((i64)z * G.dims[1] + y) * G.dims[0];
+                const i64 first = ((i64)z * G.dims[1] + y) * G.dims[0];
                 if (nd_iabs(z - c[2]) == r || nd_iabs(y - c[1]) == r) {
-                    for (int x = b0[0]; x <= b1[0]; ++x) nd_try_row(B, p, a, row + x, limit);
+                    for (int x = b0[0]; x <= b1[0]; ++x) row(first + x);
                 } else {
-                    if (c[0] - r >= 0) nd_try_row(B, p, a, row + (c[0] - r), limit);
-                    if (r > 0 && c[0] + r < G.dims[0]) nd_try_row(B, p, a, row + (c[0] + r), limit);
+                    if (c[0] - r >= 0) row(first + (c[0] - r));
+                    if (r > 0 && c[0] + r < G.dims[0]) row(first + (c[0] + r));
                 }
             }
         float bound = INFINITY;
@@ -302,12 +295,23 @@ __device__ __forceinline__ void nd_walk_grid(NdBest& B, const float* p, const nf
     }
 }
 
+// what nfl_mesh_closest asks: the queries, the limit, and where the answers go
+struct NdClosest {
+    NtMesh M;
+    const float *points, *normals;
+    i64 n;
+    float max_distance;
+    float* distance;
+    int32_t* triangle;
+    float *point, *bary, *dot;
+};
+
 template <bool GRID>
-__global__ __launch_bounds__(NM_THREADS) void nfl_mesh_closest_kernel(const nfl_mesh_closest_args a) {
+__global__ __launch_bounds__(NM_THREADS) void nfl_mesh_closest_kernel(const NdClosest a) {
     const i64 n = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
-    const bool mine = n < a.n_points;
+    const bool mine = n < a.n;
     float p[3] = {0.f, 0.f, 0.f};
-    if (mine) p[0] = a.d_points[3 * n], p[1] = a.d_points[3 * n + 1], p[2] = a.d_points[3 * n + 2];
+    if (mine) p[0] = a.points[3 * n], p[1] = a.points[3 * n + 1], p[2] = a.points[3 * n + 2];
     const bool asks = mine && ng_is_finite(p[0]) && ng_is_finite(p[1]) && ng_is_finite(p[2]);
     const float limit = a.max_distance * a.max_distance;
     NdBest B;
@@ -315,52 +319,31 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_mesh_closest_kernel(const nfl_
 #pragma unroll
     for (int k = 0; k < 3; ++k) B.q[k] = B.uvw[k] = NAN;
     if (GRID) {
-        if (asks) nd_walk_grid(B, p, a, limit);
+        if (asks) nd_walk_grid(B, p, a.M, limit);
     } else {
-        __shared__ float corner[9][ND_TILE];
-        __shared__ int32_t usable[ND_TILE];
-        for (i64 base = 0; base < a.n_triangles; base += ND_TILE) {     // the same trips for every thread: barriers inside
-            const i64 t = base + threadIdx.x;
-            float ca[3] = {0.f, 0.f, 0.f}, cb[3] = {0.f, 0.f, 0.f}, cc[3] = {0.f, 0.f, 0.f};
-            const bool ok = t < a.n_triangles && nm_corners(a.d_vertices, a.d_triangles, a.n_vertices, t, ca, cb, cc);
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                corner[k][threadIdx.x] = ca[k];
-                corner[3 + k][threadIdx.x] = cb[k];
-                corner[6 + k][threadIdx.x] = cc[k];
-            }
-            usable[threadIdx.x] = ok ? 1 : 0;
-            __syncthreads();
-            if (asks) {
-                const int len = (int)(a.n_triangles - base < ND_TILE ? a.n_triangles - base : ND_TILE);
-                for (int j = 0; j < len; ++j) {
-                    if (!usable[j]) continue;
-                    const float ta[3] = {corner[0][j], corner[1][j], corner[2][j]};
-                    const float tb[3] = {corner[3][j], corner[4][j], corner[5][j]};
-                    const float tc[3] = {corner[6][j], corner[7][j], corner[8][j]};
-                    nd_try(B, p, (int32_t)(base + j), ta, tb, tc, limit);
-                }
-            }
-        }
+        const auto still = [&]() NT_INLINE { return asks; };
+        const auto attempt = [&](int32_t t, const float* ta, const float* tb, const float* tc) NT_INLINE {
+            nd_try(B, p, t, ta, tb, tc, limit);
+        };
+        nt_tiles(a.M, still, attempt);
     }
     if (!mine) return;
-    a.d_distance[n] = B.t >= 0 ? sqrtf(B.dd) : INFINITY;
-    a.d_triangle[n] = B.t;
+    a.distance[n] = B.t >= 0 ? sqrtf(B.dd) : INFINITY;
+    a.triangle[n] = B.t;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) a.d_point[3 * n + k] = B.q[k], a.d_bary[3 * n + k] = B.uvw[k];
-    if (a.d_dot) {
+    for (int k = 0; k < 3; ++k) a.point[3 * n + k] = B.q[k], a.bary[3 * n + k] = B.uvw[k];
+    if (a.dot) {
         float dot = NAN;
         float ca[3], cb[3], cc[3];
-        if (B.t >= 0 && nm_corners(a.d_vertices, a.d_triangles, a.n_vertices, B.t, ca, cb, cc)) {
+        if (B.t >= 0 && nm_corners(a.M.ver, a.M.tri, a.M.V, B.t, ca, cb, cc)) {
             float cr[3], len;
             nm_face_cross(ca, cb, cc, cr, &len);
             float nf[3] = {0.f, 0.f, 0.f};                              // a face without a normal: dot = 0
             if (len > 0.f) nf[0] = cr[0] / len, nf[1] = cr[1] / len, nf[2] = cr[2] / len;
-            const float nq[3] = {a.d_normals[3 * n], a.d_normals[3 * n + 1], a.d_normals[3 * n + 2]};
+            const float nq[3] = {a.normals[3 * n], a.normals[3 * n + 1], a.normals[3 * n + 2]};
             dot = nd_dot(nq, nf);
         }
-        a.d_dot[n] = dot;
+        a.dot[n] = dot;
     }
 }
 
@@ -369,22 +352,22 @@ extern "C" int nfl_mesh_closest(const nfl_mesh_closest_args* a, void* stream) {
     if (!nd_mesh_ok(a->d_vertices, a->d_triangles, a->n_vertices, a->n_triangles)) return NFL_EINVAL;
     if (!(a->max_distance > 0.f)) return NFL_EINVAL;                                    // NaN included
     if ((a->d_normals == nullptr) != (a->d_dot == nullptr)) return NFL_EINVAL;
-    const bool grid = a->d_offsets != nullptr;
-    if (grid) {
-        if (!nd_grid_ok(a->lo, a->cell, a->dims) || ng_misaligned(a->d_offsets, 8)) return NFL_EINVAL;
-        if (a->n_entries < 0 || a->n_entries > ND_MAX_ENTRIES) return NFL_EINVAL;
-        if (a->n_entries && ng_bad(a->d_entries, 4)) return NFL_EINVAL;
-    }
+    const bool grid = a->d_offsets != nullptr;                                          // without rows lo, cell, dims are not read
+    if (grid && !nt_rows_ok(a->d_offsets, a->d_entries, a->n_entries, a->lo, a->cell, a->dims)) return NFL_EINVAL;
     if (a->n_points == 0) return NFL_OK;
     const void* need[] = {a->d_points, a->d_distance, a->d_triangle, a->d_point, a->d_bary};
     for (const void* p : need)
         if (ng_bad(p, 4)) return NFL_EINVAL;
     if (ng_misaligned(a->d_normals, 4) || ng_misaligned(a->d_dot, 4)) return NFL_EINVAL;
+    const NdClosest q = {{a->d_vertices, a->d_triangles, a->n_vertices, a->n_triangles, a->d_offsets, a->d_entries,
+                          grid ? a->n_entries : 0, nd_grid_of(a->lo, a->cell, a->dims)},
+                         a->d_points, a->d_normals, a->n_points, a->max_distance, a->d_distance, a->d_triangle, a->d_point,
+                         a->d_bary, a->d_dot};
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (grid)
-        hipLaunchKernelGGL(nfl_mesh_closest_kernel<true>, dim3(nm_grid(a->n_points)), dim3(NM_THREADS), 0, s, *a);
+        hipLaunchKernelGGL(nfl_mesh_closest_kernel<true>, dim3(nm_grid(a->n_points)), dim3(NM_THREADS), 0, s, q);
     else
-        hipLaunchKernelGGL(nfl_mesh_closest_kernel<false>, dim3(nm_grid(a->n_points)), dim3(NM_THREADS), 0, s, *a);
+        hipLaunchKernelGGL(nfl_mesh_closest_kernel<false>, dim3(nm_grid(a->n_points)), dim3(NM_THREADS), 0, s, q);
     return ng_launched() ? NFL_OK : NFL_ELAUNCH;
 }
 

@@ -1,5 +1,6 @@
-"""What every stage of the geometry package calls: the argument checks, the one launch line, the counting half of a
-sized call, and the small parsers.  Nothing else in the package calls into the library or reads a device tensor back."""
+"""What every stage of the geometry package calls, and the modules that stand beside it (meshdist, registration, raycast):
+the argument checks, the launch line in its two forms (_launch for a struct, _call for plain arguments), the counting half
+of a sized call, and the small parsers.  Nothing else in the package calls into the library or reads a device tensor back."""
 import ctypes as C
 
 import numpy as np
@@ -26,6 +27,27 @@ def _is(t, dtype, dim, tail=(), device=None, contiguous=True):
     """Whether `t` has this dtype and `dim` axes, the last ones `tail` long, is contiguous and (when given) on `device`."""
     return (t.dtype == dtype and t.dim() == dim and t.shape[dim - len(tail):] == tail
             and (t.is_contiguous() or not contiguous) and (device is None or t.device == device))
+
+
+def _f32(x):
+    """`x` rounded to fp32, as a Python float: what a kernel is handed."""
+    return float(np.float32(x))
+
+
+def _positive(x, message):
+    """`x` as a float, None meaning +inf; ValueError(`message`) unless it is positive and still positive in fp32."""
+    x = float("inf") if x is None else float(x)
+    if not x > 0.0 or not _f32(x) > 0.0:
+        raise ValueError(message)
+    return x
+
+
+def _seed(seed, message):
+    """`seed` as an int; ValueError(`message`) unless it lies in [0, 2^64)."""
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(message)
+    return seed
 
 
 def _three(v, message, number=float):
@@ -73,6 +95,12 @@ def _launch(name, a, *before):
     fails.  `before` is what nfl_render_pass takes ahead of its struct (the plan pointers); every other entry point takes
     the struct and the stream alone."""
     _lib.check(getattr(_lib.lib(), name)(*before, C.byref(a), rendering._stream()), name)
+
+
+def _call(name, *args):
+    """Entry point `name` of the library with its plain arguments, on the current device's stream; RuntimeError when it
+    fails.  (_launch is for the entry points that take a struct.)"""
+    _lib.check(getattr(_lib.lib(), name)(*args, rendering._stream()), name)
 
 
 def _count(a, name, nbytes, n_totals, dev):

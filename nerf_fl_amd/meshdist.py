@@ -7,6 +7,7 @@ to a ground-truth one (Chamfer distance, Hausdorff distance, F-score: what recon
     sample_surface   nfl_mesh_sample_count / _emit: area-weighted random points of a surface, with their triangles and normals
     mesh_distance    both directions between two meshes, reduced on the device (nfl_meshdist_reduce), as plain numbers
     read_ply         what write_ply writes, and the plain variants ground-truth meshes come in, back as a mesh dict
+                     (geometry/files.py, beside write_ply; this module is where it is public)
 
 The definitions are written out in include/nerf_fl_amd.h, "mesh distance"; DESIGN.md section 33.  A mesh is the geometry
 package's dict (vertices, normals, triangles on a ROCm device); grid mode returns exactly the bits of brute mode."""
@@ -16,7 +17,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .geometry._call import _count, _is, _launch, _mesh_tensors, _on_device, _ptr, _refuse_outside, _scratch
+from .geometry._call import (_count, _f32, _is, _launch, _mesh_tensors, _on_device, _positive, _ptr, _refuse_outside,
+                             _scratch, _seed)
+from .geometry.files import read_ply
 
 __all__ = ["triangle_grid", "closest_on_mesh", "sample_surface", "mesh_distance", "read_ply"]
 
@@ -43,8 +46,14 @@ class TriangleGrid:
         return sorted(self.entries[o[0]:o[1]].tolist())
 
 
-def _f32(x):
-    return float(np.float32(x))
+def _finite_box(p, rows):
+    """(lo, hi) of the finite part of p ((N, 3), N > 0) as device tensors: +inf and -inf where nothing is finite.  `rows`:
+    a row with any non-finite coordinate is left out whole; else every coordinate counts on its own."""
+    fin = torch.isfinite(p)
+    if rows:
+        fin = fin.all(dim=1, keepdim=True)
+    inf = torch.full((), float("inf"), dtype=p.dtype, device=p.device)
+    return torch.where(fin, p, inf).amin(0), torch.where(fin, p, -inf).amax(0)
 
 
 def _mesh_box(ver, tri):
@@ -53,9 +62,7 @@ def _mesh_box(ver, tri):
     V, T = ver.shape[0], tri.shape[0]
     if V == 0:
         return [0.0] * 3, [0.0] * 3, 0.0
-    fin = torch.isfinite(ver)
-    inf = torch.full((), float("inf"), dtype=ver.dtype, device=ver.device)
-    lo, hi = torch.where(fin, ver, inf).amin(0), torch.where(fin, ver, -inf).amax(0)
+    lo, hi = _finite_box(ver, rows=False)
     ext = torch.zeros((), dtype=torch.float64, device=ver.device)
     if T:
         corners = ver[tri.long().clamp(0, V - 1)]                       # (T, 3, 3); an index out of range is refused later
@@ -120,15 +127,17 @@ def triangle_grid(mesh, cell=None, margin=0.0):
     return TriangleGrid(lo, cell, dims, offsets, rows, ver, tri)
 
 
-def _grid_or_mesh(mesh_or_grid, method):
-    """(vertices, triangles, grid or None) of what closest_on_mesh was handed."""
+def _mesh_or_grid(mesh_or_grid, method):
+    """(vertices, triangles, grid or None, whether its rows are walked) of what a query was handed: a TriangleGrid as it
+    is, whatever the method (its box still holds for a cast that tries every triangle); a mesh dict with its grid built
+    here when the method walks one."""
     if method not in ("grid", "brute"):
         raise ValueError(f"method: 'grid' or 'brute', got {method!r}")
+    rows = method == "grid"
     if isinstance(mesh_or_grid, TriangleGrid):
-        g = mesh_or_grid
-        return g.vertices, g.triangles, g if method == "grid" else None
+        return mesh_or_grid.vertices, mesh_or_grid.triangles, mesh_or_grid, rows
     ver, _, _, tri = _mesh_tensors(mesh_or_grid)
-    return ver, tri, triangle_grid(mesh_or_grid) if method == "grid" else None
+    return ver, tri, triangle_grid(mesh_or_grid) if rows else None, rows
 
 
 def closest_on_mesh(points, mesh_or_grid, max_distance=None, method="grid", normals=None):
@@ -145,7 +154,7 @@ def closest_on_mesh(points, mesh_or_grid, max_distance=None, method="grid", norm
                    of the answering triangle (NaN without an answer).
 
     No host synchronisation when handed a TriangleGrid (or with method="brute"); with a mesh dict, triangle_grid's."""
-    ver, tri, grid = _grid_or_mesh(mesh_or_grid, method)
+    ver, tri, grid, rows = _mesh_or_grid(mesh_or_grid, method)
     dev = ver.device
     _on_device(points)
     if not _is(points, torch.float32, 2, (3,), dev):
@@ -155,9 +164,7 @@ def closest_on_mesh(points, mesh_or_grid, max_distance=None, method="grid", norm
         _on_device(normals)
         if not _is(normals, torch.float32, 2, (N, 3), dev):
             raise ValueError(f"normals: expected a contiguous fp32 ({N}, 3) tensor on the mesh's device")
-    limit = float("inf") if max_distance is None else float(max_distance)
-    if not limit > 0.0 or (max_distance is not None and not _f32(limit) > 0.0):
-        raise ValueError("max_distance: None or a positive number")
+    limit = _positive(max_distance, "max_distance: None or a positive number")
     new = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=dev)
     out = {"distance": new(N), "triangle": new(N, dtype=torch.int32), "point": new(N, 3), "bary": new(N, 3)}
     if normals is not None:
@@ -165,7 +172,7 @@ def closest_on_mesh(points, mesh_or_grid, max_distance=None, method="grid", norm
     a = _lib.MeshClosestArgs()
     a.d_points, a.n_points, a.d_vertices, a.d_triangles = _ptr(points.detach()), N, _ptr(ver), _ptr(tri)
     a.n_vertices, a.n_triangles, a.max_distance = ver.shape[0], tri.shape[0], limit
-    if grid is not None:
+    if rows:
         a.d_offsets, a.d_entries, a.n_entries = _ptr(grid.offsets), _ptr(grid.entries), grid.entries.shape[0]
         a.lo[:], a.cell, a.dims[:] = grid.lo, grid.cell, grid.dims
     a.d_normals, a.d_dot = _ptr(normals), _ptr(out.get("dot"))
@@ -200,9 +207,7 @@ def sample_surface(mesh, density=None, n=None, seed=0):
         raise ValueError("sample_surface: exactly one of `density` and `n`")
     ver, _, _, tri = _mesh_tensors(mesh)
     dev, V, T = ver.device, ver.shape[0], tri.shape[0]
-    seed = int(seed)
-    if not 0 <= seed < 2 ** 64:
-        raise ValueError("seed: an integer in [0, 2^64)")
+    seed = _seed(seed, "seed: an integer in [0, 2^64)")
     if n is not None:
         if isinstance(n, bool) or int(n) != n or n < 0:
             raise ValueError("n: a non-negative integer")
@@ -300,122 +305,3 @@ def mesh_distance(a, b, n=100_000, thresholds=(), max_distance=None, seed=0, poi
     return {"a_to_b": ab, "b_to_a": ba, "chamfer": 0.5 * (ab["mean"] + ba["mean"]), "hausdorff": max(ab["max"], ba["max"]),
             "normal_consistency": 0.5 * (nc_ab + nc_ba), "thresholds": thresholds, "precision": prec, "recall": rec,
             "fscore": fs}
-
-
-# ---- PLY back in
-
-_PLY_FLOAT = {"float": "f4", "float32": "f4"}
-_PLY_UCHAR = {"uchar": "u1", "uint8": "u1"}
-_PLY_INDEX = {"int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4"}
-_PLY_VERTEX = ("x", "y", "z", "nx", "ny", "nz", "red", "green", "blue")
-
-
-def _ply_header(f):
-    """(format, V, T, vertex properties [(name, numpy type)], face (count type, index type)) of a PLY stream, which is left
-    at the first byte of the body."""
-    if f.readline().strip() != b"ply":
-        raise ValueError("read_ply: not a PLY file (the first line is not 'ply')")
-    fmt, elements, current = None, [], None
-    while True:
-        raw = f.readline()
-        if not raw:
-            raise ValueError("read_ply: the header has no end_header")
-        words = raw.decode("ascii", "replace").split()
-        if not words or words[0] in ("comment", "obj_info"):
-            continue
-        if words[0] == "end_header":
-            break
-        if words[0] == "format":
-            fmt = words[1] if len(words) > 1 else ""
-        elif words[0] == "element" and len(words) == 3:
-            current = {"name": words[1], "count": int(words[2]), "props": []}
-            elements.append(current)
-        elif words[0] == "property" and current is not None:
-            current["props"].append(words[1:])
-        else:
-            raise ValueError(f"read_ply: header line {' '.join(words)!r}")
-    if fmt not in ("binary_little_endian", "ascii"):
-        raise ValueError(f"read_ply: format {fmt!r}; binary_little_endian and ascii are read")
-    if [e["name"] for e in elements] != ["vertex", "face"]:
-        raise ValueError(f"read_ply: elements {[e['name'] for e in elements]}; 'vertex' then 'face' are read")
-    vprops = []
-    for p in elements[0]["props"]:
-        if len(p) != 2 or p[1] not in _PLY_VERTEX:
-            raise ValueError(f"read_ply: vertex property {' '.join(p)!r}; float x y z nx ny nz and uchar red green blue are read")
-        kinds = _PLY_UCHAR if p[1] in ("red", "green", "blue") else _PLY_FLOAT
-        if p[0] not in kinds:
-            raise ValueError(f"read_ply: vertex property {p[1]!r} of type {p[0]!r}; {sorted(kinds)} is read")
-        vprops.append((p[1], kinds[p[0]]))
-    names = [n for n, _ in vprops]
-    if len(set(names)) != len(names) or not {"x", "y", "z"} <= set(names):
-        raise ValueError(f"read_ply: vertex properties {names}; x, y and z are needed, each once")
-    for group in (("nx", "ny", "nz"), ("red", "green", "blue")):
-        if 0 < len(set(group) & set(names)) < 3:
-            raise ValueError(f"read_ply: vertex properties {names}; {group} come together")
-    fprops = elements[1]["props"]
-    if (len(fprops) != 1 or len(fprops[0]) != 4 or fprops[0][0] != "list" or fprops[0][1] not in _PLY_UCHAR
-            or fprops[0][2] not in _PLY_INDEX or fprops[0][3] not in ("vertex_indices", "vertex_index")):
-        raise ValueError(f"read_ply: face properties {[' '.join(p) for p in fprops]}; one 'list uchar int vertex_indices' is read")
-    return fmt, elements[0]["count"], elements[1]["count"], vprops, _PLY_INDEX[fprops[0][2]]
-
-
-def read_ply(path, device=None):
-    """Read a triangle mesh from a PLY file: what geometry.write_ply writes, and the plain variants ground-truth meshes come
-    in -- `binary_little_endian` or `ascii`; vertex properties float x y z, optionally float nx ny nz and uchar red green
-    blue, in any order; faces as lists of 3 indices named vertex_indices or vertex_index.  Anything else is refused with a
-    ValueError that names what was found.  Parsed with numpy alone; a round trip through write_ply is exact.
-
-    Returns a mesh dict: vertices (V, 3) fp32, normals (V, 3) fp32, triangles (T, 3) int32 and, when the file has them,
-    colors (V, 3) fp32 = byte / 255.  With a `device` they are tensors there, and missing normals are filled through
-    geometry.vertex_normals; without one they are numpy arrays and missing normals are zeros."""
-    with open(path, "rb") as f:
-        fmt, V, T, vprops, index = _ply_header(f)
-        body = f.read()
-    if V < 0 or T < 0 or V > INT32_MAX or 3 * T > INT32_MAX:
-        raise ValueError(f"read_ply: {V} vertices and {T} faces")
-    vtype = np.dtype([(n, "<" + t) for n, t in vprops])
-    if fmt == "binary_little_endian":
-        ftype = np.dtype([("n", "u1"), ("v", "<" + index, (3,))])
-        if len(body) != V * vtype.itemsize + T * ftype.itemsize:
-            raise ValueError(f"read_ply: a body of {len(body)} bytes; {V} vertices and {T} triangles take "
-                             f"{V * vtype.itemsize + T * ftype.itemsize} (faces that are not triangles are not read)")
-        vrec = np.frombuffer(body, dtype=vtype, count=V)
-        frec = np.frombuffer(body, dtype=ftype, count=T, offset=V * vtype.itemsize)
-        counts, tri = frec["n"], frec["v"]
-    else:
-        words = body.split()
-        nv = V * len(vprops)
-        if len(words) != nv + 4 * T:
-            raise ValueError(f"read_ply: a body of {len(words)} numbers; {V} vertices and {T} triangles take {nv + 4 * T} "
-                             "(faces that are not triangles are not read)")
-        try:
-            table = np.array(words[:nv], dtype=np.float64).reshape(V, len(vprops))
-            faces = np.array(words[nv:], dtype=np.int64).reshape(T, 4)
-        except ValueError:
-            raise ValueError("read_ply: a word of the body is not a number") from None
-        vrec = np.empty(V, dtype=vtype)
-        for k, (name, _) in enumerate(vprops):
-            vrec[name] = table[:, k]
-        counts, tri = faces[:, 0], faces[:, 1:]
-    if T and (counts != 3).any():
-        raise ValueError(f"read_ply: a face of {int(counts[counts != 3][0])} vertices; triangles are read")
-    if T and (tri.min() < 0 or tri.max() >= V):
-        raise ValueError("read_ply: a face index lies outside the vertices")
-    names = vrec.dtype.names
-    stack = lambda keys: np.ascontiguousarray(np.stack([vrec[k] for k in keys], axis=1), dtype=np.float32).reshape(V, 3)
-    mesh = {"vertices": stack("xyz"), "triangles": np.ascontiguousarray(tri, dtype=np.int32).reshape(T, 3)}
-    mesh["normals"] = stack(("nx", "ny", "nz")) if "nx" in names else None
-    if "red" in names:
-        mesh["colors"] = stack(("red", "green", "blue")) / np.float32(255.0)
-    if device is None:
-        if mesh["normals"] is None:
-            mesh["normals"] = np.zeros((V, 3), dtype=np.float32)
-        return mesh
-    missing = mesh["normals"] is None
-    if missing:
-        mesh["normals"] = np.zeros((V, 3), dtype=np.float32)
-    out = {k: torch.from_numpy(v).to(device) for k, v in mesh.items()}
-    if missing:
-        from .geometry import vertex_normals
-        out["normals"] = vertex_normals(out)
-    return out

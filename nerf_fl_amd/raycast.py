@@ -14,32 +14,15 @@ dict (vertices, normals, triangles on a ROCm device); a ray is a row [o, d, near
 renderer takes them, and t is in the ray's own parameter.  Grid mode returns exactly the bits of brute mode."""
 import math
 
-import numpy as np
 import torch
 
 from . import _lib
-from .geometry._call import _is, _mesh_tensors, _on_device, _ptr
-from .meshdist import TriangleGrid, triangle_grid
-from .registration import _call
+from .geometry._call import _call, _f32, _is, _mesh_tensors, _on_device, _positive, _ptr, _seed
+from .meshdist import TriangleGrid, _mesh_or_grid, triangle_grid
 
 __all__ = ["cast_rays", "vertex_occlusion", "clip_rays_to_mesh", "MeshBand"]
 
 MAX_RAYS_PER_POINT = 4096                # NC_MAX_DIRECTIONS
-
-
-def _f32(x):
-    return float(np.float32(x))
-
-
-def _target(mesh_or_grid, method):
-    """(vertices, triangles, the grid whose box holds or None, whether its rows are walked) of what a cast was handed."""
-    if method not in ("grid", "brute"):
-        raise ValueError(f"method: 'grid' or 'brute', got {method!r}")
-    if isinstance(mesh_or_grid, TriangleGrid):
-        g = mesh_or_grid
-        return g.vertices, g.triangles, g, method == "grid"
-    ver, _, _, tri = _mesh_tensors(mesh_or_grid)
-    return ver, tri, (triangle_grid(mesh_or_grid) if method == "grid" else None), method == "grid"
 
 
 def _grid_args(ver, tri, grid, rows):
@@ -78,7 +61,7 @@ def cast_rays(rays, mesh_or_grid, mode="first", method="grid"):
     dict, triangle_grid's."""
     if mode not in _lib.CAST_MODES:
         raise ValueError(f"mode: 'first' or 'any', got {mode!r}")
-    ver, tri, grid, rows = _target(mesh_or_grid, method)
+    ver, tri, grid, rows = _mesh_or_grid(mesh_or_grid, method)
     dev = ver.device
     r = _rays(rays, dev)
     R = r.shape[0]
@@ -124,14 +107,10 @@ def vertex_occlusion(mesh, rays=64, radius=None, bias=None, seed=0, grid=None, p
         write_ply(path, mesh, colors * openness[:, None])"""
     if isinstance(rays, bool) or int(rays) != rays or not 1 <= rays <= MAX_RAYS_PER_POINT:
         raise ValueError(f"rays: an integer in [1, {MAX_RAYS_PER_POINT}]")
-    radius = float("inf") if radius is None else float(radius)
-    if not radius > 0.0 or not _f32(radius) > 0.0:
-        raise ValueError("radius: None or a positive number")
+    radius = _positive(radius, "radius: None or a positive number")
     if bias is not None and not (float(bias) >= 0.0 and math.isfinite(_f32(bias))):
         raise ValueError("bias: None or a finite number, not negative")
-    seed = int(seed)
-    if not 0 <= seed < 2 ** 64:
-        raise ValueError("seed: an integer in [0, 2^64)")
+    seed = _seed(seed, "seed: an integer in [0, 2^64)")
     if (points is None) != (normals is None):
         raise ValueError("points and normals come together")
     if grid is not None and not isinstance(grid, TriangleGrid):

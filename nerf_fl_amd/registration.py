@@ -16,19 +16,13 @@ import math
 import numpy as np
 import torch
 
-from . import _lib, rendering
-from .geometry._call import _is, _mesh_tensors, _on_device, _ptr, _scratch
-from .meshdist import TriangleGrid, closest_on_mesh, mesh_distance, sample_surface, triangle_grid
+from . import _lib
+from .geometry._call import _call, _is, _mesh_tensors, _on_device, _positive, _ptr, _scratch
+from .meshdist import _finite_box, _mesh_or_grid, closest_on_mesh, mesh_distance, sample_surface
 
 __all__ = ["fit_transform", "transform_points", "transform_mesh", "register_mesh", "registered_distance"]
 
 _STATUS = {v: k for k, v in _lib.REGISTER_STATUS.items()}
-
-
-def _call(name, *args):
-    """Entry point `name` of the library with its plain arguments, on the current device's stream; RuntimeError when it
-    fails.  (geometry._call._launch is for the entry points that take a struct.)"""
-    _lib.check(getattr(_lib.lib(), name)(*args, rendering._stream()), name)
 
 
 def _identity(dev):
@@ -100,9 +94,7 @@ def _box_centre(p):
     """The middle of the box of the finite rows of p, as three Python floats: ONE host read."""
     if p.shape[0] == 0:
         return [0.0, 0.0, 0.0]
-    fin = torch.isfinite(p).all(dim=1, keepdim=True)
-    inf = torch.full((), float("inf"), dtype=p.dtype, device=p.device)
-    box = torch.cat([torch.where(fin, p, inf).amin(0), torch.where(fin, p, -inf).amax(0)]).double().cpu().numpy()
+    box = torch.cat(_finite_box(p, rows=True)).double().cpu().numpy()
     if not np.isfinite(box).all():
         return [0.0, 0.0, 0.0]
     return [float(0.5 * (box[k] + box[3 + k])) for k in range(3)]
@@ -165,13 +157,7 @@ def _schedule(max_distance, iterations):
     limits = [max_distance] * iterations if not many else list(max_distance)
     if len(limits) != iterations:
         raise ValueError(f"max_distance: a number, or one per iteration ({iterations}), got {len(limits)}")
-    out = []
-    for m in limits:
-        m = float("inf") if m is None else float(m)
-        if not m > 0.0 or not float(np.float32(m)) > 0.0:
-            raise ValueError("max_distance: None, a positive number, or a positive number per iteration")
-        out.append(m)
-    return out
+    return [_positive(m, "max_distance: None, a positive number, or a positive number per iteration") for m in limits]
 
 
 def register_mesh(source, target, initial=None, mode="plane", scale=False, iterations=30, n=50_000, points="samples",
@@ -206,7 +192,7 @@ def register_mesh(source, target, initial=None, mode="plane", scale=False, itera
         raise ValueError("min_pairs: a positive integer")
     iterations, min_pairs = int(iterations), int(min_pairs)
     limits = _schedule(max_distance, iterations)
-    grid = target if isinstance(target, TriangleGrid) else triangle_grid(target)
+    grid = _mesh_or_grid(target, "grid")[2]
     dev = grid.vertices.device
     src = sample_surface(source, n=n, seed=seed)["points"] if points == "samples" else _mesh_tensors(source)[0]
     if src.device != dev:

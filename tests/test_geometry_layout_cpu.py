@@ -55,12 +55,18 @@ def test_every_public_name_is_defined_in_one_module():
 def test_one_launch_line_one_host_read_one_refusal():
     # nfl_render_pass goes through the launch helper too (it takes the plan pointers ahead of the struct): no exception
     assert _where("_lib.check(") == ["_call.py"] and _where("C.byref(") == ["_call.py"]
-    assert SOURCES["_call.py"].count("_lib.check(") == 1 and SOURCES["_call.py"].count("C.byref(") == 1
+    # the launch line in its two forms, side by side: _launch for a struct, _call for plain arguments
+    assert SOURCES["_call.py"].count("_lib.check(") == 2 and SOURCES["_call.py"].count("C.byref(") == 1
+    assert SOURCES["_call.py"].count("rendering._stream()") == 2
     assert _where("rendering._stream()") == ["_call.py"]
     # .tolist(): the totals of a sized call, once.  files.py is the one other place that spells it, on numpy arrays it has
-    # already brought to the host (the OBJ writer's numbers); nothing in its source names the library, a launch or torch
+    # already brought to the host (the OBJ writer's numbers); nothing in its source names the library or a launch, and torch
+    # only where read_ply, handed a device, uploads what it read
     assert _where(".tolist()") == ["_call.py", "files.py"] and SOURCES["_call.py"].count(".tolist()") == 1
-    assert not re.search(r"_lib|rendering|_launch|_count|torch", SOURCES["files.py"])
+    assert not re.search(r"_lib|rendering|_launch|_count", SOURCES["files.py"])
+    reader = SOURCES["files.py"].split("def read_ply(")[1].split("\ndef ")[0]
+    assert SOURCES["files.py"].count("torch") == 2 == reader.count("torch") and "    import torch" in reader
+    assert not re.search(r"^(import|from) .*torch", SOURCES["files.py"], flags=re.M)
     assert _where("triangles have an index outside") == ["_call.py"]
     assert SOURCES["_call.py"].count("triangles have an index outside") == 1
     for struct in ("MeshDepthArgs", "MeshVisibilityArgs", "MeshShadeArgs", "MeshShadeAtlasArgs"):

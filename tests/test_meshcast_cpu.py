@@ -39,13 +39,29 @@ def test_the_tables_and_the_header_name_the_new_entry_points_and_no_new_struct()
 def test_the_unit_is_built_with_the_common_flags():
     make = open(os.path.join(ROOT, "nerf_fl_amd", "csrc", "Makefile")).read()
     assert "nfl_meshcast.o" in make.split("all:")[0]                       # in OBJS
-    assert re.search(r"^nfl_meshcast\.o:.*nfl_geom\.h.*nfl_geom_layout\.h", make, flags=re.M)
+    assert re.search(r"^nfl_meshcast\.o:.*nfl_geom\.h.*nfl_geom_layout\.h.*nfl_trigrid\.h", make, flags=re.M)
+    assert re.search(r"^nfl_meshdist\.o:.*nfl_geom\.h.*nfl_geom_layout\.h.*nfl_trigrid\.h", make, flags=re.M)
+    assert len(re.findall(r"^.*nfl_trigrid\.h", make, flags=re.M)) == 3      # those two lines and a comment: no other unit compiles it
     assert "-ffp-contract=off" in re.search(r"^CXXFLAGS = .*$", make, flags=re.M).group(0)
-    assert not re.search(r"^nfl_meshcast\.o:.*\n\t", make, flags=re.M)       # no recipe of its own: the common rule builds it
+    for unit in ("nfl_meshcast", "nfl_meshdist"):                           # no recipe of its own: the common rule builds it
+        assert not re.search(rf"^{unit}\.o:.*\n\t", make, flags=re.M)
     csrc = os.path.join(ROOT, "nerf_fl_amd", "csrc")
-    geom, dist, cast = (open(os.path.join(csrc, n)).read() for n in ("nfl_geom.h", "nfl_meshdist.hip", "nfl_meshcast.hip"))
+    geom, shared, dist, cast = (open(os.path.join(csrc, n)).read()
+                                for n in ("nfl_geom.h", "nfl_trigrid.h", "nfl_meshdist.hip", "nfl_meshcast.hip"))
     for piece in ("struct NdGrid", "nd_cellf(float", "nd_grid_ok(const", "nd_face(float"):      # the grid's pieces, once
-        assert piece in geom and piece not in dist and piece not in cast, piece
+        assert piece in geom and piece not in shared and piece not in dist and piece not in cast, piece
+    # the view, the host check of the rows, the row read with its clamps and skips, the staged tile with its barriers: once
+    for piece in ("struct NtMesh", "nt_rows_ok(const", "corner[9]", "usable[NT_TILE]", "r0 = r0 < 0 ? 0 : r0", "r1 = r1 > M.E ? M.E : r1",
+                  "if (t < 0 || t >= M.T) continue", "ng_misaligned(off, 8)"):
+        assert piece in shared and piece not in geom and piece not in dist and piece not in cast, piece
+    assert shared.count("__syncthreads()") == 2 and "__syncthreads()" not in dist and "__syncthreads()" not in cast
+    assert '#include "nfl_geom.h"' in shared
+    for unit in (dist, cast):
+        assert '#include "nfl_trigrid.h"' in unit and "nt_tiles(" in unit and "nt_row(" in unit and "nt_rows_ok(" in unit
+        assert "_TILE" not in unit and "struct NcMesh" not in unit and "_try_row" not in unit
+    others = [n for n in os.listdir(csrc) if n.endswith((".hip", ".h", ".cpp")) and n not in ("nfl_trigrid.h", "nfl_meshdist.hip", "nfl_meshcast.hip")]
+    assert len(others) > 40 and not [n for n in others if "nfl_trigrid.h" in open(os.path.join(csrc, n)).read()]
+    assert "nfl_mesh_closest_args a)" not in dist                             # the kernel takes the view, not the ABI struct by value
 
 
 def _cast_args(grid=True):
@@ -122,10 +138,21 @@ def test_the_module_stands_beside_meshdist():
     source = open(os.path.join(pkg, "raycast.py")).read()
     assert "_lib.check(" not in source and "C.byref(" not in source and "import ctypes" not in source
     assert ".item()" not in source and ".tolist()" not in source and ".cpu()" not in source
-    assert re.search(r"^from \.registration import _call$", source, flags=re.M)
-    for helper in ("_is", "_mesh_tensors", "_on_device", "_ptr"):
-        assert re.search(rf"^from \.geometry\._call import .*\b{helper}\b", source, flags=re.M)
-    assert open(os.path.join(pkg, "registration.py")).read().count("_lib.check(") == 1
+    assert "registration" not in re.sub(r'""".*?"""', "", source, flags=re.S)        # nothing of the ICP module, private or public
+    for helper in ("_call", "_f32", "_is", "_mesh_tensors", "_on_device", "_positive", "_ptr", "_seed"):
+        assert re.search(rf"^from \.geometry\._call import .*\b{helper}\b", source, flags=re.M), helper
+    assert re.search(r"^from \.meshdist import .*\b_mesh_or_grid\b", source, flags=re.M) and "def _target" not in source
+    sources = {n: open(os.path.join(pkg, n)).read() for n in ("meshdist.py", "registration.py", "raycast.py")}
+    call = open(os.path.join(pkg, "geometry", "_call.py")).read()
+    assert call.count("_lib.check(") == 2 and call.count("rendering._stream()") == 2      # _launch and _call, side by side
+    for n, text in sources.items():
+        assert "_lib.check(" not in text and "rendering." not in text and "def _f32" not in text and "def _call" not in text, n
+        assert "2 ** 64" not in text and "np.float32(" not in text, n          # the seed check and the fp32 rounding, once
+    everything = "".join(open(os.path.join(d, n)).read() for d, _, names in os.walk(pkg) for n in names if n.endswith(".py"))
+    assert everything.count("def _f32(") == 1 == call.count("def _f32(") and call.count("2 ** 64") == 1
+    assert everything.count("def _mesh_or_grid(") == 1 == sources["meshdist.py"].count("def _mesh_or_grid(")
+    assert everything.count("def _finite_box(") == 1 and everything.count("def read_ply(") == 1
+    assert "def _grid_or_mesh" not in everything
     assert sorted(n for n in os.listdir(os.path.join(pkg, "geometry")) if n.endswith(".py")) == [
         "__init__.py", "_call.py", "files.py", "images.py", "lattice.py", "mesh.py", "occupancy.py"]
     from nerf_fl_amd import fusion, geometry, meshdist, raycast, registration

@@ -9,7 +9,7 @@ the device for every cell size and origin of tests/test_meshcast_cpu.py.  render
 of a cross-check that shares no code with the cast.
 
 Sizes.  About 400 rays cross a workgroup of 256; 40 triangles and the ball's few thousand cross the 256-triangle tile of brute
-mode; the occlusion mesh has at most 200 vertices at 64 rays each, the analytic scenes one point at up to 4096."""
+mode, and 255, 256, 257 and 513 stand at its seams; the occlusion mesh has at most 200 vertices at 64 rays each, the analytic scenes one point at up to 4096."""
 import ctypes as C
 
 import numpy as np
@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import meshcast_ref as cref
+import meshcolor_ref as mref
 from geom_gpu_util import EYES, PAD, ball_mesh, dev as _dev, framed, intrinsics, pose, ptr, same as _same, stream, unframe
 from gpu_util import DEV
 from nerf_fl_amd import NeRF, PosEmbedding, _lib, eval as nfl_eval, geometry, meshdist, raycast, rendering, synth
@@ -94,6 +95,51 @@ def test_brute_mode_without_a_box_and_the_default_grid(soup):
     for bad in (torch.zeros(4, 7, device=DEV), torch.zeros(4, 8, device=DEV, dtype=torch.float64), torch.zeros(4, 8)):
         with pytest.raises((ValueError, RuntimeError)):
             raycast.cast_rays(bad, grid)
+
+
+def tile_case(T):
+    """The soup of test_meshdist_gpu.py's test_the_lds_tile_of_brute_mode with one triangle made unusable (a NaN corner) at a
+    seam of the 256-triangle tile -- index 255 or 256, the last of a full tile or the first of the next; with T = 255, which
+    has neither, the last slot of the ragged tile -- and 300 rays: the first eight aimed along the face normals at the
+    centroids of the last eight triangles from 0.05 away, 100 aimed at triangles drawn at random from 3 away, the rest
+    random through the soup's box.  300 rays are a workgroup and 44 threads of a second one, whose other 212 stage without
+    asking.  An aimed ray hits its target or something before it, so a third of the rays hit by construction; the one aimed
+    at the unusable triangle, where that is among the last eight, has a NaN origin: no ray, it asks nothing and hits nothing.
+    On the restatement 158 to 172 of the 300 hit, and seven of the last eight triangles answer, in all four sizes."""
+    ver, tri = mref.soup(T, T)
+    ver = ver.copy()
+    bad = 255 if T == 256 else min(256, T - 1)
+    ver[3 * bad + 1, 0] = NAN
+    rng = np.random.default_rng(T)
+    c = ver.reshape(T, 3, 3).astype(np.float64)
+    centre, normal = c.mean(1), np.cross(c[:, 1] - c[:, 0], c[:, 2] - c[:, 0])
+    last = np.arange(T - 8, T)
+    some = rng.choice(np.setdiff1d(np.arange(T), [bad]), 100, replace=False)
+    d = np.concatenate([-normal[last] / np.linalg.norm(normal[last], axis=1, keepdims=True), rng.normal(size=(100, 3))])
+    back = np.concatenate([np.full(8, 0.05), np.full(100, 3.0)])[:, None]
+    o = centre[np.concatenate([last, some])] - back * d / np.linalg.norm(d, axis=1, keepdims=True)
+    o = np.concatenate([o, rng.uniform([-2.5, -1.5, -6.5], [2.5, 1.5, -1.5], (192, 3))])
+    d = np.concatenate([d, rng.normal(size=(192, 3))])
+    rays = np.concatenate([o, d, np.zeros((300, 1)), np.full((300, 1), INF)], axis=1).astype(F)
+    return ver, tri, bad, rays
+
+
+@pytest.mark.parametrize("T", [255, 256, 257, 513])
+def test_the_lds_tile_of_brute_mode(T):
+    """Brute mode at the seams of its 256-triangle tile, first hit and any hit, with a grid's box and without."""
+    ver, tri, bad, rays = tile_case(T)
+    mesh = _mesh(ver, tri)
+    grid = meshdist.triangle_grid(mesh, margin=0.5)
+    dev = _dev(rays, F)
+    for target, box in ((mesh, None), (grid, _box(grid))):
+        exp = cref.cast(rays, ver, tri, box)
+        assert exp["triangle"].max() >= T - 8                                 # the last, ragged tile answers too
+        assert (exp["triangle"] >= 0).sum() >= 75 and bad not in exp["triangle"]
+        got = raycast.cast_rays(dev, target, method="brute")
+        _same_fields(got, exp, ("brute", T, box is not None))
+        assert bad not in got["triangle"].tolist()
+        got = raycast.cast_rays(dev, target, mode="any", method="brute")
+        _same(got["t"], np.where(exp["triangle"] >= 0, F(0), F(INF)).astype(F), ("brute, any", T, box is not None))
 
 
 def test_through_the_c_abi_outputs_framed_and_optional(soup):

@@ -32,7 +32,7 @@ def test_the_unit_is_built_and_has_its_section():
     assert "---- mesh distance:" in open(os.path.join(ROOT, "include", "nerf_fl_amd.h")).read()
     make = open(os.path.join(ROOT, "nerf_fl_amd", "csrc", "Makefile")).read()
     assert "nfl_meshdist.o" in make.split("all:")[0]                       # in OBJS
-    assert re.search(r"^nfl_meshdist\.o:.*nfl_geom\.h.*nfl_geom_layout\.h", make, flags=re.M)
+    assert re.search(r"^nfl_meshdist\.o:.*nfl_geom\.h.*nfl_geom_layout\.h.*nfl_trigrid\.h", make, flags=re.M)
 
 
 def test_sizes(L):
@@ -199,12 +199,21 @@ def test_the_module_stands_beside_the_geometry_package():
     pkg = os.path.join(ROOT, "nerf_fl_amd")
     source = open(os.path.join(pkg, "meshdist.py")).read()
     assert "_lib.check(" not in source and "C.byref(" not in source and "import ctypes" not in source
-    assert re.search(r"^from \.geometry\._call import .*\b_launch\b", source, flags=re.M)
-    for helper in ("_count", "_mesh_tensors", "_refuse_outside"):
-        assert re.search(rf"^from \.geometry\._call import .*\b{helper}\b", source, flags=re.M)
+    imported = re.search(r"^from \.geometry\._call import \((.*?)\)$", source, flags=re.M | re.S).group(1)
+    for helper in ("_launch", "_count", "_mesh_tensors", "_refuse_outside", "_f32", "_positive", "_seed"):
+        assert re.search(rf"\b{helper}\b", imported), helper
+    # read_ply stands beside write_ply and is public here; its helpers went with it
+    assert re.search(r"^from \.geometry\.files import read_ply$", source, flags=re.M) and "_ply_" not in source and "_PLY_" not in source
+    files = open(os.path.join(pkg, "geometry", "files.py")).read()
+    assert "def read_ply(" in files and "def _ply_header(" in files and "def write_ply(" in files
+    # one reduction of a finite box, on the device; each user keeps its one read and its zero fallback
+    assert source.count("def _finite_box(") == 1 and source.count("_finite_box(") == 2
+    assert "def _mesh_or_grid(" in source and "def _grid_or_mesh" not in source
+    assert source.count("method: 'grid' or 'brute', got {method!r}") == 1
     assert sorted(n for n in os.listdir(os.path.join(pkg, "geometry")) if n.endswith(".py")) == [
         "__init__.py", "_call.py", "files.py", "images.py", "lattice.py", "mesh.py", "occupancy.py"]
     from nerf_fl_amd import fusion, geometry, meshdist
+    assert meshdist.read_ply is geometry.files.read_ply and not hasattr(geometry, "read_ply")
     assert meshdist.__all__ == ["triangle_grid", "closest_on_mesh", "sample_surface", "mesh_distance", "read_ply"]
     assert len(geometry.__all__) == 24 and not set(meshdist.__all__) & set(geometry.__all__)
     assert fusion.__all__ == ["depth_maps", "fuse_depth", "tsdf_lattice", "surface_support", "drop_unsupported", "fuse_mesh"]

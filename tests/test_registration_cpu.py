@@ -64,10 +64,13 @@ def test_the_unit_is_built_and_has_its_section():
 def test_the_module_stands_beside_meshdist():
     pkg = os.path.join(ROOT, "nerf_fl_amd")
     source = open(os.path.join(pkg, "registration.py")).read()
-    assert source.count("_lib.check(") == 1 and "C.byref(" not in source and "import ctypes" not in source
-    for helper in ("_ptr", "_scratch", "_is", "_on_device"):
+    assert "_lib.check(" not in source and "C.byref(" not in source and "import ctypes" not in source and "rendering." not in source
+    for helper in ("_call", "_positive", "_ptr", "_scratch", "_is", "_on_device"):
         assert re.search(rf"^from \.geometry\._call import .*\b{helper}\b", source, flags=re.M), helper
     assert ".tolist()" not in source and ".item()" not in source and source.count(".cpu()") == 4      # the reads its docstrings name
+    # the target goes through meshdist's one front, the box through its one reduction; the fp32 rule of a limit is _positive's
+    assert re.search(r"^from \.meshdist import .*\b_finite_box\b.*\b_mesh_or_grid\b", source, flags=re.M)
+    assert "isinstance(target" not in source and "torch.where(" not in source and "np.float32(" not in source
     assert sorted(n for n in os.listdir(os.path.join(pkg, "geometry")) if n.endswith(".py")) == [
         "__init__.py", "_call.py", "files.py", "images.py", "lattice.py", "mesh.py", "occupancy.py"]
     from nerf_fl_amd import fusion, geometry, meshdist, registration
