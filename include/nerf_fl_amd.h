@@ -1704,6 +1704,53 @@ int nfl_mesh_occlusion(const float* d_points, const float* d_normals, int64_t n,
                        int32_t nx, int32_t ny, int32_t nz, int32_t n_directions, float radius, float bias, uint64_t seed,
                        int32_t* d_hits, float* d_open, void* stream);
 
+/* ---- mesh solid: how often a ray crosses a mesh, and from that whether a point lies inside a closed one ----------------------
+ * Everything here stands on "mesh cast": the rays, the usable triangles, THE RAY TEST with its clamp, its consistency condition
+ * and its box rule, THE WALK.  Nothing of them changes.
+ *
+ * THE CROSSINGS of a ray: the number of usable triangles whose RAY TEST accepts the ray (with the box rule wherever a grid or a
+ * box is given).  A ray that can hit nothing counts 0; far = +inf is served.  Every triangle counts at most once; a triangle
+ * that the mesh holds twice is two triangles.
+ * THE ONCE-ONLY RULE (grid mode).  THE WALK is run to its end -- there is no held hit, so it ends at te_i > tf' or at the grid's
+ * last slab only -- and reads a triangle in every cell of its bounding box that it passes.  An accepted hit counts only in
+ * the cell (cellf(qf[0]), cellf(qf[1]), cellf(qf[2])) of its own clamped point qf.  That cell lists the triangle (the clamp
+ * keeps qf in its bounding box), it is read while slab cellf(qf[m]) is walked ("mesh cast": the hit's parameter lies in that
+ * slab's interval, and on the two other axes qf lies within E of the ray there), and no cell is read twice, the slabs being
+ * taken in order.  THE CONTRACT: grid mode returns the integer of brute mode given the same box.
+ *
+ * THE DIRECTIONS: 7 fixed fp32 vectors, NFL_SOLID_DIRECTIONS below, component k of direction j being sign * sqrt(prime) rounded
+ * to fp32, 21 distinct primes: no component is zero, none runs along a lattice line or in a face of an axis-aligned box, the
+ * major axes go x, y, z, x, y, z, x and the signs differ.  They are not normalised.
+ *   j     0: (+29, +3, +7)   1: (-5, +31, -2)   2: (+11, -13, +37)   3: (-41, -17, +19)   4: (+23, -53, -43)   5: (-47, -59, -67)
+ *         6: (+73, +61, -71)
+ * INSIDE, for a point p and an odd K in {1, 3, 5, 7}: votes = the number of j < K for which the ray [p, DIRECTIONS[j], 0, +inf]
+ * has an odd number of CROSSINGS; inside = 2 * votes > K.  A point with a non-finite coordinate: votes = 255, inside = 0.
+ * A point outside a grid's box needs no special case: the space outside the box is empty.  A point ON the surface gets the side
+ * the roundings give; an open mesh has no inside, and its votes tell how far the directions disagree; a ray through a shared
+ * edge may count 0 or 2 there (no watertight edge rule), which the majority over K directions absorbs.
+ *
+ * nfl_mesh_crossings   one launch, a thread per ray of d_rays (n_rays, 8): d_count (n_rays) int32.  Brute and grid mode, the box
+ *   and the mesh and grid arguments exactly as nfl_mesh_cast takes them.
+ * nfl_mesh_inside      one launch, a thread per point of d_points (n, 3), the directions one after the other: d_votes (n) and,
+ *   where given, d_inside (n), a byte each (uint8).  Brute and grid mode and their arguments as nfl_mesh_cast.
+ *
+ *   NFL_EINVAL (nothing launched): what nfl_mesh_cast refuses of n_rays / n, the mesh and the grid arguments; n_directions
+ *   outside {1, 3, 5, 7}; for n > 0 a NULL or misaligned (4 B) d_rays, d_count or d_points, a NULL d_votes.  n == 0: NFL_OK, no
+ *   launch. */
+#define NFL_SOLID_MAX_DIRECTIONS 7
+#define NFL_SOLID_DIRECTIONS {{5.38516474f, 1.73205078f, 2.64575124f}, {-2.23606801f, 5.56776428f, -1.41421354f}, \
+                              {3.31662488f, -3.60555124f, 6.08276272f}, {-6.40312433f, -4.12310553f, 4.35889912f}, \
+                              {4.79583168f, -7.28010988f, -6.55743837f}, {-6.85565472f, -7.68114567f, -8.18535233f}, \
+                              {8.54400349f, 7.81024981f, -8.42614937f}}
+int nfl_mesh_crossings(const float* d_rays, int64_t n_rays, const float* d_vertices, const int32_t* d_triangles,
+                       int64_t n_vertices, int64_t n_triangles, const int64_t* d_offsets, const int32_t* d_entries,
+                       int64_t n_entries, float lo_x, float lo_y, float lo_z, float cell, int32_t nx, int32_t ny, int32_t nz,
+                       int32_t* d_count, void* stream);
+int nfl_mesh_inside(const float* d_points, int64_t n, const float* d_vertices, const int32_t* d_triangles, int64_t n_vertices,
+                    int64_t n_triangles, const int64_t* d_offsets, const int32_t* d_entries, int64_t n_entries,
+                    float lo_x, float lo_y, float lo_z, float cell, int32_t nx, int32_t ny, int32_t nz, int32_t n_directions,
+                    void* d_votes, void* d_inside, void* stream);
+
 /* ---- hierarchical sampling (reference sample_pdf, rendering.py:7-46, plus the
  * concat + sort of rendering.py:267-272) -------------------------------------
  * d_z_coarse (R,S), d_weights_coarse (R,S); d_u (R,I) or NULL with d_u_row (I)

@@ -407,6 +407,9 @@ REGISTER_ROW = {"COUNT": 0, "SUM_DD": 1, "SUM_P": 2, "SUM_Q": 5, "SUM_PP": 8, "S
 # mesh cast (nerf_fl_amd/raycast.py): plain arguments, no struct
 CAST_MODES = {"first": 0, "any": 1}
 
+# mesh solid (nerf_fl_amd/solid.py): plain arguments, no struct
+SOLID_MAX_DIRECTIONS = 7
+
 # every struct include/nerf_fl_amd.h declares: C name -> its mirror
 STRUCTS = {
     "nfl_field_desc": FieldDesc, "nfl_field_params": FieldParams, "nfl_pack_job": PackJob, "nfl_camera": Camera,
@@ -453,6 +456,7 @@ CONSTANTS = {
     "NFL_REGISTER_TRANSFORM": REGISTER_TRANSFORM, "NFL_REGISTER_HISTORY": REGISTER_HISTORY,
     **{"NFL_REGISTER_" + k: v for k, v in REGISTER_ROW.items()},
     "NFL_CAST_FIRST": CAST_MODES["first"], "NFL_CAST_ANY": CAST_MODES["any"],
+    "NFL_SOLID_MAX_DIRECTIONS": SOLID_MAX_DIRECTIONS,
 }
 
 # every function include/nerf_fl_amd.h declares: (name, restype, argtypes)
@@ -561,6 +565,12 @@ SYMBOLS = [
                                      C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
+    ("nfl_mesh_crossings", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                     C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_void_p, C.c_void_p]),
+    ("nfl_mesh_inside", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                  C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32,
+                                  C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("nfl_abi_version", C.c_int, []),
     ("nfl_version", C.c_char_p, []),
     ("nfl_strerror", C.c_char_p, [C.c_int]),

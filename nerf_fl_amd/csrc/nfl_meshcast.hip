@@ -10,6 +10,9 @@
 //           every thread tries them all.  Grid: the thread walks.  Rays of a frame arrive in pixel order, so neighbouring lanes
 //           walk neighbouring rows.  First-hit mode keeps (t, triangle) only and tests the answer once more for its point.
 //   occlusion   a wave per point: lane l casts directions l, l + 64, ... in any-hit mode, the hits are counted by ballot.
+//   solid   ("mesh solid") THE CROSSINGS of a ray, a thread per ray: the same walk run to its end, every
+//           accepted hit counted in the cell of its own point alone (nc_walk_count); and INSIDE, a thread per point: the parity
+//           of the crossings along the header's fixed directions, one direction after the other for the whole wave.
 //
 // No atomics, no scratch buffer, nothing that depends on an order.  The grid (NdGrid, nd_cellf, nd_face), the triangle fetch and
 // the hash are nfl_geom.h's, the pointer checks nfl_geom_layout.h's: a ray meets the cells nfl_trigrid_emit filled.  The view
@@ -180,14 +183,12 @@ __device__ __forceinline__ void nc_span(float lo, float cell, int n, double o, d
     *c1 = nd_cellf(nc_up(fmax(xa, xb) + E), lo, cell, n);
 }
 
-// THE WALK of the header.  ANY: stops at the first accepted hit.
-template <bool ANY>
-__device__ __forceinline__ void nc_walk(NcBest& best, const NcRay& R, const NcBox& B, const NtMesh& M) {
+// THE WALK of the header, written once for what is done along it.  attempt(t, a, b, c, x, y, z) is handed every usable triangle
+// of every row read, with the row's cell, and says whether the walk is over; settled(te) says whether nothing at a parameter
+// from te on can change the answer.  Both are lambdas marked NT_INLINE.
+template <typename Try, typename Settled>
+__device__ __forceinline__ void nc_walk(const NcRay& R, const NcBox& B, const NtMesh& M, Try&& attempt, Settled&& settled) {
     const NdGrid& G = M.G;
-    const auto attempt = [&](int32_t t, const float* ca, const float* cb, const float* cc) NT_INLINE {
-        nc_try(best, R, B, true, t, ca, cb, cc);                        // where rows are walked the box rule holds
-        return ANY && best.t >= 0;
-    };
     int m = 0;
     double am = fabs(R.d[0]);
     if (fabs(R.d[1]) > am) m = 1, am = fabs(R.d[1]);
@@ -218,8 +219,8 @@ __device__ __forceinline__ void nc_walk(NcBest& best, const NcRay& R, const NcBo
         double te, tx;
         nc_slab(lm, G.cell, i, up, om, dm, E, &te, &tx);
         if (te > tf) return;                                // this slab and every later one begin beyond far
-        // every hit of this slab and the later ones has t >= te: nothing there can win or tie
-        if (best.t >= 0 && best.tf < nc_down(te - fabs(te) * NC_2M40)) return;
+        // every hit of this slab and the later ones has t >= te
+        if (settled(te)) return;
         if (tx < tn) continue;                              // the slab ends before near
         const double ta = fmax(te, tn), tb = fmin(tx, tf);
         int a0, a1, b0, b1;
@@ -230,10 +231,43 @@ __device__ __forceinline__ void nc_walk(NcBest& best, const NcRay& R, const NcBo
                 const int x = m == 0 ? i : (m == 1 ? j2 : j1), y = m == 0 ? j1 : (m == 1 ? i : j2);
                 const int z = m == 0 ? j2 : (m == 1 ? j1 : i);
                 NC_DEBUG_ADD(1, 1);
-                nt_row(M, ((i64)z * G.dims[1] + y) * G.dims[0] + x, attempt);
-                if (ANY && best.t >= 0) return;
+                bool over = false;
+                nt_row(M, ((i64)z * G.dims[1] + y) * G.dims[0] + x,
+                       [&](int32_t t, const float* ca, const float* cb, const float* cc) NT_INLINE {
+                           return over = attempt(t, ca, cb, cc, x, y, z);
+                       });
+                if (over) return;
             }
     }
+}
+
+// the walk for THE ANSWER.  ANY: stops at the first accepted hit.
+template <bool ANY>
+__device__ __forceinline__ void nc_walk_best(NcBest& best, const NcRay& R, const NcBox& B, const NtMesh& M) {
+    nc_walk(R, B, M,
+            [&](int32_t t, const float* ca, const float* cb, const float* cc, int, int, int) NT_INLINE {
+                nc_try(best, R, B, true, t, ca, cb, cc);                // where rows are walked the box rule holds
+                return ANY && best.t >= 0;
+            },
+            // nothing from te on can win or tie
+            [&](double te) NT_INLINE { return best.t >= 0 && best.tf < nc_down(te - fabs(te) * NC_2M40); });
+}
+
+// the walk for THE CROSSINGS of "mesh solid": no early stop, and THE ONCE-ONLY RULE -- a triangle is listed in every cell of its
+// bounding box and the walk reads several of them, so an accepted hit counts in the cell of its own point qf alone
+__device__ __forceinline__ int32_t nc_walk_count(const NcRay& R, const NcBox& B, const NtMesh& M) {
+    const NdGrid& G = M.G;
+    int32_t count = 0;
+    nc_walk(R, B, M,
+            [&](int32_t, const float* ca, const float* cb, const float* cc, int x, int y, int z) NT_INLINE {
+                NcHit H;
+                NC_DEBUG_ADD(0, 1);
+                if (nc_test(R, B, true, ca, cb, cc, H) && nd_cellf(H.q[0], G.lo[0], G.cell, G.dims[0]) == x &&
+                    nd_cellf(H.q[1], G.lo[1], G.cell, G.dims[1]) == y && nd_cellf(H.q[2], G.lo[2], G.cell, G.dims[2]) == z) ++count;
+                return false;
+            },
+            [](double) NT_INLINE { return false; });
+    return count;
 }
 
 // ------------------------------------------------------------------------------------------------------------------ cast
@@ -264,7 +298,7 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_mesh_cast_kernel(const NcCast 
     if (boxed) B = nc_box(a.M.G);
     NcBest best = {INFINITY, -1};
     if (GRID) {
-        if (asks) nc_walk<ANY>(best, R, B, a.M);
+        if (asks) nc_walk_best<ANY>(best, R, B, a.M);
     } else {
         const auto still = [&]() NT_INLINE { return asks && !(ANY && best.t >= 0); };
         const auto attempt = [&](int32_t t, const float* ta, const float* tb, const float* tc) NT_INLINE {
@@ -299,6 +333,14 @@ static bool nc_grid_args_ok(const int64_t* d_offsets, const int32_t* d_entries, 
     return nt_rows_ok(d_offsets, d_entries, n_entries, lo, cell, dims);
 }
 
+// the mesh and grid part of a call as the kernels see it: the rows where they are given, the grid's box where one is given
+static NtMesh nc_view(const float* d_vertices, const int32_t* d_triangles, int64_t n_vertices, int64_t n_triangles,
+                      const int64_t* d_offsets, const int32_t* d_entries, int64_t n_entries, const float* lo, float cell,
+                      const int32_t* dims) {
+    return {d_vertices, d_triangles, n_vertices, n_triangles, d_offsets, d_entries, d_offsets ? n_entries : 0,
+            dims[0] != 0 ? nd_grid_of(lo, cell, dims) : NdGrid{{0.f, 0.f, 0.f}, 1.f, {1, 1, 1}}};
+}
+
 extern "C" int nfl_mesh_cast(const float* d_rays, int64_t n_rays, const float* d_vertices, const int32_t* d_triangles,
                              int64_t n_vertices, int64_t n_triangles, const int64_t* d_offsets, const int32_t* d_entries,
                              int64_t n_entries, float lo_x, float lo_y, float lo_z, float cell, int32_t nx, int32_t ny, int32_t nz,
@@ -312,10 +354,9 @@ extern "C" int nfl_mesh_cast(const float* d_rays, int64_t n_rays, const float* d
     if (n_rays == 0) return NFL_OK;
     if (ng_bad(d_rays, 4) || ng_bad(d_t, 4)) return NFL_EINVAL;
     if (ng_misaligned(d_triangle, 4) || ng_misaligned(d_bary, 4) || ng_misaligned(d_point, 4)) return NFL_EINVAL;
-    const bool grid = d_offsets != nullptr, boxed = nx != 0;
-    NcCast a = {d_rays, n_rays, {d_vertices, d_triangles, n_vertices, n_triangles, d_offsets, d_entries, grid ? n_entries : 0,
-                                 boxed ? nd_grid_of(lo, cell, dims) : NdGrid{{0.f, 0.f, 0.f}, 1.f, {1, 1, 1}}},
-                boxed ? 1 : 0, d_t, d_triangle, d_bary, d_point};
+    const bool grid = d_offsets != nullptr;
+    NcCast a = {d_rays, n_rays, nc_view(d_vertices, d_triangles, n_vertices, n_triangles, d_offsets, d_entries, n_entries, lo, cell, dims),
+                nx != 0 ? 1 : 0, d_t, d_triangle, d_bary, d_point};
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 blocks(nm_grid(n_rays)), threads(NM_THREADS);
     if (grid && mode == NFL_CAST_FIRST) hipLaunchKernelGGL((nfl_mesh_cast_kernel<true, false>), blocks, threads, 0, s, a);
@@ -390,7 +431,7 @@ __global__ __launch_bounds__(NM_THREADS) void nfl_mesh_occlusion_kernel(const Nc
             nc_direction(a.seed, i, j, n, d);
             NcRay R;
             NcBest best = {INFINITY, -1};
-            if (nc_ray(o, d, 0.f, a.radius, R)) nc_walk<true>(best, R, B, a.M);
+            if (nc_ray(o, d, 0.f, a.radius, R)) nc_walk_best<true>(best, R, B, a.M);
             hit = best.t >= 0;
         }
         hits += (int32_t)__popcll(__ballot(hit));
@@ -416,5 +457,141 @@ extern "C" int nfl_mesh_occlusion(const float* d_points, const float* d_normals,
                n_directions, radius, bias, seed, d_hits, d_open};
     hipLaunchKernelGGL(nfl_mesh_occlusion_kernel, dim3((unsigned)ng_cdiv(n, NM_THREADS / 64)), dim3(NM_THREADS), 0,
                        static_cast<hipStream_t>(stream), a);
+    return ng_launched() ? NFL_OK : NFL_ELAUNCH;
+}
+
+// ----------------------------------------------------------------------------------------------------------------- solid
+
+// THE CROSSINGS of the header ("mesh solid"): a thread per ray, as the cast.  Brute: every usable triangle is tried once, which
+// is the definition.  Grid: the count-mode walk, which returns the same integer.
+struct NcCross {
+    const float* rays;
+    i64 n;
+    NtMesh M;
+    int boxed;
+    int32_t* count;
+};
+
+template <bool GRID>
+__global__ __launch_bounds__(NM_THREADS) void nfl_mesh_crossings_kernel(const NcCross a) {
+    const i64 n = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
+    const bool mine = n < a.n;
+    float w[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (mine) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) w[k] = a.rays[8 * n + k];
+    }
+    NcRay R;
+    const bool asks = nc_ray(w, w + 3, w[6], w[7], R) && mine;
+    const bool boxed = a.boxed != 0;
+    NcBox B = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+    if (boxed) B = nc_box(a.M.G);
+    int32_t count = 0;
+    if (GRID) {
+        if (asks) count = nc_walk_count(R, B, a.M);
+    } else {
+        nt_tiles(a.M, [&]() NT_INLINE { return asks; },
+                 [&](int32_t, const float* ta, const float* tb, const float* tc) NT_INLINE {
+                     NcHit H;
+                     NC_DEBUG_ADD(0, 1);
+                     if (nc_test(R, B, boxed, ta, tb, tc, H)) ++count;
+                 });
+    }
+    if (mine) a.count[n] = count;
+}
+
+extern "C" int nfl_mesh_crossings(const float* d_rays, int64_t n_rays, const float* d_vertices, const int32_t* d_triangles,
+                                  int64_t n_vertices, int64_t n_triangles, const int64_t* d_offsets, const int32_t* d_entries,
+                                  int64_t n_entries, float lo_x, float lo_y, float lo_z, float cell, int32_t nx, int32_t ny,
+                                  int32_t nz, int32_t* d_count, void* stream) {
+    if (n_rays < 0 || n_rays > ND_MAX_ENTRIES) return NFL_EINVAL;
+    if (!nd_mesh_ok(d_vertices, d_triangles, n_vertices, n_triangles)) return NFL_EINVAL;
+    const float lo[3] = {lo_x, lo_y, lo_z};
+    const int32_t dims[3] = {nx, ny, nz};
+    if (!nc_grid_args_ok(d_offsets, d_entries, n_entries, lo, cell, dims, false)) return NFL_EINVAL;
+    if (n_rays == 0) return NFL_OK;
+    if (ng_bad(d_rays, 4) || ng_bad(d_count, 4)) return NFL_EINVAL;
+    NcCross a = {d_rays, n_rays, nc_view(d_vertices, d_triangles, n_vertices, n_triangles, d_offsets, d_entries, n_entries, lo, cell, dims),
+                 nx != 0 ? 1 : 0, d_count};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 blocks(nm_grid(n_rays)), threads(NM_THREADS);
+    if (d_offsets) hipLaunchKernelGGL(nfl_mesh_crossings_kernel<true>, blocks, threads, 0, s, a);
+    else hipLaunchKernelGGL(nfl_mesh_crossings_kernel<false>, blocks, threads, 0, s, a);
+    return ng_launched() ? NFL_OK : NFL_ELAUNCH;
+}
+
+// INSIDE of the header: a thread per point, direction j of THE DIRECTIONS after direction j - 1.  Every lane of a wave walks
+// the same direction at the same time, from a neighbouring point when the points are a lattice's: the coherent case.  The
+// table is read by j from constant memory; the parities are the bits of one word, so nothing is indexed in registers.
+__device__ const float nc_directions[NFL_SOLID_MAX_DIRECTIONS][3] = NFL_SOLID_DIRECTIONS;
+
+struct NcSolid {
+    const float* points;
+    i64 n;
+    NtMesh M;
+    int boxed;
+    int32_t K;
+    uint8_t *votes, *inside;
+};
+
+template <bool GRID>
+__global__ __launch_bounds__(NM_THREADS) void nfl_mesh_inside_kernel(const NcSolid a) {
+    const i64 n = (i64)blockIdx.x * NM_THREADS + threadIdx.x;
+    const bool mine = n < a.n;
+    float p[3] = {0.f, 0.f, 0.f};
+    if (mine) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p[k] = a.points[3 * n + k];
+    }
+    const bool finite = ng_is_finite(p[0]) && ng_is_finite(p[1]) && ng_is_finite(p[2]);
+    const bool asks = mine && finite;
+    const bool boxed = a.boxed != 0;
+    NcBox B = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+    if (boxed) B = nc_box(a.M.G);
+    const auto ray = [&](int j, NcRay& R) NT_INLINE {
+        const float d[3] = {nc_directions[j][0], nc_directions[j][1], nc_directions[j][2]};
+        return nc_ray(p, d, 0.f, INFINITY, R);
+    };
+    uint32_t odd = 0;                                       // bit j: direction j has an odd crossings count
+    if (GRID) {
+        for (int j = 0; j < a.K; ++j) {
+            NcRay R;
+            if (ray(j, R) && asks) odd |= (uint32_t)(nc_walk_count(R, B, a.M) & 1) << j;
+        }
+    } else {
+        nt_tiles(a.M, [&]() NT_INLINE { return asks; },
+                 [&](int32_t, const float* ta, const float* tb, const float* tc) NT_INLINE {
+                     for (int j = 0; j < a.K; ++j) {
+                         NcRay R;
+                         NcHit H;
+                         NC_DEBUG_ADD(0, 1);
+                         if (ray(j, R) && nc_test(R, B, boxed, ta, tb, tc, H)) odd ^= 1u << j;
+                     }
+                 });
+    }
+    if (!mine) return;
+    const int votes = __popc(odd);
+    a.votes[n] = finite ? (uint8_t)votes : (uint8_t)255;
+    if (a.inside) a.inside[n] = finite && 2 * votes > a.K ? 1 : 0;
+}
+
+extern "C" int nfl_mesh_inside(const float* d_points, int64_t n, const float* d_vertices, const int32_t* d_triangles,
+                               int64_t n_vertices, int64_t n_triangles, const int64_t* d_offsets, const int32_t* d_entries,
+                               int64_t n_entries, float lo_x, float lo_y, float lo_z, float cell, int32_t nx, int32_t ny, int32_t nz,
+                               int32_t n_directions, void* d_votes, void* d_inside, void* stream) {
+    if (n < 0 || n > ND_MAX_ENTRIES) return NFL_EINVAL;
+    if (n_directions < 1 || n_directions > NFL_SOLID_MAX_DIRECTIONS || n_directions % 2 == 0) return NFL_EINVAL;
+    if (!nd_mesh_ok(d_vertices, d_triangles, n_vertices, n_triangles)) return NFL_EINVAL;
+    const float lo[3] = {lo_x, lo_y, lo_z};
+    const int32_t dims[3] = {nx, ny, nz};
+    if (!nc_grid_args_ok(d_offsets, d_entries, n_entries, lo, cell, dims, false)) return NFL_EINVAL;
+    if (n == 0) return NFL_OK;
+    if (ng_bad(d_points, 4) || !d_votes) return NFL_EINVAL;
+    NcSolid a = {d_points, n, nc_view(d_vertices, d_triangles, n_vertices, n_triangles, d_offsets, d_entries, n_entries, lo, cell, dims),
+                 nx != 0 ? 1 : 0, n_directions, static_cast<uint8_t*>(d_votes), static_cast<uint8_t*>(d_inside)};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 blocks(nm_grid(n)), threads(NM_THREADS);
+    if (d_offsets) hipLaunchKernelGGL(nfl_mesh_inside_kernel<true>, blocks, threads, 0, s, a);
+    else hipLaunchKernelGGL(nfl_mesh_inside_kernel<false>, blocks, threads, 0, s, a);
     return ng_launched() ? NFL_OK : NFL_ELAUNCH;
 }
