@@ -1751,6 +1751,99 @@ int nfl_mesh_inside(const float* d_points, int64_t n, const float* d_vertices, c
                     float lo_x, float lo_y, float lo_z, float cell, int32_t nx, int32_t ny, int32_t nz, int32_t n_directions,
                     void* d_votes, void* d_inside, void* stream);
 
+/* ---- mesh edges: the edge table of an indexed mesh, its boundary loops, and the caps that close them ------------------------
+ * "mesh solid" is defined for a closed, consistently wound mesh.  This section tells whether a mesh is one, where it is open,
+ * and closes it.  The mesh has V vertices and T triangles.  A triangle with an index outside [0, V) is counted and takes part
+ * in nothing.
+ *
+ * HALF-EDGE h = 3 t + c, c in 0..2, runs from tri[t][c] to tri[t][(c + 1) % 3].  One whose two ends are equal is DEGENERATE: it
+ * lies on no edge, has edge id -1 and is counted in n_degenerate.
+ * EDGE: an unordered pair {a, b}, a < b, that has at least one half-edge.  Edges are numbered in ascending (a, b); E is their
+ * number.  edges (E, 2) int32; half_edge (3T) int32, the edge of every half-edge or -1; edge_offsets (E + 1) int64 and
+ * edge_halves (H) int32, the half-edges on each edge ASCENDING.  H = 3 T - n_degenerate for a mesh in range.
+ * KIND (E) uint8: NFL_EDGE_INTERIOR exactly two half-edges, one in each direction; NFL_EDGE_BOUNDARY exactly one;
+ * NFL_EDGE_FLIPPED exactly two in the same direction; NFL_EDGE_NONMANIFOLD three or more.
+ * TWIN (3T) int32: the other half-edge of an INTERIOR edge, -1 everywhere else.
+ * TOTALS of the edges, NFL_EDGE_TOTALS int64: E, H, n_boundary, n_flipped, n_nonmanifold (edges of each kind), n_degenerate,
+ * and the number of triangles out of range.
+ *
+ * SUCCESSOR of a boundary half-edge h = (a -> b) of triangle t (one on a BOUNDARY edge).  Let g be the half-edge after h in t;
+ * it starts at b.  While twin[g] >= 0: g becomes the half-edge after twin[g] in its triangle, which again starts at b.  If the
+ * walk stops at a half-edge on a BOUNDARY edge, that is succ[h]; if it stops on a FLIPPED or NONMANIFOLD edge or at a
+ * degenerate half-edge, or runs longer than 3 T steps (tables that are not this mesh's), succ[h] = -1.  The walk has an inverse,
+ * so succ is a partial injection and the boundary half-edges fall into cycles and open chains.
+ * LOOP: a cycle of succ.  Loops are numbered in ascending order of their smallest half-edge and listed from that half-edge
+ * along succ.  loop_offsets (L + 1) int64, loop_halves (B') int32, loop_of (3T) int32 with -1 for a half-edge on no loop.  The
+ * boundary half-edges on open chains are counted in n_open and belong to no loop.  A loop has at least 3 half-edges.
+ * THE TABLE per loop: length int32; perimeter fp32 = the fp64 sum, in walk order, of the fp64 lengths sqrt((dx dx + dy dy) +
+ * dz dz) of d = p_b - p_a taken in fp64 on the fp32 positions, rounded once; centroid (L, 3) fp32 = the fp64 sum, in walk
+ * order, of the start vertices, divided by the length, rounded once.  A loop with a non-finite start vertex has perimeter =
+ * +inf and centroid = 0 and is never filled.
+ * TOTALS of the loops, NFL_LOOP_TOTALS int64: L, B', n_open.
+ *
+ * FILL.  A loop is SELECTED when its length is at least 3 and at most max_edges, its perimeter is finite and <= max_perimeter
+ * (compared in fp32; +inf: no limit), and the byte of d_keep (L), where given, is not zero.  A selected loop of length 3
+ * with half-edges a->b, b->c, c->a gets the ONE triangle (b, a, c) and no vertex.  A selected loop of length > 3 gets one new
+ * vertex z and one triangle (b, a, z) per half-edge a -> b, in walk order.  z lies at the loop's centroid (the table's fp32,
+ * bit for bit); its normal is the normalised fp64 sum, in walk order, of the new triangles' (p1 - p0) x (p2 - p0), zeros when
+ * that sum is zero or not finite; its colour is the fp64 sum, in walk order, of the colours of the loop's start vertices over
+ * the length, rounded once.  New vertices follow the V inputs in loop order; new triangles follow the T inputs in loop order and
+ * then walk order; input rows are copied bit for bit.  Every new triangle runs against the boundary half-edge it covers, so
+ * that edge becomes INTERIOR and the spokes of a fan are INTERIOR among themselves.
+ * TOTALS of the fill, NFL_FILL_TOTALS int64: n_filled, n_new_vertices, n_new_triangles.
+ *
+ * nfl_mesh_edges_count   takes the vertex adjacency of "mesh smoothing" (d_offsets (V + 1), d_neighbors (n_neighbors): the
+ *   sorted distinct neighbour rows).  Vertex a owns the edges to its neighbours b > a; a scan of those counts numbers the edges;
+ *   a half-edge finds its edge by a binary search for max(a, b) in the row of min(a, b); a count per edge, a scan, a fill and a
+ *   sort of each row (by its thread up to NFL_EDGE_SHORT_ROW half-edges, by the wave of its thread beyond) make the rows.
+ *   Writes d_totals and the scratch (nfl_mesh_edges_bytes) that nfl_mesh_edges_emit reads, with E and H given back.
+ * nfl_mesh_loops_count   takes the tables of the edges and n_boundary.  succ by a thread per half-edge; ceil(log2 n_boundary) + 1
+ *   rounds of pointer doubling carry the smallest half-edge ahead and a dead end; a thread per loop walks it for the places and
+ *   the sums.  Scratch: nfl_mesh_loops_bytes.  nfl_mesh_loops_emit takes L and B' given back.
+ * nfl_mesh_fill_count    takes the loops' table and the selection; nfl_mesh_fill_emit the mesh, the loops and the totals, and
+ *   writes the whole new mesh and, where given, a byte per output vertex and triangle: 1 = new.  d_colors and d_out_colors are
+ *   both given or both NULL.  Scratch: nfl_mesh_fill_bytes(n_loops).
+ * Everything read from the scratch or from a caller's table is bounded before it is used: tables that are not this mesh's
+ * give wrong output, never an access out of range.
+ *
+ *   NFL_EINVAL (nothing launched): sizes negative or beyond int32 indices (n_vertices > INT32_MAX, n_triangles > INT32_MAX / 3,
+ *   n_loops > INT32_MAX / 3), n_neighbors outside [0, 6 T]; a misaligned pointer (4 B, 8 B for int64); for a mesh that is not
+ *   empty a NULL pointer that the sizes need; totals outside what the count can give (E, H, n_boundary, B' in [0, 3 T]; L in
+ *   [0, T]; n_new_vertices in [0, L], n_new_triangles in [0, B']); max_edges < 3; max_perimeter not > 0.  NFL_ESMALL: a scratch
+ *   below the _bytes size.  An empty mesh (V == 0 or T == 0; for the fill also L == 0): NFL_OK, no launch. */
+#define NFL_EDGE_INTERIOR 0
+#define NFL_EDGE_BOUNDARY 1
+#define NFL_EDGE_FLIPPED 2
+#define NFL_EDGE_NONMANIFOLD 3
+#define NFL_EDGE_SHORT_ROW 8
+#define NFL_EDGE_TOTALS 7
+#define NFL_LOOP_TOTALS 3
+#define NFL_FILL_TOTALS 3
+size_t nfl_mesh_edges_bytes(int64_t n_vertices, int64_t n_triangles);
+int nfl_mesh_edges_count(const int32_t* d_triangles, int64_t n_vertices, int64_t n_triangles, const int64_t* d_offsets,
+                         const int32_t* d_neighbors, int64_t n_neighbors, void* d_scratch, size_t scratch_bytes,
+                         int64_t* d_totals, void* stream);
+int nfl_mesh_edges_emit(const int32_t* d_triangles, int64_t n_vertices, int64_t n_triangles, const void* d_scratch,
+                        size_t scratch_bytes, int64_t n_edges, int64_t n_halves, int32_t* d_edges, int32_t* d_half_edge,
+                        int64_t* d_edge_offsets, int32_t* d_edge_halves, void* d_kind, int32_t* d_twin, void* stream);
+size_t nfl_mesh_loops_bytes(int64_t n_triangles);
+int nfl_mesh_loops_count(const float* d_vertices, const int32_t* d_triangles, int64_t n_vertices, int64_t n_triangles,
+                         const int32_t* d_half_edge, const int32_t* d_twin, const void* d_kind, int64_t n_edges,
+                         int64_t n_boundary, void* d_scratch, size_t scratch_bytes, int64_t* d_totals, void* stream);
+int nfl_mesh_loops_emit(int64_t n_triangles, const void* d_scratch, size_t scratch_bytes, int64_t n_loops,
+                        int64_t n_loop_halves, int64_t* d_loop_offsets, int32_t* d_loop_halves, int32_t* d_loop_of,
+                        int32_t* d_length, float* d_perimeter, float* d_centroid, void* stream);
+size_t nfl_mesh_fill_bytes(int64_t n_loops);
+int nfl_mesh_fill_count(int64_t n_loops, const int32_t* d_length, const float* d_perimeter, const void* d_keep,
+                        int64_t max_edges, float max_perimeter, void* d_scratch, size_t scratch_bytes, int64_t* d_totals,
+                        void* stream);
+int nfl_mesh_fill_emit(const float* d_vertices, const float* d_normals, const float* d_colors, const int32_t* d_triangles,
+                       int64_t n_vertices, int64_t n_triangles, const int64_t* d_loop_offsets, const int32_t* d_loop_halves,
+                       const int32_t* d_loop_of, const float* d_centroid, int64_t n_loops, int64_t n_loop_halves,
+                       const void* d_scratch, size_t scratch_bytes, int64_t n_new_vertices, int64_t n_new_triangles,
+                       float* d_out_vertices, float* d_out_normals, float* d_out_colors, int32_t* d_out_triangles,
+                       void* d_new_vertices, void* d_new_triangles, void* stream);
+
 /* ---- hierarchical sampling (reference sample_pdf, rendering.py:7-46, plus the
  * concat + sort of rendering.py:267-272) -------------------------------------
  * d_z_coarse (R,S), d_weights_coarse (R,S); d_u (R,I) or NULL with d_u_row (I)

@@ -410,6 +410,11 @@ CAST_MODES = {"first": 0, "any": 1}
 # mesh solid (nerf_fl_amd/solid.py): plain arguments, no struct
 SOLID_MAX_DIRECTIONS = 7
 
+# mesh edges (nerf_fl_amd/topology.py): plain arguments, no struct
+EDGE_KINDS = {"interior": 0, "boundary": 1, "flipped": 2, "nonmanifold": 3}
+EDGE_SHORT_ROW = 8
+EDGE_TOTALS, LOOP_TOTALS, FILL_TOTALS = 7, 3, 3
+
 # every struct include/nerf_fl_amd.h declares: C name -> its mirror
 STRUCTS = {
     "nfl_field_desc": FieldDesc, "nfl_field_params": FieldParams, "nfl_pack_job": PackJob, "nfl_camera": Camera,
@@ -457,6 +462,8 @@ CONSTANTS = {
     **{"NFL_REGISTER_" + k: v for k, v in REGISTER_ROW.items()},
     "NFL_CAST_FIRST": CAST_MODES["first"], "NFL_CAST_ANY": CAST_MODES["any"],
     "NFL_SOLID_MAX_DIRECTIONS": SOLID_MAX_DIRECTIONS,
+    **{"NFL_EDGE_" + k.upper(): v for k, v in EDGE_KINDS.items()}, "NFL_EDGE_SHORT_ROW": EDGE_SHORT_ROW,
+    "NFL_EDGE_TOTALS": EDGE_TOTALS, "NFL_LOOP_TOTALS": LOOP_TOTALS, "NFL_FILL_TOTALS": FILL_TOTALS,
 }
 
 # every function include/nerf_fl_amd.h declares: (name, restype, argtypes)
@@ -571,6 +578,23 @@ SYMBOLS = [
     ("nfl_mesh_inside", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                   C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nfl_mesh_edges_bytes", C.c_size_t, [C.c_int64, C.c_int64]),
+    ("nfl_mesh_edges_count", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                       C.c_size_t, C.c_void_p, C.c_void_p]),
+    ("nfl_mesh_edges_emit", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nfl_mesh_loops_bytes", C.c_size_t, [C.c_int64]),
+    ("nfl_mesh_loops_count", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    ("nfl_mesh_loops_emit", C.c_int, [C.c_int64, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nfl_mesh_fill_bytes", C.c_size_t, [C.c_int64]),
+    ("nfl_mesh_fill_count", C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p,
+                                      C.c_size_t, C.c_void_p, C.c_void_p]),
+    ("nfl_mesh_fill_emit", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t,
+                                     C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
     ("nfl_abi_version", C.c_int, []),
     ("nfl_version", C.c_char_p, []),
     ("nfl_strerror", C.c_char_p, [C.c_int]),

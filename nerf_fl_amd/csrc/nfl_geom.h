@@ -1,6 +1,6 @@
 // nfl_geom.h -- what the geometry translation units share on the device side (every unit that makes, cleans, simplifies,
-// smooths, colours, renders, fuses, measures, registers or casts rays against a lattice or a mesh: nfl_surface, nfl_mesh,
-// nfl_mesh_scan, nfl_occupancy, nfl_simplify, nfl_meshsmooth, nfl_tsdf, nfl_meshdist, nfl_register, nfl_meshcast, and through
+// smooths, colours, renders, fuses, measures, registers, closes or casts rays against a lattice or a mesh: nfl_surface, nfl_mesh,
+// nfl_mesh_scan, nfl_occupancy, nfl_simplify, nfl_meshsmooth, nfl_tsdf, nfl_meshdist, nfl_register, nfl_meshcast, nfl_meshedge, and through
 // nfl_meshray.h nfl_meshcolor, nfl_meshrender and nfl_atlas): launch sizes, the finite test, the splitmix64 hash, the fetch of
 // an fp32 triangle and its face normal, the triangle grid's cell function and faces, the workgroup prefix sum, the library's
 // tiled scan and the small pieces of the mesh kernels.  The scratch layouts, the size checks and the pointer checks are host

@@ -1,5 +1,5 @@
 // nfl_geom_layout.h -- the host arithmetic of the geometry entry points.  The scratch of every one of them (surface, mesh,
-// occupancy, simplify, smoothing, mesh distance, registration) is written ONCE, as an ordered list of regions, and one
+// occupancy, simplify, smoothing, mesh distance, registration, mesh edges) is written ONCE, as an ordered list of regions, and one
 // routine walks it.  Without a base the walk gives the size (what the nfl_*_bytes functions return); with the caller's
 // buffer it gives the pointers (what the entry points launch on), so the two cannot disagree.  Beside the layouts: the size
 // limits, and the pointer and finite checks every entry point makes of its arguments (ng_misaligned, ng_bad, ng_finite).
@@ -222,3 +222,62 @@ enum { NR_M_PARTS, NR_M_REGIONS };
 static inline NgLayout<NR_M_REGIONS> nr_moments_layout(i64 n) {
     return {{{8 * NFL_REGISTER_COLUMNS, (size_t)nd_reduce_blocks(n)}}, {}};    // one fp64 row per workgroup
 }
+
+// ---- mesh edges: nfl_mesh_edges_count / nfl_mesh_edges_emit.  Per-edge regions are 3 T long: every edge has a half-edge
+enum { NE_OWN, NE_EOFF, NE_HE, NE_CNT, NE_CUR, NE_HOFF, NE_TMP, NE_EH, NE_KIND, NE_SUMS, NE_RAW, NE_REGIONS };
+static inline NgLayout<NE_REGIONS> ne_layout(i64 V, i64 T) {
+    const size_t v = (size_t)V, h = 3 * (size_t)T;
+    return {{{4, v},                                        // int32 edges vertex a owns: its neighbours b > a
+             {8, v},                                        // int64 edges before those of a
+             {4, h},                                        // int32 edge of half-edge h, -1: none
+             {4, h},                                        // int32 half-edges on edge e
+             {4, h},                                        // int32 cursor of e while its row is filled
+             {8, h},                                        // int64 half-edges before the row of e
+             {4, h},                                        // int32 the rows in order of arrival
+             {4, h},                                        // int32 the rows ascending
+             {1, h},                                        // uint8 kind of e
+             {1, ng_max(nm_scan_bytes(V), nm_scan_bytes(3 * T))},   // tile sums of the two scans, one after the other
+             {8, 2}}, {}};                                  // int64 E and H as the scans gave them
+}
+// the bounds of the totals emit takes: every edge has a half-edge, every half-edge lies on one edge at most
+static inline bool ne_totals_ok(i64 T, i64 E, i64 H) { return E >= 0 && H >= 0 && E <= 3 * T && H <= 3 * T; }
+
+// ---- mesh edges: nfl_mesh_loops_count / nfl_mesh_loops_emit.  A loop has at least 3 half-edges: per-loop regions are T long
+enum { NL_SUCC, NL_PTR0, NL_MIN0, NL_PTR1, NL_MIN1, NL_ROOT, NL_FLAG, NL_RANK, NL_POS, NL_LEN, NL_LOFF, NL_PER, NL_CEN, NL_SUMS,
+       NL_RAW, NL_REGIONS };
+static inline NgLayout<NL_REGIONS> nl_layout(i64 T) {
+    const size_t t = (size_t)T, h = 3 * t;
+    return {{{4, h},                                        // int32 successor; -1: a dead end; -2: not a boundary half-edge
+             {4, h}, {4, h},                                // int32 the pointer and the smallest half-edge ahead, even rounds
+             {4, h}, {4, h},                                // the same, odd rounds
+             {4, h},                                        // int32 the loop's smallest half-edge, -1: on no loop
+             {4, h},                                        // int32 1 = the smallest of its loop
+             {8, h},                                        // int64 loops before that of h
+             {4, h},                                        // int32 place of h in its loop
+             {4, t},                                        // int32 length of loop l
+             {8, t},                                        // int64 half-edges before loop l
+             {4, t},                                        // fp32 perimeter
+             {12, t},                                       // fp32 x 3 centroid
+             {1, nm_scan_bytes(3 * T)},                     // tile sums of the two scans, one after the other
+             {8, 2}}, {}};                                  // int64 L and B' as the scans gave them
+}
+static inline bool nl_totals_ok(i64 T, i64 L, i64 B) { return L >= 0 && B >= 0 && L <= T && B <= 3 * T; }
+// rounds of pointer doubling that reach around a cycle of up to B half-edges: ceil(log2 B) + 1
+static inline int nl_rounds(i64 B) {
+    int r = 1;
+    for (i64 reach = 1; reach < B; reach *= 2) ++r;
+    return r;
+}
+
+// ---- mesh edges: nfl_mesh_fill_count / nfl_mesh_fill_emit
+enum { NF_LEN, NF_NV, NF_VOFF, NF_NT, NF_TOFF, NF_SUMS, NF_REGIONS };
+static inline NgLayout<NF_REGIONS> nf_layout(i64 L) {
+    const size_t l = (size_t)L;
+    return {{{4, l},                                        // int32 length of a selected loop, 0: not selected
+             {4, l},                                        // int32 new vertices of loop l: 0 or 1
+             {8, l},                                        // int64 new vertices before loop l
+             {4, l},                                        // int32 new triangles of loop l
+             {8, l},                                        // int64 new triangles before loop l
+             {1, nm_scan_bytes(L)}}, {}};                   // tile sums of the two scans, one after the other
+}
+static inline bool nf_totals_ok(i64 L, i64 B, i64 nv, i64 nt) { return nv >= 0 && nt >= 0 && nv <= L && nt <= B; }
